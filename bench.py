@@ -7,12 +7,17 @@ hidden=64, synthetic 100-node / 400-directed-edge topologies, batch=1024 graphs 
 One "step" = {CSR build, zero_grad, forward, loss, backward, (gradient all-reduce), SGD}
 -- the body of topological_training/train.py:109-116 -- with the batch resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant hand-written kernel, timed
-live with events on the launch stream; ``cpu_baseline`` is the oracle's PyG-style CPU step
-(kind "port": torch_geometric itself is not installable here) on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports them
+(``value``, ``ms_per_step``).  ``--dump-outputs DIR`` then writes what the last timed step
+computed -- model output, loss, updated parameters -- as ``DIR/<name>.npy`` (float32).
+``--full`` adds everything else: the median of per-step times, the all-reduce alone, the
+per-kernel table with ``roofline`` for the dominant hand-written kernel (timed live with
+events on the launch stream), ``lightpath``, ``reference_scale`` and ``cpu_baseline``, the
+oracle's PyG-style CPU step (kind "port": torch_geometric itself is not installable here) on
+a bounded sample.
 """
 from __future__ import annotations
 
@@ -40,6 +45,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)       # ~30 ms: the part needs ~12 ms of load to reach its clock
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's model output, loss and updated parameters as "
+                         "DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: median step time, the all-reduce alone, the "
+                         "per-kernel table and roofline, lightpath (configs[2]), reference scale, CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     ap.add_argument("--steps-per-graph", type=int, default=4,
@@ -50,7 +61,10 @@ def parse():
     ap.add_argument("--lightpath-steps", type=int, default=10)
     ap.add_argument("--no-reference-scale", action="store_true",
                     help="skip the reference-scale (V=75 H=16 B=512 / F=5 C=32 B=512) eager and replayed step times")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_batch(rank, device, B=None):
@@ -94,6 +108,9 @@ class TrainStep:
         self.use_graph = use_graph
         self.collective_in_graph = None      # True: the RCCL call is captured with the rest of the step
         self.capture_error = None
+        # the model output of the latest step: captured graphs rewrite their own output tensor on every replay, so the
+        # one of the graph that ran last is the latest (--dump-outputs)
+        self.out = self.out_fb = self.out_multi = self.last_out = None
 
     def _fwd_bwd(self):
         if not os.environ.get("BENCH_PREP_OUTSIDE"):
@@ -102,6 +119,7 @@ class TrainStep:
         # forward with the criterion (SmoothL1Loss, mean) folded into the read-out head's kernel: out, loss value
         # (written with the backward epilogue) and d loss / d out; then backward from the model output
         out, _, g = self.model.forward_loss(self.batch, self.y, loss_out=self.loss)
+        self.out = out.detach()              # the storage only: the autograd graph goes as before
         out.backward(g)
         if self.dp:
             self.flat.gather_grads()         # one kernel packs all gradients into the flat buffer RCCL reduces
@@ -131,6 +149,7 @@ class TrainStep:
                 self._eager()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
+        self.out = None
         capturable = not self.dp or (dist.is_initialized() and dist.get_backend() == "nccl")
         # with a collective inside, the capture is thread-local: the process group's watchdog thread polls its events while
         # this thread captures, and in the default (global) mode a call from ANOTHER thread can invalidate a capture; one
@@ -143,11 +162,13 @@ class TrainStep:
                 self.graph_fb = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.graph_fb, **mode):
                     self._eager()
+                self.out_fb = self.out
                 if self.spg > 1:             # several whole steps per replay: every step still runs every kernel
                     self.graph_multi = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self.graph_multi, pool=self.graph_fb.pool(), **mode):
                         for _ in range(self.spg):
                             self._eager()
+                    self.out_multi = self.out
                 self.collective_in_graph = self.dp
                 return
             except Exception as e:           # noqa: BLE001 -- the runtime's refusal is recorded, the fallback measured
@@ -155,6 +176,7 @@ class TrainStep:
                     raise
                 self.capture_error = repr(e)[:400]
                 self.graph_fb = self.graph_multi = None
+                self.out = self.out_fb = self.out_multi = None
                 torch.cuda.synchronize()
         if not capturable:
             self.capture_error = f"backend {dist.get_backend() if dist.is_initialized() else None} is not stream-capturable"
@@ -163,6 +185,7 @@ class TrainStep:
         self.graph_fb = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_fb):
             self._fwd_bwd()
+        self.out_fb = self.out
         self.graph_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_opt):
             self._update()
@@ -170,8 +193,10 @@ class TrainStep:
     def __call__(self):
         if self.graph_fb is None:
             self._eager()
+            self.last_out = self.out
         else:
             self.graph_fb.replay()
+            self.last_out = self.out_fb
             if self.graph_opt is not None:
                 self._exchange()
                 self.graph_opt.replay()
@@ -181,9 +206,18 @@ class TrainStep:
         if self.graph_multi is not None:
             while n >= self.spg:
                 self.graph_multi.replay()
+                self.last_out = self.out_multi
                 n -= self.spg
         for _ in range(n):
             self()
+
+    def outputs(self):
+        """What a caller of the step receives after its latest run: the model output (``[B, out]``), the loss (SmoothL1,
+        mean) and the parameters the optimizer has just updated."""
+        res = {"out": self.last_out, "loss": self.loss}
+        for name, p in self.model.named_parameters():
+            res["param." + name] = p
+        return res
 
 
 def event_time_ms(fn, iters=20, warm=3, settle=False):
@@ -208,6 +242,19 @@ def event_time_ms(fn, iters=20, warm=3, settle=False):
             break
         prev = cur
     return cur
+
+
+def dump_outputs(path, arrays, limit_bytes=64 << 20):
+    """``--dump-outputs``: every array as ``path/<name>.npy`` in float32, so that two builds run with the same arguments
+    (same seeded inputs) can be compared output for output."""
+    import numpy as np
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > limit_bytes:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {limit_bytes}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def kernel_table(model, batch):
@@ -625,42 +672,44 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # SURVEY 8(d) asks for the MEDIAN step time: a second pass of the same K steps with an event between steps (kept out
-    # of the timed region above so that `value` stays K back-to-back steps between two synchronisations)
-    # (an event between replays: with steps_per_graph > 1 a sample is the mean of that many consecutive steps)
-    spg = step.spg if step.graph_multi is not None else 1
-    nsamp = max(1, args.steps // spg)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(nsamp + 1)]
-    evs[0].record()
-    for i in range(nsamp):
-        step.run(spg)
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    per_step = sorted(evs[i].elapsed_time(evs[i + 1]) / spg for i in range(nsamp))
-    median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
-    if world > 1:
-        t = torch.tensor([median_ms], device=device, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        median_ms = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.outputs())
+    median_ms = all_reduce_us = None
+    if args.full:
+        # SURVEY 8(d) asks for the MEDIAN step time: a second pass of the same K steps with an event between steps (kept
+        # out of the timed region above so that `value` stays K back-to-back steps between two synchronisations)
+        # (an event between replays: with steps_per_graph > 1 a sample is the mean of that many consecutive steps)
+        spg = step.spg if step.graph_multi is not None else 1
+        nsamp = max(1, args.steps // spg)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nsamp + 1)]
+        evs[0].record()
+        for i in range(nsamp):
+            step.run(spg)
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        per_step = sorted(evs[i].elapsed_time(evs[i + 1]) / spg for i in range(nsamp))
+        median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
+        if world > 1:
+            t = torch.tensor([median_ms], device=device, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            median_ms = float(t.item())
+        # the exchange step alone (outside the timed region): events around the flat-gradient all-reduce
+        if step.dp and dist.is_initialized():
+            all_reduce_us = event_time_ms(lambda: step.flat.all_reduce_grads(force=True), iters=20, warm=3) * 1e3
+            t = torch.tensor([all_reduce_us], device=device, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            all_reduce_us = float(t.item())
     loss = float(step.loss.item())
     if not (loss == loss) or loss in (float("inf"), float("-inf")):
         raise SystemExit(f"non-finite loss {loss}")
-    # the exchange step alone (outside the timed region): events around the flat-gradient all-reduce
-    all_reduce_us = None
-    if step.dp and dist.is_initialized():
-        all_reduce_us = event_time_ms(lambda: step.flat.all_reduce_grads(force=True), iters=20, warm=3) * 1e3
-        t = torch.tensor([all_reduce_us], device=device, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        all_reduce_us = float(t.item())
 
     if rank == 0:
         graphs = CFG["B"] * world * args.steps
         res = {
             "metric": "graphs/sec (train step) on 100-node/400-edge synthetic topologies, batch=1024",
             "value": graphs / dt, "unit": "graphs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "ms_per_step_median": median_ms,
-            "graphs_per_s_median": CFG["B"] * world / (median_ms * 1e-3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": "configs[1]: 2-layer TopologicalGNN (TransformerConv+NNConv) hidden=64, "
                                    "100-node/400-directed-edge topologies, batch=1024 graphs per GPU, dropout 0.5, "
                                    "SGD momentum 0.9, SmoothL1; " + ("graph index cached across steps (BENCH_PREP_OUTSIDE: the HBM-resident, cached-batch loader mode; not the headline)" if os.environ.get("BENCH_PREP_OUTSIDE") else "CSR build included in every step"),
@@ -678,22 +727,6 @@ def main():
                        "all_reduce_us": all_reduce_us,
                        "all_reduce_floats": int(step.flat.flat_grad.numel())},
         }
-        rows = kernel_table(model, batch)
-        dom = max(rows, key=lambda r: r["ms"])
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            traffic = json.load(open(tpath)).get(dom["kernel"])
-        if dom["bound"] == "mfma":
-            res["roofline"] = {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["tflops"],
-                               "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                               "frac": dom["tflops"] / MFMA_F32_PEAK_TFLOPS, "traffic": traffic,
-                               "alg_flops_per_launch": dom["flops"], "alg_bytes_per_launch": dom["alg_bytes"],
-                               "ms_per_launch": dom["ms"]}
-        else:
-            res["roofline"] = {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["gbs"], "peak": HBM_PEAK_GBS,
-                               "unit": "GB/s", "frac": dom["gbs"] / HBM_PEAK_GBS, "traffic": traffic,
-                               "alg_bytes_per_launch": dom["alg_bytes"], "ms_per_launch": dom["ms"]}
         # whole-step view against both rooflines, from SURVEY.md 8(d)'s per-graph algorithmic figures:
         # bytes: embed 2(4n+4nH) + convs (8nH+4e+4(n+1)+4eD fwd, 12nH+8e+4(n+1)+4eD bwd) + pool 2(4nH+4n+4H);
         # flops: 3 x fwd, fwd = TransformerConv 8nH^2+2eHD+4eH + NNConv 2nH^2(K+1)+2eH(K+1)+2nH^2
@@ -710,15 +743,34 @@ def main():
                                 "alg_flops_per_step": step_flops, "mfma_TFLOPs": step_flops / sec / 1e12,
                                 "mfma_frac": step_flops / sec / 1e12 / MFMA_F32_PEAK_TFLOPS,
                                 "note": "per rank; algorithmic figures of SURVEY.md 8(d)"}
-        res["kernels"] = [{k: (round(v, 5) if isinstance(v, float) else v) for k, v in r.items()} for r in rows]
-        if world == 1 and not args.no_lightpath:
-            del step, batch, model
-            torch.cuda.empty_cache()
-            res["lightpath"] = lightpath_measurement(device, args.lightpath_steps)
-        if world == 1 and not args.no_reference_scale:
-            res["reference_scale"] = reference_scale_measurement(device)
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(args.cpu_sample_graphs)
+        if args.full:
+            res["ms_per_step_median"] = median_ms
+            res["graphs_per_s_median"] = CFG["B"] * world / (median_ms * 1e-3)
+            rows = kernel_table(model, batch)
+            dom = max(rows, key=lambda r: r["ms"])
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                traffic = json.load(open(tpath)).get(dom["kernel"])
+            if dom["bound"] == "mfma":
+                res["roofline"] = {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["tflops"],
+                                   "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                   "frac": dom["tflops"] / MFMA_F32_PEAK_TFLOPS, "traffic": traffic,
+                                   "alg_flops_per_launch": dom["flops"], "alg_bytes_per_launch": dom["alg_bytes"],
+                                   "ms_per_launch": dom["ms"]}
+            else:
+                res["roofline"] = {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["gbs"], "peak": HBM_PEAK_GBS,
+                                   "unit": "GB/s", "frac": dom["gbs"] / HBM_PEAK_GBS, "traffic": traffic,
+                                   "alg_bytes_per_launch": dom["alg_bytes"], "ms_per_launch": dom["ms"]}
+            res["kernels"] = [{k: (round(v, 5) if isinstance(v, float) else v) for k, v in r.items()} for r in rows]
+            if world == 1 and not args.no_lightpath:
+                del step, batch, model
+                torch.cuda.empty_cache()
+                res["lightpath"] = lightpath_measurement(device, args.lightpath_steps)
+            if world == 1 and not args.no_reference_scale:
+                res["reference_scale"] = reference_scale_measurement(device)
+            if world == 1 and not args.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline(args.cpu_sample_graphs)
         print(json.dumps(res))
     if dist.is_initialized():
         dist.destroy_process_group()

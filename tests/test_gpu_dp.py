@@ -316,8 +316,9 @@ def test_bench_forced_data_parallel_step_holds_the_collective_in_its_graph():
     env = dict(os.environ, BENCH_FORCE_DP="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu-baseline",
-                          "--no-lightpath", "--no-reference-scale"], env=env, capture_output=True, text=True, timeout=900)
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "2", "--full",
+                          "--no-cpu-baseline", "--no-lightpath", "--no-reference-scale"],
+                         env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     cfg = line["config"]
@@ -340,7 +341,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo_reports_the_collective():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]

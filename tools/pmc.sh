@@ -1,11 +1,13 @@
 #!/bin/bash
 # usage: tools/pmc.sh <tag> <COUNTER>   (one PMC pass: per-dispatch counter rows for the eager bench)
 tag=$1; ctr=$2
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)      # the repository root
+OUT=${OUT_DIR:-$R/prof_out}; mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd)   # where the records land (OUT_DIR, default prof_out/)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/$tag -- python3 $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-graph > $GRAFT_REPO_ROOT/gpurun_out/$tag.log 2>&1
+rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $OUT/$tag -- python3 $R/bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-graph > $OUT/$tag.log 2>&1
 python3 - <<PY
 import csv,glob,collections
-f=glob.glob("$GRAFT_REPO_ROOT/gpurun_out/$tag/*/*counter_collection.csv")
+f=glob.glob("$OUT/$tag/*/*counter_collection.csv")
 print(f)
 rows=list(csv.DictReader(open(f[0])))
 print(rows[0].keys())

@@ -1,11 +1,13 @@
 #!/bin/bash
 # usage: tools/pmc_multi.sh <tag> "<COUNTER COUNTER ...>" [bench args]   (one PMC pass, several counters, per-kernel means)
 tag=$1; ctrs=$2; shift; shift
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)      # the repository root
+OUT=${OUT_DIR:-$R/prof_out}; mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd)   # where the records land (OUT_DIR, default prof_out/)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/$tag -- python3 $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-graph "$@" > $GRAFT_REPO_ROOT/gpurun_out/$tag.log 2>&1
+rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $OUT/$tag -- python3 $R/bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-graph "$@" > $OUT/$tag.log 2>&1
 python3 - <<PY
 import csv,glob,collections,json
-f=glob.glob("$GRAFT_REPO_ROOT/gpurun_out/$tag/*/*counter_collection.csv")
+f=glob.glob("$OUT/$tag/*/*counter_collection.csv")
 rows=list(csv.DictReader(open(f[0])))
 agg=collections.defaultdict(lambda: collections.defaultdict(lambda:[0,0.0]))
 for r in rows:
@@ -16,5 +18,5 @@ for k,cs in agg.items():
     if "nnconv" in k or "tconv" in k:
         out[k]={c:v/n for c,(n,v) in cs.items()}
 print(json.dumps(out, indent=1))
-json.dump(out, open("$GRAFT_REPO_ROOT/gpurun_out/$tag.json","w"), indent=1)
+json.dump(out, open("$OUT/$tag.json","w"), indent=1)
 PY
