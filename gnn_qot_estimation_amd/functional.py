@@ -372,8 +372,12 @@ class TConvFn(torch.autograd.Function):
         N = graph.num_nodes
         dev = qkvs.device
         rowmap, colf, colf_t = (maps[0], maps[1], maps[2]) if maps is not None else (None, graph.col, None)
+        # edge_attr.grad only when asked for (never in the training step): an extra launch next to whichever form runs
+        gea = tconv_edge_attr_grad(g, y, ctx.act, act_step, qkvs, edge_attr, w_edge, graph, maps) \
+            if ctx.needs_input_grad[1] else None
         if ctx.scores is not None and tconv_rows_ok(qkvs, maps, H, D):
-            return _tconv_backward_rows(ctx, g, qkvs, edge_attr, w_edge, stats, y, act_step)
+            res = _tconv_backward_rows(ctx, g, qkvs, edge_attr, w_edge, stats, y, act_step)
+            return (res[0], gea) + res[2:]
         escr = torch.empty(max(graph.cap, 1), 2, dtype=torch.float32, device=dev)
         delta = torch.empty(N, dtype=torch.float32, device=dev)
         pds = torch.empty(N, D, dtype=torch.float32, device=dev)
@@ -440,7 +444,25 @@ class TConvFn(torch.autograd.Function):
                 if LG.enabled():
                     LG.flush()                                 # (rare: the concatenation below reads the row sum)
                 gq = torch.cat([gq, gq.new_zeros(qkvs.shape[0] - n, H4)], 0)
-        return gq, None, gwe_flat.view(H, D), None, None, None
+        return gq, gea, gwe_flat.view(H, D), None, None, None
+
+
+def tconv_edge_attr_grad(g, y, act, act_step, qkvs, edge_attr, w_edge, graph: GraphIndex, maps):
+    """``edge_attr.grad`` of TransformerConv (``csrc/edge_grad.hip``): one launch that recomputes the softmax from the
+    packed rows ``qkvs`` (node rows, or table rows through ``maps``), independent of the form the forward and the parameter
+    backward took.  ``g`` is the gradient wrt the conv's (activated, when ``act``) output; ``[E, D]`` in edge order."""
+    H = qkvs.shape[1] // 4
+    E, D = edge_attr.shape
+    gea = torch.empty(E, D, dtype=torch.float32, device=g.device)
+    if act is not None:
+        slope, p, seed = act
+        act_args = (y, float(slope), float(p if act_step is not None else 0.0), int(seed), act_step)
+    else:
+        act_args = (None, 0.0, 0.0, 0, None)
+    rowmap, col = (maps[0], maps[1]) if maps is not None else (None, graph.col)
+    _lib.call("qot_tconv_edge_attr_grad", g, *act_args, qkvs, qkvs.shape[1], rowmap, col, graph.rowptr, graph.eid,
+              edge_attr, w_edge, gea, graph.num_nodes, H, D)
+    return gea
 
 
 def tconv_rows_ok(qkvs: torch.Tensor, maps, H: int, D: int) -> bool:
@@ -602,17 +624,21 @@ class TConvGraphFn(torch.autograd.Function):
         _lib.call("qot_tconv_fwd_graph", t4, 4 * H, M, Pm, w_edge_c, edge_attr, graph.rowptr, maps[1], graph.eid, graph.row,
                   out, alpha, ea_csr, aa, n, B, max_e, H, D, *_act_args(act))
         ctx.save_for_backward(table, wq, wk, wv, ws, w_edge_c, t4, alpha, ea_csr, aa, out if act is not None else None,
-                              act[3] if act is not None else None)
+                              act[3] if act is not None else None, edge_attr if ctx.needs_input_grad[10] else None)
         ctx.graph, ctx.maps, ctx.plan = graph, maps, plan
         ctx.act = None if act is None else (act[0], act[1], act[2])
         return out
 
     @staticmethod
     def backward(ctx, g):
-        table, wq, wk, wv, ws, w_edge, t4, alpha, ea_csr, aa, y, act_step = ctx.saved_tensors
+        table, wq, wk, wv, ws, w_edge, t4, alpha, ea_csr, aa, y, act_step, edge_attr = ctx.saved_tensors
         graph, maps = ctx.graph, ctx.maps
         n, B, max_e = ctx.plan
         g = _f32c(g)
+        # edge_attr.grad only when asked for: recomputed from the projected table t4 and enqueued here, before the epilogue
+        # below and before autograd adds the per-layer edge gradients
+        gea = tconv_edge_attr_grad(g, y, ctx.act, act_step, t4, edge_attr, w_edge, graph, maps) \
+            if ctx.needs_input_grad[10] else None
         V, H = table.shape
         D = w_edge.shape[1]
         dev = g.device
@@ -648,7 +674,7 @@ class TConvGraphFn(torch.autograd.Function):
             _lib.call("qot_table_project_bwd_scores", S, t4, w_edge, tab, wq_, wk_, wv_, ws_, gt, gw, gb, gwe, V, n, H, D)
         gw2 = gw.view(4 * H, H)
         return (gt.view(V, H), gw2[:H], gb[:H], gw2[H:2 * H], gb[H:2 * H], gw2[2 * H:3 * H], gb[2 * H:3 * H], gw2[3 * H:],
-                gb[3 * H:], gwe, None, None, None, None, None, None)
+                gb[3 * H:], gwe, gea, None, None, None, None, None)
 
 
 # ------------------------------------------------------------------ NNConv (a4)
@@ -801,6 +827,19 @@ def nnconv_pack_operands_gen(w2, b2, wroot, h: int, k: int):
     return packed[:n_f], packed[n_f:n_f + n_a], packed[n_f + n_a:]
 
 
+def nnconv_edge_attr_grad(GA, x, edge_attr, w1, b1, graph: GraphIndex):
+    """``edge_attr.grad`` of NNConv (mean) from ``GA = g Wk^T`` ``[N, K*H]`` (``csrc/edge_grad.hip``): the per-edge
+    ``dh_e = invdeg_i GA_i x_j`` that the grad-h kernels reduce into ``gw1`` / ``gb1``, through the edge MLP's ReLU and
+    first layer, one owner per edge.  ``[E, D]`` in edge order."""
+    N, hin = x.shape
+    E, D = edge_attr.shape
+    GA = GA.contiguous()
+    gea = torch.empty(E, D, dtype=torch.float32, device=x.device)
+    _lib.call("qot_nnconv_edge_attr_grad", GA, GA.shape[1], x, hin, edge_attr, w1, b1, graph.rowptr, graph.col, graph.eid,
+              graph.invdeg, gea, N, hin, D)
+    return gea
+
+
 class NNConvFn(torch.autograd.Function):
     """NNConv(aggr='mean') = aggregate-then-GEMM (see ``csrc/nnconv.hip``)."""
 
@@ -891,7 +930,8 @@ class NNConvFn(torch.autograd.Function):
         gb1 = torch.zeros(K, dtype=torch.float32, device=dev)
         _lib.call("qot_nnconv_bwd_edge", P(GA), K * hin, P(x), hin, P(edge_attr), P(w1), P(b1),
                   P(graph.rowptr), P(graph.col), P(graph.eid), P(graph.invdeg), P(gw1), P(gb1), N, hin, D)
-        return gx, None, gw1, gb1, gw2, gb2, gwroot, gbias, None, None, None, None
+        gea = nnconv_edge_attr_grad(GA, x, edge_attr, w1, b1, graph) if ctx.needs_input_grad[1] else None
+        return gx, gea, gw1, gb1, gw2, gb2, gwroot, gbias, None, None, None, None
 
     @staticmethod
     def backward(ctx, g):
@@ -919,6 +959,11 @@ class NNConvFn(torch.autograd.Function):
         K, D = w1.shape
         dev = x.device
         hh = hin * hout
+        gea = None
+        if ctx.needs_input_grad[1]:
+            # edge_attr.grad only when asked for (never in the training step): GA = g Wk^T materialised, then one launch
+            wk = w2.view(hin, hout, K).permute(2, 0, 1).reshape(K * hin, hout)
+            gea = nnconv_edge_attr_grad(g @ wk.t(), x, edge_attr, w1, b1, graph)
         # (flat buffers the epilogue queue may keep alive; autograd gets views of them)
         gw1f = torch.empty(K * D, dtype=torch.float32, device=dev)
         gb1f = torch.empty(K, dtype=torch.float32, device=dev)
@@ -966,7 +1011,7 @@ class NNConvFn(torch.autograd.Function):
             _lib.call("qot_nnconv_gradh_fused", *gradh_args, P(gw1), P(gb1), P(wsh), N, hin, D)
         # already in the parameters' own layouts (no permute / copy kernels)
         gw2, gb2, gwroot = gpar[:hh * K].view(hh, K), gpar[hh * K:hh * (K + 1)], gpar[hh * (K + 1):].view(hout, hin)
-        return gx, None, gw1, gb1, gw2, gb2, gwroot, gbias, None, None, None, None
+        return gx, gea, gw1, gb1, gw2, gb2, gwroot, gbias, None, None, None, None
 
 
 # ------------------------------------------------------------------ leaky_relu + dropout (a3)

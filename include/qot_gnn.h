@@ -49,7 +49,7 @@ extern "C" {
 
 typedef void* qot_stream_t; /* hipStream_t */
 
-#define QOT_ABI_VERSION 10
+#define QOT_ABI_VERSION 11
 #define QOT_OK 0
 #define QOT_ERR_UNSUPPORTED (-1) /* width / edge_dim not instantiated */
 #define QOT_ERR_BADARG (-2)      /* null pointer, negative size, workspace too small */
@@ -345,6 +345,26 @@ int qot_nnconv_bwd_edge(const float* GA, int ld_ga, const float* x, int ld_x,
                         const int32_t* rowptr, const int32_t* col, const int32_t* eid,
                         const float* invdeg, float* gw1, float* gb1, int64_t N, int H, int D,
                         qot_stream_t stream);
+
+/* ---- gradients wrt the edge features (csrc/edge_grad.hip) --------------------------
+ * edge_attr.grad of the two convolutions; the training step never asks for it.  Both kernels run in addition to the
+ * parameter backward of whichever form the forward took, recompute what they need, and write grad_edge_attr [E,D] in the
+ * caller's edge order (slot p -> row eid[p]) with plain stores: one owner per edge, bitwise reproducible, every row
+ * written (no zero fill needed).  H in {16, 32, 64, 128, 256}, D in {1..8}.
+ * TransformerConv: grad_out [N,H], y_act / act_* as qot_tconv_bwd_dst (the fused activation is undone when y_act != NULL);
+ * qkvs = the packed [q|k|v|skip] rows (ld floats per row): node rows, or table rows through rowmap (node -> table row,
+ * NULL in node mode) with col = the table row of each slot's source (colf in table mode, the CSR col in node mode).
+ *     grad ea_e = ds_e u_i + alpha_e w_i,   u_i = W_e^T q_i / sqrt(H),   w_i = W_e^T g_i,   ds_e = alpha_e (da_e - delta_i)
+ * NNConv (mean): GA [N, 2D*H] = g @ Wk^T (ld_ga, as qot_nnconv_bwd_edge), x = the forward input rows, CSR by destination.
+ *     grad ea_e = W1^T ((W1 ea_e + b1 > 0) * invdeg_i GA_i x_j)                                                        */
+int qot_tconv_edge_attr_grad(const float* grad_out, const float* y_act, float act_slope, float act_p, uint64_t act_seed,
+                             const int64_t* act_step, const float* qkvs, int ld, const int32_t* rowmap, const int32_t* col,
+                             const int32_t* rowptr, const int32_t* eid, const float* edge_attr, const float* w_edge,
+                             float* grad_edge_attr, int64_t N, int H, int D, qot_stream_t stream);
+int qot_nnconv_edge_attr_grad(const float* GA, int ld_ga, const float* x, int ld_x, const float* edge_attr,
+                              const float* w1, const float* b1, const int32_t* rowptr, const int32_t* col,
+                              const int32_t* eid, const float* invdeg, float* grad_edge_attr, int64_t N, int H, int D,
+                              qot_stream_t stream);
 
 /* ---- activation: y = dropout(leaky_relu(x, slope), p) ------------------------------
  * Counter-based RNG: keep = hash(seed, *step_counter, element) >= p.  step_counter is a
