@@ -3,6 +3,7 @@
 // the adjoint kernel 2.6 us and spills the forward one (r03; tools/experiments/r03_sched_bench.sh).
 #include "common.hpp"
 #include "mfma_tile.hpp"
+#include "split_bf16.hpp"
 
 namespace qot {
 
@@ -27,12 +28,15 @@ constexpr int kGhCap = 256;   // edges of a tile staged in LDS by the grad-h ker
 
 // VARIANT (diagnostic build only): 0 production; 2 no dot phase; 3 no GA MFMA phase; 5 GA phase with the weight fragments
 // of block 0 reused (no L2 stream)
-template <int D, int VARIANT = 0>
+// SPLIT: the GA products on the bf16 matrix pipe (split_bf16.hpp): the g tile's fragments split after each read, Bs = Wk^T
+// pre-split into three bf16 planes, each [nb][16-deep step][lane], bs_planes u32x4 apart.
+template <int D, int VARIANT = 0, bool SPLIT = false>
 __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
     const float* __restrict__ g, int ldg, const float* __restrict__ x, int ldx, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const int32_t* __restrict__ eidx, const float* __restrict__ invdeg,
-    const float* __restrict__ Bp, float* __restrict__ partials, int64_t N) {
+    const float* __restrict__ Bp, float* __restrict__ partials, int64_t N, const u32x4* __restrict__ Bs = nullptr,
+    int64_t bs_planes = 0) {
     constexpr int K = 2 * D;
     static_assert(K <= 8, "one k per lane of the 8-lane group");
     constexpr int NB = K * 2;               // 32-column blocks of GA (K*64/32)
@@ -112,8 +116,16 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
         const int64_t tend = (tile0 + 32 < N) ? tile0 + 32 : N;
         // Weight fragments of this wave's first GA block are requested before anything else of the tile, those of block
         // t + 1 before the MFMAs of block t (two buffers).
-        float4 bf[2][8];
-        {
+        // split form: the wave's NBW * 4 steps (16 deep each) as one sequence, fragments requested SL steps ahead into a
+        // ring of SL + 1 (48 VGPRs; two whole split blocks in flight, as the fp32 form keeps, spilled)
+        constexpr int SL = 3;            // SL + 1 = 4 steps per block: ring slots are compile-time in a rolled block loop
+        float4 bf[2][8];                    // (dead in the split form, bsp in the fp32 one)
+        Bf3 bsp[SL + 1];
+        const u32x4* bsw = Bs + (int64_t)(wave * NBW) * 4 * 64 + lane;
+        if constexpr (SPLIT) {
+#pragma unroll
+            for (int s = 0; s < SL; ++s) bsp[s] = load_split_b(bsw + s * 64, bs_planes);
+        } else {
             const float4* bp = reinterpret_cast<const float4*>(Bp) + (int64_t)(wave * NBW) * 8 * 64 + lane;
 #pragma unroll
             for (int gq = 0; gq < 8; ++gq) bf[0][gq] = bp[gq * 64];
@@ -158,7 +170,29 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
             }
         }
         // 2. GA tile on the matrix cores
-        if (VARIANT != 3) {
+        if (SPLIT) {
+            // A fragments split after their ds_read_b128, once per block: a split copy of the g tile in LDS (12 KB instead
+            // of 8) leaves no room for two workgroups per CU, split fragments held across the blocks (48 VGPRs) spill.
+            // The block loop is rolled: unrolled, the blocks' MFMA chains were interleaved (four accumulators live).
+#pragma unroll 1
+            for (int t = 0; t < NBW; ++t) {
+                const int nb = wave * NBW + t;
+                f32x16 c;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) c[r] = 0.f;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int q = 4 * t + s;                  // step of the wave's sequence (blocks are contiguous in Bs)
+                    if (q + SL < 4 * NBW) bsp[(s + SL) % (SL + 1)] = load_split_b(bsw + (q + SL) * 64, bs_planes);
+                    c = mfma_split_step(Gt4, 2 * s, hi, r31, bsp[s], c);
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    GAt[row * LDGA + nb * 32 + r31] = c[r];
+                }
+            }
+        } else if (VARIANT != 3) {
             float4 af[8];
 #pragma unroll
             for (int gq = 0; gq < 8; ++gq) af[gq] = Gt4[at4_slot(gq, hi, r31)];
@@ -254,7 +288,8 @@ using namespace qot;
 // launch of nnconv_gradh64_kernel (qot_nnconv_gradh_fused, nnconv_mfma.hip); variant: diagnostic builds only
 int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, int ld_x, const float* edge_attr, const float* w1,
                               const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* invdeg,
-                              const float* b_perm, float* workspace, int64_t N, int D, int grid, int variant, hipStream_t stream) {
+                              const float* b_perm, const void* b_split, int64_t split_stride, float* workspace, int64_t N, int D,
+                              int grid, int variant, hipStream_t stream) {
 #ifdef QOT_DIAG
     if (variant >= 1 && variant <= 5 && D == 4) {
 #define QOT_GH_V(V) nnconv_gradh64_kernel<4, V><<<grid, 256, 0, stream>>>(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, \
@@ -272,6 +307,16 @@ int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, i
     }
 #endif
     (void)variant;
+    if (b_split) {
+        QOT_DISPATCH_D(D, {
+            if (kD <= 4)
+                nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), 0, true><<<grid, 256, 0, stream>>>(
+                    grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
+                    static_cast<const u32x4*>(b_split), split_stride / 8);
+        });
+        QOT_LAUNCH_CHECK();
+        return QOT_OK;
+    }
     QOT_DISPATCH_D(D, {
         if (kD <= 4)
             nnconv_gradh64_kernel<(kD <= 4 ? kD : 4)><<<grid, 256, 0, stream>>>(

@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "mfma_tile.hpp"
 #include "nnconv_finalize_dev.hpp"
+#include "split_bf16.hpp"
 
 namespace qot {
 
@@ -157,12 +158,16 @@ __device__ __forceinline__ void nnconv_gather_tile(
 #define QOT_STAMP(slot)
 #endif
 
-template <int D, bool TRANSPOSE, int VARIANT = 0>
+// SPLIT (forward only): the products on the bf16 matrix pipe (split_bf16.hpp).  Ws: Wcat pre-split into three bf16
+// planes ws_planes u32x4 apart (qot_nnconv_fused_split); the A fragments are split after their ds_read_b128, i.e. by both column-half waves.
+template <int D, bool TRANSPOSE, int VARIANT = 0, bool SPLIT = false>
 __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     const float* __restrict__ x, int ldx, const float* __restrict__ ea, const float* __restrict__ w1,
     const float* __restrict__ b1, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const int32_t* __restrict__ eidx, const float* __restrict__ invdeg, const float* __restrict__ Wp,
-    const float* __restrict__ bias, float* __restrict__ out, int64_t N, ActParams act) {
+    const float* __restrict__ bias, float* __restrict__ out, int64_t N, ActParams act,
+    const u32x4* __restrict__ Ws = nullptr, int64_t ws_planes = 0) {
+    static_assert(!SPLIT || (!TRANSPOSE && VARIANT == 0), "split form: production forward only");
     constexpr int K = 2 * D;
     constexpr int KM = (K + 1) * 64;        // inner dimension held in LDS (blocks 0..K)
     constexpr int GM = KM / 16;             // float4 B groups per wave for the main part
@@ -198,6 +203,63 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nh = wave & 1, kh = wave >> 1;
     const int r31 = lane & 31, hi = lane >> 5;
+    f32x16 c;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) c[r] = 0.f;
+    if constexpr (SPLIT) {
+        // Ws: 3 planes of ws_planes u32x4, each [nh][16-deep step s][lane]; step s = fp32 groups 2s, 2s + 1 (split_bf16.hpp).  The
+        // native loop's structure: root fragments and NB - 1 chunks requested before the barrier, compile-time buffers.
+        constexpr int ST = (K + 2) * 64 / 16;      // steps per column half
+        constexpr int SM = GM / 2;                 // main steps per wave
+        constexpr int SC = 2;                      // steps per chunk
+        constexpr int NCS = SM / SC;
+        constexpr int NBS = 3;                     // buffers: 2 chunks (24 MFMAs) of lookahead
+        static_assert(GM % 4 == 0, "chunking");
+        const u32x4* wsn = Ws + (int64_t)nh * ST * 64 + lane;
+        const u32x4* wsp = wsn + (int64_t)kh * SM * 64;
+        const u32x4* rsp = wsn + (int64_t)(2 * SM + 2 * kh) * 64;
+        asm volatile("" : "+v"(rsp));
+        Bf3 rbs[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) rbs[u] = load_split_b(rsp + u * 64, ws_planes);
+        Bf3 sb[NBS][SC];
+#pragma unroll
+        for (int q = 0; q < NBS - 1; ++q)
+#pragma unroll
+            for (int u = 0; u < SC; ++u) sb[q][u] = load_split_b(wsp + (q * SC + u) * 64, ws_planes);
+        lds_barrier();
+        int ch = 0;
+#pragma unroll 1
+        for (; ch + NBS <= NCS; ch += NBS) {
+#pragma unroll
+            for (int q = 0; q < NBS; ++q) {
+                if (ch + q + NBS - 1 < NCS) {
+#pragma unroll
+                    for (int u = 0; u < SC; ++u)
+                        sb[(q + NBS - 1) % NBS][u] = load_split_b(wsp + ((ch + q + NBS - 1) * SC + u) * 64, ws_planes);
+                }
+#pragma unroll
+                for (int u = 0; u < SC; ++u) c = mfma_split_step(At4, kh * GM + 2 * ((ch + q) * SC + u), hi, r31, sb[q][u], c);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NBS - 1; ++q) {
+            if (ch + q < NCS) {
+#pragma unroll
+                for (int u = 0; u < SC; ++u) c = mfma_split_step(At4, kh * GM + 2 * ((ch + q) * SC + u), hi, r31, sb[q][u], c);
+            }
+        }
+        lds_barrier();                         // everyone is done with blocks 0..K
+        {   // root block (x_i itself) reuses block 0's slots
+            float4* At4w = reinterpret_cast<float4*>(At);
+            const int sub = threadIdx.x & 7, il = threadIdx.x >> 3;
+            At4w[at4_slot(sub, 0, il)] = make_float4(root0.x, root0.z, root1.x, root1.z);
+            At4w[at4_slot(sub, 1, il)] = make_float4(root0.y, root0.w, root1.y, root1.w);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; ++u) c = mfma_split_step(At4, kh * 4 + 2 * u, hi, r31, rbs[u], c);
+    } else {
     // Wp: [nh][group g of 4 k-steps][lane][4]; wave (nh, kh) owns main groups kh*GM.. and
     // root groups (2*GM + kh*4)..
     const float4* wpn = reinterpret_cast<const float4*>(Wp) + (int64_t)nh * (2 * GM + 8) * 64 + lane;
@@ -232,9 +294,6 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
         continue;
     }
 
-    f32x16 c;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) c[r] = 0.f;
     int ch = 0;
     // (r04, measured: the A fragment of group L + 1 read from LDS before the four MFMAs of group L instead of right in front
     //  of its use -- `ds_read_b128; s_waitcnt lgkmcnt(0)` before every group as it stands -- 96.0 -> 96.9 us: no gain, not kept)
@@ -280,6 +339,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 4; ++u) c = mfma_group(At4, kh * 4 + u, hi, r31, rb[u], c);
+    }
     QOT_STAMP(4)
     // K halves meet through LDS; every wave finishes 8 of the 16 accumulator registers of its
     // (column half), so the stores are spread over all four waves
@@ -808,26 +868,57 @@ extern "C" int qot_nnconv_fused(const float* x, int ld_x, const float* edge_attr
     return QOT_OK;
 }
 
+// The forward at H = 64 with the products on the bf16 matrix pipe: w_split = Wcat in three bf16 planes (split_bf16.hpp;
+// functional.nnconv_split_index), everything else as qot_nnconv_fused(transpose = 0).
+extern "C" int qot_nnconv_fused_split(const float* x, int ld_x, const float* edge_attr, const float* w1,
+                                      const float* b1, const int32_t* rowptr, const int32_t* col,
+                                      const int32_t* edge_ids, const float* invdeg, const void* w_split,
+                                      int64_t split_stride, const float* bias, float* out, int64_t N, int H, int D,
+                                      int act, float act_slope, float act_p, uint64_t act_seed,
+                                      const int64_t* act_step, qot_stream_t stream) {
+    if (N < 0 || !rowptr) return QOT_ERR_BADARG;
+    if (H != 64 || D > 4) return QOT_ERR_UNSUPPORTED;
+    if (N == 0) return QOT_OK;
+    if (!x || !w1 || !b1 || !invdeg || !w_split || !out || (ld_x & 3) || ((uintptr_t)w_split & 15) || (split_stride & 7) ||
+        split_stride < (int64_t)(2 * D + 2) * 4096)   // a plane holds Wcat: (K+2)*64*64
+        return QOT_ERR_BADARG;
+    int grid = grid_for(N, 32);
+    if (grid > 2 * num_cus()) grid = 2 * num_cus();
+    const ActParams ap = make_act(act, act_slope, act_p, act_seed, act_step);
+    QOT_DISPATCH_D(D, {
+        if (kD <= 4)
+            nnconv_mfma64_kernel<(kD <= 4 ? kD : 4), false, 0, true><<<grid, 256, 0, (hipStream_t)stream>>>(
+                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, nullptr, bias, out, N, ap,
+                static_cast<const u32x4*>(w_split), split_stride / 8);
+    });
+    QOT_LAUNCH_CHECK();
+    return QOT_OK;
+}
+
 // Bp layout: for 32-column block nb of GA (column n = k*64 + a), group gq of 4 k-steps over o,
 // lane l, r:  Bp[((nb*8 + gq)*64 + l)*4 + r] = W2[a*64 + o, k]  with o = 8*gq + 2*r + (l>>5),
 // n = nb*32 + (l&31)  (built by functional.nnconv_gradh_perm_index).
 int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, int ld_x, const float* edge_attr, const float* w1,
                               const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* invdeg,
-                              const float* b_perm, float* workspace, int64_t N, int D, int grid, int variant, hipStream_t stream);
+                              const float* b_perm, const void* b_split, int64_t split_stride, float* workspace, int64_t N, int D,
+                              int grid, int variant, hipStream_t stream);
 extern "C" size_t qot_nnconv_gradh_workspace_floats(int D) {
     return (size_t)2 * 256 * 2 * (size_t)(2 * D * (D + 1));
 }
 
-extern "C" int qot_nnconv_gradh_fused(const float* grad_out, int ld_g, const float* x, int ld_x,
-                                      const float* edge_attr, const float* w1, const float* b1,
-                                      const int32_t* rowptr, const int32_t* col, const int32_t* eid,
-                                      const float* invdeg, const float* b_perm, float* gw1, float* gb1,
-                                      float* workspace, int64_t N, int H, int D, qot_stream_t stream_) {
+static int nnconv_gradh_impl(const float* grad_out, int ld_g, const float* x, int ld_x,
+                             const float* edge_attr, const float* w1, const float* b1,
+                             const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                             const float* invdeg, const float* b_perm, const void* b_split, int64_t split_stride,
+                             float* gw1, float* gb1,
+                             float* workspace, int64_t N, int H, int D, qot_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (N < 0 || !rowptr) return QOT_ERR_BADARG;
     if ((H != 16 && H != 32 && H != 64 && H != 128 && H != 256) || D > 4) return QOT_ERR_UNSUPPORTED;
-    if (!grad_out || !x || !w1 || !b1 || !invdeg || !b_perm || (!gw1 != !gb1) || !workspace || (ld_g & 3) || (ld_x & 3))
+    if (!grad_out || !x || !w1 || !b1 || !invdeg || !(b_perm || b_split) || (!gw1 != !gb1) || !workspace || (ld_g & 3) ||
+        (ld_x & 3) || ((uintptr_t)b_split & 15) || (b_split && ((split_stride & 7) || split_stride < (int64_t)2 * D * 64 * 64)))
         return QOT_ERR_BADARG;
+    if (b_split && H != 64) return QOT_ERR_UNSUPPORTED;
     if (!gw1 && H != 64) return QOT_ERR_UNSUPPORTED;
 #ifdef QOT_DIAG
     if (H == 64 && g_variant == 9)       // A/B: the generic kernel at H = 64 (b_perm in ITS layout)
@@ -846,7 +937,7 @@ extern "C" int qot_nnconv_gradh_fused(const float* grad_out, int ld_g, const flo
 #endif
     {
         const int rc = qot_nnconv_gradh64_launch(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm,
-                                                 workspace, N, D, grid, variant, stream);
+                                                 b_split, split_stride, workspace, N, D, grid, variant, stream);
         if (rc != QOT_OK) return rc;
     }
     QOT_LAUNCH_CHECK();
@@ -855,6 +946,28 @@ extern "C" int qot_nnconv_gradh_fused(const float* grad_out, int ld_g, const flo
     gradh_partial_sum_kernel<<<grid_for(n, 4), 256, 0, stream>>>(workspace, grid, n, K * D, gw1, gb1);
     QOT_LAUNCH_CHECK();
     return QOT_OK;
+}
+
+extern "C" int qot_nnconv_gradh_fused(const float* grad_out, int ld_g, const float* x, int ld_x,
+                                      const float* edge_attr, const float* w1, const float* b1,
+                                      const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                                      const float* invdeg, const float* b_perm, float* gw1, float* gb1,
+                                      float* workspace, int64_t N, int H, int D, qot_stream_t stream) {
+    return nnconv_gradh_impl(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm, nullptr, 0, gw1, gb1,
+                             workspace, N, H, D, stream);
+}
+
+// As qot_nnconv_gradh_fused at H = 64 with the GA products on the bf16 matrix pipe: b_split = Wk^T in three bf16 planes
+// (split_bf16.hpp; functional.nnconv_split_index).
+extern "C" int qot_nnconv_gradh_split(const float* grad_out, int ld_g, const float* x, int ld_x,
+                                      const float* edge_attr, const float* w1, const float* b1,
+                                      const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                                      const float* invdeg, const void* b_split, int64_t split_stride, float* gw1, float* gb1,
+                                      float* workspace, int64_t N, int H, int D, qot_stream_t stream) {
+    if (!b_split) return QOT_ERR_BADARG;
+    return nnconv_gradh_impl(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, b_split, split_stride,
+                             gw1, gb1,
+                             workspace, N, H, D, stream);
 }
 
 // Both second-stage sums of the H = 64 NNConv backward in one launch: after qot_nnconv_adjoint_dw(param_layout = 2:

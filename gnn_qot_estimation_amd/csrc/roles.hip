@@ -81,7 +81,8 @@ __global__ __launch_bounds__(256) void roles_kernel(const RoleTable t_by_value) 
     }
     case QOT_ROLE_GATHER3:
         gather3_body(rp<const float>(ro, 0), (int)ro.i[0], rp<const float>(ro, 1), (int)ro.i[1], rp<const float>(ro, 2),
-                     rp<const int32_t>(ro, 3), rp<float>(ro, 4), ro.i[2], (int64_t)vb);
+                     rp<const int32_t>(ro, 3), rp<float>(ro, 4), ro.i[2], (int64_t)vb, rp<const int32_t>(ro, 5),
+                     rp<uint16_t>(ro, 6), ro.i[3]);
         break;
     case QOT_ROLE_SUM_ROWS:
         sum_rows_body(rp<const float>(ro, 0), rp<float>(ro, 1), ro.i[0], ro.i[1], ro.i[2], (int)ro.i[3], vb,
@@ -174,10 +175,11 @@ static int plan_role(qot_role_t& r, int64_t* blocks, size_t* lds) {
         return QOT_OK;
     }
     case QOT_ROLE_GATHER3: {
-        const int64_t n0 = i[0], n1 = i[1], n = i[2];
-        if (n <= 0 || n0 < 0 || n1 < 0 || n0 + n1 > 0x7fffffff) return QOT_ERR_BADARG;
+        const int64_t n0 = i[0], n1 = i[1], n = i[2], m = i[3];
+        if (n <= 0 || n0 < 0 || n1 < 0 || m < 0 || n0 + n1 > 0x7fffffff) return QOT_ERR_BADARG;
         for (int k = 0; k < 5; ++k) if (!p[k]) return QOT_ERR_BADARG;
-        *blocks = (n + 255) / 256;
+        if (m > 0 && (!p[5] || !p[6])) return QOT_ERR_BADARG;
+        *blocks = (n + m + 255) / 256;
         return QOT_OK;
     }
     case QOT_ROLE_SUM_ROWS: {

@@ -1,6 +1,7 @@
 // Device bodies of the step's small dense pieces, shared by the multi-role launch (roles.hip).
 #pragma once
 #include "common.hpp"
+#include "split_bf16.hpp"
 
 namespace qot {
 
@@ -206,13 +207,25 @@ __device__ __forceinline__ void table_project_bwd_body(const float* __restrict__
 }
 
 // ---- out[i] = concat(s0[0:n0], s1[0:n1], s2)[idx[i]] (0 where idx[i] < 0) ------------------------------------------
+// and, for m > 0, the same gather through idx2[0:m] split into three bf16 planes (split_bf16.hpp):
+// out2[t], out2[m + t], out2[2m + t] = hi, mid, lo of concat(...)[idx2[t]]
 __device__ __forceinline__ void gather3_body(const float* __restrict__ s0, int n0, const float* __restrict__ s1, int n1,
                                              const float* __restrict__ s2, const int32_t* __restrict__ idx,
-                                             float* __restrict__ out, int64_t n, int64_t vb) {
+                                             float* __restrict__ out, int64_t n, int64_t vb,
+                                             const int32_t* __restrict__ idx2 = nullptr,
+                                             uint16_t* __restrict__ out2 = nullptr, int64_t m = 0) {
     const int64_t i = vb * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int v = idx[i];          // v < 0: a padding slot (zero)
-    out[i] = v < 0 ? 0.f : (v < n0 ? s0[v] : (v < n0 + n1 ? s1[v - n0] : s2[v - n0 - n1]));
+    if (i >= n + m) return;
+    const bool sp = i >= n;
+    const int v = sp ? idx2[i - n] : idx[i];          // v < 0: a padding slot (zero)
+    const float val = v < 0 ? 0.f : (v < n0 ? s0[v] : (v < n0 + n1 ? s1[v - n0] : s2[v - n0 - n1]));
+    if (!sp) {
+        out[i] = val;
+    } else {
+        uint16_t h, md, l;
+        split3(val, h, md, l);
+        out2[i - n] = h; out2[m + i - n] = md; out2[2 * m + i - n] = l;
+    }
 }
 
 }  // namespace qot

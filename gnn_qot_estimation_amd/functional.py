@@ -769,16 +769,43 @@ def nnconv_pack_operands(w2, b2, wroot, k: int):
     return packed[:n_f], packed[n_f:n_f + n_a], packed[n_f + n_a:]
 
 
+def nnconv_split_bf16() -> bool:
+    """The H = 64 forward and grad-h kernels issue their fp32 products as split-bf16 MFMAs (csrc/split_bf16.hpp) unless
+    ``QOT_NNCONV_F32_MFMA=1``, which selects the fp32-MFMA kernels."""
+    return os.environ.get("QOT_NNCONV_F32_MFMA", "0") != "1"
+
+
+def nnconv_split_index(k: int, device) -> torch.Tensor:
+    """Gather index (into the same flat parameter triple as ``nnconv_fused_indices``) of Wcat (forward) and Wk^T (grad-h)
+    in the B-fragment order of the 32x32x16 bf16 MFMA: step s of 16 k, lane l, element j = 4 q + r takes what the fp32
+    layouts put at group 2 s + q, lane l, component r (csrc/split_bf16.hpp).  Split into bf16 planes by the gather role."""
+    key = ("splitidx", k, str(device))
+    if key not in _PERM_CACHE:
+        allidx, n_f, n_a, n_g = nnconv_fused_indices(k, "cpu")
+        fwd = allidx[:n_f].view(2, -1, 2, 64, 4).permute(0, 1, 3, 2, 4)        # [nh][g][l][r] -> [nh][s][l][q][r]
+        gh = allidx[n_f + n_a:].view(2 * k, 4, 2, 64, 4).permute(0, 1, 3, 2, 4)   # [nb][gq][l][r] -> [nb][s][l][q][r]
+        _PERM_CACHE[key] = torch.cat([fwd.reshape(-1), gh.reshape(-1)]).contiguous().to(device)
+    return _PERM_CACHE[key]
+
+
 def nnconv_pack(w2, b2, wroot, h: int, k: int, group=None):
-    """(Wcat, WcatT, Wk^T) in the fragment orders of the width's kernels.  ``group`` (a ``LaunchGroup``): the gather
-    joins the caller's multi-role launch; the operands are valid after ``group.run()``."""
+    """(Wcat, WcatT, Wk^T, split) in the fragment orders of the width's kernels; ``split`` (H = 64 unless
+    ``QOT_NNCONV_F32_MFMA=1``, else None): the bf16 planes of Wcat and Wk^T for the split-bf16 kernels, written by the
+    same gather.  ``group`` (a ``LaunchGroup``): the gather joins the caller's multi-role launch; the operands are valid
+    after ``group.run()``."""
     allidx, n_f, n_a, n_g = nnconv_fused_indices(k, w2.device) if h == 64 else nnconv_gen_indices(h, k, w2.device)
     packed = torch.empty(allidx.numel(), dtype=torch.float32, device=w2.device)
+    ptrs, ints = [w2, b2, wroot, allidx, packed], [w2.numel(), b2.numel(), allidx.numel()]
+    split = None
+    if h == 64 and nnconv_split_bf16():
+        sidx = nnconv_split_index(k, w2.device)
+        split = torch.empty(3 * sidx.numel(), dtype=torch.int16, device=w2.device)     # bf16 bit patterns
+        ptrs, ints = ptrs + [sidx, split], ints + [sidx.numel()]
     if group is not None:
-        group.add(_lib.ROLE_GATHER3, (w2, b2, wroot, allidx, packed), (w2.numel(), b2.numel(), allidx.numel()))
+        group.add(_lib.ROLE_GATHER3, tuple(ptrs), tuple(ints))
     else:
-        _lib.call("qot_gather3", P(w2), w2.numel(), P(b2), b2.numel(), P(wroot), P(allidx), P(packed), allidx.numel())
-    return packed[:n_f], packed[n_f:n_f + n_a], packed[n_f + n_a:]
+        _lib.run_roles([_lib.make_role(_lib.ROLE_GATHER3, ptrs, ints)])
+    return packed[:n_f], packed[n_f:n_f + n_a], packed[n_f + n_a:], split
 
 
 GEN_WIDTHS = (16, 32, 128, 256)       # csrc/nnconv_gen.hip; 64 has its own tuned kernels (csrc/nnconv_mfma.hip)
@@ -875,12 +902,18 @@ class NNConvFn(torch.autograd.Function):
             return NNConvFn._forward_wide_edge(ctx, x, edge_attr, w1, b1, w2, b2, wroot, bias, graph, act, side)
         # (Wcat, WcatT, Wk^T) in MFMA fragment order; every width runs gather -> LDS tile -> fp32 MFMA, the operand
         # [N, (K+2)H] never exists in HBM
-        wp, wp_adj, bp = packed if packed is not None else nnconv_pack(w2, b2, wroot, hin, K)
+        wp, wp_adj, bp, split = packed if packed is not None else nnconv_pack(w2, b2, wroot, hin, K)
         out = torch.empty(N, hout, dtype=torch.float32, device=x.device)
-        _lib.call("qot_nnconv_fused", P(x), hin, P(edge_attr), P(w1), P(b1), P(graph.rowptr), P(graph.col),
-                  P(graph.eid), P(graph.invdeg), 0, P(wp), P(bias), P(out), N, hin, D, *_act_args(act))
+        if split is not None:           # H = 64: the products as split-bf16 MFMAs (the planes of Wcat come first)
+            _lib.call("qot_nnconv_fused_split", P(x), hin, P(edge_attr), P(w1), P(b1), P(graph.rowptr), P(graph.col),
+                      P(graph.eid), P(graph.invdeg), P(split), split.numel() // 3, P(bias), P(out), N, hin, D,
+                      *_act_args(act))
+        else:
+            _lib.call("qot_nnconv_fused", P(x), hin, P(edge_attr), P(w1), P(b1), P(graph.rowptr), P(graph.col),
+                      P(graph.eid), P(graph.invdeg), 0, P(wp), P(bias), P(out), N, hin, D, *_act_args(act))
         ctx.save_for_backward(x, edge_attr, w1, b1, w2, b2, wroot, None, wp_adj, bp, out if act is not None else None,
-                              act[3] if act is not None else None)
+                              act[3] if act is not None else None, split)
+        ctx.n_wcat = wp.numel()
         ctx.graph = graph
         ctx.act = None if act is None else (act[0], act[1], act[2])
         ctx.side = side if act is not None else None
@@ -900,7 +933,7 @@ class NNConvFn(torch.autograd.Function):
             out = torch.empty_like(pre)
             _lib.call("qot_act_fwd", P(pre), P(out), pre.numel(), *_act_args(act)[1:])
         ctx.save_for_backward(x, edge_attr, w1, b1, w2, b2, wroot, A, None, None, out if act is not None else None,
-                              act[3] if act is not None else None)
+                              act[3] if act is not None else None, None)
         ctx.graph = graph
         ctx.act = None if act is None else (act[0], act[1], act[2])
         ctx.side = side if act is not None else None
@@ -908,7 +941,7 @@ class NNConvFn(torch.autograd.Function):
 
     @staticmethod
     def _backward_wide_edge(ctx, g, gbias):
-        x, edge_attr, w1, b1, w2, b2, wroot, A, _, _, _, _ = ctx.saved_tensors
+        x, edge_attr, w1, b1, w2, b2, wroot, A, _, _, _, _, _ = ctx.saved_tensors
         graph = ctx.graph
         N, hin = x.shape
         hout = wroot.shape[0]
@@ -935,7 +968,7 @@ class NNConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        x, edge_attr, w1, b1, w2, b2, wroot, A, wp_adj, bp, y, act_step = ctx.saved_tensors
+        x, edge_attr, w1, b1, w2, b2, wroot, A, wp_adj, bp, y, act_step, split = ctx.saved_tensors
         graph = ctx.graph
         g = _f32c(g)
         if ctx.side is not None:
@@ -971,7 +1004,11 @@ class NNConvFn(torch.autograd.Function):
         wsh = torch.empty(_lib.load().qot_nnconv_gradh_workspace_floats(D), dtype=torch.float32, device=dev)
         gpar = torch.empty((K + 2) * hh, dtype=torch.float32, device=dev)
         gradh_args = (P(g), hout, P(x), hin, P(edge_attr), P(w1), P(b1), P(graph.rowptr), P(graph.col), P(graph.eid),
-                      P(graph.invdeg), P(bp))
+                      P(graph.invdeg))
+        if split is not None:            # split-bf16 form: the planes of Wk^T follow those of Wcat in each plane
+            gradh_fn, gradh_args = "qot_nnconv_gradh_split", gradh_args + (P(split[ctx.n_wcat:]), split.numel() // 3)
+        else:
+            gradh_fn, gradh_args = "qot_nnconv_gradh_fused", gradh_args + (P(bp),)
         if hin == 64 and not os.environ.get("QOT_SPLIT_NNCONV_BWD"):
             # one gather feeds both products: grad_x = U @ WcatT and gWcat = X^T U; the slab sum of the weight gradient
             # and the block sum of the grad-h kernel share one launch behind both kernels
@@ -981,8 +1018,8 @@ class NNConvFn(torch.autograd.Function):
             # QOT_FORK (experiment, default off): the grad-h kernel on a side stream, "before" = next to the adjoint
             # kernel, "after" = next to the TransformerConv backward that follows on the main stream
             fork_mode = os.environ.get("QOT_FORK", "off") if deferred else "off"
-            launch_gradh = lambda: _lib.call("qot_nnconv_gradh_fused", *gradh_args, None, None, P(wsh), N, hin, D)
-            keep = (g, x, edge_attr, w1, b1, graph.rowptr, graph.col, graph.eid, graph.invdeg, bp, wsh)
+            launch_gradh = lambda: _lib.call(gradh_fn, *gradh_args, None, None, P(wsh), N, hin, D)
+            keep = (g, x, edge_attr, w1, b1, graph.rowptr, graph.col, graph.eid, graph.invdeg, bp, split, wsh)
             if fork_mode == "before":
                 LG.fork(launch_gradh, keep=keep)
             _lib.call("qot_nnconv_adjoint_dw", P(g), hout, P(x), hin, P(edge_attr), P(w1), P(b1), P(graph.rowptr_t),
@@ -1008,7 +1045,7 @@ class NNConvFn(torch.autograd.Function):
             _lib.call("qot_nnconv_dw", P(x), hin, P(g), hout, P(edge_attr), P(w1), P(b1), P(graph.rowptr), P(graph.col),
                       P(graph.eid), P(graph.invdeg), P(gpar), P(ws), N, hin, D)
             # grad of the edge MLP's first layer
-            _lib.call("qot_nnconv_gradh_fused", *gradh_args, P(gw1), P(gb1), P(wsh), N, hin, D)
+            _lib.call(gradh_fn, *gradh_args, P(gw1), P(gb1), P(wsh), N, hin, D)
         # already in the parameters' own layouts (no permute / copy kernels)
         gw2, gb2, gwroot = gpar[:hh * K].view(hh, K), gpar[hh * K:hh * (K + 1)], gpar[hh * (K + 1):].view(hout, hin)
         return gx, gea, gw1, gb1, gw2, gb2, gwroot, gbias, None, None, None, None

@@ -49,7 +49,7 @@ extern "C" {
 
 typedef void* qot_stream_t; /* hipStream_t */
 
-#define QOT_ABI_VERSION 11
+#define QOT_ABI_VERSION 12
 #define QOT_OK 0
 #define QOT_ERR_UNSUPPORTED (-1) /* width / edge_dim not instantiated */
 #define QOT_ERR_BADARG (-2)      /* null pointer, negative size, workspace too small */
@@ -289,6 +289,15 @@ int qot_nnconv_fused(const float* x, int ld_x, const float* edge_attr, const flo
                      const float* w_perm, const float* bias, float* out, int64_t N, int H, int D,
                      int act, float act_slope, float act_p, uint64_t act_seed, const int64_t* act_step,
                      qot_stream_t stream);
+/* H == 64, transpose = 0 only: as qot_nnconv_fused with the products on the bf16 matrix pipe, each fp32 product as six
+ * bf16 cross products of three-way splits (csrc/split_bf16.hpp).  w_split: Wcat split into three bf16 planes
+ * split_stride elements apart (functional.nnconv_split_index, the QOT_ROLE_GATHER3 split part), 16-byte aligned. */
+int qot_nnconv_fused_split(const float* x, int ld_x, const float* edge_attr, const float* w1,
+                           const float* b1, const int32_t* rowptr, const int32_t* col,
+                           const int32_t* edge_ids, const float* invdeg, const void* w_split,
+                           int64_t split_stride, const float* bias, float* out, int64_t N, int H, int D,
+                           int act, float act_slope, float act_p, uint64_t act_seed, const int64_t* act_step,
+                           qot_stream_t stream);
 /* C[KT,64] = A[N,KT]^T @ G[N,64] (fp32 MFMA, operands streamed from HBM in fragment order,
  * deterministic slab reduction).  Weight-gradient GEMM of NNConv (gWcat = A^T g) -- the shape
  * library GEMMs run at 13-28 TFLOP/s.  KT multiple of 128, <= 1280.  workspace:
@@ -320,6 +329,13 @@ int qot_nnconv_gradh_fused(const float* grad_out, int ld_g, const float* x, int 
                            const float* edge_attr, const float* w1, const float* b1,
                            const int32_t* rowptr, const int32_t* col, const int32_t* eid,
                            const float* invdeg, const float* b_perm, float* gw1, float* gb1,
+                           float* workspace, int64_t N, int H, int D, qot_stream_t stream);
+/* H == 64: as qot_nnconv_gradh_fused with the GA products on the bf16 matrix pipe (csrc/split_bf16.hpp).  b_split: Wk^T
+ * split into three bf16 planes split_stride elements apart (functional.nnconv_split_index), 16-byte aligned. */
+int qot_nnconv_gradh_split(const float* grad_out, int ld_g, const float* x, int ld_x,
+                           const float* edge_attr, const float* w1, const float* b1,
+                           const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                           const float* invdeg, const void* b_split, int64_t split_stride, float* gw1, float* gb1,
                            float* workspace, int64_t N, int H, int D, qot_stream_t stream);
 /* Weight gradient of NNConv for every supported width (H in {16, 32, 64, 128, 256}, D <= 4) without
  * materialising the [N, (K+2)H] operand: grad_params = [d nn.2.weight [H*H, K] | d nn.2.bias [H*H] |
@@ -643,7 +659,10 @@ int qot_skinny_linear_dw(const float* g, const float* x, float* partials, int64_
  *                             (as qot_csr_build_by_graph)                                  3 max_nodes, 4 max_edges
  * QOT_ROLE_TABLE_PROJECT_FWD  0 table, 1 wq, 2 bq, 3 wk, 4 bk, 5 wv, 6 bv, 7 ws, 8 bs, 9 out,
  *                             10 step_counter, 11 step_snapshot (as qot_table_project_fwd)  0 V (> 0), 1 H
- * QOT_ROLE_GATHER3            0 s0, 1 s1, 2 s2, 3 idx, 4 out (as qot_gather3)               0 n0, 1 n1, 2 n
+ * QOT_ROLE_GATHER3            0 s0, 1 s1, 2 s2, 3 idx, 4 out (as qot_gather3)               0 n0, 1 n1, 2 n,
+ *                             optional: 5 idx2 [m], 6 out2 (uint16 [3, m]): the gather       3 m (0: none)
+ *                             through idx2 split into bf16 planes hi / mid / lo (the split
+ *                             NNConv operands)
  * QOT_ROLE_SUM_ROWS           0 partials [nblk, n], 1 out [groups, n]:                     0 nblk, 1 n, 2 rows per
  *                             out[g, t] = sum of partials[b, t] over the rows b of group g,   group (0 = all rows:
  *                             fixed order (bitwise reproducible)                            one output row);
