@@ -26,7 +26,7 @@ _u64 = C.c_uint64
 _sz = C.c_size_t
 
 # name -> (restype, argtypes); must list every symbol include/qot_gnn.h declares
-ABI_VERSION = 12         # include/qot_gnn.h: QOT_ABI_VERSION
+ABI_VERSION = 13         # include/qot_gnn.h: QOT_ABI_VERSION
 
 SIGNATURES = {
     "qot_abi_version": (_int, []),
@@ -97,6 +97,8 @@ SIGNATURES = {
     "qot_tconv_edge_attr_grad": (_int, [_p, _p, _f, _f, _u64, _p, _p, _int, _p, _p, _p, _p, _p, _p, _p, _i64, _int, _int,
                                         _p]),
     "qot_nnconv_edge_attr_grad": (_int, [_p, _int, _p, _int, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _int, _int, _p]),
+    "qot_tconv_attention": (_int, [_p, _int, _p, _p, _p, _p, _p, _p, _p, _i64, _int, _int, _p]),
+    "qot_gat_attention": (_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _i64, _int, _f, _p]),
     "qot_act_fwd": (_int, [_p, _p, _i64, _f, _f, _u64, _p, _p]),
     "qot_act_bwd": (_int, [_p, _p, _p, _i64, _f, _f, _u64, _p, _p]),
     "qot_pool_fwd": (_int, [_p, _p, _p, _i64, _int, _p]),

@@ -57,8 +57,18 @@ def _gpu_batch(data, dev):
     return moved
 
 
-def forward(model, data):
-    """``model(data)`` for a CPU-resident ``model`` / ``data`` on the GPU engine; see the module docstring."""
+def _to(o, dev):
+    """``o`` with every tensor in it (nested tuples / lists: the attention readout) moved to ``dev``."""
+    if isinstance(o, torch.Tensor):
+        return o.to(dev)
+    if isinstance(o, (tuple, list)):
+        return type(o)(_to(v, dev) for v in o)
+    return o
+
+
+def forward(model, data, return_attention_weights=False):
+    """``model(data)`` for a CPU-resident ``model`` / ``data`` on the GPU engine; see the module docstring.
+    ``return_attention_weights`` is passed on to the model's forward."""
     if not torch.cuda.is_available():
         from . import _lib
         raise _lib.QotError("QOT_AUTO_DEVICE=1 but no GPU is visible: the HIP path has no CPU fallback")
@@ -82,13 +92,11 @@ def forward(model, data):
             setattr(shadow, attr, getattr(model, attr))
     params = {k: p.to(dev) for k, p in model.named_parameters()}
     buffers = {k: b.to(dev) for k, b in model.named_buffers() if k.rsplit(".", 1)[-1] not in _SKIP_BUFFERS}
-    out = torch.func.functional_call(shadow, {**params, **buffers}, (_gpu_batch(data, dev),))
+    kwargs = {"return_attention_weights": True} if return_attention_weights else {}
+    out = torch.func.functional_call(shadow, {**params, **buffers}, (_gpu_batch(data, dev),), kwargs)
     if model.training and buffers:
         with torch.no_grad():
             own = dict(model.named_buffers())
             for k, b in buffers.items():
                 own[k].copy_(b)
-    home = next(model.parameters()).device
-    if isinstance(out, tuple):
-        return tuple(o.to(home) for o in out)
-    return out.to(home)
+    return _to(out, next(model.parameters()).device)

@@ -465,6 +465,70 @@ def tconv_edge_attr_grad(g, y, act, act_step, qkvs, edge_attr, w_edge, graph: Gr
     return gea
 
 
+# ------------------------------------------------------------------ attention weights (return_attention_weights=True)
+class AttentionWeightsFn(torch.autograd.Function):
+    """The attention weights ``compute()`` returns, attached to the graph of ``deps`` (the tensors they are a function of)
+    so that a backward through them fails loudly instead of returning a silent zero: PyG's ``alpha`` is differentiable,
+    ours is not (yet)."""
+
+    @staticmethod
+    def forward(ctx, compute, *deps):
+        return compute()
+
+    @staticmethod
+    def backward(ctx, g):
+        raise NotImplementedError("gradient through attention weights is not implemented")
+
+
+def tconv_attention(qkvs, edge_attr, w_edge, graph: GraphIndex, maps, deps=()):
+    """TransformerConv's attention weights ``[E, 1]`` in edge order (``csrc/attention.hip``), recomputed from the packed
+    ``[q|k|v|skip]`` rows the forward built: node rows (``maps is None``) or table rows through ``maps`` -- one launch in
+    every form.  ``deps``: further tensors the rows were made from (graph form: the table and the projections)."""
+    def compute():
+        rows, ea, we = _f32c(qkvs.detach()), _f32c(edge_attr.detach()), _f32c(w_edge.detach())
+        require_cuda(rows, ea, we)
+        H = rows.shape[1] // 4
+        E, D = ea.shape
+        alpha = torch.empty(E, 1, dtype=torch.float32, device=rows.device)
+        if E > 0 and graph.num_nodes > 0:
+            rowmap, col = (maps[0], maps[1]) if maps is not None else (None, graph.col)
+            _lib.call("qot_tconv_attention", rows, rows.shape[1], rowmap, col, graph.rowptr, graph.eid, ea, we, alpha,
+                      graph.num_nodes, H, D)
+        return alpha
+    return AttentionWeightsFn.apply(compute, qkvs, edge_attr, w_edge, *deps)
+
+
+def gat_attention_index(graph: GraphIndex, edge_index):
+    """``(edge_index, edge_pos, num_kept)`` of GATConv's attention readout, built once per graph index and kept on it:
+    the self-looped ``[2, num_kept + N]`` edge list in PyG's order (``remove_self_loops`` + ``add_self_loops``:
+    ``oracle.sparse.gat_edge_set``) and each input edge's row in it (``[E]`` int32, meaningful for the kept edges).  One
+    host read (``num_kept``)."""
+    if graph.attention_index is None:
+        keep = edge_index[0] != edge_index[1]
+        kept = edge_index[:, keep]
+        loops = torch.arange(graph.num_nodes, dtype=edge_index.dtype, device=edge_index.device)
+        ei = torch.cat([kept, torch.stack([loops, loops])], dim=1)
+        pos = (torch.cumsum(keep, 0, dtype=torch.int32) - 1).to(torch.int32)
+        graph.attention_index = (ei, pos, int(kept.shape[1]))
+    return graph.attention_index
+
+
+def gat_attention(a_src, a_dst, graph: GraphIndex, edge_index, neg_slope: float, deps=()):
+    """GATConv's ``(edge_index, alpha)``: ``alpha [num_kept + N, 4]`` from the layer's logits ``a_src`` / ``a_dst [N, 4]``
+    (``csrc/attention.hip``), rows in the order of the returned self-looped ``edge_index``."""
+    ei, pos, num_kept = gat_attention_index(graph, edge_index)
+
+    def compute():
+        s, d = _f32c(a_src.detach()), _f32c(a_dst.detach())
+        N, heads = d.shape
+        alpha = torch.empty(num_kept + N, heads, dtype=torch.float32, device=d.device)
+        if N > 0:
+            _lib.call("qot_gat_attention", s, d, graph.rowptr, graph.col, graph.eid, pos if num_kept > 0 else None,
+                      num_kept, alpha, N, heads, float(neg_slope))
+        return alpha
+    return ei, AttentionWeightsFn.apply(compute, *deps)
+
+
 def tconv_rows_ok(qkvs: torch.Tensor, maps, H: int, D: int) -> bool:
     """The row form of the backward (``csrc/tconv_rows.hip``) takes this batch: table mode with ``node_ids == arange(n)`` in
     every graph, the score matrix kept from the forward, a table of exactly those n rows."""
@@ -1245,9 +1309,10 @@ class GatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, att_src, att_dst, bias, graph: GraphIndex, neg_slope: float, bn_stats: bool = False,
-                a_src=None, a_dst=None):
+                a_src=None, a_dst=None, logits_sink=None):
         """``a_src`` / ``a_dst``: the logits, when the projection that made ``z`` left them behind (``gemm_nt(att=...)``);
-        their gradient still returns through ``grad_z`` in ``backward``."""
+        their gradient still returns through ``grad_z`` in ``backward``.  ``logits_sink`` (a list): the logits the kernels
+        used are appended to it (the attention-weights readout)."""
         require_cuda(z, att_src, att_dst, bias)
         z, bias = _f32c(z), _f32c(bias)
         heads, C = att_src.shape[-2], att_src.shape[-1]
@@ -1260,6 +1325,8 @@ class GatFn(torch.autograd.Function):
             _lib.call("qot_gat_logits", P(z), P(att_s), P(att_d), P(a_src), P(a_dst), N, heads, C)
         else:
             a_src, a_dst = _f32c(a_src), _f32c(a_dst)
+        if logits_sink is not None:
+            logits_sink.append((a_src, a_dst))
         out = torch.empty(N, HC, dtype=torch.float32, device=dev)
         stats = torch.empty(N, heads, 2, dtype=torch.float32, device=dev)
         partials = None
@@ -1300,7 +1367,7 @@ class GatFn(torch.autograd.Function):
                   P(graph.col_t), P(graph.pos_t), P(gz), P(gas), N, heads, C, ns, P(att_s), P(att_d), P(gad))
         g_att = torch.empty(2, HC, dtype=torch.float32, device=dev)
         _lib.call("qot_gat_att_grad", P(z), P(gas), P(gad), _off(g_att, 0), _off(g_att, HC), P(ws), N, heads, C)
-        return gz, g_att[0].view(ctx.att_shape), g_att[1].view(ctx.att_shape), g_bias, None, None, None, None, None
+        return gz, g_att[0].view(ctx.att_shape), g_att[1].view(ctx.att_shape), g_bias, None, None, None, None, None, None
 
 
 def gat_thin_ok(x: torch.Tensor, heads: int, C: int) -> bool:
@@ -1337,7 +1404,8 @@ class GatThinFn(torch.autograd.Function):
     (its sum runs over the F features in another order).  ``x`` gets no gradient."""
 
     @staticmethod
-    def forward(ctx, x, lin_weight, att_src, att_dst, bias, graph: GraphIndex, neg_slope: float, bn_stats: bool = False):
+    def forward(ctx, x, lin_weight, att_src, att_dst, bias, graph: GraphIndex, neg_slope: float, bn_stats: bool = False,
+                logits_sink=None):
         require_cuda(x, lin_weight, att_src, att_dst, bias)
         x, w, bias = _f32c(x), _f32c(lin_weight), _f32c(bias)
         heads, C = att_src.shape[-2], att_src.shape[-1]
@@ -1351,6 +1419,8 @@ class GatThinFn(torch.autograd.Function):
         a_dst = torch.empty(N, heads, dtype=torch.float32, device=dev)
         _lib.call("qot_skinny_linear_fwd", P(x), P(v_src), P(a_src), N, F, heads)
         _lib.call("qot_skinny_linear_fwd", P(x), P(v_dst), P(a_dst), N, F, heads)
+        if logits_sink is not None:
+            logits_sink.append((a_src, a_dst))
         out = torch.empty(N, HC, dtype=torch.float32, device=dev)
         stats = torch.empty(N, heads, 2, dtype=torch.float32, device=dev)
         partials = None
@@ -1392,7 +1462,7 @@ class GatThinFn(torch.autograd.Function):
         w3 = w.view(heads, C, F)
         g_att_src = (w3 * _skinny_dw(gas, x).view(heads, 1, F)).sum(-1)              # [heads, C]
         g_att_dst = (w3 * _skinny_dw(gad, x).view(heads, 1, F)).sum(-1)
-        return (None, g_lin, g_att_src.view(ctx.att_shape), g_att_dst.view(ctx.att_shape), g_bias, None, None, None)
+        return (None, g_lin, g_att_src.view(ctx.att_shape), g_att_dst.view(ctx.att_shape), g_bias, None, None, None, None)
 
 
 # ------------------------------------------------------------------ BatchNorm (+ReLU) (a8)

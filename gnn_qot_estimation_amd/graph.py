@@ -39,6 +39,7 @@ class GraphIndex:
     ptr32: Optional[torch.Tensor] = None    # [B+1] int32 graph boundaries
     sizes: Optional[tuple] = None           # (max nodes, max edges) of one graph: the per-graph build has checked every slice
     status_pending: bool = False            # built with check=False: the caller still owes a check_index_status()
+    attention_index: Optional[tuple] = None  # GATConv's attention readout order (functional.gat_attention_index), on demand
 
 
 def require_cuda(*tensors):

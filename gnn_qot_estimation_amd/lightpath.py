@@ -62,7 +62,7 @@ class LightpathGNN(nn.Module):
             raise ValueError("No LUT node found in the batch.")
         return idx
 
-    def _forward_padded(self, data):
+    def _forward_padded(self, data, attention: bool = False):
         import torch
         from . import padded
         c, cp = self.conv1.out_channels, self._qot_cp
@@ -78,20 +78,25 @@ class LightpathGNN(nn.Module):
         shadow.allow_empty_lut = self.allow_empty_lut
         shadow.mlp[2].p = self.mlp[2].p
         params, buffers = padded.lightpath_params(self, cp)
-        out = torch.func.functional_call(shadow, {**params, **buffers}, (data,))
+        kwargs = {"return_attention_weights": True} if attention else {}
+        out = torch.func.functional_call(shadow, {**params, **buffers}, (data,), kwargs)
         if self.training:
             padded.lightpath_copy_back(self, buffers, c, cp)
         return out
 
-    def forward(self, data):
+    def forward(self, data, return_attention_weights=False):
+        """``return_attention_weights=True``: returns ``(out, lut_batch, attn)``, ``attn`` one ``(edge_index, alpha)`` per
+        GATConv layer (``GATConv.forward``'s readout; all layers share the one self-looped ``edge_index``), from the
+        logits each layer's forward formed; nothing else changes (one more launch per layer)."""
         if not self.conv1.bias.is_cuda:
             # a model left on the CPU: opt-in upload (QOT_AUTO_DEVICE=1), or a loud error -- never a CPU computation
             from . import auto_device
             if auto_device.enabled():
-                return auto_device.forward(self, data)
+                return auto_device.forward(self, data, return_attention_weights=bool(return_attention_weights))
             raise auto_device.cpu_model_error()
         if self._qot_cp is not None:
-            return self._forward_padded(data)
+            return self._forward_padded(data, bool(return_attention_weights))
+        attn = [] if return_attention_weights else None
         x, edge_index, batch = data.x, data.edge_index, data.batch
         n = x.shape[0]
         graph = graph_index_for(data, n, gat_self_loops=True, check=False)
@@ -117,12 +122,16 @@ class LightpathGNN(nn.Module):
                 else:
                     z, logits = pnorm.project_relu(praw, conv.lin.weight, partials=ppart), None
                 pending = None
+            sink = [] if attn is not None else None
             if self.training:      # the conv's epilogue leaves the BatchNorm's column partials behind
-                raw, part = (conv.attend_thin(x, graph, bn_stats=True) if thin else
-                             conv.attend(z, graph, bn_stats=True, logits=logits))
+                raw, part = (conv.attend_thin(x, graph, bn_stats=True, logits_sink=sink) if thin else
+                             conv.attend(z, graph, bn_stats=True, logits=logits, logits_sink=sink))
                 partials = (part, conv.bias)
             else:
-                raw, partials = (conv.attend_thin(x, graph) if thin else conv.attend(z, graph, logits=logits)), None
+                raw, partials = (conv.attend_thin(x, graph, logits_sink=sink) if thin else
+                                 conv.attend(z, graph, logits=logits, logits_sink=sink)), None
+            if attn is not None:
+                attn.append(conv.attention_weights(sink, graph, edge_index, x if thin else z))
             width = raw.shape[1]
             # BatchNorm + ReLU folded into the NEXT projection's operand load (QF.BnLinearFn): the normalised activations are
             # never written to / read from HBM (one [N, 4C] tensor less resident per layer); the product runs on
@@ -139,10 +148,12 @@ class LightpathGNN(nn.Module):
                 x = norm(raw, relu=True, partials=partials)        # BatchNorm + F.relu fused, materialised
         idx = self._lut_rows(data)
         if idx.numel() == 0:          # only with allow_empty_lut: zero rows that still hang on the graph
-            return x[:0, :self.mlp[3].out_features], batch[:0]
+            res = x[:0, :self.mlp[3].out_features], batch[:0]
+            return res if attn is None else res + (attn,)
         if lut_embedding is None:
             lut_embedding = QF.RowsGatherFn.apply(x, to_i32(idx))
         lut_batch = batch.index_select(0, idx)
         l0, act, drop, l3 = self.mlp[0], self.mlp[1], self.mlp[2], self.mlp[3]
         h = QF.SmallLinearFn.apply(lut_embedding, l0.weight, l0.bias)       # head MLP (models.py:17-22,43)
-        return QF.SmallLinearFn.apply(drop(act(h)), l3.weight, l3.bias), lut_batch
+        out = QF.SmallLinearFn.apply(drop(act(h)), l3.weight, l3.bias)
+        return (out, lut_batch) if attn is None else (out, lut_batch, attn)

@@ -52,14 +52,24 @@ class TransformerConv(nn.Module):
         b = torch.cat([self.lin_query.bias, self.lin_key.bias, self.lin_value.bias, self.lin_skip.bias], 0)
         return w, b
 
-    def forward(self, x, edge_index, edge_attr=None, graph: Optional[GraphIndex] = None, act=None):
+    def forward(self, x, edge_index, edge_attr=None, graph: Optional[GraphIndex] = None, act=None,
+                return_attention_weights=None):
         """``act = (slope, p, seed, step_counter)`` fuses ``dropout(leaky_relu(.))`` into the kernel
-        epilogue (build extension; ``None`` = the plain PyG operator)."""
+        epilogue (build extension; ``None`` = the plain PyG operator).  ``return_attention_weights=True``: returns
+        ``(out, (edge_index, alpha))`` as PyG does, ``alpha [E, 1]`` in the order of ``edge_index`` (no gradient)."""
         if graph is None:
             graph = build_graph_index(edge_index, x.shape[0])
         w, b = self.packed_weight()
         qkvs = QF.LinearFn.apply(x, w, b)             # one MFMA GEMM for q|k|v|skip
-        return QF.TConvFn.apply(qkvs, edge_attr, self.lin_edge.weight, graph, None, act)
+        out = QF.TConvFn.apply(qkvs, edge_attr, self.lin_edge.weight, graph, None, act)
+        if return_attention_weights:
+            return out, (edge_index, self.attention_weights(qkvs, edge_attr, graph, None))
+        return out
+
+    def attention_weights(self, rows, edge_attr, graph: GraphIndex, maps, deps=()):
+        """``alpha [E, 1]`` (edge order) from the packed ``[q|k|v|skip]`` rows a forward built: node rows, the projected
+        table of the per-destination and rows forms (``maps``), or the graph form's ``pre[0]``; one launch."""
+        return QF.tconv_attention(rows, edge_attr, self.lin_edge.weight, graph, maps, deps)
 
     def forward_table(self, table, edge_attr, graph: GraphIndex, maps, act=None, step_pair=None, t4=None):
         """``conv(table[node_ids], ...)`` without materialising per-node inputs: project the
@@ -165,9 +175,12 @@ class GATConv(nn.Module):
             nn.init.uniform_(a, -stdv, stdv)
         nn.init.zeros_(self.bias)
 
-    def forward(self, x, edge_index, graph: Optional[GraphIndex] = None, bn_stats: bool = False):
+    def forward(self, x, edge_index, graph: Optional[GraphIndex] = None, bn_stats: bool = False,
+                return_attention_weights=None):
         """``bn_stats=True`` (build extension): returns ``(out, partials)`` where ``partials`` are the column partials of
-        ``out - bias`` a following ``BatchNorm(..., partials=(partials, conv.bias))`` uses for its batch statistics."""
+        ``out - bias`` a following ``BatchNorm(..., partials=(partials, conv.bias))`` uses for its batch statistics.
+        ``return_attention_weights=True``: returns ``(out, (edge_index, alpha))`` as PyG does -- ``edge_index`` with self
+        loops ``[2, E' + N]`` (input self loops removed, one loop per node appended), ``alpha [E' + N, 4]`` (no gradient)."""
         n = x.shape[0]
         if self.heads != 4:
             raise NotImplementedError("only the reference's GATConv(F, C, heads=4, concat=True) configuration")
@@ -175,9 +188,21 @@ class GATConv(nn.Module):
             graph = build_graph_index(edge_index, n, gat_self_loops=True)
         if not graph.gat_self_loops:
             raise ValueError("GATConv needs a GraphIndex built with gat_self_loops=True")
+        sink = [] if return_attention_weights else None
         if self.thin_ok(x):
-            return self.attend_thin(x, graph, bn_stats)
-        return self.attend(self.project(x), graph, bn_stats)
+            out = self.attend_thin(x, graph, bn_stats, logits_sink=sink)
+        else:
+            out = self.attend(self.project(x), graph, bn_stats, logits_sink=sink)
+        if return_attention_weights:
+            return out, self.attention_weights(sink, graph, edge_index, x)
+        return out
+
+    def attention_weights(self, logits_sink, graph: GraphIndex, edge_index, x):
+        """``(edge_index, alpha)`` from the logits a forward left in ``logits_sink`` (``attend*(..., logits_sink=[])``);
+        ``x``: the layer's input."""
+        a_s, a_d = logits_sink[-1]
+        return QF.gat_attention(a_s, a_d, graph, edge_index, self.negative_slope,
+                                (x, self.lin.weight, self.att_src, self.att_dst))
 
     def project(self, x, with_logits: bool = False):
         """``z = x W^T`` (``lin``, no bias): own MFMA kernel where the inner width allows (``csrc/gemm.hip``), the library
@@ -204,16 +229,17 @@ class GATConv(nn.Module):
         """The first layer's form: projection inside the attention kernels (``QF.GatThinFn``)."""
         return self.heads == 4 and QF.gat_thin_ok(x, self.heads, self.out_channels)
 
-    def attend_thin(self, x, graph: GraphIndex, bn_stats: bool = False):
+    def attend_thin(self, x, graph: GraphIndex, bn_stats: bool = False, logits_sink=None):
         return QF.GatThinFn.apply(x, self.lin.weight, self.att_src, self.att_dst, self.bias, graph, self.negative_slope,
-                                  bn_stats)
+                                  bn_stats, logits_sink)
 
-    def attend(self, z, graph: GraphIndex, bn_stats: bool = False, logits=None):
+    def attend(self, z, graph: GraphIndex, bn_stats: bool = False, logits=None, logits_sink=None):
         # attention logits a[n,h] = <z[n,h,:], att[h,:]> are formed from z inside the operator (one pass over z each
         # way) unless the projection left them behind (``logits``); their gradient returns into grad_z in the source pass
         # of the backward either way
         a_s, a_d = logits if logits is not None else (None, None)
-        return QF.GatFn.apply(z, self.att_src, self.att_dst, self.bias, graph, self.negative_slope, bn_stats, a_s, a_d)
+        return QF.GatFn.apply(z, self.att_src, self.att_dst, self.bias, graph, self.negative_slope, bn_stats, a_s, a_d,
+                              logits_sink)
 
 
 class BatchNorm(nn.Module):

@@ -91,7 +91,7 @@ class TopologicalGNN(nn.Module):
         if isinstance(c, dict):
             c["ids_ok"] = tag
 
-    def _forward_padded(self, data):
+    def _forward_padded(self, data, attention: bool = False):
         from . import padded
         if data.x is not None and data.x.numel():
             raise NotImplementedError("explicit node features with a padded hidden width")
@@ -105,7 +105,8 @@ class TopologicalGNN(nn.Module):
         shadow = self._qot_shadow[0]
         shadow.train(self.training)
         shadow.dropout.p = shadow.mlp[2].p = self.dropout.p
-        return torch.func.functional_call(shadow, padded.topological_params(self, self._qot_hp), (data,))
+        kwargs = {"return_attention_weights": True} if attention else {}
+        return torch.func.functional_call(shadow, padded.topological_params(self, self._qot_hp), (data,), kwargs)
 
     def forward_loss(self, data, target, beta: float = 1.0, loss_out=None):
         """``out = self(data)`` together with the train step's criterion ``SmoothL1Loss(reduction="mean", beta)(out,
@@ -120,18 +121,23 @@ class TopologicalGNN(nn.Module):
         loss, gout = QF.smooth_l1_loss_and_grad(res, target, beta, loss_out=loss_out)
         return res, loss, gout
 
-    def forward(self, data):
+    def forward(self, data, return_attention_weights=False):
+        """``return_attention_weights=True``: returns ``(out, (edge_index, alpha))``, the attention weights of ``conv1``
+        (``alpha [E, 1]`` in the order of ``data.edge_index``, no gradient) from the rows this forward built; nothing else
+        changes (one more launch, after the forward's own)."""
+        if return_attention_weights:
+            return self._forward(data, None, attention=True)
         return self._forward(data, None)
 
-    def _forward(self, data, loss_spec):
+    def _forward(self, data, loss_spec, attention: bool = False):
         if not self.node_embeddings.weight.is_cuda:
             # a model left on the CPU (the reference's topological_training/train.py:62): opt-in upload, or a loud error
             from . import auto_device
             if auto_device.enabled():
-                return auto_device.forward(self, data)
+                return auto_device.forward(self, data, return_attention_weights=attention)
             raise auto_device.cpu_model_error()
         if self._qot_hp is not None:
-            return self._forward_padded(data)
+            return self._forward_padded(data, attention)
         x, edge_index, edge_attr = data.x, data.edge_index, data.edge_attr
         LG.drop_stale()
         # Forward prologue: the graph index of the batch, the projected embedding table and the packed NNConv operands
@@ -169,12 +175,22 @@ class TopologicalGNN(nn.Module):
         packed = {layer: getattr(self, f"conv{layer}").prepack(grp) for layer in range(2, self.num_layers + 1)}
         if grp is not None:
             grp.run()
+        attn = None
         if plan is not None:
             x = self.conv1.forward_table_graph(self.node_embeddings.weight, edge_attr, graph, maps, plan, pre,
                                                act=self._act(0, step))
+            if attention:         # pre[0]: the projected table the graph form read
+                c1 = self.conv1
+                attn = (edge_index, c1.attention_weights(pre[0], edge_attr, graph, maps,
+                                                         (self.node_embeddings.weight, c1.lin_query.weight,
+                                                          c1.lin_key.weight)))
         elif maps is not None:    # x = emb[node_ids]: project the table, gather projected rows
             x = self.conv1.forward_table(self.node_embeddings.weight, edge_attr, graph, maps, act=self._act(0, step),
                                          step_pair=step_pair, t4=t4)
+            if attention:
+                attn = (edge_index, self.conv1.attention_weights(t4, edge_attr, graph, maps))
+        elif attention:
+            x, attn = self.conv1(x, edge_index, edge_attr, graph=graph, act=self._act(0, step), return_attention_weights=True)
         else:
             x = self.conv1(x, edge_index, edge_attr, graph=graph, act=self._act(0, step))
         l0, l3 = self.mlp[0], self.mlp[3]
@@ -206,11 +222,13 @@ class TopologicalGNN(nn.Module):
                 out, gout = QF.HeadFn.apply(x, ptr, l0.weight, l0.bias, l3.weight, l3.bias, B, act,
                                             last_act if side is not None else None, side, (target, beta, loss_out, True))
                 return out, gout, loss_out
-            return QF.HeadFn.apply(x, ptr, l0.weight, l0.bias, l3.weight, l3.bias, B, act,
-                                   last_act if side is not None else None, side)
-        b32, ptr, B = batch_index_for(data, n)
-        x = QF.PoolFn.apply(x, b32, ptr, B)
-        return self._head(x)
+            out = QF.HeadFn.apply(x, ptr, l0.weight, l0.bias, l3.weight, l3.bias, B, act,
+                                  last_act if side is not None else None, side)
+        else:
+            b32, ptr, B = batch_index_for(data, n)
+            x = QF.PoolFn.apply(x, b32, ptr, B)
+            out = self._head(x)
+        return out if attn is None else (out, attn)
 
     def _head(self, x):
         """``self.mlp`` (Linear -> LeakyReLU -> Dropout -> Linear, models.py:33-38,63) with the two

@@ -49,7 +49,7 @@ extern "C" {
 
 typedef void* qot_stream_t; /* hipStream_t */
 
-#define QOT_ABI_VERSION 12
+#define QOT_ABI_VERSION 13
 #define QOT_OK 0
 #define QOT_ERR_UNSUPPORTED (-1) /* width / edge_dim not instantiated */
 #define QOT_ERR_BADARG (-2)      /* null pointer, negative size, workspace too small */
@@ -381,6 +381,24 @@ int qot_nnconv_edge_attr_grad(const float* GA, int ld_ga, const float* x, int ld
                               const float* w1, const float* b1, const int32_t* rowptr, const int32_t* col,
                               const int32_t* eid, const float* invdeg, float* grad_edge_attr, int64_t N, int H, int D,
                               qot_stream_t stream);
+
+/* ---- attention weights (csrc/attention.hip) ------------------------------------------
+ * PyG's return_attention_weights=True readout, recomputed from the rows the forward built; one owner per output row and
+ * plain stores: bitwise reproducible, every row written (no zero fill needed).
+ * qot_tconv_attention (heads = 1, H in {16, 32, 64, 128, 256}, D in {1..8}): qkvs / ld / rowmap / col as
+ * qot_tconv_edge_attr_grad (node rows, or table rows through rowmap); alpha [E] in the caller's edge order (slot p -> eid[p])
+ *     alpha_e = exp(s_e - max_i) / (sum_i + 1e-16),   s_e = <q_i, k_j + W_e ea_e> / sqrt(H)
+ * qot_gat_attention (heads = 4): a_src / a_dst [N, 4] logits, CSR with gat_self_loops; alpha [num_kept + N, 4], the order
+ * of remove_self_loops + add_self_loops: slot p with eid[p] >= 0 -> row edge_pos[eid[p]] (its index among the input's
+ * non-self-loop edges, num_kept of them; edge_pos may be NULL when num_kept = 0), the self loop of node i -> num_kept + i
+ *     alpha_p = softmax over i's slots of leaky_relu(a_src[col[p]] + a_dst[i], neg_slope).  a_src, a_dst, alpha 16-byte
+ * aligned. */
+int qot_tconv_attention(const float* qkvs, int ld, const int32_t* rowmap, const int32_t* col, const int32_t* rowptr,
+                        const int32_t* eid, const float* edge_attr, const float* w_edge, float* alpha, int64_t N, int H,
+                        int D, qot_stream_t stream);
+int qot_gat_attention(const float* a_src, const float* a_dst, const int32_t* rowptr, const int32_t* col,
+                      const int32_t* eid, const int32_t* edge_pos, int64_t num_kept, float* alpha, int64_t N, int heads,
+                      float neg_slope, qot_stream_t stream);
 
 /* ---- activation: y = dropout(leaky_relu(x, slope), p) ------------------------------
  * Counter-based RNG: keep = hash(seed, *step_counter, element) >= p.  step_counter is a
