@@ -175,7 +175,8 @@ class StepReplayer:
     runs eagerly (it also builds and caches the graph index), the second is captured, later ones replay.
     All captures share one memory pool (steps never overlap), the learning rate lives in device memory
     (``FusedSGD(device_lr=True)``), dropout draws come from the device-side counter.  Batches whose
-    forward raises (``ValueError``: no LUT node) are remembered and skipped.
+    forward raises (``ValueError``: no LUT node) are remembered and skipped; on later visits of such a training batch only
+    its train-mode forward runs (eagerly), because that forward moves the BatchNorm running statistics before it raises.
     Data parallel (r04): RCCL takes part in stream capture, so with ``collective=True`` (set by ``fit`` for a TopologicalGNN
     run on more than one rank over the nccl backend) the captured step holds forward, backward, the pack of the gradients,
     ONE all-reduce of the flat gradient and the update -- the N > 1 step is the N = 1 step plus that exchange.  Every rank
@@ -236,6 +237,16 @@ class StepReplayer:
         """One step on ``data``; returns False when the batch is (remembered as) skipped."""
         key = (id(data), training)
         if key in self.skip:
+            if training:
+                # The forward raises AFTER its layers ran in train mode (models.py:30-36), so in the eager loop -- and in
+                # the reference -- the BatchNorm running statistics move on EVERY visit of such a batch, not only on the
+                # one that found it out.  Nothing else moves: no optimizer step, no dropout draw, no statistics row.
+                self.model.train(True)
+                with torch.no_grad():
+                    try:
+                        _KINDS[self.kind](self.model, data, self.out_dim)
+                    except ValueError:
+                        pass
             return False
         g = self.graphs.get(key)
         if g is not None:

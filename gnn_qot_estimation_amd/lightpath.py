@@ -79,10 +79,13 @@ class LightpathGNN(nn.Module):
         shadow.mlp[2].p = self.mlp[2].p
         params, buffers = padded.lightpath_params(self, cp)
         kwargs = {"return_attention_weights": True} if attention else {}
-        out = torch.func.functional_call(shadow, {**params, **buffers}, (data,), kwargs)
-        if self.training:
-            padded.lightpath_copy_back(self, buffers, c, cp)
-        return out
+        try:
+            return torch.func.functional_call(shadow, {**params, **buffers}, (data,), kwargs)
+        finally:
+            # also when the forward raises for a LUT-less batch: that error comes AFTER the layers ran (models.py:30-36),
+            # so the running statistics they moved are kept, as at the widths that run unpadded
+            if self.training:
+                padded.lightpath_copy_back(self, buffers, c, cp)
 
     def forward(self, data, return_attention_weights=False):
         """``return_attention_weights=True``: returns ``(out, lut_batch, attn)``, ``attn`` one ``(edge_index, alpha)`` per

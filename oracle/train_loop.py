@@ -1,0 +1,186 @@
+"""Plain CPU restatement of the reference's two training loops, for whole-trajectory checks.
+
+TEST INFRASTRUCTURE (see ``oracle/__init__.py``).  Written from the behaviour of
+``topological_training/train.py`` and ``lightpath_training/train.py`` over the ``oracle.sparse`` models with
+torch's own ``SGD`` / ``StepLR`` / ``SmoothL1Loss``.  It shares no code with ``gnn_qot_estimation_amd.harness`` or
+``gnn_qot_estimation_amd.dp`` (only the ``Data`` / ``Batch`` containers are borrowed): it is the independent second
+statement that ``harness.fit`` is compared with, in fp32 on the CPU and in fp64 against the HIP path.
+
+What the loop does, in the order the reference does it:
+
+* 70 / 15 / 15 split in dataset order; epoch ``e`` trains on chunk ``e % int(1 / fraction)`` of
+  ``train_len // num_chunks`` graphs, unshuffled; consecutive batches, the last one ragged;
+* per batch ``zero_grad`` / forward / ``SmoothL1Loss`` (mean) / ``backward`` / ``step``;
+* epoch loss = sum of ``loss * rows`` over the batches divided by the number of graphs of the chunk (or of the
+  validation range), skipped graphs included; R2 = uniform average over outputs, two passes over the stacked
+  ``y`` / ``yhat`` in fp64, with sklearn's rule for a constant target;
+* lightpath: a batch whose forward raises ``ValueError`` (or selects no row) is skipped and counted; whatever its
+  forward did before raising (BatchNorm running statistics) stays done;
+* early stopping on the validation R2, then -- only when the run goes on -- ``scheduler.step()``.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Sequence, Tuple
+
+import torch
+
+from gnn_qot_estimation_amd.batch import Batch, Data
+
+
+def split(total: int) -> Tuple[List[int], List[int], List[int]]:
+    """Train / validation / test graph indices: the first 70 %, the next 15 %, the rest."""
+    n_train = int(total * 0.7)
+    n_val = int(total * 0.15)
+    everything = list(range(total))
+    return everything[:n_train], everything[n_train:n_train + n_val], everything[n_train + n_val:]
+
+
+def chunk_indices(epoch: int, train_len: int, fraction: float) -> List[int]:
+    """Positions inside the training range that epoch ``epoch`` visits."""
+    num_chunks = int(1 / fraction)
+    size = train_len // num_chunks
+    first = (epoch % num_chunks) * size
+    return list(range(train_len))[first:first + size]
+
+
+def r2_uniform(y: torch.Tensor, yhat: torch.Tensor) -> float:
+    """``r2_score(y, yhat, multioutput="uniform_average")``: per output ``1 - sse / sst`` around the column mean; a
+    constant target scores 1 when hit exactly and 0 otherwise."""
+    y, yhat = y.detach().double(), yhat.detach().double()
+    if y.shape[0] == 0:
+        return float("nan")
+    sse = ((y - yhat) ** 2).sum(0)
+    sst = ((y - y.mean(0, keepdim=True)) ** 2).sum(0)
+    per_output = []
+    for num, den in zip(sse.tolist(), sst.tolist()):
+        if den != 0.0:
+            per_output.append(1.0 - num / den)
+        else:
+            per_output.append(1.0 if num == 0.0 else 0.0)
+    return sum(per_output) / len(per_output)
+
+
+class EarlyStopping:
+    """The patience counter of the reference: a strictly better validation R2 resets it, anything else (a NaN
+    included) advances it, and reaching ``patience`` ends the run."""
+
+    def __init__(self, patience: int):
+        self.patience = patience
+        self.best = float("-inf")
+        self.best_epoch = -1
+        self.counter = 0
+
+    def update(self, epoch: int, val_r2: float) -> Tuple[bool, bool]:
+        """``(improved, stop)`` for this epoch's validation R2."""
+        if val_r2 > self.best:
+            self.best, self.best_epoch, self.counter = val_r2, epoch, 0
+            return True, False
+        self.counter += 1
+        return False, self.counter >= self.patience
+
+
+def _cast(graph: Data, dtype) -> Data:
+    out = Data(num_nodes=graph.num_nodes)
+    for name in ("x", "edge_index", "edge_attr", "y", "node_ids"):
+        t = getattr(graph, name, None)
+        if isinstance(t, torch.Tensor):
+            t = t.detach().cpu()
+            if t.is_floating_point():
+                t = t.to(dtype)
+        setattr(out, name, t)
+    return out
+
+
+def _forward(model, batch, kind: str, output_dim: int):
+    """``(out, y)`` of one batch, or ``None`` when the lightpath batch is to be skipped."""
+    if kind == "topological":
+        return model(batch), batch.y.view(-1, output_dim)
+    try:
+        out, lut_batch = model(batch)
+    except ValueError:
+        return None
+    y = batch.y.view(-1, output_dim)[lut_batch]
+    if y.shape[0] == 0:
+        return None
+    return out, y
+
+
+def _one_pass(model, graphs: Sequence[Data], kind: str, batch_size: int, output_dim: int, criterion,
+              optimizer=None) -> Dict[str, float]:
+    training = optimizer is not None
+    model.train(training)
+    total, skipped, ys, yhats = 0.0, 0, [], []
+    with torch.set_grad_enabled(training):
+        for first in range(0, len(graphs), batch_size):
+            batch = Batch.from_data_list(graphs[first:first + batch_size])
+            if training:
+                optimizer.zero_grad()
+            res = _forward(model, batch, kind, output_dim)
+            if res is None:
+                skipped += batch.num_graphs
+                continue
+            out, y = res
+            loss = criterion(out, y)
+            if training:
+                loss.backward()
+                optimizer.step()
+            total += float(loss.item()) * y.shape[0]
+            ys.append(y.detach())
+            yhats.append(out.detach())
+    r2 = r2_uniform(torch.cat(ys), torch.cat(yhats)) if ys else float("nan")
+    return {"loss": total / max(len(graphs), 1), "r2": r2, "skipped": skipped}
+
+
+def _snapshot(model) -> Dict[str, torch.Tensor]:
+    return {k: v.detach().clone() for k, v in model.state_dict().items()}
+
+
+def train(model, graphs: Sequence[Data], kind: str, *, dtype=torch.float32, batch_size: int = 512,
+          num_epochs: int = 35, patience: int = 10, lr: float = 0.1, momentum: float = 0.9, step_size: int = 10,
+          gamma: float = 0.5, chunk_fraction: float = 0.10, output_dim: int = 3,
+          on_epoch=None) -> Dict[str, object]:
+    """Train ``model`` (an ``oracle.sparse`` model, modified in place) on ``graphs`` as the reference scripts do.
+
+    ``on_epoch(epoch, model)`` is called after each epoch's validation (a hook for tests).  Returns the histories, the
+    learning rate used in every epoch, the early-stopping outcome, the final and the best-epoch ``state_dict`` and the
+    momentum buffers in parameter order."""
+    if kind not in ("topological", "lightpath"):
+        raise ValueError(kind)
+    model.to(dtype)
+    graphs = [_cast(g, dtype) for g in graphs]
+    train_idx, val_idx, _ = split(len(graphs))
+    train_graphs = [graphs[i] for i in train_idx]
+    val_graphs = [graphs[i] for i in val_idx]
+    params = [p for p in model.parameters() if p.requires_grad]
+    optimizer = torch.optim.SGD(params, lr=lr, momentum=momentum)
+    scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=step_size, gamma=gamma)
+    criterion = torch.nn.SmoothL1Loss()
+    stopper = EarlyStopping(patience)
+    res: Dict[str, object] = {"loss": [], "r2": [], "val_loss": [], "val_r2": [], "lr": [], "skipped_graphs": 0,
+                              "stopped_early": False, "epochs_run": 0, "best_state_dict": None}
+    for epoch in range(num_epochs):
+        chunk = [train_graphs[i] for i in chunk_indices(epoch, len(train_graphs), chunk_fraction)]
+        res["lr"].append(float(optimizer.param_groups[0]["lr"]))
+        t = _one_pass(model, chunk, kind, batch_size, output_dim, criterion, optimizer)
+        v = _one_pass(model, val_graphs, kind, batch_size, output_dim, criterion)
+        res["loss"].append(t["loss"]); res["r2"].append(t["r2"])
+        res["val_loss"].append(v["loss"]); res["val_r2"].append(v["r2"])
+        res["skipped_graphs"] += t["skipped"]
+        res["epochs_run"] = epoch + 1
+        if on_epoch is not None:
+            on_epoch(epoch, model)
+        improved, stop = stopper.update(epoch, v["r2"])
+        if improved:
+            res["best_state_dict"] = _snapshot(model)
+        if stop:
+            res["stopped_early"] = True
+            break
+        scheduler.step()
+    res["best_val_r2"] = stopper.best
+    res["best_epoch"] = stopper.best_epoch
+    res["state_dict"] = _snapshot(model)
+    res["momentum_buffers"] = [
+        optimizer.state[p]["momentum_buffer"].detach().clone()
+        if p in optimizer.state and optimizer.state[p].get("momentum_buffer") is not None else torch.zeros_like(p)
+        for p in params]
+    return res

@@ -139,7 +139,17 @@ def test_replayed_training_equals_eager_training():
     for replay in (False, True):
         m = copy.deepcopy(lbase)
         lruns[replay] = Hn.fit(m, shard, kind="lightpath", batch_size=4, num_epochs=5, chunk_fraction=0.5,
-                               log=lambda s: None, replay=replay)
-    assert lruns[True].skipped_graphs == lruns[False].skipped_graphs > 0
-    np.testing.assert_allclose(lruns[True].loss, lruns[False].loss, rtol=2e-4)
-    np.testing.assert_allclose(lruns[True].val_loss, lruns[False].val_loss, rtol=2e-4)
+                               log=lambda s: None, replay=replay), m
+    (lh0, lm0), (lh1, lm1) = lruns[False], lruns[True]
+    assert lh1.skipped_graphs == lh0.skipped_graphs > 0
+    # the same kernels on the same inputs in the same order: 2e-5 (it was 2e-4 while the replayed run left the running
+    # statistics alone on later visits of the LUT-less batch, which moved the validation loss by up to 1e-3)
+    np.testing.assert_allclose(lh1.loss, lh0.loss, rtol=2e-5)
+    np.testing.assert_allclose(lh1.val_loss, lh0.val_loss, rtol=2e-5)
+    np.testing.assert_allclose(lh1.val_r2, lh0.val_r2, rtol=2e-5, atol=2e-5)
+    for a, b in zip(lm0.parameters(), lm1.parameters()):
+        assert float((a - b).abs().max()) <= 2e-5 * max(float(b.abs().max()), 1e-3)
+    sd0, sd1 = lm0.state_dict(), lm1.state_dict()
+    for k in ("norm1.module.running_mean", "norm1.module.running_var"):
+        assert float((sd0[k] - sd1[k]).abs().max()) <= 2e-5 * max(float(sd0[k].abs().max()), 1e-3), k
+    assert int(sd0["norm1.module.num_batches_tracked"]) == int(sd1["norm1.module.num_batches_tracked"]) > 0
