@@ -1,0 +1,245 @@
+// Device-side staging of a slice of an HBM-resident shard into the static buffers of a batch slot
+// (loader.StageSlot; the streamed replay of harness.StepReplayer).
+//
+// A captured train step reads its batch through fixed device pointers.  To run a DIFFERENT batch on every replay of
+// ONE captured graph, the launch below -- captured in front of the step -- copies graphs [lo, lo + B) of the shard into
+// those buffers, and takes `lo` from device memory: a control block holds this epoch's schedule of `lo` values and a
+// position that the launch itself advances.  No kernel argument changes between replays, nothing is allocated, the
+// host is not involved.
+//
+// Two kernels per call:
+//   stage_plan_kernel   one workgroup.  Reads the position, takes schedule[position], validates the slice against
+//                       the slot (range, node / edge totals, every graph within (max_nodes, max_edges)), writes the
+//                       verdict -- `lo`, or -1 -- into the control block's snapshot word and advances the position
+//                       (as step_advance_kernel does for the dropout counter: the copy's workgroups all read the
+//                       snapshot, none can see a half-advanced position).  A violation ORs a bit into `status`.
+//   stage_copy_kernel   the copy, grid-stride over every field.  Returns at once when the snapshot is -1, so a
+//                       structural violation stages NOTHING.  Given the plan's checks every load stays inside the
+//                       shard's arrays and every store inside the slot's buffers (sized exactly B, N, E).
+//                       int64 fields (edge_index rows, ptr, edge_ptr, batch, node_ids) are copied two per lane with
+//                       a 16-byte store (and a 16-byte load when the slice's byte offset allows: slices start at
+//                       arbitrary e0 * 8 bytes; else two 8-byte loads), re-based on the way; fp32 fields (edge_attr, x,
+//                       y) four dwords per lane likewise (slices start at e0 * D * 4 bytes), dword head / tail.
+//                       A node id outside [0, V) is staged as 0 and flagged: the step that follows gathers no row
+//                       outside the embedding table, and the host raises from `status` at the end of the epoch.
+//
+// Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+//   stage_plan_kernel  VGPRs 16, AGPRs 0, SGPRs 50, scratch 0, LDS 272 B, occupancy 8 waves / SIMD
+//   stage_copy_kernel  VGPRs 18, AGPRs 0, SGPRs 80, scratch 0, LDS 0,     occupancy 8 waves / SIMD
+// At the headline shape (1024 graphs x 100 nodes / 400 edges, D = 4) the copy moves ~15 MB (read + write ~30 MB).
+#include "common.hpp"
+
+namespace qot {
+
+typedef long long ll2_t __attribute__((ext_vector_type(2)));
+typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+
+constexpr int kStagePos = 0, kStageCount = 1, kStageSnap = 2, kStageHeader = 4;
+
+struct StageShard {
+    const int64_t* node_ptr;        // [G + 1]
+    const int64_t* edge_ptr;        // [G + 1]
+    const int64_t* graph_of_node;   // [N_total]
+    const int64_t* edge_index;      // [2, E_total]
+    const uint32_t* edge_attr;      // [E_total, D] dwords, or NULL
+    const int64_t* node_ids;        // [N_total], or NULL
+    const uint32_t* x;              // [N_total, F] dwords, or NULL
+    const uint32_t* y;              // [G, Y] dwords, or NULL
+    int64_t G, N_total, E_total;
+    int D, F, Y;
+};
+
+struct StageSlot {
+    int64_t* edge_index;            // [2, E]
+    uint32_t* edge_attr;
+    int64_t* node_ids;
+    uint32_t* x;
+    uint32_t* y;
+    int64_t* ptr;                   // [B + 1]
+    int64_t* edge_ptr;              // [B + 1]
+    int64_t* batch;                 // [N]
+    int64_t B, N, E, max_n, max_m, V;
+};
+
+__global__ __launch_bounds__(256) void stage_plan_kernel(int64_t* __restrict__ ctl, int64_t sched_cap,
+                                                         int32_t* __restrict__ status, const int64_t* __restrict__ node_ptr,
+                                                         const int64_t* __restrict__ edge_ptr, int64_t G, int64_t N_total,
+                                                         int64_t E_total, int64_t B, int64_t N, int64_t E, int64_t max_n,
+                                                         int64_t max_m) {
+    __shared__ int64_t s_lo;
+    __shared__ int s_bits;
+    if (threadIdx.x == 0) {
+        int bits = 0;
+        int64_t lo = -1;
+        const int64_t pos = ctl[kStagePos];
+        int64_t cnt = ctl[kStageCount];
+        if (cnt > sched_cap) cnt = sched_cap;
+        if (pos < 0 || pos >= cnt) {
+            bits |= QOT_STAGE_BAD_RANGE;                 // the schedule is used up: the position stays where it is
+        } else {
+            lo = ctl[kStageHeader + pos];
+            ctl[kStagePos] = pos + 1;
+            if (lo < 0 || lo > G - B) {
+                bits |= QOT_STAGE_BAD_RANGE;
+            } else {
+                const int64_t n0 = node_ptr[lo], n1 = node_ptr[lo + B], e0 = edge_ptr[lo], e1 = edge_ptr[lo + B];
+                if (n0 < 0 || n1 > N_total || e0 < 0 || e1 > E_total) bits |= QOT_STAGE_BAD_RANGE;
+                else if (n1 - n0 != N || e1 - e0 != E) bits |= QOT_STAGE_BAD_SHAPE;
+            }
+        }
+        s_lo = bits ? -1 : lo;
+        s_bits = bits;
+    }
+    __syncthreads();
+    const int64_t lo = s_lo;
+    int bad = 0;
+    if (lo >= 0) {
+        for (int64_t g = threadIdx.x; g < B; g += blockDim.x) {
+            const int64_t n = node_ptr[lo + g + 1] - node_ptr[lo + g], m = edge_ptr[lo + g + 1] - edge_ptr[lo + g];
+            if (n < 0 || n > max_n || m < 0 || m > max_m) bad = 1;
+        }
+    }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) {
+        const int bits = s_bits | (bad ? QOT_STAGE_BAD_SHAPE : 0);
+        ctl[kStageSnap] = bits ? -1 : lo;
+        if (bits) atomicOr(status, bits);
+    }
+}
+
+// dst[i] = src[i] - sub, i < n.  dst and src are 8-byte aligned.  CHECK: values outside [0, V) are stored as 0 and
+// reported through the return value.
+template <bool CHECK>
+__device__ __forceinline__ bool stage_i64(int64_t* __restrict__ dst, const int64_t* __restrict__ src, int64_t n, int64_t sub,
+                                          int64_t V, int64_t tid, int64_t nthreads) {
+    bool flagged = false;
+    auto fix = [&](int64_t v) -> int64_t {
+        v -= sub;
+        if (CHECK && (v < 0 || v >= V)) { flagged = true; v = 0; }
+        return v;
+    };
+    if (n <= 0) return false;
+    const int64_t head = (reinterpret_cast<uintptr_t>(dst) & 15u) ? 1 : 0;      // elements in front of the first 16-byte line
+    const int64_t pairs = (n - head) >> 1;
+    const bool src16 = (reinterpret_cast<uintptr_t>(src + head) & 15u) == 0;    // uniform over the launch
+    if (src16) {
+        for (int64_t p = tid; p < pairs; p += nthreads) {
+            const int64_t i = head + 2 * p;
+            const ll2_t v = *reinterpret_cast<const ll2_t*>(src + i);
+            ll2_t o;
+            o.x = fix(v.x);
+            o.y = fix(v.y);
+            *reinterpret_cast<ll2_t*>(dst + i) = o;
+        }
+    } else {
+        for (int64_t p = tid; p < pairs; p += nthreads) {
+            const int64_t i = head + 2 * p;
+            ll2_t o;
+            o.x = fix(src[i]);
+            o.y = fix(src[i + 1]);
+            *reinterpret_cast<ll2_t*>(dst + i) = o;
+        }
+    }
+    if (tid == 0) {
+        if (head) dst[0] = fix(src[0]);
+        const int64_t done = head + 2 * pairs;
+        if (done < n) dst[done] = fix(src[done]);
+    }
+    return flagged;
+}
+
+// dst[i] = src[i], i < n dwords.  dst and src are 4-byte aligned.
+__device__ __forceinline__ void stage_u32(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, int64_t n, int64_t tid,
+                                          int64_t nthreads) {
+    if (n <= 0) return;
+    int64_t head = ((16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2;
+    if (head > n) head = n;
+    const int64_t quads = (n - head) >> 2;
+    const int64_t tail0 = head + 4 * quads;
+    const bool src16 = (reinterpret_cast<uintptr_t>(src + head) & 15u) == 0;
+    if (src16) {
+        for (int64_t q = tid; q < quads; q += nthreads) {
+            const int64_t i = head + 4 * q;
+            *reinterpret_cast<u4_t*>(dst + i) = *reinterpret_cast<const u4_t*>(src + i);
+        }
+    } else {
+        for (int64_t q = tid; q < quads; q += nthreads) {
+            const int64_t i = head + 4 * q;
+            u4_t o;
+            o.x = src[i];
+            o.y = src[i + 1];
+            o.z = src[i + 2];
+            o.w = src[i + 3];
+            *reinterpret_cast<u4_t*>(dst + i) = o;
+        }
+    }
+    if (tid < head) dst[tid] = src[tid];
+    if (tid < n - tail0) dst[tail0 + tid] = src[tail0 + tid];
+}
+
+__global__ __launch_bounds__(256) void stage_copy_kernel(const int64_t* __restrict__ ctl, int32_t* __restrict__ status,
+                                                         StageShard s, StageSlot d) {
+    const int64_t lo = ctl[kStageSnap];
+    if (lo < 0) return;                                  // the plan refused the slice: nothing is staged
+    const int64_t n0 = s.node_ptr[lo], e0 = s.edge_ptr[lo];
+    const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+    stage_i64<false>(d.edge_index, s.edge_index + e0, d.E, n0, 0, tid, nth);
+    stage_i64<false>(d.edge_index + d.E, s.edge_index + s.E_total + e0, d.E, n0, 0, tid, nth);
+    if (s.edge_attr) stage_u32(d.edge_attr, s.edge_attr + e0 * s.D, d.E * s.D, tid, nth);
+    if (s.x) stage_u32(d.x, s.x + n0 * s.F, d.N * s.F, tid, nth);
+    if (s.y) stage_u32(d.y, s.y + lo * s.Y, d.B * s.Y, tid, nth);
+    stage_i64<false>(d.batch, s.graph_of_node + n0, d.N, lo, 0, tid, nth);
+    stage_i64<false>(d.ptr, s.node_ptr + lo, d.B + 1, n0, 0, tid, nth);
+    stage_i64<false>(d.edge_ptr, s.edge_ptr + lo, d.B + 1, e0, 0, tid, nth);
+    if (s.node_ids) {
+        bool flagged;
+        if (d.V > 0) flagged = stage_i64<true>(d.node_ids, s.node_ids + n0, d.N, 0, d.V, tid, nth);
+        else         flagged = stage_i64<false>(d.node_ids, s.node_ids + n0, d.N, 0, 0, tid, nth);
+        if (flagged) atomicOr(status, QOT_STAGE_BAD_NODE_ID);
+    }
+}
+
+}  // namespace qot
+
+using namespace qot;
+
+extern "C" int qot_shard_stage(int64_t* ctl, int64_t sched_cap, int32_t* status, const int64_t* node_ptr,
+                               const int64_t* edge_ptr, const int64_t* graph_of_node, int64_t G, int64_t N_total,
+                               int64_t E_total, const int64_t* edge_index, const void* edge_attr, int D,
+                               const int64_t* node_ids, const void* x, int F, const void* y, int Y, int64_t B, int64_t N,
+                               int64_t E, int64_t max_nodes, int64_t max_edges, int64_t V, int64_t* dst_edge_index,
+                               void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x, void* dst_y, int64_t* dst_ptr,
+                               int64_t* dst_edge_ptr, int64_t* dst_batch, qot_stream_t stream) {
+    if (!ctl || !status || !node_ptr || !edge_ptr || !graph_of_node || !dst_ptr || !dst_edge_ptr) return QOT_ERR_BADARG;
+    if (sched_cap < 1 || G < 1 || N_total < 0 || E_total < 0 || B < 1 || N < 0 || E < 0 || max_nodes < 0 || max_edges < 0 || V < 0)
+        return QOT_ERR_BADARG;
+    if (D < 0 || F < 0 || Y < 0) return QOT_ERR_BADARG;
+    if ((E > 0 && (!edge_index || !dst_edge_index)) || (N > 0 && !dst_batch)) return QOT_ERR_BADARG;
+    if ((edge_attr && E > 0 && D > 0 && !dst_edge_attr) || (node_ids && N > 0 && !dst_node_ids) || (x && N > 0 && F > 0 && !dst_x) ||
+        (y && Y > 0 && !dst_y))
+        return QOT_ERR_BADARG;
+    StageShard s;
+    s.node_ptr = node_ptr; s.edge_ptr = edge_ptr; s.graph_of_node = graph_of_node; s.edge_index = edge_index;
+    s.edge_attr = D > 0 ? (const uint32_t*)edge_attr : nullptr;
+    s.node_ids = node_ids;
+    s.x = F > 0 ? (const uint32_t*)x : nullptr;
+    s.y = Y > 0 ? (const uint32_t*)y : nullptr;
+    s.G = G; s.N_total = N_total; s.E_total = E_total; s.D = D; s.F = F; s.Y = Y;
+    StageSlot d;
+    d.edge_index = dst_edge_index; d.edge_attr = (uint32_t*)dst_edge_attr; d.node_ids = dst_node_ids;
+    d.x = (uint32_t*)dst_x; d.y = (uint32_t*)dst_y; d.ptr = dst_ptr; d.edge_ptr = dst_edge_ptr; d.batch = dst_batch;
+    d.B = B; d.N = N; d.E = E; d.max_n = max_nodes; d.max_m = max_edges; d.V = V;
+    hipStream_t st = (hipStream_t)stream;
+    stage_plan_kernel<<<1, 256, 0, st>>>(ctl, sched_cap, status, node_ptr, edge_ptr, G, N_total, E_total, B, N, E, max_nodes,
+                                         max_edges);
+    QOT_LAUNCH_CHECK();
+    // 16-byte units of the whole copy; four per thread, at most 1024 workgroups (4 per CU)
+    const int64_t bytes = 16 * E + 4 * E * (int64_t)D + 16 * N + 4 * N * (int64_t)F + 4 * B * (int64_t)Y + 16 * (B + 1);
+    int64_t grid = (bytes / 16 + 256 * 4 - 1) / (256 * 4);
+    if (grid < 1) grid = 1;
+    if (grid > 1024) grid = 1024;
+    stage_copy_kernel<<<(int)grid, 256, 0, st>>>(ctl, status, s, d);
+    QOT_LAUNCH_CHECK();
+    return QOT_OK;
+}

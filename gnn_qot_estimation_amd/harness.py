@@ -27,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from .dp import FlatModel, FusedSGD, graph_range, loss_scale
-from .loader import GraphLoader, PackedGraphs
+from .loader import GraphLoader, PackedGraphs, StageSlot, check_stage_status
 
 # data constants of the reference's label scaling (constants.py:8-12), used at test.py:95-99
 TARGET_RANGES = {
@@ -127,6 +127,9 @@ class History:
     stopped_early: bool = False
     best_val_r2: float = float("-inf")
     epochs_run: int = 0
+    # how the steps of a replayed run were issued (``StepReplayer.counts``): visits run eagerly / captured (and replayed
+    # once) / replayed, and the number of captured graphs the run holds at its end; empty without a replayer
+    replay_counts: Dict[str, int] = field(default_factory=dict)
 
     def dump(self, directory: str):
         """loss_history.json etc. as the reference writes them (train.py:213-226)."""
@@ -165,6 +168,41 @@ def _local_batches(idx: Sequence[int], batch_size: int, rank: int, world: int, c
     return out
 
 
+def batch_ranges(indices: range, batch_size: int) -> List[Tuple[int, int]]:
+    """``[lo, hi)`` of every batch of ``batch_size`` consecutive graphs of ``indices`` (a ``range`` with step 1), in order."""
+    if not isinstance(indices, range) or indices.step != 1:
+        raise ValueError("streamed replay walks consecutive graphs: indices must be a range with step 1")
+    return [(b0, min(b0 + batch_size, indices.stop)) for b0 in range(indices.start, indices.stop, batch_size)]
+
+
+def batch_shape(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, lo: int, hi: int) -> Tuple[int, int, int]:
+    """``(B, N, E)`` of graphs ``[lo, hi)``: what decides which static slot (and which captured graph) runs them."""
+    return hi - lo, int(node_ptr[hi]) - int(node_ptr[lo]), int(edge_ptr[hi]) - int(edge_ptr[lo])
+
+
+def stream_schedule(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ranges: Sequence[Tuple[int, int]]
+                    ) -> Dict[Tuple[int, int, int], List[int]]:
+    """The batches of one epoch grouped by shape: ``{(B, N, E): [lo, ...]}``, every list in visiting order (pure host
+    arithmetic on the shard's offsets).  One static slot and one captured graph serve each key."""
+    out: Dict[Tuple[int, int, int], List[int]] = {}
+    for lo, hi in ranges:
+        out.setdefault(batch_shape(node_ptr, edge_ptr, lo, hi), []).append(lo)
+    return out
+
+
+def check_stream(dataset, kind: str, world: int) -> None:
+    """``stream=True`` needs a TopologicalGNN run on an HBM-resident shard in a single process."""
+    if kind != "topological":
+        raise ValueError("stream=True needs kind='topological': LightpathGNN's LUT row count is data-dependent and its "
+                         "skip rule is decided on the host per batch (it keeps the per-batch replay)")
+    if not isinstance(dataset, PackedGraphs) or dataset.device is None:
+        raise ValueError("stream=True needs an HBM-resident shard (PackedGraphs.to_device): batches are staged on the "
+                         "device from the shard's flat tensors")
+    if world != 1:
+        raise ValueError("stream=True needs a single process: a data-parallel rank's share and loss scale are per "
+                         "batch (it keeps the per-batch replay)")
+
+
 class StepReplayer:
     """HIP-graph replay of whole steps over the cached batches of an HBM-resident shard.
 
@@ -182,11 +220,33 @@ class StepReplayer:
     ONE all-reduce of the flat gradient and the update -- the N > 1 step is the N = 1 step plus that exchange.  Every rank
     must visit the same sequence of batches (``_local_batches`` guarantees it).  LightpathGNN under data parallelism keeps
     the eager loop: its BatchNorm exchange and the LUT skip are decided per global batch on the host.
+
+    Streamed replay (``stream=True`` with the resident ``shard``; TopologicalGNN, single process): one captured graph per
+    batch SHAPE and direction instead of one per batch object.  ``run`` then takes a range ``(lo, hi)``; every batch goes
+    through the static slot of its ``(B, N, E, training)`` (``loader.StageSlot``): the captured graph is ``stage + step``,
+    the stage launch takes its ``lo`` from the slot's device-side schedule (``begin_epoch`` writes it once per epoch), so
+    every batch of a shape -- first visits and single-epoch runs included -- replays the same graph, and the run holds
+    as many graphs, cached indices and pool blocks as it has distinct shapes.  A slot's first use runs eagerly, its
+    second is captured.  CACHE RULE: the stage launch rewrites the slot's tensors through raw pointers, their
+    ``_version`` never moves, and every per-batch cache of ``graph.py`` (``graph_index_for``, ``batch_ptr_for``,
+    ``cached_i32``, ``table_maps_for``, the checked node ids) is keyed by ``(data_ptr, _version, shape)``: left alone
+    they would serve the PREVIOUS batch's index.  So the slot's ``_qot_cache`` is emptied before the eager visit and
+    before the capture; the index build, the int32 narrowing and the table maps are then recorded inside the graph and
+    run again on every replay.  No staged batch goes through host-side checks: the stage launch validates on the device
+    and ``end_epoch`` raises from its status word (and from the index build's) once per epoch.
     """
 
     def __init__(self, model, kind: str, out_dim: int, device, flat: Optional[FlatModel], opt: Optional[FusedSGD],
-                 collective: bool = False):
+                 collective: bool = False, stream: Optional[bool] = None, shard: Optional[PackedGraphs] = None):
         self.model, self.kind, self.out_dim, self.device = model, kind, out_dim, device
+        self.stream = bool(stream)
+        if self.stream:
+            check_stream(shard, kind, 2 if collective else 1)
+        self.shard = shard
+        self.slots: Dict[Tuple[int, int, int, bool], StageSlot] = {}
+        self._stage_status = torch.zeros(1, dtype=torch.int32, device=device) if self.stream else None
+        self.schedule_capacity: Optional[int] = None   # batches of one shape per epoch (default: one pass over the shard)
+        self.counts = {"eager": 0, "captured": 0, "replayed": 0}
         self.flat, self.opt = flat, opt
         self.collective = bool(collective)
         self._scale: Dict[int, torch.Tensor] = {}      # per batch object: this rank's share of the global mean loss
@@ -234,7 +294,10 @@ class StepReplayer:
         self.stats[training].update(y, out, self._loss)
 
     def run(self, data, training: bool) -> bool:
-        """One step on ``data``; returns False when the batch is (remembered as) skipped."""
+        """One step on ``data`` (streamed replay: on graphs ``data = (lo, hi)`` of the shard); returns False when the
+        batch is (remembered as) skipped."""
+        if self.stream:
+            return self._run_streamed(data, training)
         key = (id(data), training)
         if key in self.skip:
             if training:
@@ -251,6 +314,7 @@ class StepReplayer:
         g = self.graphs.get(key)
         if g is not None:
             g.replay()
+            self.counts["replayed"] += 1
             return True
         seen = self.visits.get(key, 0)
         self.model.train(training)
@@ -263,6 +327,7 @@ class StepReplayer:
                 return False
             self.visits[key] = 1
             self._keep.append(data)
+            self.counts["eager"] += 1
             return True
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
@@ -272,15 +337,95 @@ class StepReplayer:
             self._step(data, training)
         self.graphs[key] = g
         g.replay()                      # capture records, it does not execute
+        self.counts["captured"] += 1
+        return True
+
+    # ---- streamed replay ------------------------------------------------------------------------------------------
+    def replay_counts(self) -> Dict[str, int]:
+        return dict(self.counts, graphs=len(self.graphs))
+
+    def _slot(self, shape: Tuple[int, int, int], training: bool) -> StageSlot:
+        key = shape + (bool(training),)
+        slot = self.slots.get(key)
+        if slot is None:
+            emb = getattr(self.model, "node_embeddings", None)
+            slot = self.slots[key] = self.shard.stage_slot(*shape, status=self._stage_status,
+                                                           num_embeddings=0 if emb is None else emb.num_embeddings,
+                                                           capacity=self.schedule_capacity)
+        return slot
+
+    def begin_epoch(self, ranges: Sequence[Tuple[int, int]], training: bool) -> None:
+        """Write this epoch's schedules: per shape, the ``lo`` of its batches in visiting order.  ``run`` must then be
+        called with exactly ``ranges``, in order."""
+        G = len(self.shard)
+        for lo, hi in ranges:
+            if not 0 <= lo < hi <= G:
+                raise IndexError(f"graphs [{lo}, {hi}) lie outside a shard of {G} graphs")
+        for shape, los in stream_schedule(self.shard.node_ptr, self.shard.edge_ptr, ranges).items():
+            self._slot(shape, training).set_schedule(los)
+
+    def end_epoch(self) -> None:
+        """Raise what the epoch's device-side checks flagged (two 4-byte reads behind the epoch's host synchronisation)."""
+        from .graph import check_index_status
+        check_stage_status(self._stage_status)
+        check_index_status(self.device)
+
+    def _run_streamed(self, rng: Tuple[int, int], training: bool) -> bool:
+        lo, hi = rng
+        shape = batch_shape(self.shard.node_ptr, self.shard.edge_ptr, lo, hi)
+        key = shape + (bool(training),)
+        g = self.graphs.get(key)
+        if g is not None:
+            g.replay()                  # stage (the schedule's next lo) + step
+            self.counts["replayed"] += 1
+            return True
+        slot = self._slot(shape, training)
+        self.model.train(training)
+        # the stage launch rewrites the slot's tensors behind torch's back: nothing cached on the batch object may survive
+        # into this visit (class docstring, CACHE RULE)
+        slot.batch._qot_cache = {}
+        if self.visits.get(key, 0) == 0 or (training and self.opt.steps == 0):
+            slot.stage()
+            self._step(slot.batch, training)
+            self.visits[key] = 1
+            self.counts["eager"] += 1
+            return True
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self.pool):
+            slot.stage()
+            self._step(slot.batch, training)
+        slot.batch._qot_cache = {}      # what the capture cached lives in the graph's pool: only the graph may use it
+        self.graphs[key] = g
+        g.replay()                      # capture records, it does not execute
+        self.counts["captured"] += 1
         return True
 
 
 def run_epoch(model, dataset, indices: range, *, kind: str, batch_size: int, out_dim: int, device,
               criterion, flat: Optional[FlatModel] = None, opt: Optional[FusedSGD] = None,
-              replayer: Optional[StepReplayer] = None) -> Dict[str, object]:
-    """One pass over ``indices``; trains when ``opt`` is given, else evaluates under ``no_grad``."""
+              replayer: Optional[StepReplayer] = None, stream: Optional[bool] = None) -> Dict[str, object]:
+    """One pass over ``indices``; trains when ``opt`` is given, else evaluates under ``no_grad``.  ``stream=True``
+    (with a ``StepReplayer(stream=True)``): every batch is staged on the device into the static slot of its shape and
+    run by that shape's one captured graph."""
     fwd = _KINDS[kind]
     rank, world = _rank_world()
+    if stream:
+        check_stream(dataset, kind, world)
+        if replayer is None or not replayer.stream or replayer.shard is not dataset:
+            raise ValueError("stream=True needs a StepReplayer(stream=True, shard=dataset)")
+        training = opt is not None
+        ranges = batch_ranges(indices, batch_size)
+        replayer.begin_epoch(ranges, training)
+        st = replayer.stats[training]
+        st.buf.zero_()
+        for r in ranges:
+            replayer.run(r, training)
+        res = st.result()               # the epoch's host synchronisation
+        replayer.end_epoch()            # device-side checks of the staged batches: raises before the results are used
+        res["avg_loss"] = res["loss_sum"] / max(len(indices), 1)
+        res["skipped"] = 0
+        return res
     # an HBM-resident shard keeps its batch objects (and the graph index the model attaches to them):
     # the chunks repeat every few epochs, so later visits do no graph preparation at all
     resident = isinstance(dataset, PackedGraphs) and dataset.device is not None
@@ -386,12 +531,19 @@ def run_epoch(model, dataset, indices: range, *, kind: str, batch_size: int, out
 def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num_epochs: int = 35,
         patience: int = 10, lr: float = 0.1, momentum: float = 0.9, step_size: int = 10, gamma: float = 0.5,
         chunk_fraction: float = 0.10, output_dim: int = 3, device="cuda", best_path: Optional[str] = None,
-        log: Callable[[str], None] = print, replay: Optional[bool] = None) -> History:
+        log: Callable[[str], None] = print, replay: Optional[bool] = None, stream: Optional[bool] = None) -> History:
     """The training script's main loop (train.py:24-182) on a dataset object indexable by graph.
 
     ``replay`` (default: on for an HBM-resident shard in a single process): steps over cached batches are
-    captured as HIP graphs on their second visit and replayed afterwards (``StepReplayer``)."""
+    captured as HIP graphs on their second visit and replayed afterwards (``StepReplayer``).
+    ``stream`` (default off; needs an HBM-resident shard, ``kind="topological"`` and a single process, else
+    ``ValueError``): streamed replay -- one captured graph per batch shape, every batch staged into that shape's static
+    buffers on the device, so first visits and single-epoch runs replay too.  ``History.replay_counts`` tells which
+    path the steps took."""
     device = torch.device(device)
+    stream = bool(stream)
+    if stream:
+        check_stream(dataset, kind, _rank_world()[1])
     model.to(device)
     tr, va, _ = split_ranges(len(dataset))
     flat = FlatModel(model)
@@ -400,9 +552,12 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
     resident = isinstance(dataset, PackedGraphs) and dataset.device is not None
     # more than one rank: replayed steps hold the RCCL all-reduce (nccl backend, TopologicalGNN; StepReplayer docstring)
     dp_ok = world == 1 or (kind == "topological" and dist.get_backend() == "nccl")
-    use_replay = (resident and dp_ok) if replay is None else (bool(replay) and resident and dp_ok)
+    use_replay = stream or ((resident and dp_ok) if replay is None else (bool(replay) and resident and dp_ok))
     opt = FusedSGD(flat, lr=lr, momentum=momentum, device_lr=use_replay)
-    replayer = StepReplayer(model, kind, output_dim, device, flat, opt, collective=world > 1) if use_replay else None
+    replayer = None
+    if use_replay:
+        replayer = StepReplayer(model, kind, output_dim, device, flat, opt, collective=world > 1, stream=stream,
+                                shard=dataset if stream else None)
     criterion = torch.nn.SmoothL1Loss()
     hist = History()
     counter = 0
@@ -413,9 +568,11 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
         opt.lr = step_lr(lr, epoch, step_size, gamma)
         t = run_epoch(model, dataset, range(tr[0] + chunk[0], tr[0] + chunk[-1] + 1) if len(chunk) else range(0),
                       kind=kind, batch_size=batch_size, out_dim=output_dim, device=device, criterion=criterion,
-                      flat=flat, opt=opt, replayer=replayer)
+                      flat=flat, opt=opt, replayer=replayer, stream=stream)
         v = run_epoch(model, dataset, va, kind=kind, batch_size=batch_size, out_dim=output_dim, device=device,
-                      criterion=criterion, replayer=replayer)
+                      criterion=criterion, replayer=replayer, stream=stream)
+        if replayer is not None:
+            hist.replay_counts = replayer.replay_counts()
         hist.loss.append(t["avg_loss"]); hist.r2.append(t["r2"])
         hist.val_loss.append(v["avg_loss"]); hist.val_r2.append(v["r2"])
         hist.skipped_graphs += t["skipped"]

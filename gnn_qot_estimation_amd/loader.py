@@ -210,6 +210,12 @@ class PackedGraphs:
             self._batch_cache[(lo, hi)] = out
         return out
 
+    def stage_slot(self, B: int, N: int, E: int, status: Optional[torch.Tensor] = None,
+                   num_embeddings: int = 0, capacity: Optional[int] = None) -> "StageSlot":
+        """A static ``Batch`` for slices of ``B`` graphs, ``N`` nodes and ``E`` edges of this resident shard, filled on
+        the device by ``StageSlot.stage()`` (``qot_shard_stage``): the buffers a captured step reads."""
+        return StageSlot(self, B, N, E, status=status, num_embeddings=num_embeddings, capacity=capacity)
+
     def __getitem__(self, g: int) -> Data:
         n0, n1 = int(self.node_ptr[g]), int(self.node_ptr[g + 1])
         e0, e1 = int(self.edge_ptr[g]), int(self.edge_ptr[g + 1])
@@ -264,6 +270,115 @@ class PackedGraphs:
             st.event.record(copy_stream)
         out._qot_ready = st.event
         return out
+
+
+# status bits of qot_shard_stage (include/qot_gnn.h: QOT_STAGE_*)
+STAGE_BAD_SHAPE, STAGE_BAD_RANGE, STAGE_BAD_NODE_ID = 1, 2, 4
+
+
+def check_stage_status(status: torch.Tensor) -> None:
+    """Raise what the staging launches since the last call have flagged (one 4-byte host read; the word is cleared).
+    A node id outside the embedding table is the ``IndexError`` ``nn.Embedding`` raises; a schedule entry that does not
+    fit its slot is a ``QotError``."""
+    from . import _lib
+    code = int(status.item())
+    if not code:
+        return
+    status.zero_()
+    if code & (STAGE_BAD_SHAPE | STAGE_BAD_RANGE):
+        what = []
+        if code & STAGE_BAD_RANGE:
+            what.append("a graph slice lies outside the node / edge arrays (or the schedule was used up)")
+        if code & STAGE_BAD_SHAPE:
+            what.append("a slice does not hold the slot's node / edge counts or exceeds (max_nodes, max_edges)")
+        raise _lib.QotError("qot_shard_stage: inconsistent batch slices (" + "; ".join(what) + "): nothing was staged "
+                            "for them and the steps that followed ran on the slot's previous batch")
+    raise IndexError("index out of range in self")
+
+
+class StageSlot:
+    """Static batch buffers for ONE batch shape ``(B graphs, N nodes, E edges)`` of an HBM-resident shard.
+
+    ``batch`` is a ``Batch`` whose tensors are allocated once; ``stage()`` fills them, in one launch on the current
+    stream, with graphs ``[lo, lo + B)`` of the shard -- exactly what ``PackedGraphs.device_batch(lo, lo + B)`` hands
+    out -- where ``lo`` is the next entry of a schedule that lives in device memory (``set_schedule``).  A captured
+    ``stage()`` therefore stages a different slice on every replay.  The shard-level hints (``uniform_node_ids``,
+    ``graph_sizes``, ``has_self_loops``) are the shard's.
+
+    The launch rewrites the buffers through raw pointers: their ``_version`` never moves, so everything ``graph.py``
+    caches on the batch object (graph index, int32 copies, table maps, checked node ids) goes stale with every
+    ``stage()``.  Whoever runs a model on ``batch`` resets ``batch._qot_cache = {}`` first (``harness.StepReplayer``
+    does, before the eager visit and before the capture, so that those builds are recorded inside the graph).
+
+    The device validates each slice (see ``qot_shard_stage``) and reports through ``status`` (int32 word, shared
+    between slots when given): ``check_stage_status``.  ``capacity``: the longest schedule the slot takes (default: the
+    batches of one pass over the shard; the control block is part of the captured launch and never grows).  The schedule holds graph offsets today; a gather list of
+    single graphs (shuffled batches) would be another schedule format behind the same slot."""
+
+    def __init__(self, shard: "PackedGraphs", B: int, N: int, E: int, status: Optional[torch.Tensor] = None,
+                 num_embeddings: int = 0, capacity: Optional[int] = None):
+        if not isinstance(shard, PackedGraphs) or shard.device is None:
+            raise ValueError("a batch slot stages from an HBM-resident shard (PackedGraphs.to_device)")
+        B, N, E = int(B), int(N), int(E)
+        if B < 1 or N < 0 or E < 0:
+            raise ValueError("a batch slot needs B >= 1, N >= 0, E >= 0")
+        dev = shard.device
+        G = len(shard)
+        for name, rows in (("edge_attr", int(shard.edge_ptr[-1])), ("x", int(shard.node_ptr[-1])),
+                           ("y", G * shard.y_rows)):
+            t = getattr(shard, name)
+            if t is not None and (t.element_size() != 4 or not t.is_contiguous() or t.shape[0] != rows):
+                raise ValueError(f"shard.{name}: a contiguous tensor of 4-byte elements with {rows} rows is staged, got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+        if not shard.edge_index.is_contiguous() or (shard.node_ids is not None and not shard.node_ids.is_contiguous()):
+            raise ValueError("shard.edge_index / node_ids must be contiguous")
+        self.shard, self.B, self.N, self.E = shard, B, N, E
+        self.V = int(num_embeddings)
+        self._totals = (G, int(shard.node_ptr[-1]), int(shard.edge_ptr[-1]), int(shard.graph_sizes[0]), int(shard.graph_sizes[1]))
+        self.capacity = int(capacity) if capacity is not None else G // B + 2
+        # [0] position, [1] entries, [2] snapshot, [3] reserved, [4:] schedule (include/qot_gnn.h)
+        self.ctl = torch.zeros(4 + self.capacity, dtype=torch.long, device=dev)
+        self.status = status if status is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+        rest = lambda t: tuple(t.shape[1:])
+        per = lambda t: int(t[0].numel()) if t.shape[0] else 0       # 4-byte words per row
+        b = Batch()
+        b.num_graphs, b._num_nodes = B, N
+        b.uniform_node_ids = shard.uniform_node_ids
+        b.graph_sizes = shard.graph_sizes
+        b.has_self_loops = False if shard.has_self_loops is False else None
+        z = lambda shape, like: torch.zeros(shape, dtype=like.dtype, device=dev)
+        b.edge_index = z((2, E), shard.edge_index)
+        b.edge_attr = None if shard.edge_attr is None else z((E,) + rest(shard.edge_attr), shard.edge_attr)
+        b.node_ids = None if shard.node_ids is None else z((N,), shard.node_ids)
+        b.x = None if shard.x is None else z((N,) + rest(shard.x), shard.x)
+        b.y = None if shard.y is None else z((B * shard.y_rows,) + rest(shard.y), shard.y)
+        b.ptr = torch.zeros(B + 1, dtype=torch.long, device=dev)
+        b.edge_ptr = torch.zeros(B + 1, dtype=torch.long, device=dev)
+        b.batch = torch.zeros(N, dtype=torch.long, device=dev)
+        self.batch = b
+        self._words = (0 if shard.edge_attr is None else per(shard.edge_attr), 0 if shard.x is None else per(shard.x),
+                       0 if shard.y is None else shard.y_rows * per(shard.y))
+
+    def set_schedule(self, los: Sequence[int]) -> None:
+        """The ``lo`` values the next ``len(los)`` calls of ``stage()`` take, in order (one small copy to the device,
+        ordered on the current stream behind every earlier ``stage()``)."""
+        los = [int(v) for v in los]
+        if len(los) > self.capacity:
+            raise ValueError(f"a schedule of {len(los)} batches exceeds the slot's capacity of {self.capacity}")
+        self.ctl[:4 + len(los)].copy_(torch.tensor([0, len(los), -1, 0] + los, dtype=torch.long))
+
+    def stage(self, lo: Optional[int] = None) -> Batch:
+        """Stage the schedule's next slice (``lo`` given: that slice, as a schedule of one) into ``batch``."""
+        from . import _lib
+        if lo is not None:
+            self.set_schedule([lo])
+        s, b = self.shard, self.batch
+        D, F, Y = self._words
+        G, n_total, e_total, max_n, max_m = self._totals
+        _lib.call("qot_shard_stage", self.ctl, self.capacity, self.status, s.node_ptr_dev, s.edge_ptr_dev, s.graph_of_node,
+                  G, n_total, e_total, s.edge_index, s.edge_attr, D, s.node_ids, s.x, F, s.y, Y, self.B, self.N, self.E,
+                  max_n, max_m, self.V, b.edge_index, b.edge_attr, b.node_ids, b.x, b.y, b.ptr, b.edge_ptr, b.batch)
+        return b
 
 
 class GraphLoader:

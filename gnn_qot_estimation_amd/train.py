@@ -59,6 +59,9 @@ def main(argv=None):
     ap.add_argument("--dropout", type=float, default=0.5)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--host-shard", action="store_true", help="keep the shard in pinned host memory instead of HBM")
+    ap.add_argument("--stream", action="store_true",
+                    help="streamed replay: one captured step graph per batch shape, batches staged on the device "
+                         "(topological, HBM-resident shard, single process)")
     args = ap.parse_args(argv)
 
     from . import LightpathGNN, TopologicalGNN
@@ -83,7 +86,8 @@ def main(argv=None):
         params = {"in_channels": num_features, "hidden_channels": hidden, "output_dim": 3,
                   "NODE_FEATURES": meta.get("NODE_FEATURES"), "feature_indices": fidx}  # lightpath train.py:227-233
     hist = harness.fit(model, dataset, kind=kind, batch_size=args.batch_size, num_epochs=args.epochs,
-                       patience=args.patience, device=device, best_path=os.path.join(root, "best_model.pth"), log=log)
+                       patience=args.patience, device=device, best_path=os.path.join(root, "best_model.pth"), log=log,
+                       stream=True if args.stream else None)
     if kind == "lightpath":
         log(f"Total skipped {hist.skipped_graphs} graphs due to missing LUT nodes.")
     path, k = harness.next_model_path(os.path.join(root, "models"))

@@ -617,6 +617,30 @@ int qot_table_maps(const int64_t* node_ids, const int32_t* col, const int32_t* c
 /* ---- dropout draw counter: *counter += 1 and *snapshot = *counter, on the stream (replay-safe). */
 int qot_step_advance(int64_t* counter, int64_t* snapshot, qot_stream_t stream);
 
+/* ---- streamed replay: stage graphs [lo, lo + B) of an HBM-resident shard into the static buffers of a batch slot, `lo`
+ * taken from DEVICE memory, so that one captured launch stages a different slice on every replay (csrc/stage.hip;
+ * loader.StageSlot).  No counterpart in the reference: its DataLoader collates on the host (train.py:93-95,107).
+ * ctl[4 + sched_cap] (int64, device): [0] position, [1] number of valid schedule entries, [2] snapshot (written by the
+ * call: the `lo` it staged, or -1), [3] reserved, [4 ...] the schedule of `lo` values.  Each call takes
+ * schedule[position] and advances the position on the device.
+ * Shard: node_ptr / edge_ptr [G + 1] and graph_of_node [N_total] (int64, device), edge_index [2, E_total] (int64, numbered
+ * within the shard), and optionally (NULL: absent) edge_attr [E_total, D], node_ids [N_total] (int64), x [N_total, F],
+ * y [G, Y]; D, F, Y count 4-byte words per row.  Slot: buffers for exactly B graphs, N nodes, E edges; what is written is
+ * what PackedGraphs.device_batch(lo, lo + B) hands out (edge_index, ptr, edge_ptr re-based, batch = graph id per node).
+ * Validated on the device before anything is written: the position lies inside the schedule, 0 <= lo <= G - B and the
+ * slice inside the arrays (else QOT_STAGE_BAD_RANGE); the slice holds exactly N nodes and E edges and no graph more than
+ * max_nodes / max_edges (else QOT_STAGE_BAD_SHAPE).  On either, NOTHING is staged.  V > 0: a node id outside [0, V) is
+ * staged as 0 and reported as QOT_STAGE_BAD_NODE_ID.  The bits are ORed into status (device int32, caller-zeroed). */
+#define QOT_STAGE_BAD_SHAPE 1
+#define QOT_STAGE_BAD_RANGE 2
+#define QOT_STAGE_BAD_NODE_ID 4
+int qot_shard_stage(int64_t* ctl, int64_t sched_cap, int32_t* status, const int64_t* node_ptr, const int64_t* edge_ptr,
+                    const int64_t* graph_of_node, int64_t G, int64_t N_total, int64_t E_total, const int64_t* edge_index,
+                    const void* edge_attr, int D, const int64_t* node_ids, const void* x, int F, const void* y, int Y,
+                    int64_t B, int64_t N, int64_t E, int64_t max_nodes, int64_t max_edges, int64_t V,
+                    int64_t* dst_edge_index, void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x, void* dst_y,
+                    int64_t* dst_ptr, int64_t* dst_edge_ptr, int64_t* dst_batch, qot_stream_t stream);
+
 /* ---- out[i] = concat(s0[0:n0], s1[0:n1], s2)[idx[i]]: one gather builds the fragment-ordered NNConv
  * operands from nn.2.weight / nn.2.bias / lin.weight (topological_training/models.py:20-25). */
 int qot_gather3(const float* s0, int64_t n0, const float* s1, int64_t n1, const float* s2, const int32_t* idx,
