@@ -23,9 +23,17 @@
 //                       A node id outside [0, V) is staged as 0 and flagged: the step that follows gathers no row
 //                       outside the embedding table, and the host raises from `status` at the end of the epoch.
 //
+// Padded slots (qot_shard_stage_padded; loader.PaddedStageSlot): batches of B graphs whose edge totals DIFFER go through
+// one slot of B + P graphs and E_cap edges.  The plan kernel accepts a slice that falls short of E_cap by at most
+// P * max_m edges and publishes its edge total next to `lo` (no load it did not already make);
+// stage_copy_padded_kernel copies the real slice as above and then writes P pad graphs that hold the spare edges as
+// rings over their own n nodes, with zero edge features: computed from (E_real, E_cap, P, n, max_m), nothing loaded.
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
-//   stage_plan_kernel  VGPRs 16, AGPRs 0, SGPRs 50, scratch 0, LDS 272 B, occupancy 8 waves / SIMD
-//   stage_copy_kernel  VGPRs 18, AGPRs 0, SGPRs 80, scratch 0, LDS 0,     occupancy 8 waves / SIMD
+//   stage_plan_kernel<false>  VGPRs 16, AGPRs 0, SGPRs 50,  scratch 0, LDS 272 B, occupancy 8 waves / SIMD
+//   stage_plan_kernel<true>   VGPRs 16, AGPRs 0, SGPRs 52,  scratch 0, LDS 280 B, occupancy 8 waves / SIMD
+//   stage_copy_kernel         VGPRs 18, AGPRs 0, SGPRs 92,  scratch 0, LDS 0,     occupancy 8 waves / SIMD
+//   stage_copy_padded_kernel  VGPRs 26, AGPRs 0, SGPRs 105, scratch 0, LDS 0,     occupancy 7 waves / SIMD
 // At the headline shape (1024 graphs x 100 nodes / 400 edges, D = 4) the copy moves ~15 MB (read + write ~30 MB).
 #include "common.hpp"
 
@@ -34,7 +42,7 @@ namespace qot {
 typedef long long ll2_t __attribute__((ext_vector_type(2)));
 typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
 
-constexpr int kStagePos = 0, kStageCount = 1, kStageSnap = 2, kStageHeader = 4;
+constexpr int kStagePos = 0, kStageCount = 1, kStageSnap = 2, kStageEdges = 3, kStageHeader = 4;
 
 struct StageShard {
     const int64_t* node_ptr;        // [G + 1]
@@ -61,16 +69,20 @@ struct StageSlot {
     int64_t B, N, E, max_n, max_m, V;
 };
 
+// PAD (qot_shard_stage_padded): N counts the REAL nodes, E is the slot's edge capacity and a slice may fall short of it by
+// up to pad_cap edges; its own edge total -- already loaded for the check -- goes to the control block's fourth word.
+template <bool PAD>
 __global__ __launch_bounds__(256) void stage_plan_kernel(int64_t* __restrict__ ctl, int64_t sched_cap,
                                                          int32_t* __restrict__ status, const int64_t* __restrict__ node_ptr,
                                                          const int64_t* __restrict__ edge_ptr, int64_t G, int64_t N_total,
                                                          int64_t E_total, int64_t B, int64_t N, int64_t E, int64_t max_n,
-                                                         int64_t max_m) {
+                                                         int64_t max_m, int64_t pad_cap) {
     __shared__ int64_t s_lo;
+    __shared__ int64_t s_edges;
     __shared__ int s_bits;
     if (threadIdx.x == 0) {
         int bits = 0;
-        int64_t lo = -1;
+        int64_t lo = -1, edges = 0;
         const int64_t pos = ctl[kStagePos];
         int64_t cnt = ctl[kStageCount];
         if (cnt > sched_cap) cnt = sched_cap;
@@ -84,10 +96,13 @@ __global__ __launch_bounds__(256) void stage_plan_kernel(int64_t* __restrict__ c
             } else {
                 const int64_t n0 = node_ptr[lo], n1 = node_ptr[lo + B], e0 = edge_ptr[lo], e1 = edge_ptr[lo + B];
                 if (n0 < 0 || n1 > N_total || e0 < 0 || e1 > E_total) bits |= QOT_STAGE_BAD_RANGE;
-                else if (n1 - n0 != N || e1 - e0 != E) bits |= QOT_STAGE_BAD_SHAPE;
+                else if (!PAD && (n1 - n0 != N || e1 - e0 != E)) bits |= QOT_STAGE_BAD_SHAPE;
+                else if (PAD && (n1 - n0 != N || e1 - e0 < 0 || e1 - e0 > E || E - (e1 - e0) > pad_cap)) bits |= QOT_STAGE_BAD_SHAPE;
+                edges = e1 - e0;
             }
         }
         s_lo = bits ? -1 : lo;
+        if (PAD) s_edges = edges;
         s_bits = bits;
     }
     __syncthreads();
@@ -103,6 +118,7 @@ __global__ __launch_bounds__(256) void stage_plan_kernel(int64_t* __restrict__ c
     if (threadIdx.x == 0) {
         const int bits = s_bits | (bad ? QOT_STAGE_BAD_SHAPE : 0);
         ctl[kStageSnap] = bits ? -1 : lo;
+        if (PAD) ctl[kStageEdges] = bits ? 0 : s_edges;
         if (bits) atomicOr(status, bits);
     }
 }
@@ -177,32 +193,133 @@ __device__ __forceinline__ void stage_u32(uint32_t* __restrict__ dst, const uint
     if (tid < n - tail0) dst[tail0 + tid] = src[tail0 + tid];
 }
 
+// dst[i] = f(i), i < n.  dst is 8-byte aligned (pad regions start wherever the real slice ends).
+template <class F>
+__device__ __forceinline__ void stage_fill_i64(int64_t* __restrict__ dst, int64_t n, F f, int64_t tid, int64_t nthreads) {
+    if (n <= 0) return;
+    const int64_t head = (reinterpret_cast<uintptr_t>(dst) & 15u) ? 1 : 0;
+    const int64_t pairs = (n - head) >> 1;
+    for (int64_t p = tid; p < pairs; p += nthreads) {
+        const int64_t i = head + 2 * p;
+        ll2_t o;
+        o.x = f(i);
+        o.y = f(i + 1);
+        *reinterpret_cast<ll2_t*>(dst + i) = o;
+    }
+    if (tid == 0) {
+        if (head) dst[0] = f(0);
+        const int64_t done = head + 2 * pairs;
+        if (done < n) dst[done] = f(done);
+    }
+}
+
+// dst[i] = 0, i < n dwords.  dst is 4-byte aligned.
+__device__ __forceinline__ void stage_zero_u32(uint32_t* __restrict__ dst, int64_t n, int64_t tid, int64_t nthreads) {
+    if (n <= 0) return;
+    int64_t head = ((16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2;
+    if (head > n) head = n;
+    const int64_t quads = (n - head) >> 2;
+    const int64_t tail0 = head + 4 * quads;
+    u4_t z;
+    z.x = 0; z.y = 0; z.z = 0; z.w = 0;
+    for (int64_t q = tid; q < quads; q += nthreads) *reinterpret_cast<u4_t*>(dst + head + 4 * q) = z;
+    if (tid < head) dst[tid] = 0;
+    if (tid < n - tail0) dst[tail0 + tid] = 0;
+}
+
+// Graphs [lo, lo + B) of the shard -- N nodes, E edges -- into the front of the slot's buffers; ld_e: the slot's edge
+// capacity (the distance between the two rows of its edge_index).
+__device__ __forceinline__ void stage_slice(const StageShard& s, const StageSlot& d, int64_t lo, int64_t B, int64_t N, int64_t E,
+                                            int64_t ld_e, int32_t* __restrict__ status, int64_t tid, int64_t nth) {
+    const int64_t n0 = s.node_ptr[lo], e0 = s.edge_ptr[lo];
+    stage_i64<false>(d.edge_index, s.edge_index + e0, E, n0, 0, tid, nth);
+    stage_i64<false>(d.edge_index + ld_e, s.edge_index + s.E_total + e0, E, n0, 0, tid, nth);
+    if (s.edge_attr) stage_u32(d.edge_attr, s.edge_attr + e0 * s.D, E * s.D, tid, nth);
+    if (s.x) stage_u32(d.x, s.x + n0 * s.F, N * s.F, tid, nth);
+    if (s.y) stage_u32(d.y, s.y + lo * s.Y, B * s.Y, tid, nth);
+    stage_i64<false>(d.batch, s.graph_of_node + n0, N, lo, 0, tid, nth);
+    stage_i64<false>(d.ptr, s.node_ptr + lo, B + 1, n0, 0, tid, nth);
+    stage_i64<false>(d.edge_ptr, s.edge_ptr + lo, B + 1, e0, 0, tid, nth);
+    if (s.node_ids) {
+        bool flagged;
+        if (d.V > 0) flagged = stage_i64<true>(d.node_ids, s.node_ids + n0, N, 0, d.V, tid, nth);
+        else         flagged = stage_i64<false>(d.node_ids, s.node_ids + n0, N, 0, 0, tid, nth);
+        if (flagged) atomicOr(status, QOT_STAGE_BAD_NODE_ID);
+    }
+}
+
 __global__ __launch_bounds__(256) void stage_copy_kernel(const int64_t* __restrict__ ctl, int32_t* __restrict__ status,
                                                          StageShard s, StageSlot d) {
     const int64_t lo = ctl[kStageSnap];
     if (lo < 0) return;                                  // the plan refused the slice: nothing is staged
-    const int64_t n0 = s.node_ptr[lo], e0 = s.edge_ptr[lo];
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const int64_t nth = (int64_t)gridDim.x * blockDim.x;
-    stage_i64<false>(d.edge_index, s.edge_index + e0, d.E, n0, 0, tid, nth);
-    stage_i64<false>(d.edge_index + d.E, s.edge_index + s.E_total + e0, d.E, n0, 0, tid, nth);
-    if (s.edge_attr) stage_u32(d.edge_attr, s.edge_attr + e0 * s.D, d.E * s.D, tid, nth);
-    if (s.x) stage_u32(d.x, s.x + n0 * s.F, d.N * s.F, tid, nth);
-    if (s.y) stage_u32(d.y, s.y + lo * s.Y, d.B * s.Y, tid, nth);
-    stage_i64<false>(d.batch, s.graph_of_node + n0, d.N, lo, 0, tid, nth);
-    stage_i64<false>(d.ptr, s.node_ptr + lo, d.B + 1, n0, 0, tid, nth);
-    stage_i64<false>(d.edge_ptr, s.edge_ptr + lo, d.B + 1, e0, 0, tid, nth);
-    if (s.node_ids) {
-        bool flagged;
-        if (d.V > 0) flagged = stage_i64<true>(d.node_ids, s.node_ids + n0, d.N, 0, d.V, tid, nth);
-        else         flagged = stage_i64<false>(d.node_ids, s.node_ids + n0, d.N, 0, 0, tid, nth);
-        if (flagged) atomicOr(status, QOT_STAGE_BAD_NODE_ID);
-    }
+    stage_slice(s, d, lo, d.B, d.N, d.E, d.E, status, tid, nth);
+}
+
+// The padded slot: d.B / d.N count the REAL graphs / nodes, d.E is the edge capacity, d.max_n the node count n of every
+// graph; the buffers hold d.B + P graphs, (d.B + P) * n nodes, d.E edges.  The real slice, then P pad graphs that take
+// the E_cap - E_real spare edges, max_m apiece until they are used up, as rings over their own n nodes.  Everything
+// behind the real slice is computed from (E_real, E_cap, P, n, max_m): no load.  The pad regions are a few hundred
+// elements (at most P * max_m edges, P * n nodes), so their 64-bit divisions do not show.
+__global__ __launch_bounds__(256) void stage_copy_padded_kernel(const int64_t* __restrict__ ctl, int32_t* __restrict__ status,
+                                                                StageShard s, StageSlot d, int64_t P) {
+    const int64_t lo = ctl[kStageSnap];
+    if (lo < 0) return;                                  // the plan refused the slice: nothing is staged
+    const int64_t E_real = ctl[kStageEdges];
+    const int64_t E_cap = d.E, n = d.max_n, max_m = d.max_m, B = d.B, N = d.N;
+    const int64_t spare = E_cap - E_real;
+    if (E_real < 0 || spare < 0 || spare > P * max_m) return;      // what the plan accepted, once more: bounds every store below
+    const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+    stage_slice(s, d, lo, B, N, E_real, E_cap, status, tid, nth);
+    // pad edge j: pad graph p = j / max_m, its edge k = j mod max_m: (k mod n) -> ((k + 1) mod n) from node N + p n on
+    auto ring = [&](int64_t j, int64_t step) -> int64_t {
+        const int64_t p = j / max_m, k = j - p * max_m;
+        return N + p * n + (k + step) % n;
+    };
+    stage_fill_i64(d.edge_index + E_real, spare, [&](int64_t j) { return ring(j, 0); }, tid, nth);
+    stage_fill_i64(d.edge_index + E_cap + E_real, spare, [&](int64_t j) { return ring(j, 1); }, tid, nth);
+    if (s.edge_attr) stage_zero_u32(d.edge_attr + E_real * s.D, spare * s.D, tid, nth);
+    if (s.x) stage_zero_u32(d.x + N * s.F, P * n * s.F, tid, nth);
+    if (s.node_ids) stage_fill_i64(d.node_ids + N, P * n, [&](int64_t i) { return i % n; }, tid, nth);
+    stage_fill_i64(d.batch + N, P * n, [&](int64_t i) { return B + i / n; }, tid, nth);
+    stage_fill_i64(d.ptr + B + 1, P, [&](int64_t p) { return N + (p + 1) * n; }, tid, nth);
+    stage_fill_i64(d.edge_ptr + B + 1, P, [&](int64_t p) {
+        const int64_t used = (p + 1) * max_m;
+        return E_real + (used < spare ? used : spare);
+    }, tid, nth);
 }
 
 }  // namespace qot
 
 using namespace qot;
+
+static void stage_structs(StageShard& s, StageSlot& d, const int64_t* node_ptr, const int64_t* edge_ptr,
+                          const int64_t* graph_of_node, int64_t G, int64_t N_total, int64_t E_total, const int64_t* edge_index,
+                          const void* edge_attr, int D, const int64_t* node_ids, const void* x, int F, const void* y, int Y,
+                          int64_t B, int64_t N, int64_t E, int64_t max_nodes, int64_t max_edges, int64_t V,
+                          int64_t* dst_edge_index, void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x, void* dst_y,
+                          int64_t* dst_ptr, int64_t* dst_edge_ptr, int64_t* dst_batch) {
+    s.node_ptr = node_ptr; s.edge_ptr = edge_ptr; s.graph_of_node = graph_of_node; s.edge_index = edge_index;
+    s.edge_attr = D > 0 ? (const uint32_t*)edge_attr : nullptr;
+    s.node_ids = node_ids;
+    s.x = F > 0 ? (const uint32_t*)x : nullptr;
+    s.y = Y > 0 ? (const uint32_t*)y : nullptr;
+    s.G = G; s.N_total = N_total; s.E_total = E_total; s.D = D; s.F = F; s.Y = Y;
+    d.edge_index = dst_edge_index; d.edge_attr = (uint32_t*)dst_edge_attr; d.node_ids = dst_node_ids;
+    d.x = (uint32_t*)dst_x; d.y = (uint32_t*)dst_y; d.ptr = dst_ptr; d.edge_ptr = dst_edge_ptr; d.batch = dst_batch;
+    d.B = B; d.N = N; d.E = E; d.max_n = max_nodes; d.max_m = max_edges; d.V = V;
+}
+
+// 16-byte units of the whole copy; four per thread, at most 1024 workgroups (4 per CU)
+static int stage_grid(int64_t B, int64_t N, int64_t E, int D, int F, int Y) {
+    const int64_t bytes = 16 * E + 4 * E * (int64_t)D + 16 * N + 4 * N * (int64_t)F + 4 * B * (int64_t)Y + 16 * (B + 1);
+    int64_t grid = (bytes / 16 + 256 * 4 - 1) / (256 * 4);
+    if (grid < 1) grid = 1;
+    if (grid > 1024) grid = 1024;
+    return (int)grid;
+}
 
 extern "C" int qot_shard_stage(int64_t* ctl, int64_t sched_cap, int32_t* status, const int64_t* node_ptr,
                                const int64_t* edge_ptr, const int64_t* graph_of_node, int64_t G, int64_t N_total,
@@ -220,26 +337,47 @@ extern "C" int qot_shard_stage(int64_t* ctl, int64_t sched_cap, int32_t* status,
         (y && Y > 0 && !dst_y))
         return QOT_ERR_BADARG;
     StageShard s;
-    s.node_ptr = node_ptr; s.edge_ptr = edge_ptr; s.graph_of_node = graph_of_node; s.edge_index = edge_index;
-    s.edge_attr = D > 0 ? (const uint32_t*)edge_attr : nullptr;
-    s.node_ids = node_ids;
-    s.x = F > 0 ? (const uint32_t*)x : nullptr;
-    s.y = Y > 0 ? (const uint32_t*)y : nullptr;
-    s.G = G; s.N_total = N_total; s.E_total = E_total; s.D = D; s.F = F; s.Y = Y;
     StageSlot d;
-    d.edge_index = dst_edge_index; d.edge_attr = (uint32_t*)dst_edge_attr; d.node_ids = dst_node_ids;
-    d.x = (uint32_t*)dst_x; d.y = (uint32_t*)dst_y; d.ptr = dst_ptr; d.edge_ptr = dst_edge_ptr; d.batch = dst_batch;
-    d.B = B; d.N = N; d.E = E; d.max_n = max_nodes; d.max_m = max_edges; d.V = V;
+    stage_structs(s, d, node_ptr, edge_ptr, graph_of_node, G, N_total, E_total, edge_index, edge_attr, D, node_ids, x, F, y, Y, B,
+                  N, E, max_nodes, max_edges, V, dst_edge_index, dst_edge_attr, dst_node_ids, dst_x, dst_y, dst_ptr, dst_edge_ptr,
+                  dst_batch);
     hipStream_t st = (hipStream_t)stream;
-    stage_plan_kernel<<<1, 256, 0, st>>>(ctl, sched_cap, status, node_ptr, edge_ptr, G, N_total, E_total, B, N, E, max_nodes,
-                                         max_edges);
+    stage_plan_kernel<false><<<1, 256, 0, st>>>(ctl, sched_cap, status, node_ptr, edge_ptr, G, N_total, E_total, B, N, E,
+                                                max_nodes, max_edges, 0);
     QOT_LAUNCH_CHECK();
-    // 16-byte units of the whole copy; four per thread, at most 1024 workgroups (4 per CU)
-    const int64_t bytes = 16 * E + 4 * E * (int64_t)D + 16 * N + 4 * N * (int64_t)F + 4 * B * (int64_t)Y + 16 * (B + 1);
-    int64_t grid = (bytes / 16 + 256 * 4 - 1) / (256 * 4);
-    if (grid < 1) grid = 1;
-    if (grid > 1024) grid = 1024;
-    stage_copy_kernel<<<(int)grid, 256, 0, st>>>(ctl, status, s, d);
+    stage_copy_kernel<<<stage_grid(B, N, E, D, F, Y), 256, 0, st>>>(ctl, status, s, d);
+    QOT_LAUNCH_CHECK();
+    return QOT_OK;
+}
+
+extern "C" int qot_shard_stage_padded(int64_t* ctl, int64_t sched_cap, int32_t* status, const int64_t* node_ptr,
+                                      const int64_t* edge_ptr, const int64_t* graph_of_node, int64_t G, int64_t N_total,
+                                      int64_t E_total, const int64_t* edge_index, const void* edge_attr, int D,
+                                      const int64_t* node_ids, const void* x, int F, const void* y, int Y, int64_t B,
+                                      int64_t n, int64_t E_cap, int64_t P, int64_t max_edges, int64_t V,
+                                      int64_t* dst_edge_index, void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x,
+                                      void* dst_y, int64_t* dst_ptr, int64_t* dst_edge_ptr, int64_t* dst_batch,
+                                      qot_stream_t stream) {
+    if (!ctl || !status || !node_ptr || !edge_ptr || !graph_of_node || !dst_ptr || !dst_edge_ptr) return QOT_ERR_BADARG;
+    if (sched_cap < 1 || G < 1 || N_total < 0 || E_total < 0 || B < 1 || n < 1 || E_cap < 0 || P < 0 || max_edges < 0 || V < 0)
+        return QOT_ERR_BADARG;
+    if (P > 0 && (n < 2 || max_edges < 1)) return QOT_ERR_BADARG;      // a ring over one node is a self loop; no room to pad
+    if (B > (INT64_MAX >> 24) || P > (INT64_MAX >> 24) || n > (1 << 20) || max_edges > (1 << 20)) return QOT_ERR_BADARG;
+    if (D < 0 || F < 0 || Y < 0) return QOT_ERR_BADARG;
+    if ((E_cap > 0 && (!edge_index || !dst_edge_index)) || !dst_batch) return QOT_ERR_BADARG;
+    if ((edge_attr && E_cap > 0 && D > 0 && !dst_edge_attr) || (node_ids && !dst_node_ids) || (x && F > 0 && !dst_x) ||
+        (y && Y > 0 && !dst_y))
+        return QOT_ERR_BADARG;
+    StageShard s;
+    StageSlot d;
+    stage_structs(s, d, node_ptr, edge_ptr, graph_of_node, G, N_total, E_total, edge_index, edge_attr, D, node_ids, x, F, y, Y, B,
+                  B * n, E_cap, n, max_edges, V, dst_edge_index, dst_edge_attr, dst_node_ids, dst_x, dst_y, dst_ptr, dst_edge_ptr,
+                  dst_batch);
+    hipStream_t st = (hipStream_t)stream;
+    stage_plan_kernel<true><<<1, 256, 0, st>>>(ctl, sched_cap, status, node_ptr, edge_ptr, G, N_total, E_total, B, B * n, E_cap,
+                                               n, max_edges, P * max_edges);
+    QOT_LAUNCH_CHECK();
+    stage_copy_padded_kernel<<<stage_grid(B + P, (B + P) * n, E_cap, D, F, Y), 256, 0, st>>>(ctl, status, s, d, P);
     QOT_LAUNCH_CHECK();
     return QOT_OK;
 }

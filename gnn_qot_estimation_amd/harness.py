@@ -27,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from .dp import FlatModel, FusedSGD, graph_range, loss_scale
-from .loader import GraphLoader, PackedGraphs, StageSlot, check_stage_status
+from .loader import GraphLoader, PackedGraphs, StageSlot, check_stage_status, uniform_node_count
 
 # data constants of the reference's label scaling (constants.py:8-12), used at test.py:95-99
 TARGET_RANGES = {
@@ -190,6 +190,53 @@ def stream_schedule(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ranges: Sequ
     return out
 
 
+def stream_pad_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ranges: Sequence[Tuple[int, int]],
+                    graph_sizes: Tuple[int, int]) -> Dict[int, Dict[str, object]]:
+    """Padded slots for the batches ``ranges`` of a shard whose graphs all have ``n`` nodes, per graph count ``B``:
+    ``{B: {"E_cap", "E_min", "P", "shape"}}`` -- ``E_cap`` / ``E_min`` the largest / smallest edge total of a batch of
+    ``B`` graphs, ``P = ceil((E_cap - E_min) / max_m)`` pad graphs (``max_m = graph_sizes[1]``, the shard's largest
+    per-graph edge count: a pad graph never exceeds it), ``shape = (B + P, (B + P) n, E_cap)`` the one slot that takes
+    them all.  Equal totals give ``P = 0`` and the exact shape.  Pure host arithmetic on the offsets; ``ValueError`` for
+    mixed node counts (the pad graphs, ``node_ids`` in table mode and the graph form of TransformerConv take one ``n``)."""
+    n = uniform_node_count(node_ptr)
+    if n is None:
+        raise ValueError("pad_edges=True needs a shard whose graphs all have the same node count (mixed node counts keep "
+                         "stream=True with exact-shape slots)")
+    max_m = int(graph_sizes[1])
+    totals: Dict[int, List[int]] = {}
+    for lo, hi in ranges:
+        totals.setdefault(hi - lo, []).append(int(edge_ptr[hi]) - int(edge_ptr[lo]))
+    plan: Dict[int, Dict[str, object]] = {}
+    for B, es in totals.items():
+        e_cap, e_min = max(es), min(es)
+        P = 0 if e_cap == e_min else -(-(e_cap - e_min) // max_m)
+        if P and n < 2:
+            raise ValueError("pad_edges=True needs graphs of at least 2 nodes (a pad graph is a ring without self loops)")
+        plan[B] = {"E_cap": e_cap, "E_min": e_min, "P": P, "shape": (B + P, (B + P) * n, e_cap)}
+    return plan
+
+
+def fit_batch_ranges(total: int, batch_size: int, chunk_fraction: float) -> List[Tuple[int, int]]:
+    """Every batch ``fit`` can ever run on a dataset of ``total`` graphs: all training chunks, then the validation range."""
+    tr, va, _ = split_ranges(total)
+    out: List[Tuple[int, int]] = []
+    for epoch in range(int(1 / chunk_fraction)):
+        chunk = epoch_chunk(epoch, len(tr), chunk_fraction)
+        if len(chunk):
+            out += batch_ranges(range(tr[0] + chunk[0], tr[0] + chunk[-1] + 1), batch_size)
+    return out + batch_ranges(va, batch_size)
+
+
+def check_pad_edges(dataset, kind: str, world: int, stream) -> None:
+    """``pad_edges=True`` needs ``stream=True``, everything ``stream=True`` needs, and graphs of one node count."""
+    if not stream:
+        raise ValueError("pad_edges=True needs stream=True: the padding belongs to the static slots of streamed replay")
+    check_stream(dataset, kind, world)
+    if uniform_node_count(dataset.node_ptr) is None:
+        raise ValueError("pad_edges=True needs a shard whose graphs all have the same node count (mixed node counts keep "
+                         "stream=True with exact-shape slots)")
+
+
 def check_stream(dataset, kind: str, world: int) -> None:
     """``stream=True`` needs a TopologicalGNN run on an HBM-resident shard in a single process."""
     if kind != "topological":
@@ -234,15 +281,28 @@ class StepReplayer:
     before the capture; the index build, the int32 narrowing and the table maps are then recorded inside the graph and
     run again on every replay.  No staged batch goes through host-side checks: the stage launch validates on the device
     and ``end_epoch`` raises from its status word (and from the index build's) once per epoch.
+
+    Padded slots (``pad_edges=True`` on top of ``stream=True``; graphs of one node count): batches of ``B`` graphs whose
+    edge totals differ share ONE slot and one captured graph per ``(B, training)``.  ``plan_padding(ranges)`` -- once,
+    over every batch the run will ever see -- fixes ``E_cap`` and the number ``P`` of pad graphs per ``B``
+    (``stream_pad_plan``); the slot (``loader.PaddedStageSlot``) holds ``B + P`` graphs and the staging launch appends pad
+    graphs that take the spare edges.  The graphs of a batch are independent, the step takes ``out[:B]`` before the
+    loss, its gradient and the statistics, so the pad rows of the output's gradient are zero and with them everything
+    the pad graphs add to a parameter gradient.
     """
 
     def __init__(self, model, kind: str, out_dim: int, device, flat: Optional[FlatModel], opt: Optional[FusedSGD],
-                 collective: bool = False, stream: Optional[bool] = None, shard: Optional[PackedGraphs] = None):
+                 collective: bool = False, stream: Optional[bool] = None, shard: Optional[PackedGraphs] = None,
+                 pad_edges: Optional[bool] = None):
         self.model, self.kind, self.out_dim, self.device = model, kind, out_dim, device
         self.stream = bool(stream)
-        if self.stream:
+        self.pad_edges = bool(pad_edges)
+        if self.pad_edges:
+            check_pad_edges(shard, kind, 2 if collective else 1, self.stream)
+        elif self.stream:
             check_stream(shard, kind, 2 if collective else 1)
         self.shard = shard
+        self.pad_plan: Dict[int, Dict[str, object]] = {}       # per graph count B (plan_padding)
         self.slots: Dict[Tuple[int, int, int, bool], StageSlot] = {}
         self._stage_status = torch.zeros(1, dtype=torch.int32, device=device) if self.stream else None
         self.schedule_capacity: Optional[int] = None   # batches of one shape per epoch (default: one pass over the shard)
@@ -261,6 +321,7 @@ class StepReplayer:
     def _step(self, data, training: bool):
         from . import functional as QF
         fwd = _KINDS[self.kind]
+        real = getattr(data, "real_graphs", None)
         if training:
             # The step differentiates with respect to fresh leaves that alias the parameters
             # (functional_call), not the Parameters themselves: a Parameter's gradient accumulator has the
@@ -271,6 +332,8 @@ class StepReplayer:
             leaves = {n: p.detach().requires_grad_(True) for n, p in zip(names, self.flat.params)}
             functional = lambda d: torch.func.functional_call(self.model, leaves, (d,))
             out, y = fwd(functional, data, self.out_dim)
+            if real is not None:
+                out = out[:real]                 # a padded slot: the pad graphs' rows take no part (zero gradient)
             _, g = QF.smooth_l1_loss_and_grad(out, y, loss_out=self._loss)
             if self.collective:
                 # this rank's share of the global mean loss (dp.loss_scale: one host-built scalar per batch object, made
@@ -290,6 +353,8 @@ class StepReplayer:
         else:
             with torch.no_grad():
                 out, y = fwd(self.model, data, self.out_dim)
+                if real is not None:
+                    out = out[:real]
                 QF.smooth_l1_loss_and_grad(out, y, loss_out=self._loss)
         self.stats[training].update(y, out, self._loss)
 
@@ -354,13 +419,48 @@ class StepReplayer:
                                                            capacity=self.schedule_capacity)
         return slot
 
+    def plan_padding(self, ranges: Sequence[Tuple[int, int]]) -> Dict[int, Dict[str, object]]:
+        """Fix the padded slots (``stream_pad_plan``) for every batch the run will ever stage.  Called once, before the
+        first slot exists: a slot's buffers are part of its captured graph and never grow."""
+        if not self.pad_edges:
+            raise ValueError("plan_padding belongs to a StepReplayer(stream=True, pad_edges=True)")
+        if self.slots:
+            raise ValueError("the padding plan is fixed before the first batch is staged: slots never grow")
+        self.pad_plan = stream_pad_plan(self.shard.node_ptr, self.shard.edge_ptr, ranges, self.shard.graph_sizes)
+        return self.pad_plan
+
+    def _padded_slot(self, B: int, training: bool) -> StageSlot:
+        key = (B, bool(training))
+        slot = self.slots.get(key)
+        if slot is None:
+            plan = self.pad_plan[B]
+            emb = getattr(self.model, "node_embeddings", None)
+            slot = self.slots[key] = self.shard.padded_stage_slot(B, plan["E_cap"], plan["P"], status=self._stage_status,
+                                                                  num_embeddings=0 if emb is None else emb.num_embeddings,
+                                                                  capacity=self.schedule_capacity)
+        return slot
+
     def begin_epoch(self, ranges: Sequence[Tuple[int, int]], training: bool) -> None:
-        """Write this epoch's schedules: per shape, the ``lo`` of its batches in visiting order.  ``run`` must then be
-        called with exactly ``ranges``, in order."""
+        """Write this epoch's schedules: per shape (padded slots: per graph count), the ``lo`` of its batches in visiting
+        order.  ``run`` must then be called with exactly ``ranges``, in order."""
         G = len(self.shard)
         for lo, hi in ranges:
             if not 0 <= lo < hi <= G:
                 raise IndexError(f"graphs [{lo}, {hi}) lie outside a shard of {G} graphs")
+        if self.pad_edges:
+            max_m = int(self.shard.graph_sizes[1])
+            by_count: Dict[int, List[int]] = {}
+            for lo, hi in ranges:
+                plan = self.pad_plan.get(hi - lo)
+                e = int(self.shard.edge_ptr[hi]) - int(self.shard.edge_ptr[lo])
+                if plan is None or not 0 <= plan["E_cap"] - e <= plan["P"] * max_m:
+                    raise ValueError(f"graphs [{lo}, {hi}) ({e} edges) are not covered by the padding plan "
+                                     f"({'no slot for this graph count' if plan is None else plan}): plan_padding takes "
+                                     "every batch of the run")
+                by_count.setdefault(hi - lo, []).append(lo)
+            for B, los in by_count.items():
+                self._padded_slot(B, training).set_schedule(los)
+            return
         for shape, los in stream_schedule(self.shard.node_ptr, self.shard.edge_ptr, ranges).items():
             self._slot(shape, training).set_schedule(los)
 
@@ -372,14 +472,17 @@ class StepReplayer:
 
     def _run_streamed(self, rng: Tuple[int, int], training: bool) -> bool:
         lo, hi = rng
-        shape = batch_shape(self.shard.node_ptr, self.shard.edge_ptr, lo, hi)
-        key = shape + (bool(training),)
+        if self.pad_edges:
+            key = (hi - lo, bool(training))
+        else:
+            shape = batch_shape(self.shard.node_ptr, self.shard.edge_ptr, lo, hi)
+            key = shape + (bool(training),)
         g = self.graphs.get(key)
         if g is not None:
             g.replay()                  # stage (the schedule's next lo) + step
             self.counts["replayed"] += 1
             return True
-        slot = self._slot(shape, training)
+        slot = self._padded_slot(hi - lo, training) if self.pad_edges else self._slot(shape, training)
         self.model.train(training)
         # the stage launch rewrites the slot's tensors behind torch's back: nothing cached on the batch object may survive
         # into this visit (class docstring, CACHE RULE)
@@ -404,16 +507,22 @@ class StepReplayer:
 
 def run_epoch(model, dataset, indices: range, *, kind: str, batch_size: int, out_dim: int, device,
               criterion, flat: Optional[FlatModel] = None, opt: Optional[FusedSGD] = None,
-              replayer: Optional[StepReplayer] = None, stream: Optional[bool] = None) -> Dict[str, object]:
+              replayer: Optional[StepReplayer] = None, stream: Optional[bool] = None,
+              pad_edges: Optional[bool] = None) -> Dict[str, object]:
     """One pass over ``indices``; trains when ``opt`` is given, else evaluates under ``no_grad``.  ``stream=True``
     (with a ``StepReplayer(stream=True)``): every batch is staged on the device into the static slot of its shape and
-    run by that shape's one captured graph."""
+    run by that shape's one captured graph.  ``pad_edges=True`` (with a ``StepReplayer(stream=True, pad_edges=True)``
+    whose ``plan_padding`` covered these batches): one padded slot per graph count instead."""
     fwd = _KINDS[kind]
     rank, world = _rank_world()
+    if pad_edges:
+        check_pad_edges(dataset, kind, world, stream)
     if stream:
         check_stream(dataset, kind, world)
         if replayer is None or not replayer.stream or replayer.shard is not dataset:
             raise ValueError("stream=True needs a StepReplayer(stream=True, shard=dataset)")
+        if bool(pad_edges) != replayer.pad_edges:
+            raise ValueError("pad_edges must be what the StepReplayer was built with")
         training = opt is not None
         ranges = batch_ranges(indices, batch_size)
         replayer.begin_epoch(ranges, training)
@@ -531,7 +640,8 @@ def run_epoch(model, dataset, indices: range, *, kind: str, batch_size: int, out
 def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num_epochs: int = 35,
         patience: int = 10, lr: float = 0.1, momentum: float = 0.9, step_size: int = 10, gamma: float = 0.5,
         chunk_fraction: float = 0.10, output_dim: int = 3, device="cuda", best_path: Optional[str] = None,
-        log: Callable[[str], None] = print, replay: Optional[bool] = None, stream: Optional[bool] = None) -> History:
+        log: Callable[[str], None] = print, replay: Optional[bool] = None, stream: Optional[bool] = None,
+        pad_edges: Optional[bool] = None) -> History:
     """The training script's main loop (train.py:24-182) on a dataset object indexable by graph.
 
     ``replay`` (default: on for an HBM-resident shard in a single process): steps over cached batches are
@@ -539,10 +649,17 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
     ``stream`` (default off; needs an HBM-resident shard, ``kind="topological"`` and a single process, else
     ``ValueError``): streamed replay -- one captured graph per batch shape, every batch staged into that shape's static
     buffers on the device, so first visits and single-epoch runs replay too.  ``History.replay_counts`` tells which
-    path the steps took."""
+    path the steps took.
+    ``pad_edges`` (default off; needs ``stream=True`` and graphs of one node count, else ``ValueError``): batches whose
+    edge totals differ -- one edge per distinct connection of a sample, as the reference builds its graphs -- share one
+    slot and one captured graph per graph count; pad graphs appended on the device bring every batch to the slot's edge
+    count and take no part in the loss (``StepReplayer``, ``stream_pad_plan``)."""
     device = torch.device(device)
     stream = bool(stream)
-    if stream:
+    pad_edges = bool(pad_edges)
+    if pad_edges:
+        check_pad_edges(dataset, kind, _rank_world()[1], stream)
+    elif stream:
         check_stream(dataset, kind, _rank_world()[1])
     model.to(device)
     tr, va, _ = split_ranges(len(dataset))
@@ -557,7 +674,10 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
     replayer = None
     if use_replay:
         replayer = StepReplayer(model, kind, output_dim, device, flat, opt, collective=world > 1, stream=stream,
-                                shard=dataset if stream else None)
+                                shard=dataset if stream else None, pad_edges=pad_edges)
+        if pad_edges:
+            # every batch the run can ever stage, so that no slot has to grow
+            replayer.plan_padding(fit_batch_ranges(len(dataset), batch_size, chunk_fraction))
     criterion = torch.nn.SmoothL1Loss()
     hist = History()
     counter = 0
@@ -568,9 +688,9 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
         opt.lr = step_lr(lr, epoch, step_size, gamma)
         t = run_epoch(model, dataset, range(tr[0] + chunk[0], tr[0] + chunk[-1] + 1) if len(chunk) else range(0),
                       kind=kind, batch_size=batch_size, out_dim=output_dim, device=device, criterion=criterion,
-                      flat=flat, opt=opt, replayer=replayer, stream=stream)
+                      flat=flat, opt=opt, replayer=replayer, stream=stream, pad_edges=pad_edges)
         v = run_epoch(model, dataset, va, kind=kind, batch_size=batch_size, out_dim=output_dim, device=device,
-                      criterion=criterion, replayer=replayer, stream=stream)
+                      criterion=criterion, replayer=replayer, stream=stream, pad_edges=pad_edges)
         if replayer is not None:
             hist.replay_counts = replayer.replay_counts()
         hist.loss.append(t["avg_loss"]); hist.r2.append(t["r2"])

@@ -216,6 +216,12 @@ class PackedGraphs:
         the device by ``StageSlot.stage()`` (``qot_shard_stage``): the buffers a captured step reads."""
         return StageSlot(self, B, N, E, status=status, num_embeddings=num_embeddings, capacity=capacity)
 
+    def padded_stage_slot(self, B: int, E_cap: int, pad_graphs: int, status: Optional[torch.Tensor] = None,
+                          num_embeddings: int = 0, capacity: Optional[int] = None) -> "PaddedStageSlot":
+        """A static ``Batch`` for slices of ``B`` graphs of this resident shard whose edge totals differ: ``pad_graphs``
+        extra graphs take what a slice leaves of ``E_cap`` edges (``qot_shard_stage_padded``)."""
+        return PaddedStageSlot(self, B, E_cap, pad_graphs, status=status, num_embeddings=num_embeddings, capacity=capacity)
+
     def __getitem__(self, g: int) -> Data:
         n0, n1 = int(self.node_ptr[g]), int(self.node_ptr[g + 1])
         e0, e1 = int(self.edge_ptr[g]), int(self.edge_ptr[g + 1])
@@ -290,7 +296,8 @@ def check_stage_status(status: torch.Tensor) -> None:
         if code & STAGE_BAD_RANGE:
             what.append("a graph slice lies outside the node / edge arrays (or the schedule was used up)")
         if code & STAGE_BAD_SHAPE:
-            what.append("a slice does not hold the slot's node / edge counts or exceeds (max_nodes, max_edges)")
+            what.append("a slice does not hold the slot's node / edge counts (padded slot: leaves more spare edges than its "
+                        "pad graphs take) or exceeds (max_nodes, max_edges)")
         raise _lib.QotError("qot_shard_stage: inconsistent batch slices (" + "; ".join(what) + "): nothing was staged "
                             "for them and the steps that followed ran on the slot's previous batch")
     raise IndexError("index out of range in self")
@@ -378,6 +385,60 @@ class StageSlot:
         _lib.call("qot_shard_stage", self.ctl, self.capacity, self.status, s.node_ptr_dev, s.edge_ptr_dev, s.graph_of_node,
                   G, n_total, e_total, s.edge_index, s.edge_attr, D, s.node_ids, s.x, F, s.y, Y, self.B, self.N, self.E,
                   max_n, max_m, self.V, b.edge_index, b.edge_attr, b.node_ids, b.x, b.y, b.ptr, b.edge_ptr, b.batch)
+        return b
+
+
+def uniform_node_count(node_ptr: torch.Tensor) -> Optional[int]:
+    """The node count every graph of the offsets has, or ``None`` when they differ (or there is no graph)."""
+    cnt = node_ptr[1:] - node_ptr[:-1]
+    if cnt.numel() == 0 or int(cnt.min()) != int(cnt.max()):
+        return None
+    return int(cnt[0])
+
+
+class PaddedStageSlot(StageSlot):
+    """One slot for every slice of ``B`` graphs of a shard whose graphs all have ``n`` nodes but differ in edges.
+
+    The buffers hold ``B + P`` graphs, ``(B + P) n`` nodes and ``E_cap`` edges; ``y`` keeps ``B`` rows.  ``stage()`` writes
+    the slice as ``StageSlot`` does and behind it ``P`` *pad graphs* that take the ``E_cap - E_real`` spare edges
+    (``qot_shard_stage_padded``: ``min(max_m, spare left)`` edges per pad graph as a ring over its own ``n`` nodes, zero
+    ``edge_attr`` rows, ``node_ids`` ``0 .. n-1``), so no pad graph exceeds the shard's ``(n, max_m)`` or brings an
+    in-degree above ``ceil(max_m / n)``.  ``batch.num_graphs`` is ``B + P``, ``batch.real_graphs`` is ``B``: the model's
+    output has ``B + P`` rows, whoever forms a loss takes the first ``real_graphs`` of them (``harness.StepReplayer``).
+    A slice whose spare exceeds ``P * max_m`` (or that holds more than ``E_cap`` edges) stages nothing and sets
+    ``STAGE_BAD_SHAPE``.  ``harness.stream_pad_plan`` chooses ``E_cap`` and ``P`` for a run."""
+
+    def __init__(self, shard: "PackedGraphs", B: int, E_cap: int, pad_graphs: int, status: Optional[torch.Tensor] = None,
+                 num_embeddings: int = 0, capacity: Optional[int] = None):
+        if not isinstance(shard, PackedGraphs) or shard.device is None:
+            raise ValueError("a batch slot stages from an HBM-resident shard (PackedGraphs.to_device)")
+        B, E_cap, P = int(B), int(E_cap), int(pad_graphs)
+        n = uniform_node_count(shard.node_ptr)
+        if n is None:
+            raise ValueError("a padded batch slot needs a shard whose graphs all have the same node count")
+        if B < 1 or E_cap < 0 or P < 0:
+            raise ValueError("a padded batch slot needs B >= 1, E_cap >= 0, pad_graphs >= 0")
+        if P > 0 and (n < 2 or int(shard.graph_sizes[1]) < 1):
+            raise ValueError("pad graphs are rings over n >= 2 nodes of at most max_m >= 1 edges")
+        super().__init__(shard, B + P, (B + P) * n, E_cap, status=status, num_embeddings=num_embeddings,
+                         capacity=capacity if capacity is not None else len(shard) // B + 2)
+        self.real_graphs, self.pad_graphs, self.n = B, P, n
+        b = self.batch
+        b.real_graphs = B
+        if shard.y is not None:
+            b.y = torch.zeros((B * shard.y_rows,) + tuple(shard.y.shape[1:]), dtype=shard.y.dtype, device=shard.device)
+
+    def stage(self, lo: Optional[int] = None) -> Batch:
+        from . import _lib
+        if lo is not None:
+            self.set_schedule([lo])
+        s, b = self.shard, self.batch
+        D, F, Y = self._words
+        G, n_total, e_total, _, max_m = self._totals
+        _lib.call("qot_shard_stage_padded", self.ctl, self.capacity, self.status, s.node_ptr_dev, s.edge_ptr_dev,
+                  s.graph_of_node, G, n_total, e_total, s.edge_index, s.edge_attr, D, s.node_ids, s.x, F, s.y, Y,
+                  self.real_graphs, self.n, self.E, self.pad_graphs, max_m, self.V, b.edge_index, b.edge_attr, b.node_ids,
+                  b.x, b.y, b.ptr, b.edge_ptr, b.batch)
         return b
 
 

@@ -62,6 +62,9 @@ def main(argv=None):
     ap.add_argument("--stream", action="store_true",
                     help="streamed replay: one captured step graph per batch shape, batches staged on the device "
                          "(topological, HBM-resident shard, single process)")
+    ap.add_argument("--pad-edges", action="store_true",
+                    help="with --stream: batches of unequal edge totals share one slot per graph count, brought to a fixed "
+                         "edge count by pad graphs (graphs of one node count)")
     args = ap.parse_args(argv)
 
     from . import LightpathGNN, TopologicalGNN
@@ -87,7 +90,7 @@ def main(argv=None):
                   "NODE_FEATURES": meta.get("NODE_FEATURES"), "feature_indices": fidx}  # lightpath train.py:227-233
     hist = harness.fit(model, dataset, kind=kind, batch_size=args.batch_size, num_epochs=args.epochs,
                        patience=args.patience, device=device, best_path=os.path.join(root, "best_model.pth"), log=log,
-                       stream=True if args.stream else None)
+                       stream=True if args.stream else None, pad_edges=True if args.pad_edges else None)
     if kind == "lightpath":
         log(f"Total skipped {hist.skipped_graphs} graphs due to missing LUT nodes.")
     path, k = harness.next_model_path(os.path.join(root, "models"))

@@ -621,7 +621,7 @@ int qot_step_advance(int64_t* counter, int64_t* snapshot, qot_stream_t stream);
  * taken from DEVICE memory, so that one captured launch stages a different slice on every replay (csrc/stage.hip;
  * loader.StageSlot).  No counterpart in the reference: its DataLoader collates on the host (train.py:93-95,107).
  * ctl[4 + sched_cap] (int64, device): [0] position, [1] number of valid schedule entries, [2] snapshot (written by the
- * call: the `lo` it staged, or -1), [3] reserved, [4 ...] the schedule of `lo` values.  Each call takes
+ * call: the `lo` it staged, or -1), [3] reserved (qot_shard_stage_padded: the slice's edge total), [4 ...] the schedule of `lo` values.  Each call takes
  * schedule[position] and advances the position on the device.
  * Shard: node_ptr / edge_ptr [G + 1] and graph_of_node [N_total] (int64, device), edge_index [2, E_total] (int64, numbered
  * within the shard), and optionally (NULL: absent) edge_attr [E_total, D], node_ids [N_total] (int64), x [N_total, F],
@@ -640,6 +640,21 @@ int qot_shard_stage(int64_t* ctl, int64_t sched_cap, int32_t* status, const int6
                     int64_t B, int64_t N, int64_t E, int64_t max_nodes, int64_t max_edges, int64_t V,
                     int64_t* dst_edge_index, void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x, void* dst_y,
                     int64_t* dst_ptr, int64_t* dst_edge_ptr, int64_t* dst_batch, qot_stream_t stream);
+/* qot_shard_stage for batches of UNEQUAL edge totals through one slot (loader.PaddedStageSlot): every graph of the shard
+ * has n nodes and at most max_edges edges; the slot holds B + P graphs, (B + P) * n nodes and E_cap edges, dst_y B rows.
+ * A slice of B graphs with E_real edges is accepted when it holds B * n nodes and 0 <= E_cap - E_real <= P * max_edges
+ * (else QOT_STAGE_BAD_SHAPE, nothing staged); ctl[2] receives `lo`, ctl[3] E_real.  The first B graphs / B * n nodes /
+ * E_real edges of the slot are what qot_shard_stage writes.  Behind them P pad graphs take the spare edges: pad graph p
+ * gets m_p = min(max_edges, spare left) edges, edge k of it runs (k mod n) -> ((k + 1) mod n) inside its own node range
+ * (a ring: in-degree <= ceil(max_edges / n)), with zero edge_attr rows; its nodes carry node_ids 0 .. n-1 and zero x rows;
+ * batch / ptr / edge_ptr continue to B + P graphs.  n >= 2 when P > 0 (a ring over one node would be a self loop). */
+int qot_shard_stage_padded(int64_t* ctl, int64_t sched_cap, int32_t* status, const int64_t* node_ptr,
+                           const int64_t* edge_ptr, const int64_t* graph_of_node, int64_t G, int64_t N_total,
+                           int64_t E_total, const int64_t* edge_index, const void* edge_attr, int D,
+                           const int64_t* node_ids, const void* x, int F, const void* y, int Y, int64_t B, int64_t n,
+                           int64_t E_cap, int64_t P, int64_t max_edges, int64_t V, int64_t* dst_edge_index,
+                           void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x, void* dst_y, int64_t* dst_ptr,
+                           int64_t* dst_edge_ptr, int64_t* dst_batch, qot_stream_t stream);
 
 /* ---- out[i] = concat(s0[0:n0], s1[0:n1], s2)[idx[i]]: one gather builds the fragment-ordered NNConv
  * operands from nn.2.weight / nn.2.bias / lin.weight (topological_training/models.py:20-25). */

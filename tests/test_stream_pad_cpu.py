@@ -1,0 +1,197 @@
+"""Padded streamed replay (``fit(..., stream=True, pad_edges=True)``), host part: the padding plan, the layout of the
+pad graphs restated in plain Python, the refusals, and the conditioning of the two whole-run cases of
+tests/test_gpu_stream_pad.py (the oracle loop in fp32 against fp64 within TOL / 10, every
+``val_r2 > best`` decision with a margin of at least 10 x TOL).
+
+Expected numbers are derived by hand from ``e_g = 26 + 2 ((g g + g // 5) mod 6)`` and the split of 240 graphs with batch 16
+and two chunks: full batches start at 0, 16, .. 64, 84, .. 148 (training) and 168, 184 (validation), ragged batches of 4 at
+80, 164 and 200.
+"""
+import functools
+import inspect
+
+import pytest
+import torch
+
+import helpers as H
+import stream_pad_cases as PC
+from helpers import TOL
+
+
+def _plan():
+    from gnn_qot_estimation_amd import harness as Hn
+    node_ptr, edge_ptr = PC.offsets()
+    train, val = PC.run_ranges(H._topo_fit())
+    return Hn.stream_pad_plan(node_ptr, edge_ptr, train + val, (PC.N_NODES, 36)), train, val
+
+
+# --------------------------------------------------------------------------- 1. the plan
+def test_plan_by_hand():
+    from gnn_qot_estimation_amd import harness as Hn
+    # five graphs of 3 nodes with 4, 2, 6, 3, 5 edges; largest per-graph edge count 6
+    node_ptr = torch.tensor([0, 3, 6, 9, 12, 15])
+    edge_ptr = torch.tensor([0, 4, 6, 12, 15, 20])
+    # batches of two: [0,2) 6 edges, [2,4) 9, [1,3) 8, [3,5) 8; one of one: [4,5) 5
+    plan = Hn.stream_pad_plan(node_ptr, edge_ptr, [(0, 2), (2, 4), (1, 3), (3, 5), (4, 5)], (3, 6))
+    assert plan == {2: {"E_cap": 9, "E_min": 6, "P": 1, "shape": (3, 9, 9)},
+                    1: {"E_cap": 5, "E_min": 5, "P": 0, "shape": (1, 3, 5)}}
+    # one batch per graph count: nothing to pad
+    plan = Hn.stream_pad_plan(node_ptr, edge_ptr, [(0, 2), (0, 5)], (3, 6))
+    assert plan[2]["P"] == 0 and plan[5] == {"E_cap": 20, "E_min": 20, "P": 0, "shape": (5, 15, 20)}
+    # a spread wider than one graph's edges takes two pad graphs
+    wide = torch.tensor([0, 1, 2, 9, 16, 16])              # 1, 1, 7, 7, 0 edges; max 7: totals 2, 14, 7
+    plan = Hn.stream_pad_plan(node_ptr, wide, [(0, 2), (2, 4), (3, 5)], (3, 7))
+    assert plan == {2: {"E_cap": 14, "E_min": 2, "P": 2, "shape": (4, 12, 14)}}      # ceil(12 / 7) = 2
+
+
+def test_plan_of_an_equal_sized_shard_is_the_exact_shape():
+    from gnn_qot_estimation_amd import harness as Hn
+    import stream_cases as SC
+    case = H.TRAJECTORY_CASES["topo_h16"]
+    node_ptr, edge_ptr = SC.case_offsets(case)
+    train, val = PC.run_ranges(case["fit"])
+    plan = Hn.stream_pad_plan(node_ptr, edge_ptr, train + val, (12, 30))
+    assert plan == {16: {"E_cap": 480, "E_min": 480, "P": 0, "shape": (16, 192, 480)},
+                    4: {"E_cap": 120, "E_min": 120, "P": 0, "shape": (4, 48, 120)}}
+    assert set(v["shape"] for v in plan.values()) == set(Hn.stream_schedule(node_ptr, edge_ptr, train + val))
+
+
+def test_plan_refuses_mixed_node_counts():
+    from gnn_qot_estimation_amd import harness as Hn
+    import stream_cases as SC
+    node_ptr, edge_ptr = SC.case_offsets(H.TRAJECTORY_CASES["topo_mixed_nodes"])
+    with pytest.raises(ValueError, match="same node count"):
+        Hn.stream_pad_plan(node_ptr, edge_ptr, [(0, 16), (16, 32)], (12, 30))
+
+
+def test_plan_of_the_unequal_shard():
+    """The data exercises the feature: 10 distinct exact shapes, two padded slots."""
+    from gnn_qot_estimation_amd import harness as Hn
+    plan, train, val = _plan()
+    node_ptr, edge_ptr = PC.offsets()
+    counts = [PC.edge_count(g) for g in range(PC.COUNT)]
+    assert min(counts) == 26 and max(counts) == 36 and len(set(counts)) == 6
+    full = [sum(counts[lo:lo + 16]) for lo in (0, 16, 32, 48, 64, 84, 100, 116, 132, 148, 168, 184)]
+    ragged = [sum(counts[lo:lo + 4]) for lo in (80, 164, 200)]
+    assert (min(full), max(full), min(ragged), max(ragged)) == (484, 492, 114, 124)
+    assert plan == {16: {"E_cap": 492, "E_min": 484, "P": 1, "shape": (17, 204, 492)},
+                    4: {"E_cap": 124, "E_min": 114, "P": 1, "shape": (5, 60, 124)}}
+    # exact-shape slots: 7 shapes in training, 3 in validation -- 10 slots and captured graphs where the padded run has 4
+    assert len(Hn.stream_schedule(node_ptr, edge_ptr, train)) == 7 and len(Hn.stream_schedule(node_ptr, edge_ptr, val)) == 3
+    assert Hn.fit_batch_ranges(PC.COUNT, 16, 0.5) == train + val
+    # the generator gives what the rule says
+    graphs = PC.pad_graphs()
+    assert [g.num_edges for g in graphs] == counts and all(g.num_nodes == 12 for g in graphs)
+    assert all(bool((g.edge_index[0] != g.edge_index[1]).all()) for g in graphs)
+
+
+# --------------------------------------------------------------------------- 2. the layout
+@pytest.mark.parametrize("B", [16, 4])
+def test_layout_of_the_smallest_and_the_largest_batch(B):
+    plan, train, val = _plan()
+    _, edge_ptr = PC.offsets()
+    n, max_m = PC.N_NODES, 36
+    P, E_cap = plan[B]["P"], plan[B]["E_cap"]
+    totals = [int(edge_ptr[hi] - edge_ptr[lo]) for lo, hi in train + val if hi - lo == B]
+    for E_real in (min(totals), max(totals)):
+        lay = PC.pad_layout(B, n, max_m, P, E_real, E_cap)
+        src, dst = lay["edge_index"]
+        # totals equal to the slot shape
+        assert E_real + len(src) == E_cap == plan[B]["shape"][2] and len(dst) == len(src)
+        assert B * n + len(lay["node_ids"]) == plan[B]["shape"][1] and len(lay["batch"]) == len(lay["node_ids"])
+        assert B + len(lay["ptr"]) == plan[B]["shape"][0] == B + len(lay["edge_ptr"])
+        assert lay["edge_ptr"][-1] == E_cap and lay["ptr"][-1] == plan[B]["shape"][1]
+        k = 0
+        for p, m in enumerate(lay["sizes"]):
+            assert 0 <= m <= max_m                                       # within the shard's (n, max_m)
+            lo, hi = (B + p) * n, (B + p + 1) * n
+            indeg = {}
+            for s, d in zip(src[k:k + m], dst[k:k + m]):
+                assert lo <= s < hi and lo <= d < hi and s != d          # inside its own node range, no self loop
+                indeg[d] = indeg.get(d, 0) + 1
+            assert max(indeg.values(), default=0) <= -(-max_m // n)      # ceil(max_m / n): a degree the shard contains
+            assert lay["node_ids"][p * n:(p + 1) * n] == list(range(n)) and lay["batch"][p * n:(p + 1) * n] == [B + p] * n
+            k += m
+        assert k == len(src)
+    # the largest batch of the plan leaves nothing to pad, the smallest the whole spread
+    assert PC.pad_layout(B, n, max_m, P, max(totals), E_cap)["sizes"] == [0]
+    assert PC.pad_layout(B, n, max_m, P, min(totals), E_cap)["sizes"] == [E_cap - min(totals)]
+
+
+def test_layout_spills_into_the_next_pad_graph():
+    lay = PC.pad_layout(2, 3, 7, 2, 2, 14)                 # the third plan of test_plan_by_hand: 12 spare edges, 7 + 5
+    assert lay["sizes"] == [7, 5] and lay["edge_ptr"] == [9, 14] and lay["ptr"] == [9, 12]
+    assert lay["edge_index"][0] == [6, 7, 8, 6, 7, 8, 6, 9, 10, 11, 9, 10]
+    assert lay["edge_index"][1] == [7, 8, 6, 7, 8, 6, 7, 10, 11, 9, 10, 11]
+    with pytest.raises(AssertionError):
+        PC.pad_layout(2, 3, 7, 2, -1, 14)                  # 15 spare edges do not fit two pad graphs of 7
+
+
+# --------------------------------------------------------------------------- refusals and defaults
+def test_pad_edges_refusals():
+    import gnn_qot_estimation_amd as q
+    from gnn_qot_estimation_amd import harness as Hn
+    case = PC.PAD_CASES["pad_h16"]
+    model = q.TopologicalGNN(**case["model"])
+    graphs = PC.pad_graphs()
+    quiet = dict(device="cpu", log=lambda s: None)
+    host = q.PackedGraphs.from_data_list(graphs)
+    with pytest.raises(ValueError, match="stream=True"):
+        Hn.fit(model, host, kind="topological", pad_edges=True, **quiet, **case["fit"])
+    with pytest.raises(ValueError, match="HBM-resident"):
+        Hn.fit(model, host, kind="topological", stream=True, pad_edges=True, **quiet, **case["fit"])
+    with pytest.raises(ValueError, match="topological"):
+        Hn.fit(model, host, kind="lightpath", stream=True, pad_edges=True, **quiet, **case["fit"])
+    with pytest.raises(ValueError, match="HBM-resident"):
+        Hn.run_epoch(model, host, range(0, 16), kind="topological", batch_size=16, out_dim=3, device="cpu", criterion=None,
+                     stream=True, pad_edges=True)
+    with pytest.raises(ValueError, match="stream=True"):
+        Hn.run_epoch(model, host, range(0, 16), kind="topological", batch_size=16, out_dim=3, device="cpu", criterion=None,
+                     pad_edges=True)
+    # mixed node counts: refused before anything runs (the shard only has to claim residency for this check)
+    mixed = q.PackedGraphs.from_data_list(H.trajectory_graphs(H.TRAJECTORY_CASES["topo_mixed_nodes"])).to_device("cpu")
+    with pytest.raises(ValueError, match="same node count"):
+        Hn.fit(model, mixed, kind="topological", stream=True, pad_edges=True, **quiet, **case["fit"])
+    with pytest.raises(ValueError, match="same node count"):
+        Hn.check_pad_edges(mixed, "topological", 1, True)
+    with pytest.raises(ValueError, match="single process"):
+        Hn.check_pad_edges(host.to_device("cpu"), "topological", 2, True)
+    with pytest.raises(ValueError, match="same node count"):
+        q.PaddedStageSlot(mixed, 16, 500, 1)
+    with pytest.raises(ValueError, match="HBM-resident"):
+        q.PaddedStageSlot(host, 16, 500, 1)
+
+
+def test_pad_edges_is_off_by_default():
+    from gnn_qot_estimation_amd import harness as Hn, train
+    for fn in (Hn.fit, Hn.run_epoch, Hn.StepReplayer.__init__):
+        assert inspect.signature(fn).parameters["pad_edges"].default is None
+    assert "--pad-edges" in inspect.getsource(train)
+
+
+# --------------------------------------------------------------------------- conditioning of the whole-run cases
+@functools.lru_cache(maxsize=None)
+def _run(name, dtype):
+    return PC.oracle_run(PC.PAD_CASES[name], dtype)
+
+
+@pytest.mark.parametrize("name", list(PC.PAD_CASES))
+def test_padded_case_is_well_conditioned(name):
+    """The rule of tests/test_oracle_train_loop_cpu.py on the unequal shard: fp32 rounding alone moves no compared quantity
+    by more than TOL / 10, and no early-stopping decision is within 10 x TOL of a tie."""
+    r32, r64 = _run(name, torch.float32), _run(name, torch.float64)
+    H.assert_trajectory_counters(r32, r64)
+    assert r32["best_epoch"] == r64["best_epoch"]
+    err = H.trajectory_errors(r32, r64)
+    worst = max(err, key=err.get)
+    print(f"{name}: worst fp32-vs-fp64 {worst} {err[worst]:.2e}")
+    assert err[worst] <= TOL / 10, (worst, err[worst])
+    best, margin = float("-inf"), float("inf")
+    for v in r64["val_r2"]:
+        if best > float("-inf"):
+            need = 10 * TOL * max(1.0, abs(v), abs(best))
+            margin = min(margin, abs(v - best) / need)
+            assert abs(v - best) >= need, (name, v, best)
+        best = max(best, v)
+    print(f"{name}: smallest val_r2 margin {margin:.1f} x the required 10 x TOL")
+    assert not r64["stopped_early"] and r64["epochs_run"] == PC.PAD_CASES[name]["fit"]["num_epochs"]

@@ -19,6 +19,13 @@ of this script (one tree per process), the two trees alternating:
     reference   75              300             16       512
     headline    100             400             64       1024
 
+``--unequal``: the shard's graphs keep their node count but differ in EDGES (``unequal_edge_count``: spread evenly over
+148 .. 452 around the scale's 300, 148 = 2 (n - 1) being the generator's floor of a spanning tree), as the reference's
+topological data does.  Compared on that shard: the other tree's two modes -- ``fit(replay=True)`` and ``fit(stream=True)``
+with exact-shape slots -- against ``fit(stream=True, pad_edges=True)`` here (wall time of both runs of a process, captured
+graphs, reserved memory); and (a) the padded streamed step on it against the exact-shape streamed step on the equal-sized
+shard of the same mean size (both in this tree), with the plan's ``P``, ``E_cap``, ``E_min``.
+
 Prints one JSON object (and writes it to ``--out``).
 """
 import argparse
@@ -32,6 +39,21 @@ import time
 
 SCALES = {"reference": dict(n=75, e=300, hidden=16, batch=512), "headline": dict(n=100, e=400, hidden=64, batch=1024)}
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def unequal_edge_count(g, e):
+    """Directed edges of graph ``g`` of the unequal shard: ``e - 152 .. e + 152`` in steps of 2, mean ``e``."""
+    return e + 2 * ((g * 7919) % 153 - 76)
+
+
+def unequal_shard(graphs, n, e):
+    import gnn_qot_estimation_amd as q
+    from gnn_qot_estimation_amd import synthetic as S
+    out = []
+    for g in range(graphs):
+        b = S.topological_batch(2, 1, n=n, e=unequal_edge_count(g, e), first_graph=g)
+        out.append(q.Data(edge_index=b.edge_index, edge_attr=b.edge_attr, node_ids=b.node_ids, y=b.y, num_nodes=n))
+    return q.PackedGraphs.from_data_list(out)
 
 
 def _child(args):
@@ -48,15 +70,19 @@ def _child(args):
     model = q.TopologicalGNN(sc["n"], sc["hidden"], 3, 4, dropout_p=0.5).to(dev)
     B = sc["batch"]
     out = {"mode": args.child}
-    if args.child in ("step_streamed", "step_per_batch"):
+    if args.child in ("step_streamed", "step_per_batch", "step_padded"):
         flat = Hn.FlatModel(model)
         opt = Hn.FusedSGD(flat, lr=0.01, momentum=0.9, device_lr=True)
         opt.lr = 0.01
         nb = len(shard) // B
-        if args.child == "step_streamed":
-            rep = Hn.StepReplayer(model, "topological", 3, dev, flat, opt, stream=True, shard=shard)
+        if args.child in ("step_streamed", "step_padded"):
+            pad = args.child == "step_padded"
+            rep = Hn.StepReplayer(model, "topological", 3, dev, flat, opt, stream=True, shard=shard,
+                                  **(dict(pad_edges=True) if pad else {}))
             ranges = [((k % nb) * B, (k % nb) * B + B) for k in range(3 + 20 + args.replays)]
             rep.schedule_capacity = len(ranges)       # the walk wraps round the shard inside one schedule
+            if pad:
+                out["pad_plan"] = {str(k): v for k, v in rep.plan_padding(ranges).items()}
             feed = lambda k: ranges[k]
             begin = lambda: rep.begin_epoch(ranges, True)
         else:
@@ -76,10 +102,10 @@ def _child(args):
             t1.record()
             torch.cuda.synchronize(dev)
             rounds.append(t0.elapsed_time(t1) * 1e3 / args.replays)
-            if args.child == "step_streamed":
+            if args.child != "step_per_batch":
                 rep.end_epoch()
         out.update(step_us_rounds=rounds, step_us_median=statistics.median(rounds), graphs=len(rep.graphs),
-                   batches_walked=nb if args.child == "step_streamed" else 1)
+                   batches_walked=nb if args.child != "step_per_batch" else 1)
     else:
         made = []
 
@@ -89,7 +115,8 @@ def _child(args):
                 made.append(self)
 
         Hn.StepReplayer = _Rec
-        kw = dict(stream=True) if args.child == "fit_streamed" else dict(replay=True)
+        kw = {"fit_streamed": dict(stream=True), "fit_padded": dict(stream=True, pad_edges=True),
+              "fit_per_batch": dict(replay=True)}[args.child]
         walls = []
         for _ in range(2):        # the first run also loads every code object; the second (a fresh model, replayer and
             made.clear()          # captures) is the run alone
@@ -104,7 +131,8 @@ def _child(args):
         out.update(fit_wall_s=walls[0], fit_wall_warm_s=walls[1], epochs_run=hist.epochs_run, graphs=len(made[0].graphs),
                    memory_reserved_mb=torch.cuda.memory_reserved(dev) / 2 ** 20,
                    memory_allocated_mb=torch.cuda.memory_allocated(dev) / 2 ** 20,
-                   replay_counts=getattr(hist, "replay_counts", None), final_loss=hist.loss[-1])
+                   replay_counts=getattr(hist, "replay_counts", None), final_loss=hist.loss[-1],
+                   pad_plan={str(k): v for k, v in getattr(made[0], "pad_plan", {}).items()})
     print("CHILD_JSON " + json.dumps(out), flush=True)
 
 
@@ -130,6 +158,8 @@ def main():
     ap.add_argument("--scale", choices=list(SCALES), default="headline")
     ap.add_argument("--parent-tree", default=None, help="tree of the commit to compare with (built)")
     ap.add_argument("--graphs", type=int, default=30000, help="graphs in the shard (70 %% train, 10 chunks)")
+    ap.add_argument("--unequal", action="store_true", help="graphs of unequal edge counts: the padded mode against both "
+                                                            "modes of the other tree (module docstring)")
     ap.add_argument("--replays", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=2, help="alternations of the two trees per measurement")
@@ -153,6 +183,8 @@ def main():
     res = {"scale": args.scale, **sc, "graphs_in_shard": args.graphs, "dropout": 0.5, "replays": args.replays,
            "this_commit": args.this_commit or _commit(ROOT),
            "parent_commit": args.parent_commit or (_commit(args.parent_tree) if args.parent_tree else None)}
+    if args.unequal:
+        return _main_unequal(args, res, sc)
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "shard.pt")
         save_shard(path, q.PackedGraphs.from_batch(S.topological_batch(2, args.graphs, n=sc["n"], e=sc["e"])))
@@ -173,6 +205,40 @@ def main():
         "streamed_reserved_mb": med("fit_streamed", "memory_reserved_mb"),
         "per_batch_reserved_mb": med("fit_per_batch", "memory_reserved_mb"),
     }
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def _main_unequal(args, res, sc):
+    import gnn_qot_estimation_amd as q
+    from gnn_qot_estimation_amd import synthetic as S
+    from gnn_qot_estimation_amd.dataset import save_shard
+    other = args.parent_tree or ROOT
+    res.update(unequal=True, edge_counts=[sc["e"] - 152, sc["e"] + 152],
+               other_tree_is_parent=bool(args.parent_tree))
+    with tempfile.TemporaryDirectory() as tmp:
+        uneq, equal = os.path.join(tmp, "unequal.pt"), os.path.join(tmp, "equal.pt")
+        save_shard(uneq, unequal_shard(args.graphs, sc["n"], sc["e"]))
+        save_shard(equal, q.PackedGraphs.from_batch(S.topological_batch(2, args.graphs, n=sc["n"], e=sc["e"])))
+        runs = [("fit_padded", ROOT, uneq, "fit_padded"), ("fit_streamed", other, uneq, "fit_streamed_exact"),
+                ("fit_per_batch", other, uneq, "fit_per_batch"), ("step_padded", ROOT, uneq, "step_padded"),
+                ("step_streamed", ROOT, equal, "step_streamed_equal")]
+        for rep in range(args.repeats):
+            for mode, tree, shard, key in runs:
+                r = _run_child(mode, tree, args, shard)
+                res.setdefault(key, []).append(r)
+                print(f"# {key} [{rep}]: " + json.dumps({k: v for k, v in r.items() if k != "mode"}), flush=True)
+    res["summary"] = {key: {"fit_wall_s": [r["fit_wall_s"] for r in res[key]],
+                            "fit_wall_warm_s": [r["fit_wall_warm_s"] for r in res[key]],
+                            "graphs": res[key][0]["graphs"], "memory_reserved_mb": res[key][0]["memory_reserved_mb"]}
+                      for key in ("fit_padded", "fit_streamed_exact", "fit_per_batch")}
+    res["summary"]["step_padded_us"] = [r["step_us_median"] for r in res["step_padded"]]
+    res["summary"]["step_streamed_equal_us"] = [r["step_us_median"] for r in res["step_streamed_equal"]]
+    res["summary"]["pad_plan"] = res["fit_padded"][0]["pad_plan"]
     line = json.dumps(res)
     print(line)
     if args.out:
