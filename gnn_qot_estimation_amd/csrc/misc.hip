@@ -77,14 +77,23 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
 // ----------------------------------------------------------------------------- activation
 template <bool BWD>
 __global__ void act_kernel(const float* __restrict__ a, const float* __restrict__ yref,
-                           float* __restrict__ o, int64_t n4, float slope, uint32_t thr16,
+                           float* __restrict__ o, int64_t n, float slope, uint32_t thr16,
                            float keep_scale, uint64_t seed, const int64_t* __restrict__ step_counter) {
+    // thread t owns elements 4t .. 4t+3 (one hash); the last thread of an n that is no multiple of 4 owns n - 4t < 4 of them
     int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (t >= n4) return;
-    float4 in = ld4(a + 4 * t);
-    float vi[4] = {in.x, in.y, in.z, in.w};
-    float vr[4];
-    if (BWD) { float4 r = ld4(yref + 4 * t); vr[0] = r.x; vr[1] = r.y; vr[2] = r.z; vr[3] = r.w; }
+    if (4 * t >= n) return;
+    const int cnt = n - 4 * t >= 4 ? 4 : (int)(n - 4 * t);
+    float vi[4] = {0.f, 0.f, 0.f, 0.f}, vr[4] = {0.f, 0.f, 0.f, 0.f};
+    if (cnt == 4) {
+        float4 in = ld4(a + 4 * t);
+        vi[0] = in.x; vi[1] = in.y; vi[2] = in.z; vi[3] = in.w;
+        if (BWD) { float4 r = ld4(yref + 4 * t); vr[0] = r.x; vr[1] = r.y; vr[2] = r.z; vr[3] = r.w; }
+    } else {
+        for (int c = 0; c < cnt; ++c) {
+            vi[c] = a[4 * t + c];
+            if (BWD) vr[c] = yref[4 * t + c];
+        }
+    }
     uint64_t z = 0;
     if (thr16) z = act_hash64(seed, (uint64_t)step_counter[0], (uint64_t)t);
     float vo[4];
@@ -95,7 +104,8 @@ __global__ void act_kernel(const float* __restrict__ a, const float* __restrict_
         if (BWD) vo[c] = vi[c] * ks * (vr[c] > 0.f ? 1.0f : slope);
         else     vo[c] = (vi[c] > 0.f ? vi[c] : slope * vi[c]) * ks;
     }
-    st4(o + 4 * t, make_float4(vo[0], vo[1], vo[2], vo[3]));
+    if (cnt == 4) st4(o + 4 * t, make_float4(vo[0], vo[1], vo[2], vo[3]));
+    else for (int c = 0; c < cnt; ++c) o[4 * t + c] = vo[c];
 }
 
 // ----------------------------------------------------------------------------- pool
@@ -726,7 +736,7 @@ extern "C" int qot_embed_bwd(const float* grad_out, const int32_t* ids, float* g
 
 static int act_launch(bool bwd, const float* a, const float* yref, float* o, int64_t n, float slope, float p,
                       uint64_t seed, const int64_t* step_counter, hipStream_t stream) {
-    if (n < 0 || (n & 3)) return (n & 3) ? QOT_ERR_UNSUPPORTED : QOT_ERR_BADARG;
+    if (n < 0) return QOT_ERR_BADARG;
     if (n == 0) return QOT_OK;
     if (!a || !o || (bwd && !yref) || p < 0.f || p >= 1.f) return QOT_ERR_BADARG;
     uint32_t thr = 0;
@@ -736,9 +746,9 @@ static int act_launch(bool bwd, const float* a, const float* yref, float* o, int
         if (thr > 65535u) thr = 65535u;
         ks = 1.0f / (1.0f - p);
     }
-    int64_t n4 = n / 4;
-    if (bwd) act_kernel<true><<<grid_for(n4, 256), 256, 0, stream>>>(a, yref, o, n4, slope, thr, ks, seed, step_counter);
-    else     act_kernel<false><<<grid_for(n4, 256), 256, 0, stream>>>(a, yref, o, n4, slope, thr, ks, seed, step_counter);
+    int64_t n4 = (n + 3) / 4;            // any n: the last thread takes the n % 4 tail elements one by one
+    if (bwd) act_kernel<true><<<grid_for(n4, 256), 256, 0, stream>>>(a, yref, o, n, slope, thr, ks, seed, step_counter);
+    else     act_kernel<false><<<grid_for(n4, 256), 256, 0, stream>>>(a, yref, o, n, slope, thr, ks, seed, step_counter);
     QOT_LAUNCH_CHECK();
     return QOT_OK;
 }

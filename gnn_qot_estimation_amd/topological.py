@@ -105,8 +105,14 @@ class TopologicalGNN(nn.Module):
         shadow = self._qot_shadow[0]
         shadow.train(self.training)
         shadow.dropout.p = shadow.mlp[2].p = self.dropout.p
+        # one dropout state per model: the shadow draws with THIS model's base seed and advances THIS model's counter
+        # (left to itself it would seed from torch's and count in a buffer of its own, so that ``_qot_seed`` /
+        # ``_qot_step`` of a padded model meant nothing)
+        shadow._qot_seed = self._seed()
+        state = padded.topological_params(self, self._qot_hp)
+        state["_qot_step"] = self._qot_step
         kwargs = {"return_attention_weights": True} if attention else {}
-        return torch.func.functional_call(shadow, padded.topological_params(self, self._qot_hp), (data,), kwargs)
+        return torch.func.functional_call(shadow, state, (data,), kwargs)
 
     def forward_loss(self, data, target, beta: float = 1.0, loss_out=None):
         """``out = self(data)`` together with the train step's criterion ``SmoothL1Loss(reduction="mean", beta)(out,

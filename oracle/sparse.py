@@ -215,17 +215,32 @@ class TopologicalGNN(nn.Module):
         self.dropout = nn.Dropout(p=dropout_p)
         self.num_layers = num_layers
 
-    def forward(self, data):
+    def _drop(self, x, module, keep, site):
+        """``module`` (an ``nn.Dropout``) on ``x``, or -- where ``keep`` names ``site`` -- the given realisation of it:
+        ``x * keep / (1 - p)`` in the model's dtype (``oracle.dropout`` restates the masks of the HIP kernels)."""
+        if keep is None or site not in keep:
+            return module(x)
+        mask = keep[site]
+        if tuple(mask.shape) != tuple(x.shape):
+            raise ValueError(f"{site}: mask {tuple(mask.shape)} for an activation {tuple(x.shape)}")
+        return x * mask.to(x.dtype) / (1.0 - module.p)
+
+    def forward(self, data, keep=None):
+        """``keep``: ``{site: bool tensor}`` for the sites ``conv1``, ``conv2``, ... (after each convolution's
+        ``leaky_relu``) and ``head`` (inside the read-out MLP); a site without an entry runs its ``nn.Dropout``."""
         x = data.x
         if x is None or x.numel() == 0:
             x = self.node_embeddings(data.node_ids)
         x = self.conv1(x, data.edge_index, data.edge_attr)
-        x = self.dropout(F.leaky_relu(x))
+        x = self._drop(F.leaky_relu(x), self.dropout, keep, "conv1")
         for layer in range(2, self.num_layers + 1):
             x = getattr(self, f"conv{layer}")(x, data.edge_index, data.edge_attr)
-            x = self.dropout(F.leaky_relu(x))
+            x = self._drop(F.leaky_relu(x), self.dropout, keep, f"conv{layer}")
         x = global_mean_pool(x, data.batch)
-        return self.mlp(x)
+        if keep is None or "head" not in keep:
+            return self.mlp(x)
+        x = self._drop(self.mlp[1](self.mlp[0](x)), self.mlp[2], keep, "head")
+        return self.mlp[3](x)
 
 
 class LightpathGNN(nn.Module):
@@ -252,11 +267,20 @@ class LightpathGNN(nn.Module):
         self.is_lut_index = is_lut_index
         self.num_layers = num_layers
 
-    def forward(self, data):
+    def forward(self, data, keep=None):
+        """``keep``: ``{"head": bool tensor [rows, hidden]}`` replaces the MLP's ``nn.Dropout`` by that realisation
+        (``x * keep / (1 - p)``); ``None`` runs the module as it stands."""
         x = data.x
         for layer in range(1, self.num_layers + 1):
             x = F.relu(getattr(self, f"norm{layer}")(getattr(self, f"conv{layer}")(x, data.edge_index)))
         lut_mask = data.x[:, self.is_lut_index] == 1.0
         if not lut_mask.any():
             raise ValueError("No LUT node found in the batch.")
-        return self.mlp(x[lut_mask]), data.batch[lut_mask]
+        if keep is None or "head" not in keep:
+            return self.mlp(x[lut_mask]), data.batch[lut_mask]
+        h = self.mlp[1](self.mlp[0](x[lut_mask]))
+        mask = keep["head"]
+        if tuple(mask.shape) != tuple(h.shape):
+            raise ValueError(f"head: mask {tuple(mask.shape)} for an activation {tuple(h.shape)}")
+        h = h * mask.to(h.dtype) / (1.0 - self.mlp[2].p)
+        return self.mlp[3](h), data.batch[lut_mask]

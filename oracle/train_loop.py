@@ -91,10 +91,11 @@ def _cast(graph: Data, dtype) -> Data:
     return out
 
 
-def _forward(model, batch, kind: str, output_dim: int):
+def _forward(model, batch, kind: str, output_dim: int, keep=None):
     """``(out, y)`` of one batch, or ``None`` when the lightpath batch is to be skipped."""
     if kind == "topological":
-        return model(batch), batch.y.view(-1, output_dim)
+        out = model(batch) if keep is None else model(batch, keep=keep)
+        return out, batch.y.view(-1, output_dim)
     try:
         out, lut_batch = model(batch)
     except ValueError:
@@ -105,8 +106,26 @@ def _forward(model, batch, kind: str, output_dim: int):
     return out, y
 
 
+class _Draws:
+    """The dropout realisations of a run: train-mode forward number ``k`` (1-based over the whole run) of a
+    ``TopologicalGNN`` draws the masks of step ``first_step + k`` (``oracle.dropout``); evaluation draws nothing."""
+
+    def __init__(self, base_seed: int, first_step: int):
+        self.base_seed, self.first_step, self.count = int(base_seed), int(first_step), 0
+
+    def masks(self, model, batch):
+        from . import dropout as OD
+        self.count += 1
+        p = model.dropout.p
+        if not p > 0.0:
+            return None
+        width = model.node_embeddings.embedding_dim
+        return OD.topological_masks(self.base_seed, self.first_step + self.count, p, batch.num_nodes,
+                                    batch.num_graphs, width, num_layers=model.num_layers)
+
+
 def _one_pass(model, graphs: Sequence[Data], kind: str, batch_size: int, output_dim: int, criterion,
-              optimizer=None) -> Dict[str, float]:
+              optimizer=None, draws=None) -> Dict[str, float]:
     training = optimizer is not None
     model.train(training)
     total, skipped, ys, yhats = 0.0, 0, [], []
@@ -115,7 +134,8 @@ def _one_pass(model, graphs: Sequence[Data], kind: str, batch_size: int, output_
             batch = Batch.from_data_list(graphs[first:first + batch_size])
             if training:
                 optimizer.zero_grad()
-            res = _forward(model, batch, kind, output_dim)
+            keep = draws.masks(model, batch) if (training and draws is not None) else None
+            res = _forward(model, batch, kind, output_dim, keep)
             if res is None:
                 skipped += batch.num_graphs
                 continue
@@ -138,14 +158,21 @@ def _snapshot(model) -> Dict[str, torch.Tensor]:
 def train(model, graphs: Sequence[Data], kind: str, *, dtype=torch.float32, batch_size: int = 512,
           num_epochs: int = 35, patience: int = 10, lr: float = 0.1, momentum: float = 0.9, step_size: int = 10,
           gamma: float = 0.5, chunk_fraction: float = 0.10, output_dim: int = 3,
-          on_epoch=None) -> Dict[str, object]:
+          on_epoch=None, dropout=None) -> Dict[str, object]:
     """Train ``model`` (an ``oracle.sparse`` model, modified in place) on ``graphs`` as the reference scripts do.
 
     ``on_epoch(epoch, model)`` is called after each epoch's validation (a hook for tests).  Returns the histories, the
     learning rate used in every epoch, the early-stopping outcome, the final and the best-epoch ``state_dict`` and the
-    momentum buffers in parameter order."""
+    momentum buffers in parameter order.
+
+    ``dropout=(base_seed, first_step)`` (topological only): every train-mode forward runs the counter-based masks of the
+    HIP kernels, restated by ``oracle.dropout`` -- forward number ``k`` of the run those of step ``first_step + k``;
+    ``res["dropout_draws"]`` is the number of draws made (0 without the argument)."""
     if kind not in ("topological", "lightpath"):
         raise ValueError(kind)
+    if dropout is not None and kind != "topological":
+        raise ValueError("restated dropout masks exist for the topological model only")
+    draws = _Draws(*dropout) if dropout is not None else None
     model.to(dtype)
     graphs = [_cast(g, dtype) for g in graphs]
     train_idx, val_idx, _ = split(len(graphs))
@@ -161,7 +188,7 @@ def train(model, graphs: Sequence[Data], kind: str, *, dtype=torch.float32, batc
     for epoch in range(num_epochs):
         chunk = [train_graphs[i] for i in chunk_indices(epoch, len(train_graphs), chunk_fraction)]
         res["lr"].append(float(optimizer.param_groups[0]["lr"]))
-        t = _one_pass(model, chunk, kind, batch_size, output_dim, criterion, optimizer)
+        t = _one_pass(model, chunk, kind, batch_size, output_dim, criterion, optimizer, draws)
         v = _one_pass(model, val_graphs, kind, batch_size, output_dim, criterion)
         res["loss"].append(t["loss"]); res["r2"].append(t["r2"])
         res["val_loss"].append(v["loss"]); res["val_r2"].append(v["r2"])
@@ -176,6 +203,7 @@ def train(model, graphs: Sequence[Data], kind: str, *, dtype=torch.float32, batc
             res["stopped_early"] = True
             break
         scheduler.step()
+    res["dropout_draws"] = draws.count if draws is not None else 0
     res["best_val_r2"] = stopper.best
     res["best_epoch"] = stopper.best_epoch
     res["state_dict"] = _snapshot(model)

@@ -13,6 +13,28 @@ def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:
 TOL = 1e-4  # BASELINE.json north_star: outputs match the reference forward to <=1e-4 rel fp32
 
 
+def grad_compare(ref, hip, analytic_zero=()):
+    """Every parameter gradient of ``hip`` against ``ref``'s; returns the worst error.
+
+    A gradient that is analytically zero (e.g. lin_key.bias: softmax is shift invariant) is pure rounding noise in both
+    implementations, so each parameter's error is taken relative to max(its own magnitude, 1e-3 x the largest gradient
+    in the model); a name in ``analytic_zero`` relative to the largest gradient."""
+    worst = 0.0
+    rp = dict(ref.named_parameters())
+    gmax = max(float(p.grad.abs().max()) for p in rp.values() if p.grad is not None)
+    for name, p in hip.named_parameters():
+        if rp[name].grad is None:                        # unused on both sides (the embedding when data.x is given)
+            assert p.grad is None, name
+            continue
+        assert p.grad is not None, name
+        a, b = p.grad.detach().double().cpu(), rp[name].grad.detach().double()
+        floor = gmax if name in analytic_zero else 1e-3 * gmax
+        e = float((a - b).abs().max() / max(float(b.abs().max()), floor))
+        worst = max(worst, e)
+        assert e <= TOL, (name, e)
+    return worst
+
+
 # --------------------------------------------------------------------------- whole training runs
 # The cases of tests/test_gpu_training_trajectory.py (HIP ``harness.fit`` against ``oracle.train_loop.train`` in fp64)
 # and of tests/test_oracle_train_loop_cpu.py (conditioning: the oracle loop in fp32 against itself in fp64 must stay
@@ -32,13 +54,17 @@ def _lp_fit(**kw):
                      chunk_fraction=0.5, output_dim=3), **kw)
 
 
-def _topo_model(H, V=12, D=4):
-    return dict(num_nodes=V, hidden_channels=H, out_channels=3, edge_dim=D, dropout_p=0.0)
+def _topo_model(H, V=12, D=4, p=0.0):
+    return dict(num_nodes=V, hidden_channels=H, out_channels=3, edge_dim=D, dropout_p=p)
 
 
 def _lp_model(C, layers=1):
     return dict(in_channels=5, hidden_channels=C, output_dim=3, is_lut_index=1, dropout_p=0.0, num_layers=layers)
 
+
+# base seed of the dropout-on cases: bit 62 set, so that the site seeds (base + golden ratio * site, mod 2^64) use all
+# 64 bits; the HIP model gets it as ``_qot_seed``
+DROPOUT_SEED = (1 << 62) + 20240517
 
 TRAJECTORY_CASES = {
     # reference scale; ragged last batch (84 = 5 * 16 + 4)
@@ -71,6 +97,18 @@ TRAJECTORY_CASES = {
                           fit=_lp_fit()),
     # zero-padded width with buffers
     "lp_c24": dict(kind="lightpath", model=_lp_model(24), data=dict(count=96, no_lut=range(8, 12)), fit=_lp_fit()),
+    # dropout ON (p = 0.5, the models' default): the oracle loop runs the kernels' own masks, restated by
+    # oracle/dropout.py from ``dropout_seed`` and the number of the train-mode forward.  Copies of topo_h16 / topo_h64 /
+    # topo_h48 / topo_d6_h32: graph-form and split-bf16 epilogues, masks numbered at the padded width 64, and the
+    # separate activation kernel of the materialised path.
+    "topo_h16_drop": dict(kind="topological", model=_topo_model(16, p=0.5), data=dict(count=240), fit=_topo_fit(),
+                          dropout_seed=DROPOUT_SEED),
+    "topo_h64_drop": dict(kind="topological", model=_topo_model(64, p=0.5), data=dict(count=240), fit=_topo_fit(),
+                          dropout_seed=DROPOUT_SEED),
+    "topo_h48_drop": dict(kind="topological", model=_topo_model(48, p=0.5), data=dict(count=240), fit=_topo_fit(),
+                          dropout_seed=DROPOUT_SEED),
+    "topo_d6_h32_drop": dict(kind="topological", model=_topo_model(32, D=6, p=0.5), data=dict(count=240, D=6),
+                             fit=_topo_fit(), dropout_seed=DROPOUT_SEED),
 }
 
 
@@ -176,10 +214,13 @@ def assert_trajectory_counters(got, ref):
                 assert int(got[which][k]) == int(v), (which, k, int(got[which][k]), int(v))
 
 
-def oracle_trajectory(case, dtype):
-    """``oracle.train_loop.train`` on a case, with the parameter names added."""
+def oracle_trajectory(case, dtype, **kw):
+    """``oracle.train_loop.train`` on a case, with the parameter names added.  A case with a ``dropout_seed`` runs the
+    restated masks from step counter 0 (a fresh model's): train-mode forward ``k`` draws step ``k``."""
     from oracle import train_loop
     model = trajectory_oracle_model(case)
-    res = train_loop.train(model, trajectory_graphs(case), case["kind"], dtype=dtype, **case["fit"])
+    if case.get("dropout_seed") is not None:
+        kw = dict(dict(dropout=(case["dropout_seed"], 0)), **kw)
+    res = train_loop.train(model, trajectory_graphs(case), case["kind"], dtype=dtype, **case["fit"], **kw)
     res["param_names"] = [n for n, p in model.named_parameters() if p.requires_grad]
     return res

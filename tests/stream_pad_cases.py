@@ -27,6 +27,14 @@ PAD_CASES = {
     "pad_h64": dict(kind="topological", model=H._topo_model(64), fit=H._topo_fit()),
 }
 
+# dropout ON (p = 0.5): the oracle loop runs the kernels' masks (oracle/dropout.py).  Pad graphs are appended AFTER the real
+# ones, so real elements keep their flat indices and the oracle's masks are the [N_real, H] / [B_real, H] prefixes of the
+# slot's -- which is what the loop draws for the unpadded batch.
+PAD_DROP_CASES = {
+    "pad_h64_drop": dict(kind="topological", model=H._topo_model(64, p=0.5), fit=H._topo_fit(), dropout_seed=H.DROPOUT_SEED),
+}
+ALL_CASES = dict(PAD_CASES, **PAD_DROP_CASES)
+
 
 def edge_count(g):
     return 26 + 2 * ((g * g + g // 5) % 6)
@@ -64,10 +72,12 @@ def run_ranges(fit):
 
 
 def oracle_run(case, dtype):
-    """``oracle.train_loop.train`` on a case of ``PAD_CASES``, with the parameter names added."""
+    """``oracle.train_loop.train`` on a case of ``ALL_CASES``, with the parameter names added (a case with a
+    ``dropout_seed``: restated masks from step counter 0, as ``helpers.oracle_trajectory``)."""
     from oracle import train_loop
     model = H.trajectory_oracle_model(case)
-    res = train_loop.train(model, pad_graphs(), case["kind"], dtype=dtype, **case["fit"])
+    kw = dict(dropout=(case["dropout_seed"], 0)) if case.get("dropout_seed") is not None else {}
+    res = train_loop.train(model, pad_graphs(), case["kind"], dtype=dtype, **case["fit"], **kw)
     res["param_names"] = [n for n, p in model.named_parameters() if p.requires_grad]
     return res
 

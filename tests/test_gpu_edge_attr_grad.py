@@ -2,12 +2,13 @@
 oracle's plain autograd, in every form the forward and backward can take (graph, per-destination plain / tiled, rows,
 node path; NNConv at H = 64, the generic widths, the wide edge MLP), with the parameter gradients checked alongside.
 Plus the invariants: asking for the edge gradient changes nothing else, and it is bitwise reproducible.  Dropout on is
-checked against a central difference (the oracle cannot replay the masks)."""
+checked against a central difference here (parameter gradients with dropout on are checked against the oracle running the
+same masks in tests/test_gpu_dropout_oracle.py)."""
 import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import TOL, rel_err
+from helpers import TOL, grad_compare as _grad_compare, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -28,26 +29,6 @@ def _models(kind, device, **kw):
                 p.uniform_(-0.1, 0.1)
     hip.load_state_dict(ref.state_dict(), strict=True)
     return ref, hip.to(device)
-
-
-def _grad_compare(ref, hip, analytic_zero=()):
-    # A gradient that is analytically zero (e.g. lin_key.bias: softmax is shift invariant)
-    # is pure rounding noise in both implementations, so each parameter's error is taken
-    # relative to max(its own magnitude, 1e-3 x the largest gradient in the model).
-    worst = 0.0
-    rp = dict(ref.named_parameters())
-    gmax = max(float(p.grad.abs().max()) for p in rp.values() if p.grad is not None)
-    for name, p in hip.named_parameters():
-        if rp[name].grad is None:                        # unused on both sides (the embedding when data.x is given)
-            assert p.grad is None, name
-            continue
-        assert p.grad is not None, name
-        a, b = p.grad.detach().double().cpu(), rp[name].grad.detach().double()
-        floor = gmax if name in analytic_zero else 1e-3 * gmax
-        e = float((a - b).abs().max() / max(float(b.abs().max()), floor))
-        worst = max(worst, e)
-        assert e <= TOL, (name, e)
-    return worst
 
 
 def _record(monkeypatch):

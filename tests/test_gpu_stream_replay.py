@@ -5,7 +5,9 @@ the device into that shape's static buffers.
    (``TOL = 1e-4``), the metric and the printout of tests/test_gpu_training_trajectory.py (worst figures measured on an
    MI355X: DESIGN.md section 2, rows "streamed");
 2. the run took the path: number of captured graphs, how the visits were issued, the staging kernel among the calls;
-3. dropout on: bit-equal to the per-batch replay (the oracle cannot follow the counter-based masks);
+3. dropout on: the ``*_drop`` cases of 1. run against the oracle loop with the kernels' own masks restated
+   (oracle/dropout.py; one draw per visit of a training batch, whichever way it is issued), which is the correctness
+   check; bit-equality with the per-batch replay checks that the two modes agree;
 4. the per-batch caches of ``graph.py`` do not survive a staging;
 5. a node id outside the embedding table in a batch that is only ever replayed is reported at the end of its epoch.
 """
@@ -30,6 +32,8 @@ def _fit(name, device, tmp_path, monkeypatch, model_kw=None, graphs=None, **fit_
     ref_model = H.trajectory_oracle_model(case)
     hip = q.TopologicalGNN(**dict(case["model"], **(model_kw or {})))
     hip.load_state_dict(ref_model.state_dict(), strict=True)
+    if case.get("dropout_seed") is not None:
+        hip._qot_seed = case["dropout_seed"]
     data = q.PackedGraphs.from_data_list(H.trajectory_graphs(case) if graphs is None else graphs).to_device(device)
     made, calls = [], set()
 
@@ -57,6 +61,7 @@ def _fit(name, device, tmp_path, monkeypatch, model_kw=None, graphs=None, **fit_
         "best_state_dict": torch.load(best, map_location="cpu", weights_only=True),
         "momentum_buffers": [b.cpu() for b in opt.buf.split(sizes)],
         "param_names": [n for n, p in hip.named_parameters() if p.requires_grad],
+        "dropout_draws": int(hip._qot_step),
     }
     return got, hist, calls
 

@@ -8,6 +8,12 @@ tests/test_oracle_train_loop_cpu.py) runs under the three ways of feeding ``fit`
 without replay, a resident shard with captured and replayed steps.  Everything is compared with ``TOL = 1e-4`` in the
 metric of ``helpers.trajectory_errors``.
 
+The ``*_drop`` cases train with dropout ON (p = 0.5): the oracle loop runs the kernels' own counter-based masks, restated
+by ``oracle/dropout.py`` from the base seed the HIP model is given (``_qot_seed``) and the number of the train-mode forward.
+Every visit of a training batch -- eager, the one replay that follows its capture (a capture records, it does not
+execute), every later replay -- is exactly one draw, and evaluation draws nothing, so the step sequence of all three
+modes is 1, 2, 3, ... in batch order; the run's final ``_qot_step`` must equal the oracle loop's draw count.
+
 Worst HIP-vs-fp64 figures measured on an MI355X are listed per case in DESIGN.md section 2.
 """
 import functools
@@ -35,6 +41,8 @@ def _fit_hip(name, mode, device, tmp_path, monkeypatch):
     ref_model = H.trajectory_oracle_model(case)
     hip = (q.TopologicalGNN if case["kind"] == "topological" else q.LightpathGNN)(**case["model"])
     hip.load_state_dict(ref_model.state_dict(), strict=True)
+    if case.get("dropout_seed") is not None:
+        hip._qot_seed = case["dropout_seed"]
     graphs = H.trajectory_graphs(case)
     if mode == "host":
         # the eager loader's two sources: a pinned shard (DMA'd slices) and a plain host list (collated per batch)
@@ -67,6 +75,7 @@ def _fit_hip(name, mode, device, tmp_path, monkeypatch):
         "best_state_dict": torch.load(best, map_location="cpu", weights_only=True),
         "momentum_buffers": [b.cpu() for b in opt.buf.split(sizes)],
         "param_names": [n for n, p in hip.named_parameters() if p.requires_grad],
+        "dropout_draws": int(getattr(hip, "_qot_step", 0)),
     }
 
 
@@ -84,6 +93,9 @@ def _compare(name, mode, got):
             groups[g] = (k, v)
     print(f"\n[trajectory] {name} / {mode}: " + ", ".join(f"{g} {v:.2e}" for g, (k, v) in sorted(groups.items())))
     H.assert_trajectory_counters(got, ref)
+    assert got["dropout_draws"] == ref["dropout_draws"], (got["dropout_draws"], ref["dropout_draws"])
+    if case.get("dropout_seed") is not None:
+        assert ref["dropout_draws"] > 0
     bad = {k: v for k, v in err.items() if not v <= TOL}
     assert not bad, (name, mode, sorted(bad.items(), key=lambda kv: -kv[1])[:8])
 

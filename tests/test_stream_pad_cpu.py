@@ -172,10 +172,10 @@ def test_pad_edges_is_off_by_default():
 # --------------------------------------------------------------------------- conditioning of the whole-run cases
 @functools.lru_cache(maxsize=None)
 def _run(name, dtype):
-    return PC.oracle_run(PC.PAD_CASES[name], dtype)
+    return PC.oracle_run(PC.ALL_CASES[name], dtype)
 
 
-@pytest.mark.parametrize("name", list(PC.PAD_CASES))
+@pytest.mark.parametrize("name", list(PC.ALL_CASES))
 def test_padded_case_is_well_conditioned(name):
     """The rule of tests/test_oracle_train_loop_cpu.py on the unequal shard: fp32 rounding alone moves no compared quantity
     by more than TOL / 10, and no early-stopping decision is within 10 x TOL of a tie."""
@@ -194,4 +194,4 @@ def test_padded_case_is_well_conditioned(name):
             assert abs(v - best) >= need, (name, v, best)
         best = max(best, v)
     print(f"{name}: smallest val_r2 margin {margin:.1f} x the required 10 x TOL")
-    assert not r64["stopped_early"] and r64["epochs_run"] == PC.PAD_CASES[name]["fit"]["num_epochs"]
+    assert not r64["stopped_early"] and r64["epochs_run"] == PC.ALL_CASES[name]["fit"]["num_epochs"]
