@@ -151,6 +151,8 @@ SIGNATURES = {
                                _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "qot_shard_stage_padded": (_int, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _int, _p, _p, _int, _p, _int, _i64,
                                       _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "qot_shard_stage_gather": (_int, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _int, _p, _p, _int, _p, _int, _i64,
+                                      _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "qot_gather3": (_int, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
     "qot_gemm_nt": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _int, _int, _p, _p, _p, _p]),
     "qot_gemm_nt_planes": (_int, [_p, _i64, _p, _i64, _p, _i64, _int, _int, _int, _p]),

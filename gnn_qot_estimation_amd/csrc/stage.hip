@@ -29,11 +29,22 @@
 // stage_copy_padded_kernel copies the real slice as above and then writes P pad graphs that hold the spare edges as
 // rings over their own n nodes, with zero edge features: computed from (E_real, E_cap, P, n, max_m), nothing loaded.
 //
+// Gather slots (qot_shard_stage_gather; loader.GatherStageSlot): the padded slot filled from a LIST of single graphs
+// (shuffled batches).  The schedule holds graph ids, B per batch.  stage_plan_gather_kernel validates the batch's ids,
+// forms the exclusive prefix sum of their edge counts (workgroup scan, carried between rounds of 256 graphs) into a
+// scratch array owned by the slot -- not into the slot's edge_ptr: a refused batch leaves the previous one untouched --
+// and accepts E_real as the padded plan does.  stage_copy_gather_kernel is the segmented copy: QOT_GATHER_LANES lanes per
+// graph, grid-stride over the graphs, each group running the helpers below on its graph's segments (which start at
+// arbitrary 8-byte / 4-byte alignment on BOTH sides: 16-byte stores, 16-byte loads where the source allows); then the
+// pad graphs of the padded slot (stage_pad_graphs, shared).
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   stage_plan_kernel<false>  VGPRs 16, AGPRs 0, SGPRs 50,  scratch 0, LDS 272 B, occupancy 8 waves / SIMD
 //   stage_plan_kernel<true>   VGPRs 16, AGPRs 0, SGPRs 52,  scratch 0, LDS 280 B, occupancy 8 waves / SIMD
 //   stage_copy_kernel         VGPRs 18, AGPRs 0, SGPRs 92,  scratch 0, LDS 0,     occupancy 8 waves / SIMD
 //   stage_copy_padded_kernel  VGPRs 26, AGPRs 0, SGPRs 105, scratch 0, LDS 0,     occupancy 7 waves / SIMD
+//   stage_plan_gather_kernel  VGPRs 36, AGPRs 0, SGPRs 75,  scratch 0, LDS 48 B,  occupancy 8 waves / SIMD
+//   stage_copy_gather_kernel  VGPRs 83, AGPRs 0, SGPRs 106, scratch 0, LDS 0,     occupancy 5 waves / SIMD
 // At the headline shape (1024 graphs x 100 nodes / 400 edges, D = 4) the copy moves ~15 MB (read + write ~30 MB).
 #include "common.hpp"
 
@@ -227,6 +238,31 @@ __device__ __forceinline__ void stage_zero_u32(uint32_t* __restrict__ dst, int64
     if (tid < n - tail0) dst[tail0 + tid] = 0;
 }
 
+// What lies behind the real part of a padded slot: P pad graphs that take the E_cap - E_real spare edges, max_m apiece
+// until they are used up, as rings over their own n nodes.  Computed from (E_real, E_cap, P, n, max_m): no load.  The pad
+// regions are a few hundred elements (at most P * max_m edges, P * n nodes), so their 64-bit divisions do not show.
+__device__ __forceinline__ void stage_pad_graphs(const StageShard& s, const StageSlot& d, int64_t E_real, int64_t P, int64_t tid,
+                                                 int64_t nth) {
+    const int64_t E_cap = d.E, n = d.max_n, max_m = d.max_m, B = d.B, N = d.N;
+    const int64_t spare = E_cap - E_real;
+    // pad edge j: pad graph p = j / max_m, its edge k = j mod max_m: (k mod n) -> ((k + 1) mod n) from node N + p n on
+    auto ring = [&](int64_t j, int64_t step) -> int64_t {
+        const int64_t p = j / max_m, k = j - p * max_m;
+        return N + p * n + (k + step) % n;
+    };
+    stage_fill_i64(d.edge_index + E_real, spare, [&](int64_t j) { return ring(j, 0); }, tid, nth);
+    stage_fill_i64(d.edge_index + E_cap + E_real, spare, [&](int64_t j) { return ring(j, 1); }, tid, nth);
+    if (s.edge_attr) stage_zero_u32(d.edge_attr + E_real * s.D, spare * s.D, tid, nth);
+    if (s.x) stage_zero_u32(d.x + N * s.F, P * n * s.F, tid, nth);
+    if (s.node_ids) stage_fill_i64(d.node_ids + N, P * n, [&](int64_t i) { return i % n; }, tid, nth);
+    stage_fill_i64(d.batch + N, P * n, [&](int64_t i) { return B + i / n; }, tid, nth);
+    stage_fill_i64(d.ptr + B + 1, P, [&](int64_t p) { return N + (p + 1) * n; }, tid, nth);
+    stage_fill_i64(d.edge_ptr + B + 1, P, [&](int64_t p) {
+        const int64_t used = (p + 1) * max_m;
+        return E_real + (used < spare ? used : spare);
+    }, tid, nth);
+}
+
 // Graphs [lo, lo + B) of the shard -- N nodes, E edges -- into the front of the slot's buffers; ld_e: the slot's edge
 // capacity (the distance between the two rows of its edge_index).
 __device__ __forceinline__ void stage_slice(const StageShard& s, const StageSlot& d, int64_t lo, int64_t B, int64_t N, int64_t E,
@@ -258,37 +294,152 @@ __global__ __launch_bounds__(256) void stage_copy_kernel(const int64_t* __restri
 }
 
 // The padded slot: d.B / d.N count the REAL graphs / nodes, d.E is the edge capacity, d.max_n the node count n of every
-// graph; the buffers hold d.B + P graphs, (d.B + P) * n nodes, d.E edges.  The real slice, then P pad graphs that take
-// the E_cap - E_real spare edges, max_m apiece until they are used up, as rings over their own n nodes.  Everything
-// behind the real slice is computed from (E_real, E_cap, P, n, max_m): no load.  The pad regions are a few hundred
-// elements (at most P * max_m edges, P * n nodes), so their 64-bit divisions do not show.
+// graph; the buffers hold d.B + P graphs, (d.B + P) * n nodes, d.E edges.  The real slice, then the pad graphs.
 __global__ __launch_bounds__(256) void stage_copy_padded_kernel(const int64_t* __restrict__ ctl, int32_t* __restrict__ status,
                                                                 StageShard s, StageSlot d, int64_t P) {
     const int64_t lo = ctl[kStageSnap];
     if (lo < 0) return;                                  // the plan refused the slice: nothing is staged
     const int64_t E_real = ctl[kStageEdges];
-    const int64_t E_cap = d.E, n = d.max_n, max_m = d.max_m, B = d.B, N = d.N;
+    const int64_t E_cap = d.E, B = d.B, N = d.N;
     const int64_t spare = E_cap - E_real;
-    if (E_real < 0 || spare < 0 || spare > P * max_m) return;      // what the plan accepted, once more: bounds every store below
+    if (E_real < 0 || spare < 0 || spare > P * d.max_m) return;    // what the plan accepted, once more: bounds every store below
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const int64_t nth = (int64_t)gridDim.x * blockDim.x;
     stage_slice(s, d, lo, B, N, E_real, E_cap, status, tid, nth);
-    // pad edge j: pad graph p = j / max_m, its edge k = j mod max_m: (k mod n) -> ((k + 1) mod n) from node N + p n on
-    auto ring = [&](int64_t j, int64_t step) -> int64_t {
-        const int64_t p = j / max_m, k = j - p * max_m;
-        return N + p * n + (k + step) % n;
-    };
-    stage_fill_i64(d.edge_index + E_real, spare, [&](int64_t j) { return ring(j, 0); }, tid, nth);
-    stage_fill_i64(d.edge_index + E_cap + E_real, spare, [&](int64_t j) { return ring(j, 1); }, tid, nth);
-    if (s.edge_attr) stage_zero_u32(d.edge_attr + E_real * s.D, spare * s.D, tid, nth);
-    if (s.x) stage_zero_u32(d.x + N * s.F, P * n * s.F, tid, nth);
-    if (s.node_ids) stage_fill_i64(d.node_ids + N, P * n, [&](int64_t i) { return i % n; }, tid, nth);
-    stage_fill_i64(d.batch + N, P * n, [&](int64_t i) { return B + i / n; }, tid, nth);
-    stage_fill_i64(d.ptr + B + 1, P, [&](int64_t p) { return N + (p + 1) * n; }, tid, nth);
-    stage_fill_i64(d.edge_ptr + B + 1, P, [&](int64_t p) {
-        const int64_t used = (p + 1) * max_m;
-        return E_real + (used < spare ? used : spare);
-    }, tid, nth);
+    stage_pad_graphs(s, d, E_real, P, tid, nth);
+}
+
+// ---- gather slots: a batch is a list of B graph ids ------------------------------------------------------------------
+#ifndef QOT_GATHER_LANES
+#define QOT_GATHER_LANES 64          // lanes per graph of the segmented copy (a power of two <= 64; measured: file header)
+#endif
+constexpr int kGatherLanes = QOT_GATHER_LANES;
+static_assert(kGatherLanes >= 1 && kGatherLanes <= 64 && (kGatherLanes & (kGatherLanes - 1)) == 0, "lanes per graph");
+
+// ctl: [position, batches in the schedule, snapshot, E_real], then B ids per batch.  Batch `position` is validated id by
+// id -- 0 <= g < G (else RANGE), n nodes and 0 <= m_g <= max_m edges inside the arrays (else SHAPE) -- and offs[i]
+// receives the exclusive prefix sum of the edge counts: 256 graphs per round, a wave scan, the four wave totals through
+// LDS, the running total carried into the next round.  The verdict (the batch's number, or -1) goes to the snapshot
+// word and E_real beside it, as stage_plan_kernel<true> publishes them; the position advances under the same rule.
+__global__ __launch_bounds__(256) void stage_plan_gather_kernel(int64_t* __restrict__ ctl, int64_t sched_cap,
+                                                                int32_t* __restrict__ status, int64_t* __restrict__ offs,
+                                                                const int64_t* __restrict__ node_ptr,
+                                                                const int64_t* __restrict__ edge_ptr, int64_t G, int64_t N_total,
+                                                                int64_t E_total, int64_t B, int64_t n, int64_t E_cap,
+                                                                int64_t max_m, int64_t pad_cap) {
+    __shared__ int64_t s_pos;
+    __shared__ int64_t s_wave[4];
+    __shared__ int s_bits;
+    if (threadIdx.x == 0) {
+        int64_t pos = ctl[kStagePos];
+        int64_t cnt = ctl[kStageCount];
+        if (cnt > sched_cap) cnt = sched_cap;
+        if (pos < 0 || pos >= cnt) {
+            s_bits = QOT_STAGE_BAD_RANGE;                // the schedule is used up: the position stays where it is
+            pos = -1;
+        } else {
+            s_bits = 0;
+            ctl[kStagePos] = pos + 1;
+        }
+        s_pos = pos;
+    }
+    __syncthreads();
+    const int64_t pos = s_pos;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t carry = 0;
+    int bits = 0;
+    if (pos >= 0) {
+        const int64_t* ids = ctl + kStageHeader + pos * B;
+        for (int64_t base = 0; base < B; base += 256) {  // uniform trip count: every thread meets every barrier
+            const int64_t i = base + threadIdx.x;
+            int64_t m = 0;
+            if (i < B) {
+                const int64_t g = ids[i];
+                if (g < 0 || g >= G) {
+                    bits |= QOT_STAGE_BAD_RANGE;
+                } else {
+                    const int64_t n0 = node_ptr[g], e0 = edge_ptr[g];
+                    m = edge_ptr[g + 1] - e0;
+                    if (n0 < 0 || n0 > N_total - n || e0 < 0 || m < 0 || m > E_total - e0) { bits |= QOT_STAGE_BAD_RANGE; m = 0; }
+                    else if (node_ptr[g + 1] - n0 != n || m > max_m) { bits |= QOT_STAGE_BAD_SHAPE; m = 0; }
+                }
+            }
+            int64_t incl = m;                            // inclusive scan over the wave
+            for (int d = 1; d < 64; d <<= 1) {
+                const int64_t up = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += up;
+            }
+            if (lane == 63) s_wave[wave] = incl;
+            __syncthreads();
+            int64_t before = 0, total = 0;
+            for (int w = 0; w < 4; ++w) {
+                const int64_t t = s_wave[w];
+                if (w < wave) before += t;
+                total += t;
+            }
+            if (i < B) offs[i] = carry + before + incl - m;
+            carry += total;
+            __syncthreads();                             // s_wave is rewritten by the next round
+        }
+    }
+    if (bits) atomicOr(&s_bits, bits);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int all = s_bits;
+        const int64_t E_real = carry;
+        if (!all && (E_real > E_cap || E_cap - E_real > pad_cap)) all |= QOT_STAGE_BAD_SHAPE;
+        ctl[kStageSnap] = all ? -1 : pos;
+        ctl[kStageEdges] = all ? 0 : E_real;
+        if (all) atomicOr(status, all);
+    }
+}
+
+// The segmented copy.  Graph i of the batch (id g, m edges, destination columns off_i ..) is copied by ONE group of
+// kGatherLanes lanes running the helpers above with (lane in group, kGatherLanes); groups stride over the graphs.  d as in
+// stage_copy_padded_kernel.  Every segment is checked against the slot once more before it is written (what the plan
+// accepted: bounds every store below).  Then the pad graphs, by the whole grid.
+__global__ __launch_bounds__(256) void stage_copy_gather_kernel(const int64_t* __restrict__ ctl, const int64_t* __restrict__ offs,
+                                                                int32_t* __restrict__ status, StageShard s, StageSlot d,
+                                                                int64_t P) {
+    const int64_t k = ctl[kStageSnap];
+    if (k < 0) return;                                   // the plan refused the batch: nothing is staged
+    const int64_t E_real = ctl[kStageEdges];
+    const int64_t E_cap = d.E, B = d.B, n = d.max_n;
+    const int64_t spare = E_cap - E_real;
+    if (E_real < 0 || spare < 0 || spare > P * d.max_m) return;
+    const int64_t* ids = ctl + kStageHeader + k * B;
+    const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t = tid & (kGatherLanes - 1);
+    bool flagged = false;
+    for (int64_t i = tid / kGatherLanes; i < B; i += nth / kGatherLanes) {
+        const int64_t g = ids[i], off = offs[i];
+        if (g < 0 || g >= s.G) continue;
+        const int64_t n0 = s.node_ptr[g], e0 = s.edge_ptr[g];
+        const int64_t m = s.edge_ptr[g + 1] - e0;
+        if (m < 0 || m > d.max_m || off < 0 || off > E_real - m) continue;
+        const int64_t sub = n0 - i * n;                  // shard numbering -> batch numbering
+        stage_i64<false>(d.edge_index + off, s.edge_index + e0, m, sub, 0, t, kGatherLanes);
+        stage_i64<false>(d.edge_index + E_cap + off, s.edge_index + s.E_total + e0, m, sub, 0, t, kGatherLanes);
+        if (s.edge_attr) stage_u32(d.edge_attr + off * s.D, s.edge_attr + e0 * s.D, m * s.D, t, kGatherLanes);
+        if (s.x) stage_u32(d.x + i * n * s.F, s.x + n0 * s.F, n * s.F, t, kGatherLanes);
+        if (s.y) stage_u32(d.y + i * s.Y, s.y + g * s.Y, s.Y, t, kGatherLanes);
+        stage_fill_i64(d.batch + i * n, n, [&](int64_t) { return i; }, t, kGatherLanes);
+        if (s.node_ids) {
+            if (d.V > 0) flagged |= stage_i64<true>(d.node_ids + i * n, s.node_ids + n0, n, 0, d.V, t, kGatherLanes);
+            else         stage_i64<false>(d.node_ids + i * n, s.node_ids + n0, n, 0, 0, t, kGatherLanes);
+        }
+        if (t == 0) {
+            d.ptr[i] = i * n;
+            d.edge_ptr[i] = off;
+        }
+    }
+    if (flagged) atomicOr(status, QOT_STAGE_BAD_NODE_ID);
+    if (tid == 0) {
+        d.ptr[B] = B * n;
+        d.edge_ptr[B] = E_real;
+    }
+    stage_pad_graphs(s, d, E_real, P, tid, nth);
 }
 
 }  // namespace qot
@@ -378,6 +529,47 @@ extern "C" int qot_shard_stage_padded(int64_t* ctl, int64_t sched_cap, int32_t* 
                                                n, max_edges, P * max_edges);
     QOT_LAUNCH_CHECK();
     stage_copy_padded_kernel<<<stage_grid(B + P, (B + P) * n, E_cap, D, F, Y), 256, 0, st>>>(ctl, status, s, d, P);
+    QOT_LAUNCH_CHECK();
+    return QOT_OK;
+}
+
+// groups of kGatherLanes lanes: one per graph, at most 2048 workgroups (8 per CU); the pad part needs no more
+static int stage_gather_grid(int64_t B) {
+    const int64_t per_block = 256 / kGatherLanes;
+    int64_t grid = (B + per_block - 1) / per_block;
+    if (grid < 1) grid = 1;
+    if (grid > 2048) grid = 2048;
+    return (int)grid;
+}
+
+extern "C" int qot_shard_stage_gather(int64_t* ctl, int64_t sched_cap, int32_t* status, int64_t* offs, const int64_t* node_ptr,
+                                      const int64_t* edge_ptr, int64_t G, int64_t N_total, int64_t E_total,
+                                      const int64_t* edge_index, const void* edge_attr, int D, const int64_t* node_ids,
+                                      const void* x, int F, const void* y, int Y, int64_t B, int64_t n, int64_t E_cap, int64_t P,
+                                      int64_t max_edges, int64_t V, int64_t* dst_edge_index, void* dst_edge_attr,
+                                      int64_t* dst_node_ids, void* dst_x, void* dst_y, int64_t* dst_ptr, int64_t* dst_edge_ptr,
+                                      int64_t* dst_batch, qot_stream_t stream) {
+    if (!ctl || !status || !offs || !node_ptr || !edge_ptr || !dst_ptr || !dst_edge_ptr) return QOT_ERR_BADARG;
+    if (sched_cap < 1 || G < 1 || N_total < 0 || E_total < 0 || B < 1 || n < 1 || E_cap < 0 || P < 0 || max_edges < 0 || V < 0)
+        return QOT_ERR_BADARG;
+    if (P > 0 && (n < 2 || max_edges < 1)) return QOT_ERR_BADARG;      // a ring over one node is a self loop; no room to pad
+    if (B > (INT64_MAX >> 24) || P > (INT64_MAX >> 24) || n > (1 << 20) || max_edges > (1 << 20)) return QOT_ERR_BADARG;
+    if (sched_cap > (INT64_MAX >> 4) / B) return QOT_ERR_BADARG;       // sched_cap * B ids
+    if (D < 0 || F < 0 || Y < 0) return QOT_ERR_BADARG;
+    if ((E_cap > 0 && (!edge_index || !dst_edge_index)) || !dst_batch) return QOT_ERR_BADARG;
+    if ((edge_attr && E_cap > 0 && D > 0 && !dst_edge_attr) || (node_ids && !dst_node_ids) || (x && F > 0 && !dst_x) ||
+        (y && Y > 0 && !dst_y))
+        return QOT_ERR_BADARG;
+    StageShard s;
+    StageSlot d;
+    stage_structs(s, d, node_ptr, edge_ptr, nullptr, G, N_total, E_total, edge_index, edge_attr, D, node_ids, x, F, y, Y, B, B * n,
+                  E_cap, n, max_edges, V, dst_edge_index, dst_edge_attr, dst_node_ids, dst_x, dst_y, dst_ptr, dst_edge_ptr,
+                  dst_batch);
+    hipStream_t st = (hipStream_t)stream;
+    stage_plan_gather_kernel<<<1, 256, 0, st>>>(ctl, sched_cap, status, offs, node_ptr, edge_ptr, G, N_total, E_total, B, n, E_cap,
+                                                max_edges, P * max_edges);
+    QOT_LAUNCH_CHECK();
+    stage_copy_gather_kernel<<<stage_gather_grid(B), 256, 0, st>>>(ctl, offs, status, s, d, P);
     QOT_LAUNCH_CHECK();
     return QOT_OK;
 }

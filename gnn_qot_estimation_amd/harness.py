@@ -216,6 +216,74 @@ def stream_pad_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ranges: Sequ
     return plan
 
 
+def epoch_order(indices: range, seed: int, epoch: int) -> List[int]:
+    """The order in which a shuffled epoch ``epoch`` visits the graphs ``indices``: a permutation of them drawn from a CPU
+    generator seeded from ``(seed, epoch)`` alone.  A pure host function, so the padding plan, the streamed run and the
+    eager loop of a host dataset all see the same orders."""
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed((int(seed) * 1000003 + int(epoch)) % (1 << 63))
+    idx = list(indices)
+    return [idx[i] for i in torch.randperm(len(idx), generator=gen).tolist()]
+
+
+def fit_train_chunks(total: int, chunk_fraction: float, num_epochs: int) -> List[range]:
+    """The graphs each of the ``num_epochs`` epochs of ``fit`` trains on, as ranges of dataset indices."""
+    tr, _, _ = split_ranges(total)
+    out = []
+    for epoch in range(num_epochs):
+        chunk = epoch_chunk(epoch, len(tr), chunk_fraction)
+        out.append(range(tr[0] + chunk[0], tr[0] + chunk[-1] + 1) if len(chunk) else range(0))
+    return out
+
+
+def stream_shuffle_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, chunks: Sequence[range], batch_size: int, seed: int,
+                        graph_sizes: Tuple[int, int]) -> Dict[int, Dict[str, object]]:
+    """Gather slots for the shuffled training batches of a run, per graph count ``B``, in the format of
+    ``stream_pad_plan``.  ``chunks[e]`` are the graphs epoch ``e`` trains on; its batches are consecutive pieces of
+    ``epoch_order(chunks[e], seed, e)``.  ``E_cap`` / ``E_min`` are the largest / smallest edge total over EVERY batch of
+    EVERY epoch -- the orders are known up front, so this is host arithmetic on the edge counts -- and
+    ``P = ceil((E_cap - E_min) / max_m)``.  The totals of random subsets concentrate around ``B`` times the mean edge count, so
+    ``P`` stays far below the worst case (the ``B`` largest graphs against the ``B`` smallest), which is not used."""
+    n = uniform_node_count(node_ptr)
+    if n is None:
+        raise ValueError("shuffle=True on a resident shard needs graphs that all have the same node count")
+    max_m = int(graph_sizes[1])
+    counts = (edge_ptr[1:] - edge_ptr[:-1]).tolist()
+    totals: Dict[int, List[int]] = {}
+    for epoch, chunk in enumerate(chunks):
+        order = epoch_order(chunk, seed, epoch)
+        for b0 in range(0, len(order), batch_size):
+            ids = order[b0:b0 + batch_size]
+            totals.setdefault(len(ids), []).append(sum(counts[g] for g in ids))
+    plan: Dict[int, Dict[str, object]] = {}
+    for B, es in totals.items():
+        e_cap, e_min = max(es), min(es)
+        P = 0 if e_cap == e_min else -(-(e_cap - e_min) // max_m)
+        if P and n < 2:
+            raise ValueError("shuffle=True needs graphs of at least 2 nodes (a pad graph is a ring without self loops)")
+        plan[B] = {"E_cap": e_cap, "E_min": e_min, "P": P, "shape": (B + P, (B + P) * n, e_cap)}
+    return plan
+
+
+def check_shuffle(dataset, kind: str, world: int, stream, pad_edges) -> None:
+    """``shuffle=True``: a single process; on an HBM-resident shard the batches are gathered on the device, which needs
+    ``stream=True, pad_edges=True`` and everything those need.  A host dataset takes the eager loop."""
+    if world != 1:
+        raise ValueError("shuffle=True needs a single process: every rank would have to gather its share of every batch")
+    if not (isinstance(dataset, PackedGraphs) and dataset.device is not None):
+        if stream or pad_edges:
+            raise ValueError("stream=True needs an HBM-resident shard (PackedGraphs.to_device); shuffle=True on a host "
+                             "dataset runs the eager loop")
+        return
+    if kind != "topological":
+        raise ValueError("shuffle=True on a resident shard needs kind='topological' (streamed replay does)")
+    if not stream or not pad_edges:
+        raise ValueError("shuffle=True on a resident shard needs stream=True, pad_edges=True: shuffled batches are gathered "
+                         "on the device into padded slots (or keep the shard on the host: PackedGraphs.pin)")
+    if uniform_node_count(dataset.node_ptr) is None:
+        raise ValueError("shuffle=True on a resident shard needs graphs that all have the same node count")
+
+
 def fit_batch_ranges(total: int, batch_size: int, chunk_fraction: float) -> List[Tuple[int, int]]:
     """Every batch ``fit`` can ever run on a dataset of ``total`` graphs: all training chunks, then the validation range."""
     tr, va, _ = split_ranges(total)
@@ -289,14 +357,28 @@ class StepReplayer:
     graphs that take the spare edges.  The graphs of a batch are independent, the step takes ``out[:B]`` before the
     loss, its gradient and the statistics, so the pad rows of the output's gradient are zero and with them everything
     the pad graphs add to a parameter gradient.
+
+    Shuffled epochs (``shuffle=True`` on top of ``stream=True, pad_edges=True``): the training slots are gather slots
+    (``loader.GatherStageSlot``), whose schedule is the epoch's ORDER of graph ids instead of offsets;
+    ``begin_epoch(ranges, True, order=...)`` writes it, ``plan_shuffle(chunks, batch_size)`` fixes ``E_cap`` and ``P`` over
+    every batch of every epoch (``stream_shuffle_plan``).  Batches of arbitrary graphs never repeat, and still every
+    step replays the one graph of its ``(graph count, direction)``.  A gathered batch is block-diagonal with graphs of
+    ``n`` nodes and at most ``max_m`` edges, as a consecutive one: the model needs nothing new.  Validation stays
+    consecutive on padded slots.
     """
 
     def __init__(self, model, kind: str, out_dim: int, device, flat: Optional[FlatModel], opt: Optional[FusedSGD],
                  collective: bool = False, stream: Optional[bool] = None, shard: Optional[PackedGraphs] = None,
-                 pad_edges: Optional[bool] = None):
+                 pad_edges: Optional[bool] = None, shuffle: Optional[bool] = None, seed: int = 0):
         self.model, self.kind, self.out_dim, self.device = model, kind, out_dim, device
         self.stream = bool(stream)
         self.pad_edges = bool(pad_edges)
+        self.shuffle, self.seed = bool(shuffle), int(seed)
+        self.shuffle_plan: Dict[int, Dict[str, object]] = {}   # per graph count B of the training batches (plan_shuffle)
+        if self.shuffle:
+            check_shuffle(shard, kind, 2 if collective else 1, self.stream, self.pad_edges)
+            if shard is None or shard.device is None:
+                raise ValueError("a StepReplayer shuffles on an HBM-resident shard (a host dataset takes the eager loop)")
         if self.pad_edges:
             check_pad_edges(shard, kind, 2 if collective else 1, self.stream)
         elif self.stream:
@@ -429,21 +511,62 @@ class StepReplayer:
         self.pad_plan = stream_pad_plan(self.shard.node_ptr, self.shard.edge_ptr, ranges, self.shard.graph_sizes)
         return self.pad_plan
 
+    def plan_shuffle(self, chunks: Sequence[range], batch_size: int) -> Dict[int, Dict[str, object]]:
+        """Fix the gather slots of the training batches (``stream_shuffle_plan``): ``chunks[e]`` are the graphs epoch ``e``
+        trains on.  Called once, before the first slot exists."""
+        if not self.shuffle:
+            raise ValueError("plan_shuffle belongs to a StepReplayer(stream=True, pad_edges=True, shuffle=True)")
+        if self.slots:
+            raise ValueError("the padding plan is fixed before the first batch is staged: slots never grow")
+        self.shuffle_plan = stream_shuffle_plan(self.shard.node_ptr, self.shard.edge_ptr, chunks, batch_size, self.seed,
+                                                self.shard.graph_sizes)
+        return self.shuffle_plan
+
     def _padded_slot(self, B: int, training: bool) -> StageSlot:
         key = (B, bool(training))
         slot = self.slots.get(key)
         if slot is None:
-            plan = self.pad_plan[B]
+            gather = self.shuffle and training
+            plan = (self.shuffle_plan if gather else self.pad_plan)[B]
             emb = getattr(self.model, "node_embeddings", None)
-            slot = self.slots[key] = self.shard.padded_stage_slot(B, plan["E_cap"], plan["P"], status=self._stage_status,
-                                                                  num_embeddings=0 if emb is None else emb.num_embeddings,
-                                                                  capacity=self.schedule_capacity)
+            make = self.shard.gather_stage_slot if gather else self.shard.padded_stage_slot
+            slot = self.slots[key] = make(B, plan["E_cap"], plan["P"], status=self._stage_status,
+                                          num_embeddings=0 if emb is None else emb.num_embeddings,
+                                          capacity=self.schedule_capacity)
         return slot
 
-    def begin_epoch(self, ranges: Sequence[Tuple[int, int]], training: bool) -> None:
+    def begin_epoch(self, ranges: Sequence[Tuple[int, int]], training: bool, order: Optional[Sequence[int]] = None) -> None:
         """Write this epoch's schedules: per shape (padded slots: per graph count), the ``lo`` of its batches in visiting
-        order.  ``run`` must then be called with exactly ``ranges``, in order."""
+        order.  ``run`` must then be called with exactly ``ranges``, in order.  ``order`` (a shuffled training epoch):
+        the graphs to visit instead, batch ``k`` taking as many of them as ``ranges[k]`` holds."""
         G = len(self.shard)
+        if order is not None:
+            if not (self.shuffle and training):
+                raise ValueError("an epoch order belongs to the training epochs of a StepReplayer(shuffle=True)")
+            order = [int(g) for g in order]
+            if len(order) != sum(hi - lo for lo, hi in ranges):
+                raise ValueError(f"an order of {len(order)} graphs for batches of {sum(hi - lo for lo, hi in ranges)}")
+            if any(not 0 <= g < G for g in order):
+                raise IndexError(f"the epoch order names graphs outside a shard of {G} graphs")
+            max_m = int(self.shard.graph_sizes[1])
+            counts = self.shard.edge_ptr[1:] - self.shard.edge_ptr[:-1]
+            by_count: Dict[int, List[int]] = {}
+            at = 0
+            for lo, hi in ranges:
+                ids = order[at:at + hi - lo]
+                at += hi - lo
+                plan = self.shuffle_plan.get(hi - lo)
+                e = int(counts[torch.as_tensor(ids, dtype=torch.long)].sum())
+                if plan is None or not 0 <= plan["E_cap"] - e <= plan["P"] * max_m:
+                    raise ValueError(f"a shuffled batch of {hi - lo} graphs ({e} edges) is not covered by the padding plan "
+                                     f"({'no slot for this graph count' if plan is None else plan}): plan_shuffle takes "
+                                     "every epoch of the run")
+                by_count.setdefault(hi - lo, []).extend(ids)
+            for B, ids in by_count.items():
+                self._padded_slot(B, True).set_schedule(ids)
+            return
+        if self.shuffle and training:
+            raise ValueError("a training epoch of a StepReplayer(shuffle=True) needs its order")
         for lo, hi in ranges:
             if not 0 <= lo < hi <= G:
                 raise IndexError(f"graphs [{lo}, {hi}) lie outside a shard of {G} graphs")
@@ -508,13 +631,21 @@ class StepReplayer:
 def run_epoch(model, dataset, indices: range, *, kind: str, batch_size: int, out_dim: int, device,
               criterion, flat: Optional[FlatModel] = None, opt: Optional[FusedSGD] = None,
               replayer: Optional[StepReplayer] = None, stream: Optional[bool] = None,
-              pad_edges: Optional[bool] = None) -> Dict[str, object]:
+              pad_edges: Optional[bool] = None, shuffle: Optional[bool] = None, seed: int = 0,
+              epoch: int = 0) -> Dict[str, object]:
     """One pass over ``indices``; trains when ``opt`` is given, else evaluates under ``no_grad``.  ``stream=True``
     (with a ``StepReplayer(stream=True)``): every batch is staged on the device into the static slot of its shape and
     run by that shape's one captured graph.  ``pad_edges=True`` (with a ``StepReplayer(stream=True, pad_edges=True)``
-    whose ``plan_padding`` covered these batches): one padded slot per graph count instead."""
+    whose ``plan_padding`` covered these batches): one padded slot per graph count instead.  ``shuffle=True`` (training
+    passes only): the graphs are visited in ``epoch_order(indices, seed, epoch)`` -- gathered on the device by a
+    ``StepReplayer(..., shuffle=True)`` whose ``plan_shuffle`` covered the epoch, or, on a host dataset, collated by the
+    eager loop."""
     fwd = _KINDS[kind]
     rank, world = _rank_world()
+    shuffle = bool(shuffle)
+    if shuffle:
+        check_shuffle(dataset, kind, world, stream, pad_edges)
+    order = epoch_order(indices, seed, epoch) if shuffle and opt is not None else None
     if pad_edges:
         check_pad_edges(dataset, kind, world, stream)
     if stream:
@@ -524,8 +655,13 @@ def run_epoch(model, dataset, indices: range, *, kind: str, batch_size: int, out
         if bool(pad_edges) != replayer.pad_edges:
             raise ValueError("pad_edges must be what the StepReplayer was built with")
         training = opt is not None
+        if training and (shuffle != replayer.shuffle or (shuffle and int(seed) != replayer.seed)):
+            raise ValueError("shuffle and seed of a training pass must be what the StepReplayer was built with")
         ranges = batch_ranges(indices, batch_size)
-        replayer.begin_epoch(ranges, training)
+        if order is not None:
+            replayer.begin_epoch(ranges, training, order=order)
+        else:
+            replayer.begin_epoch(ranges, training)
         st = replayer.stats[training]
         st.buf.zero_()
         for r in ranges:
@@ -538,8 +674,13 @@ def run_epoch(model, dataset, indices: range, *, kind: str, batch_size: int, out
     # an HBM-resident shard keeps its batch objects (and the graph index the model attaches to them):
     # the chunks repeat every few epochs, so later visits do no graph preparation at all
     resident = isinstance(dataset, PackedGraphs) and dataset.device is not None
-    loader = GraphLoader(dataset, batch_size, shuffle=False, device=device, cache_batches=resident,
-                         batches=_local_batches(indices, batch_size, rank, world, _graph_costs(dataset, indices)))
+    if order is not None:
+        # a shuffled epoch of a host dataset: the same loop over collated batches of arbitrary graphs (nothing to cache)
+        loader = GraphLoader(dataset, batch_size, shuffle=False, device=device,
+                             batches=[order[b0:b0 + batch_size] for b0 in range(0, len(order), batch_size)])
+    else:
+        loader = GraphLoader(dataset, batch_size, shuffle=False, device=device, cache_batches=resident,
+                             batches=_local_batches(indices, batch_size, rank, world, _graph_costs(dataset, indices)))
     stats = RegressionStats(out_dim, device)
     skipped = 0
     training = opt is not None
@@ -641,7 +782,7 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
         patience: int = 10, lr: float = 0.1, momentum: float = 0.9, step_size: int = 10, gamma: float = 0.5,
         chunk_fraction: float = 0.10, output_dim: int = 3, device="cuda", best_path: Optional[str] = None,
         log: Callable[[str], None] = print, replay: Optional[bool] = None, stream: Optional[bool] = None,
-        pad_edges: Optional[bool] = None) -> History:
+        pad_edges: Optional[bool] = None, shuffle: Optional[bool] = None, seed: int = 0) -> History:
     """The training script's main loop (train.py:24-182) on a dataset object indexable by graph.
 
     ``replay`` (default: on for an HBM-resident shard in a single process): steps over cached batches are
@@ -653,10 +794,18 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
     ``pad_edges`` (default off; needs ``stream=True`` and graphs of one node count, else ``ValueError``): batches whose
     edge totals differ -- one edge per distinct connection of a sample, as the reference builds its graphs -- share one
     slot and one captured graph per graph count; pad graphs appended on the device bring every batch to the slot's edge
-    count and take no part in the loss (``StepReplayer``, ``stream_pad_plan``)."""
+    count and take no part in the loss (``StepReplayer``, ``stream_pad_plan``).
+    ``shuffle`` (default off): every epoch trains on its chunk in a fresh random order, ``epoch_order(chunk, seed,
+    epoch)``; validation is unchanged.  On an HBM-resident shard it needs ``stream=True, pad_edges=True`` (and what they
+    need, else ``ValueError``): the batches are gathered on the device into one slot per graph count
+    (``loader.GatherStageSlot``, ``stream_shuffle_plan``), every step replays.  On a host dataset the eager loop collates
+    the same batches."""
     device = torch.device(device)
     stream = bool(stream)
     pad_edges = bool(pad_edges)
+    shuffle = bool(shuffle)
+    if shuffle:
+        check_shuffle(dataset, kind, _rank_world()[1], stream, pad_edges)
     if pad_edges:
         check_pad_edges(dataset, kind, _rank_world()[1], stream)
     elif stream:
@@ -674,10 +823,13 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
     replayer = None
     if use_replay:
         replayer = StepReplayer(model, kind, output_dim, device, flat, opt, collective=world > 1, stream=stream,
-                                shard=dataset if stream else None, pad_edges=pad_edges)
+                                shard=dataset if stream else None, pad_edges=pad_edges,
+                                **(dict(shuffle=True, seed=seed) if shuffle else {}))
         if pad_edges:
             # every batch the run can ever stage, so that no slot has to grow
             replayer.plan_padding(fit_batch_ranges(len(dataset), batch_size, chunk_fraction))
+        if shuffle:
+            replayer.plan_shuffle(fit_train_chunks(len(dataset), chunk_fraction, num_epochs), batch_size)
     criterion = torch.nn.SmoothL1Loss()
     hist = History()
     counter = 0
@@ -688,7 +840,8 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
         opt.lr = step_lr(lr, epoch, step_size, gamma)
         t = run_epoch(model, dataset, range(tr[0] + chunk[0], tr[0] + chunk[-1] + 1) if len(chunk) else range(0),
                       kind=kind, batch_size=batch_size, out_dim=output_dim, device=device, criterion=criterion,
-                      flat=flat, opt=opt, replayer=replayer, stream=stream, pad_edges=pad_edges)
+                      flat=flat, opt=opt, replayer=replayer, stream=stream, pad_edges=pad_edges,
+                      **(dict(shuffle=True, seed=seed, epoch=epoch) if shuffle else {}))
         v = run_epoch(model, dataset, va, kind=kind, batch_size=batch_size, out_dim=output_dim, device=device,
                       criterion=criterion, replayer=replayer, stream=stream, pad_edges=pad_edges)
         if replayer is not None:

@@ -222,6 +222,12 @@ class PackedGraphs:
         extra graphs take what a slice leaves of ``E_cap`` edges (``qot_shard_stage_padded``)."""
         return PaddedStageSlot(self, B, E_cap, pad_graphs, status=status, num_embeddings=num_embeddings, capacity=capacity)
 
+    def gather_stage_slot(self, B: int, E_cap: int, pad_graphs: int, status: Optional[torch.Tensor] = None,
+                          num_embeddings: int = 0, capacity: Optional[int] = None) -> "GatherStageSlot":
+        """The padded slot for batches given as lists of ``B`` graph ids of this resident shard (shuffled batches;
+        ``qot_shard_stage_gather``)."""
+        return GatherStageSlot(self, B, E_cap, pad_graphs, status=status, num_embeddings=num_embeddings, capacity=capacity)
+
     def __getitem__(self, g: int) -> Data:
         n0, n1 = int(self.node_ptr[g]), int(self.node_ptr[g + 1])
         e0, e1 = int(self.edge_ptr[g]), int(self.edge_ptr[g + 1])
@@ -319,8 +325,8 @@ class StageSlot:
 
     The device validates each slice (see ``qot_shard_stage``) and reports through ``status`` (int32 word, shared
     between slots when given): ``check_stage_status``.  ``capacity``: the longest schedule the slot takes (default: the
-    batches of one pass over the shard; the control block is part of the captured launch and never grows).  The schedule holds graph offsets today; a gather list of
-    single graphs (shuffled batches) would be another schedule format behind the same slot."""
+    batches of one pass over the shard; the control block is part of the captured launch and never grows).  The schedule holds graph offsets; ``GatherStageSlot``
+    is the other schedule format behind the same slot: lists of single graphs (shuffled batches)."""
 
     def __init__(self, shard: "PackedGraphs", B: int, N: int, E: int, status: Optional[torch.Tensor] = None,
                  num_embeddings: int = 0, capacity: Optional[int] = None):
@@ -439,6 +445,48 @@ class PaddedStageSlot(StageSlot):
                   s.graph_of_node, G, n_total, e_total, s.edge_index, s.edge_attr, D, s.node_ids, s.x, F, s.y, Y,
                   self.real_graphs, self.n, self.E, self.pad_graphs, max_m, self.V, b.edge_index, b.edge_attr, b.node_ids,
                   b.x, b.y, b.ptr, b.edge_ptr, b.batch)
+        return b
+
+
+class GatherStageSlot(PaddedStageSlot):
+    """The padded slot filled from a LIST of graphs: batch ``k`` of the schedule is graphs ``ids[k B : (k + 1) B]`` of the
+    shard, in that order, wherever they lie (``qot_shard_stage_gather``): what ``Batch.from_data_list([shard[g] for g in
+    ids])`` collates, then the pad graphs.  ``set_schedule(order)`` takes one epoch's ids as a flat sequence -- one
+    host-to-device copy, outside any capture; ``capacity`` counts BATCHES.  An id may repeat.  The device validates every id
+    and the batch's edge total before anything is written (``STAGE_BAD_RANGE`` / ``STAGE_BAD_SHAPE``: nothing is staged);
+    the per-graph edge offsets of a batch go through ``offs``, scratch of the slot, so a refused batch leaves
+    ``batch.edge_ptr`` alone too.  Cache rule as for every slot.  ``harness.stream_shuffle_plan`` chooses ``E_cap`` and
+    ``P`` for a run."""
+
+    def __init__(self, shard: "PackedGraphs", B: int, E_cap: int, pad_graphs: int, status: Optional[torch.Tensor] = None,
+                 num_embeddings: int = 0, capacity: Optional[int] = None):
+        super().__init__(shard, B, E_cap, pad_graphs, status=status, num_embeddings=num_embeddings, capacity=capacity)
+        # [0] position, [1] batches, [2] snapshot, [3] E_real, [4:] B ids per batch (include/qot_gnn.h)
+        self.ctl = torch.zeros(4 + self.capacity * self.real_graphs, dtype=torch.long, device=shard.device)
+        self.offs = torch.zeros(self.real_graphs, dtype=torch.long, device=shard.device)
+
+    def set_schedule(self, order: Sequence[int]) -> None:
+        """The graph ids of the next ``len(order) / B`` calls of ``stage()``, ``B`` per batch, in order."""
+        order = [int(v) for v in order]
+        B = self.real_graphs
+        if len(order) % B:
+            raise ValueError(f"a gather schedule holds {B} graph ids per batch, got {len(order)} ids")
+        if len(order) // B > self.capacity:
+            raise ValueError(f"a schedule of {len(order) // B} batches exceeds the slot's capacity of {self.capacity}")
+        self.ctl[:4 + len(order)].copy_(torch.tensor([0, len(order) // B, -1, 0] + order, dtype=torch.long))
+
+    def stage(self, ids: Optional[Sequence[int]] = None) -> Batch:
+        """Stage the schedule's next batch (``ids`` given: those ``B`` graphs, as a schedule of one) into ``batch``."""
+        from . import _lib
+        if ids is not None:
+            self.set_schedule(ids)
+        s, b = self.shard, self.batch
+        D, F, Y = self._words
+        G, n_total, e_total, _, max_m = self._totals
+        _lib.call("qot_shard_stage_gather", self.ctl, self.capacity, self.status, self.offs, s.node_ptr_dev, s.edge_ptr_dev,
+                  G, n_total, e_total, s.edge_index, s.edge_attr, D, s.node_ids, s.x, F, s.y, Y, self.real_graphs, self.n,
+                  self.E, self.pad_graphs, max_m, self.V, b.edge_index, b.edge_attr, b.node_ids, b.x, b.y, b.ptr, b.edge_ptr,
+                  b.batch)
         return b
 
 

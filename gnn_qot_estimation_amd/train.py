@@ -65,6 +65,11 @@ def main(argv=None):
     ap.add_argument("--pad-edges", action="store_true",
                     help="with --stream: batches of unequal edge totals share one slot per graph count, brought to a fixed "
                          "edge count by pad graphs (graphs of one node count)")
+    ap.add_argument("--shuffle", action="store_true",
+                    help="a fresh random order of every epoch's training graphs, a pure function of (--seed, epoch); on an "
+                         "HBM-resident shard with --stream --pad-edges (batches gathered on the device), else (--host-shard) "
+                         "through the eager loop")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the --shuffle orders")
     args = ap.parse_args(argv)
 
     from . import LightpathGNN, TopologicalGNN
@@ -90,7 +95,8 @@ def main(argv=None):
                   "NODE_FEATURES": meta.get("NODE_FEATURES"), "feature_indices": fidx}  # lightpath train.py:227-233
     hist = harness.fit(model, dataset, kind=kind, batch_size=args.batch_size, num_epochs=args.epochs,
                        patience=args.patience, device=device, best_path=os.path.join(root, "best_model.pth"), log=log,
-                       stream=True if args.stream else None, pad_edges=True if args.pad_edges else None)
+                       stream=True if args.stream else None, pad_edges=True if args.pad_edges else None,
+                       shuffle=True if args.shuffle else None, seed=args.seed)
     if kind == "lightpath":
         log(f"Total skipped {hist.skipped_graphs} graphs due to missing LUT nodes.")
     path, k = harness.next_model_path(os.path.join(root, "models"))

@@ -655,6 +655,22 @@ int qot_shard_stage_padded(int64_t* ctl, int64_t sched_cap, int32_t* status, con
                            int64_t E_cap, int64_t P, int64_t max_edges, int64_t V, int64_t* dst_edge_index,
                            void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x, void* dst_y, int64_t* dst_ptr,
                            int64_t* dst_edge_ptr, int64_t* dst_batch, qot_stream_t stream);
+/* qot_shard_stage_padded for batches given as a LIST of single graphs (shuffled batches; loader.GatherStageSlot).  The
+ * slot is the padded slot.  ctl[4 + sched_cap * B]: [0] position, [1] number of valid BATCHES in the schedule, [2] snapshot
+ * (the number of the batch the call staged, or -1), [3] its edge total E_real, then B graph ids per batch; a call takes ids
+ * [position * B, (position + 1) * B) and advances the position.  offs[B] (int64, device): scratch owned by the slot, the
+ * exclusive prefix sum of the batch's edge counts.  Validated on the device before anything is written: the position lies
+ * inside the schedule and every id in [0, G) with its slices inside the arrays (else QOT_STAGE_BAD_RANGE); every graph
+ * holds n nodes and at most max_edges edges and 0 <= E_cap - E_real <= P * max_edges (else QOT_STAGE_BAD_SHAPE).  On
+ * either, nothing is staged.  Graph i of the batch lands where collating the listed graphs puts it: nodes i n .., edge
+ * columns offs[i] .., edge_index re-based to batch numbering, batch = i, ptr[i] = i n, edge_ptr[i] = offs[i]; an id may
+ * repeat.  Node ids and the pad graphs as in qot_shard_stage_padded. */
+int qot_shard_stage_gather(int64_t* ctl, int64_t sched_cap, int32_t* status, int64_t* offs, const int64_t* node_ptr,
+                           const int64_t* edge_ptr, int64_t G, int64_t N_total, int64_t E_total, const int64_t* edge_index,
+                           const void* edge_attr, int D, const int64_t* node_ids, const void* x, int F, const void* y, int Y,
+                           int64_t B, int64_t n, int64_t E_cap, int64_t P, int64_t max_edges, int64_t V,
+                           int64_t* dst_edge_index, void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x, void* dst_y,
+                           int64_t* dst_ptr, int64_t* dst_edge_ptr, int64_t* dst_batch, qot_stream_t stream);
 
 /* ---- out[i] = concat(s0[0:n0], s1[0:n1], s2)[idx[i]]: one gather builds the fragment-ordered NNConv
  * operands from nn.2.weight / nn.2.bias / lin.weight (topological_training/models.py:20-25). */

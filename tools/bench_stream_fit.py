@@ -26,6 +26,11 @@ with exact-shape slots -- against ``fit(stream=True, pad_edges=True)`` here (wal
 graphs, reserved memory); and (a) the padded streamed step on it against the exact-shape streamed step on the equal-sized
 shard of the same mean size (both in this tree), with the plan's ``P``, ``E_cap``, ``E_min``.
 
+``--unequal --shuffle``: (a) alone, on the unequal shard -- the shuffled streamed step of this tree
+(``StepReplayer(stream=True, pad_edges=True, shuffle=True)``: gather staging of ``epoch_order`` batches, epoch after epoch
+over the whole shard) against the other tree's consecutive padded streamed step, alternating fresh processes; with both
+plans.  ``--shard-cache DIR`` keeps the generated shards between calls.
+
 Prints one JSON object (and writes it to ``--out``).
 """
 import argparse
@@ -70,12 +75,24 @@ def _child(args):
     model = q.TopologicalGNN(sc["n"], sc["hidden"], 3, 4, dropout_p=0.5).to(dev)
     B = sc["batch"]
     out = {"mode": args.child}
-    if args.child in ("step_streamed", "step_per_batch", "step_padded"):
+    if args.child in ("step_streamed", "step_per_batch", "step_padded", "step_shuffled"):
         flat = Hn.FlatModel(model)
         opt = Hn.FusedSGD(flat, lr=0.01, momentum=0.9, device_lr=True)
         opt.lr = 0.01
         nb = len(shard) // B
-        if args.child in ("step_streamed", "step_padded"):
+        if args.child == "step_shuffled":
+            rep = Hn.StepReplayer(model, "topological", 3, dev, flat, opt, stream=True, shard=shard, pad_edges=True,
+                                  shuffle=True, seed=0)
+            steps = 3 + 20 + args.replays
+            epochs = -(-steps // nb)
+            chunks = [range(0, nb * B)] * epochs      # every epoch walks the whole shard in a fresh order
+            order = [g for e in range(epochs) for g in Hn.epoch_order(chunks[e], 0, e)][:steps * B]
+            ranges = [(0, B)] * steps                 # a gather slot is keyed by the graph count alone
+            rep.schedule_capacity = steps
+            out["pad_plan"] = {str(k): v for k, v in rep.plan_shuffle(chunks, B).items()}
+            feed = lambda k: ranges[k]
+            begin = lambda: rep.begin_epoch(ranges, True, order=order)
+        elif args.child in ("step_streamed", "step_padded"):
             pad = args.child == "step_padded"
             rep = Hn.StepReplayer(model, "topological", 3, dev, flat, opt, stream=True, shard=shard,
                                   **(dict(pad_edges=True) if pad else {}))
@@ -160,6 +177,9 @@ def main():
     ap.add_argument("--graphs", type=int, default=30000, help="graphs in the shard (70 %% train, 10 chunks)")
     ap.add_argument("--unequal", action="store_true", help="graphs of unequal edge counts: the padded mode against both "
                                                             "modes of the other tree (module docstring)")
+    ap.add_argument("--shuffle", action="store_true", help="with --unequal: the shuffled streamed step here against the "
+                                                            "other tree's consecutive padded streamed step")
+    ap.add_argument("--shard-cache", default=None, help="directory that keeps the generated shards between calls")
     ap.add_argument("--replays", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=2, help="alternations of the two trees per measurement")
@@ -221,9 +241,17 @@ def _main_unequal(args, res, sc):
     res.update(unequal=True, edge_counts=[sc["e"] - 152, sc["e"] + 152],
                other_tree_is_parent=bool(args.parent_tree))
     with tempfile.TemporaryDirectory() as tmp:
-        uneq, equal = os.path.join(tmp, "unequal.pt"), os.path.join(tmp, "equal.pt")
-        save_shard(uneq, unequal_shard(args.graphs, sc["n"], sc["e"]))
-        save_shard(equal, q.PackedGraphs.from_batch(S.topological_batch(2, args.graphs, n=sc["n"], e=sc["e"])))
+        if args.shard_cache:
+            os.makedirs(args.shard_cache, exist_ok=True)
+            tmp = args.shard_cache
+        uneq = os.path.join(tmp, f"unequal_{args.scale}_{args.graphs}.pt")
+        equal = os.path.join(tmp, f"equal_{args.scale}_{args.graphs}.pt")
+        if not os.path.exists(uneq):
+            save_shard(uneq, unequal_shard(args.graphs, sc["n"], sc["e"]))
+        if args.shuffle:
+            return _main_shuffle(args, res, other, uneq)
+        if not os.path.exists(equal):
+            save_shard(equal, q.PackedGraphs.from_batch(S.topological_batch(2, args.graphs, n=sc["n"], e=sc["e"])))
         runs = [("fit_padded", ROOT, uneq, "fit_padded"), ("fit_streamed", other, uneq, "fit_streamed_exact"),
                 ("fit_per_batch", other, uneq, "fit_per_batch"), ("step_padded", ROOT, uneq, "step_padded"),
                 ("step_streamed", ROOT, equal, "step_streamed_equal")]
@@ -239,6 +267,24 @@ def _main_unequal(args, res, sc):
     res["summary"]["step_padded_us"] = [r["step_us_median"] for r in res["step_padded"]]
     res["summary"]["step_streamed_equal_us"] = [r["step_us_median"] for r in res["step_streamed_equal"]]
     res["summary"]["pad_plan"] = res["fit_padded"][0]["pad_plan"]
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def _main_shuffle(args, res, other, uneq):
+    res["shuffle"] = True
+    for rep in range(args.repeats):
+        for mode, tree, key in (("step_shuffled", ROOT, "step_shuffled"), ("step_padded", other, "step_padded_other")):
+            r = _run_child(mode, tree, args, uneq)
+            res.setdefault(key, []).append(r)
+            print(f"# {key} [{rep}]: " + json.dumps({k: v for k, v in r.items() if k != "mode"}), flush=True)
+    res["summary"] = {"step_shuffled_us": [r["step_us_median"] for r in res["step_shuffled"]],
+                      "step_padded_other_us": [r["step_us_median"] for r in res["step_padded_other"]],
+                      "shuffle_plan": res["step_shuffled"][0]["pad_plan"], "pad_plan": res["step_padded_other"][0]["pad_plan"]}
     line = json.dumps(res)
     print(line)
     if args.out:
