@@ -12,6 +12,7 @@ from .lightpath import LightpathGNN
 from .loader import GatherStageSlot, GraphLoader, PackedGraphs, PaddedStageSlot, StageSlot
 from .nn import BatchNorm, GATConv, NNConv, TransformerConv, global_mean_pool
 from .topological import TopologicalGNN
+from .infer import TopologicalPredictor
 
-__all__ = ["Batch", "Data", "shard_graphs", "TopologicalGNN", "LightpathGNN", "TransformerConv", "NNConv",
+__all__ = ["Batch", "Data", "shard_graphs", "TopologicalGNN", "TopologicalPredictor", "LightpathGNN", "TransformerConv", "NNConv",
            "GATConv", "BatchNorm", "global_mean_pool", "GraphLoader", "PackedGraphs", "StageSlot", "PaddedStageSlot", "GatherStageSlot", "harness", "dataset"]

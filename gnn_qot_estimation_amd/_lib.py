@@ -167,6 +167,10 @@ SIGNATURES = {
     "qot_run_roles": (_int, [_p, _int, _p]),
     "qot_rows_gather": (_int, [_p, _p, _p, _i64, _int, _p]),
     "qot_rows_scatter": (_int, [_p, _p, _p, _i64, _int, _p]),
+    "qot_topological_infer_supported": (_int, [_int, _int, _int, _int, _int]),
+    "qot_topological_infer_max_edges": (_int, [_int, _int, _int]),
+    "qot_topological_infer": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _int, _p, _int, _p, _int, _p, _p,
+                                     _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _int, _int, _int, _p, _p]),
 }
 
 MAX_ROLES = 12           # include/qot_gnn.h: QOT_MAX_ROLES

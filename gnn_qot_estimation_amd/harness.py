@@ -869,19 +869,35 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
 def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: str = "topological",
              batch_size: int = 512, output_dim: int = 3, device="cuda",
              output_keys: Sequence[str] = ("osnr", "snr", "ber"),
-             target_ranges: Dict[str, Dict[str, float]] = TARGET_RANGES, return_predictions: bool = False):
+             target_ranges: Dict[str, Dict[str, float]] = TARGET_RANGES, return_predictions: bool = False,
+             fused: bool = False):
     """test.py's metric block: per-output R2 and MSE on min-max descaled values (test.py:76-121).
+
+    ``fused=True`` (opt-in, ``kind="topological"`` on one process; ``ValueError`` otherwise or when the model or a batch
+    is outside ``TopologicalPredictor``'s envelope): every batch runs as the single-launch inference kernel
+    (``infer.TopologicalPredictor``) instead of ``model(data)``.  Same function to fp32 rounding.  Meant for the
+    latency-bound regime -- one graph or a handful per call, up to batches of the reference's scale (hidden 16, 512
+    graphs); at hidden 64 with a thousand graphs per batch the default path's MFMA NNConv kernel is expected to have the
+    advantage (fp32 FMA here).  Neither side of that has been measured on an MI355X yet: DESIGN.md 4.12.
 
     ``return_predictions``: also return ``(y_true_descaled, y_pred_descaled, skipped_graphs)`` -- the arrays test.py
     writes to ``y_true_descaled.json`` / ``y_pred_descaled.json`` (test.py:92-103,129-136), in dataset order; they stay
     on the device until the loop is over (one host copy)."""
+    rank, world = _rank_world()
+    if fused and kind != "topological":
+        raise ValueError(f"evaluate(fused=True) is for kind='topological' only, got kind={kind!r}")
+    if fused and world > 1:
+        raise ValueError(f"evaluate(fused=True) runs on one process, got a world of {world}")
     device = torch.device(device)
     model.to(device)
     idx = range(len(dataset)) if indices is None else indices
     fwd = _KINDS[kind]
     stats = RegressionStats(output_dim, device)
     model.eval()
-    rank, world = _rank_world()
+    if fused:
+        from .infer import TopologicalPredictor
+        predictor = TopologicalPredictor(model)
+        fwd = lambda _model, data, out_dim: (predictor(data), data.y.view(-1, out_dim))      # noqa: E731
     loader = GraphLoader(dataset, batch_size, shuffle=False, device=device,
                          batches=_local_batches(idx, batch_size, rank, world, _graph_costs(dataset, idx)))
     kept, skipped = [], 0
@@ -910,6 +926,8 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
             try:
                 out, y = fwd(model, data, output_dim)
             except ValueError:
+                if fused:                             # outside the predictor's envelope: an error, not a LUT-less batch
+                    raise
                 skipped += data.num_graphs            # lightpath_training/test.py:82-85
                 continue
             stats.update(y, out)

@@ -775,6 +775,42 @@ int qot_rows_gather(const float* x, const int32_t* idx, float* out, int64_t n_id
 int qot_rows_scatter(const float* grad_out, const int32_t* idx, float* grad_x, int64_t n_idx, int C,
                      qot_stream_t stream);
 
+/* ---- single-launch inference: the whole eval-mode TopologicalGNN forward -----------------------------------------
+ * topological_training/models.py:49-64 with dropout off (test.py:58-64), for a block-diagonal batch of B graphs in ONE
+ * launch: one workgroup per graph builds the graph's destination-sorted index in LDS, runs TransformerConv -> leaky_relu
+ * -> NNConv aggr="mean" -> leaky_relu -> mean pool -> Linear -> leaky_relu -> Linear and writes out[b, 0..O).  Every sum
+ * runs in a fixed order inside the graph's own workgroup: the result is bitwise reproducible and a graph's row does not
+ * depend on which other graphs share the launch.  Plain fp32 FMA throughout.
+ *
+ * The batch as a collate leaves it (all int64, device): node_ids[N] (table rows, NOT offset), edge_index[2, E]
+ * (row 0 = source, row 1 = target, offset by the graph's first node), edge_attr[E, D], node_ptr[B+1], edge_ptr[B+1].
+ * n_max / max_e bound the largest graph (host-known; they size the LDS image).  Nodes of in-degree 0, graphs without
+ * edges or with a single node, self loops and repeated edges are legal and come out as PyG's operators give them.
+ *
+ * Parameter-only tables (refresh them when the parameters change, not per batch), V = rows of the embedding table:
+ *   t4  [V, ld4]  projected table [q|k|v|skip] (qot_table_project_fwd; ld4 >= 4H, a multiple of 4)
+ *   M   [V, ldm]  score matrix and P [V, D] (qot_table_scores with n = V; ldm = qot_tconv_graph_ldm of V)
+ *   wcat [(2D+2)*H, H] row-major: block k < 2D holds nn.2.weight[a*H + o, k] at [k*H + a, o], block 2D holds nn.2.bias
+ *        [a*H + o], block 2D+1 holds lin.weight[o, a] (the NNConv root); read from global memory (L2-resident)
+ * and the parameters read in place: w_edge [H, D] (conv1.lin_edge), w1 [2D, D] / b1 [2D] (conv2.nn.0), bias2 [H]
+ * (conv2.bias), w0 [H, H] / b0 [H] (mlp.0), w3 [O, H] / b3 [O] (mlp.3).  slope_conv: leaky_relu slope behind both
+ * convolutions (models.py:54,58: 0.01); slope_head: the read-out's LeakyReLU.
+ *
+ * Envelope (QOT_ERR_UNSUPPORTED outside it): H in {16, 32, 64}, 1 <= D <= 4, 1 <= O <= 8, n_max <= 128 and max_e within
+ * the LDS budget -- qot_topological_infer_supported answers 1 / 0 from the kernel's own LDS layout, and
+ * qot_topological_infer_max_edges gives the largest max_e it accepts for (n_max, H, D), -1 when none.
+ * status (optional, device int32, caller-zeroed): bit 0 = an edge leaves its graph's node range, bit 1 = a graph
+ * exceeds n_max / max_e or its slices leave the arrays, bit 2 = a node id outside [0, V); the rows of such graphs are
+ * written as NaN. */
+int qot_topological_infer_supported(int n_max, int max_e, int H, int D, int O);
+int qot_topological_infer_max_edges(int n_max, int H, int D);
+int qot_topological_infer(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                          const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t B, int n_max,
+                          int max_e, const float* t4, int ld4, const float* M, int ldm, const float* P, int V,
+                          const float* w_edge, const float* w1, const float* b1, const float* wcat, const float* bias2,
+                          const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
+                          float slope_head, float* out, int H, int D, int O, int32_t* status, qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,243 @@
+"""GPU: single-launch inference (``TopologicalPredictor`` / ``qot_topological_infer``) against ``oracle.sparse``'s
+TopologicalGNN in eval mode on the CPU with the same ``state_dict``, and against the engine's own eval ``model(batch)``,
+both at ``TOL`` (the sums run in another order than the engine's: not bit-equal).  Inputs are seeded ``synthetic.py``
+graphs; shapes are the smallest that reach every path: all three widths, one graph exactly at the LDS edge cap, one at
+128 nodes, graphs of 1 / 2 / 7 nodes, more rows than one NNConv tile."""
+import os
+
+import pytest
+import torch
+
+import gnn_qot_estimation_amd as q
+from gnn_qot_estimation_amd import harness, infer, synthetic as S
+from helpers import TOL, rel_err
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _models(device, V, H, O=3, D=4, seed=0, **kw):
+    from oracle import sparse as Osp
+    torch.manual_seed(seed)
+    ref = Osp.TopologicalGNN(V, H, O, D, dropout_p=0.0, **kw).eval()
+    with torch.no_grad():
+        for p in ref.parameters():
+            if p.dim() == 1 and p.abs().max() == 0:      # zero-init biases: make them matter
+                p.uniform_(-0.1, 0.1)
+    hip = q.TopologicalGNN(V, H, O, D, dropout_p=0.0, **kw)
+    hip.load_state_dict(ref.state_dict(), strict=True)
+    return ref, hip.to(device).eval()
+
+
+def _graph(n, e, D=4, g=0, edges=None):
+    """One seeded synthetic graph of ``n`` nodes and ``e`` directed edges (both directions of e / 2 links); ``edges``
+    keeps only its first so many directed edges (odd counts, a single edge)."""
+    b = S.topological_batch(2, 1, n=n, e=e, edge_dim=D, first_graph=g)
+    ei, ea = b.edge_index, b.edge_attr
+    if edges is not None:
+        assert edges <= ei.shape[1], (edges, ei.shape[1])
+        ei, ea = ei[:, :edges].contiguous(), ea[:edges].contiguous()
+    return q.Data(edge_index=ei, edge_attr=ea, node_ids=torch.arange(n), num_nodes=n)
+
+
+def _custom(n, src, dst, D=4, seed=0, ea=None):
+    gen = torch.Generator().manual_seed(seed)
+    ei = torch.tensor([src, dst], dtype=torch.long).reshape(2, -1)
+    ea = torch.rand(ei.shape[1], D, generator=gen) if ea is None else ea
+    return q.Data(edge_index=ei, edge_attr=ea, node_ids=torch.arange(n), num_nodes=n)
+
+
+def _check(ref, hip, pred, batch, device, engine=True):
+    with torch.no_grad():
+        want = ref(batch)
+    db = batch.to(device)
+    got = pred(db)
+    assert got.grad_fn is None and not got.requires_grad and got.device == device and got.dtype == torch.float32
+    assert tuple(got.shape) == tuple(want.shape)
+    e_or = rel_err(got, want)
+    print(f"predictor vs oracle {e_or:.3e}")
+    assert e_or <= TOL, e_or
+    if engine:
+        with torch.no_grad():
+            own = hip(db)
+        e_en = rel_err(got, own)
+        print(f"predictor vs engine {e_en:.3e}")
+        assert e_en <= TOL, e_en
+    pred.check_status()
+    return got
+
+
+# ------------------------------------------------------------------ 1. parity over widths and shapes
+@pytest.mark.parametrize("O", [1, 3])
+@pytest.mark.parametrize("D", [1, 4])
+@pytest.mark.parametrize("H", [16, 32, 64])
+def test_parity_mixed_batch(cuda_device, H, D, O):
+    cap = infer.edge_cap(128, H, D)                       # the batch's largest graph has 128 nodes
+    graphs = [_graph(2, 2, D, 0, edges=1),                # a single directed edge
+              _graph(7, 12, D, 1),
+              _graph(75, 600, D, 2),
+              _graph(100, cap + 1 + (cap + 1) % 2, D, 3, edges=cap),       # exactly at the cap
+              _graph(128, 400, D, 4)]
+    batch = q.Batch.from_data_list(graphs)
+    assert batch.graph_sizes == (128, cap)
+    ref, hip = _models(cuda_device, 128, H, O, D)
+    _check(ref, hip, q.TopologicalPredictor(hip), batch, cuda_device)
+
+
+# ------------------------------------------------------------------ 2. degenerate graphs
+def _degenerate(D=4):
+    half = _graph(20, 60, D, 7)
+    keep = half.edge_index[1] < 10                        # nodes 10..19: in-degree 0
+    half = q.Data(edge_index=half.edge_index[:, keep], edge_attr=half.edge_attr[keep], node_ids=torch.arange(20),
+                  num_nodes=20)
+    return [
+        q.Data(edge_index=torch.zeros(2, 0, dtype=torch.long), edge_attr=torch.zeros(0, D), node_ids=torch.arange(9),
+               num_nodes=9),                                                     # no edges at all
+        half,
+        _custom(6, [0, 1, 2, 2, 3, 5, 4], [0, 1, 2, 3, 2, 5, 0], D, 1),          # self loops (one node: only a loop)
+        _custom(5, [0, 1, 1, 1, 2, 3, 1], [1, 2, 2, 2, 3, 4, 0], D, 2),          # 1 -> 2 three times, different features
+        _custom(1, [], [], D, 3),                                                # a single node
+        _custom(1, [0, 0], [0, 0], D, 4),                                        # ... and one with a repeated loop
+    ]
+
+
+@pytest.mark.parametrize("H", [16, 64])
+def test_degenerate_graphs(cuda_device, H):
+    graphs = _degenerate()
+    ref, hip = _models(cuda_device, 20, H)
+    pred = q.TopologicalPredictor(hip)
+    got = _check(ref, hip, pred, q.Batch.from_data_list(graphs), cuda_device)
+    assert torch.isfinite(got).all()
+    for g in graphs:                                      # ... and each of them alone (an edge-less BATCH among them)
+        _check(ref, hip, pred, q.Batch.from_data_list([g]), cuda_device, engine=False)
+
+
+# ------------------------------------------------------------------ 3. batch independence
+@pytest.mark.parametrize("H", [16, 64])
+def test_rows_do_not_depend_on_the_batch(cuda_device, H):
+    ref, hip = _models(cuda_device, 40, H)
+    pred = q.TopologicalPredictor(hip)
+    sizes = [(40, 160), (7, 12), (33, 90), (12, 30), (25, 80), (2, 2), (18, 50)]
+    graphs = [_graph(n, e, 4, 10 + k) for k, (n, e) in enumerate(sizes)]
+    g = graphs[0]
+    alone = pred(q.Batch.from_data_list([g]).to(cuda_device))
+    first = pred(q.Batch.from_data_list([g] + graphs[1:]).to(cuda_device))
+    last_b = q.Batch.from_data_list(graphs[1:] + [g]).to(cuda_device)
+    last = pred(last_b)
+    assert torch.equal(alone[0], first[0]) and torch.equal(alone[0], last[6])
+    assert torch.equal(first[1:], last[:6])
+    assert torch.equal(last, pred(last_b))
+    with torch.no_grad():
+        assert rel_err(last, ref(q.Batch.from_data_list(graphs[1:] + [g]))) <= TOL
+
+
+# ------------------------------------------------------------------ 4. parameter tracking
+def test_parameters_are_tracked(cuda_device):
+    ref, hip = _models(cuda_device, 30, 32)
+    pred = q.TopologicalPredictor(hip)
+    batch = q.Batch.from_data_list([_graph(30, 100, 4, 20 + k) for k in range(3)])
+    old = _check(ref, hip, pred, batch, cuda_device).clone()
+    # one in-place SGD step with the same gradients on both models (the oracle's, so that the weights stay identical)
+    torch.nn.functional.smooth_l1_loss(ref(batch), torch.rand(3, 3) + 1.0).backward()
+    hp = dict(hip.named_parameters())
+    for name, p in ref.named_parameters():
+        hp[name].grad = p.grad.to(cuda_device)
+    for model in (ref, hip):
+        torch.optim.SGD(model.parameters(), lr=0.5).step()
+    stepped = _check(ref, hip, pred, batch, cuda_device).clone()
+    assert rel_err(stepped, old) > TOL                    # the step moved the output by more than the comparison allows
+    # load_state_dict of other weights
+    other, _ = _models(cuda_device, 30, 32, seed=5)
+    ref.load_state_dict(other.state_dict(), strict=True)
+    hip.load_state_dict(other.state_dict(), strict=True)
+    loaded = _check(ref, hip, pred, batch, cuda_device)
+    assert rel_err(loaded, stepped) > TOL
+
+
+# ------------------------------------------------------------------ 5. node ids
+@pytest.mark.parametrize("H", [16, 64])
+def test_node_ids_need_not_be_arange(cuda_device, H):
+    ref, hip = _models(cuda_device, 40, H)
+    pred = q.TopologicalPredictor(hip)
+    gen = torch.Generator().manual_seed(3)
+    graphs = []
+    for k in range(3):
+        g = _graph(12, 40, 4, 30 + k)
+        g.node_ids = torch.randperm(40, generator=gen)[:12]          # a permuted strict subset of the table rows
+        graphs.append(g)
+    full = _graph(40, 120, 4, 33)
+    full.node_ids = torch.randperm(40, generator=gen)                # a permutation of all of them
+    batch = q.Batch.from_data_list(graphs + [full])
+    assert batch.uniform_node_ids is None
+    _check(ref, hip, pred, batch, cuda_device)
+    bad = _graph(12, 40, 4, 34)
+    bad.node_ids = torch.arange(12) + 29                             # 40 >= num_nodes
+    with pytest.raises(IndexError):
+        pred(q.Batch.from_data_list([graphs[0], bad]).to(cuda_device))
+    with pytest.raises(IndexError):                                  # arange ids, more nodes than table rows
+        pred(q.Batch.from_data_list([_graph(41, 100, 4, 35)]).to(cuda_device))
+
+
+# ------------------------------------------------------------------ 6. refusals
+def test_refusals_name_the_condition(cuda_device):
+    _, hip = _models(cuda_device, 130, 16)
+    pred = q.TopologicalPredictor(hip)
+    with pytest.raises(ValueError, match="129 nodes"):
+        pred(q.Batch.from_data_list([_graph(10, 20), _graph(129, 300, 4, 1)]).to(cuda_device))
+    cap = infer.edge_cap(100, 16, 4)
+    over = _graph(100, cap + 2 + cap % 2, 4, 2, edges=cap + 1)
+    with pytest.raises(ValueError, match=f"{cap + 1} edges is above the edge cap {cap}"):
+        pred(q.Batch.from_data_list([over]).to(cuda_device))
+    at = q.Batch.from_data_list([_graph(100, cap + 2 + cap % 2, 4, 2, edges=cap)]).to(cuda_device)
+    assert torch.isfinite(pred(at)).all()
+    withx = q.Batch.from_data_list([_graph(10, 20)]).to(cuda_device)
+    withx.x = torch.rand(10, 16, device=cuda_device)
+    with pytest.raises(ValueError, match="data.x is given"):
+        pred(withx)
+    with pytest.raises(ValueError, match="zero-padded"):
+        q.TopologicalPredictor(q.TopologicalGNN(14, 20, 3, 4).to(cuda_device))
+    with pytest.raises(ValueError, match="num_layers"):
+        q.TopologicalPredictor(q.TopologicalGNN(14, 16, 3, 4, num_layers=3).to(cuda_device))
+    hip.cpu()
+    with pytest.raises(ValueError, match="CPU"):
+        pred(withx)
+
+
+# ------------------------------------------------------------------ 7. evaluate(fused=True)
+def test_evaluate_fused_agrees_with_the_default_path(cuda_device):
+    data = []
+    for g in range(40):
+        b = S.topological_batch(2, 1, n=12, e=30, first_graph=g)
+        y = b.edge_attr[:, :3].mean(0, keepdim=True)
+        data.append(q.Data(edge_index=b.edge_index, edge_attr=b.edge_attr, node_ids=b.node_ids, y=y, num_nodes=12))
+    shard = q.PackedGraphs.from_data_list(data)
+    _, hip = _models(cuda_device, 12, 16)
+    kw = dict(kind="topological", batch_size=16, output_dim=3, device=cuda_device, return_predictions=True)
+    m0, t0, p0, _ = harness.evaluate(hip, shard, **kw)
+    m1, t1, p1, _ = harness.evaluate(hip, shard, fused=True, **kw)
+    assert p1.shape == p0.shape == (40, 3) and torch.equal(t0, t1)
+    assert rel_err(p1, p0) <= TOL
+    for key in m0:
+        for name in ("R2", "Test_MSE"):                   # the loss of the metric block, and R2 per output
+            a, b = m1[key][name], m0[key][name]
+            assert abs(a - b) <= TOL * max(abs(b), 1.0), (key, name, a, b)
+    with pytest.raises(ValueError, match="kind='topological' only"):
+        harness.evaluate(hip, shard, kind="lightpath", fused=True, device=cuda_device)
+
+
+# ------------------------------------------------------------------ 8. the shipped checkpoint
+def test_shipped_checkpoint(cuda_device):
+    fx = torch.load(os.path.join(GOLD, "topological_model_0.pt"), weights_only=True)
+    p = fx["model_params"]
+    m = q.TopologicalGNN(p["num_nodes"], p["hidden_channels"], p["output_dim"], p["edge_dim"], dropout_p=0.0)
+    m.load_state_dict(fx["state_dict"], strict=True)
+    m.to(cuda_device)
+    m.train()                                             # does not matter: the predictor computes the eval-mode function
+    b = q.Batch()
+    for k, v in fx["inputs"].items():
+        setattr(b, k, v.to(cuda_device) if isinstance(v, torch.Tensor) else v)
+    pred = q.TopologicalPredictor(m)
+    out = pred(b)
+    pred.check_status()
+    assert rel_err(out, fx["expected"]) <= TOL
+    assert rel_err(out, fx["expected_dense64"]) <= TOL

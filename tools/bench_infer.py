@@ -1,0 +1,132 @@
+"""Milliseconds per call of ``TopologicalPredictor(model)(data)`` (the single-launch inference kernel, csrc/infer.hip)
+against the two ways the default path offers for the same eval-mode forward:
+
+  (a) ``model.eval()(data)`` under ``torch.no_grad()``, eager;
+  (b) the same forward replayed from a captured graph of that one batch (a lower bound for (a): a planning tool that
+      scores fresh candidates has no captured batch to replay).
+
+Shapes: the reference's scale (V = 75, H = 16, D = 4, O = 3; 75-node graphs of 600 directed edges) at B = 1, 8 and 512,
+and the headline shape (n = 100, e = 400, H = 64) at B = 1 and 1024.  Per shape: the outputs of the three ways are compared
+first; then WARMUP calls of each, then ROUNDS rounds that alternate the three ways, each call timed by the host clock between
+two device synchronisations; the figure is the median over the rounds (min and max are printed with it).  One JSON line
+per shape, and a markdown table at the end; ``--out FILE`` also writes the JSON lines there.
+
+    python tools/bench_infer.py [--rounds 50] [--warmup 10] [--out prof_out/bench_infer.jsonl]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import gnn_qot_estimation_amd as q  # noqa: E402
+from gnn_qot_estimation_amd import synthetic as S  # noqa: E402
+
+SHAPES = [
+    dict(name="reference B=1", V=75, n=75, e=600, H=16, B=1),
+    dict(name="reference B=8", V=75, n=75, e=600, H=16, B=8),
+    dict(name="reference B=512", V=75, n=75, e=600, H=16, B=512),
+    dict(name="headline B=1", V=100, n=100, e=400, H=64, B=1),
+    dict(name="headline B=1024", V=100, n=100, e=400, H=64, B=1024),
+]
+
+
+def batch_for(shape, device):
+    distinct = min(shape["B"], 64)                         # distinct graphs are generated once, then tiled
+    base = S.topological_batch(2, distinct, n=shape["n"], e=shape["e"], edge_dim=4)
+    return S.tile_batch(base, shape["B"] // distinct).to(device)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def measure(shape, device, rounds, warmup):
+    torch.manual_seed(0)
+    model = q.TopologicalGNN(shape["V"], shape["H"], 3, 4, dropout_p=0.0).to(device).eval()
+    data = batch_for(shape, device)
+    predictor = q.TopologicalPredictor(model)
+
+    def eager():
+        with torch.no_grad():
+            return model(data)
+
+    for _ in range(3):
+        want = eager()
+    got = predictor(data)
+    torch.cuda.synchronize()
+    err = float((got.double() - want.double()).abs().max() / want.double().abs().max())
+    assert err <= 1e-4, (shape["name"], err)
+
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        eager()
+    torch.cuda.current_stream().wait_stream(side)
+    with torch.cuda.graph(graph):
+        replay_out = eager()
+    graph.replay()
+    torch.cuda.synchronize()
+    err_replay = float((replay_out.double() - want.double()).abs().max() / want.double().abs().max())
+    assert err_replay <= 1e-6, (shape["name"], err_replay)
+
+    ways = {"fused": lambda: predictor(data), "eager": eager, "replay": graph.replay}
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed(fn))
+    res = dict(shape=shape["name"], **{k: shape[k] for k in ("V", "n", "e", "H", "B")}, rounds=rounds, rel_err=err)
+    for k, ts in times.items():
+        res[f"{k}_ms"] = statistics.median(ts)
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--rounds", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.rounds < 20:
+        raise SystemExit("--rounds: at least 20 timed calls per way")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
+    device = torch.device("cuda:0")
+    commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    rows = []
+    for shape in SHAPES:
+        res = measure(shape, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| shape | fused ms | (a) eager ms | (b) replay ms | eager / fused | replay / fused |")
+    print("|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['shape']} (n={r['n']}, e={r['e']}, H={r['H']}) | {r['fused_ms']:.3f} | {r['eager_ms']:.3f} | "
+              f"{r['replay_ms']:.3f} | {r['eager_ms'] / r['fused_ms']:.2f} | {r['replay_ms'] / r['fused_ms']:.2f} |")
+
+
+if __name__ == "__main__":
+    main()
