@@ -12,7 +12,7 @@ from .lightpath import LightpathGNN
 from .loader import GatherStageSlot, GraphLoader, PackedGraphs, PaddedStageSlot, StageSlot
 from .nn import BatchNorm, GATConv, NNConv, TransformerConv, global_mean_pool
 from .topological import TopologicalGNN
-from .infer import TopologicalPredictor
+from .infer import LightpathPredictor, TopologicalPredictor
 
-__all__ = ["Batch", "Data", "shard_graphs", "TopologicalGNN", "TopologicalPredictor", "LightpathGNN", "TransformerConv", "NNConv",
+__all__ = ["Batch", "Data", "shard_graphs", "TopologicalGNN", "TopologicalPredictor", "LightpathPredictor", "LightpathGNN", "TransformerConv", "NNConv",
            "GATConv", "BatchNorm", "global_mean_pool", "GraphLoader", "PackedGraphs", "StageSlot", "PaddedStageSlot", "GatherStageSlot", "harness", "dataset"]

@@ -171,6 +171,8 @@ SIGNATURES = {
     "qot_topological_infer_max_edges": (_int, [_int, _int, _int]),
     "qot_topological_infer": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _int, _p, _int, _p, _int, _p, _p,
                                      _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _int, _int, _int, _p, _p]),
+    "qot_lightpath_infer": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f,
+                                   _p, _p, _p, _p, _f, _p, _p, _int, _int, _int, _int, _int, _p, _p]),
 }
 
 MAX_ROLES = 12           # include/qot_gnn.h: QOT_MAX_ROLES

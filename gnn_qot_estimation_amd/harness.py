@@ -870,7 +870,7 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
              batch_size: int = 512, output_dim: int = 3, device="cuda",
              output_keys: Sequence[str] = ("osnr", "snr", "ber"),
              target_ranges: Dict[str, Dict[str, float]] = TARGET_RANGES, return_predictions: bool = False,
-             fused: bool = False):
+             fused: bool = False, predictor: Optional[Callable] = None):
     """test.py's metric block: per-output R2 and MSE on min-max descaled values (test.py:76-121).
 
     ``fused=True`` (opt-in, ``kind="topological"`` on one process; ``ValueError`` otherwise or when the model or a batch
@@ -880,6 +880,10 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
     graphs); at hidden 64 with a thousand graphs per batch the default path's MFMA NNConv kernel is expected to have the
     advantage (fp32 FMA here).  Neither side of that has been measured on an MI355X yet: DESIGN.md 4.12.
 
+    ``predictor`` (opt-in, one process; ``ValueError`` in a larger world): a callable used in place of ``model(data)`` for
+    the given ``kind`` -- for ``kind="lightpath"`` an ``infer.LightpathPredictor(model)``, whose ``(out, lut_batch)`` has the
+    model's contract.  Its ``infer.EnvelopeError`` propagates; the LUT-less ``ValueError`` still skips the batch.
+
     ``return_predictions``: also return ``(y_true_descaled, y_pred_descaled, skipped_graphs)`` -- the arrays test.py
     writes to ``y_true_descaled.json`` / ``y_pred_descaled.json`` (test.py:92-103,129-136), in dataset order; they stay
     on the device until the loop is over (one host copy)."""
@@ -888,6 +892,10 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
         raise ValueError(f"evaluate(fused=True) is for kind='topological' only, got kind={kind!r}")
     if fused and world > 1:
         raise ValueError(f"evaluate(fused=True) runs on one process, got a world of {world}")
+    if predictor is not None and world > 1:
+        raise ValueError(f"evaluate(predictor=...) runs on one process, got a world of {world}")
+    if predictor is not None and fused:
+        raise ValueError("evaluate: give either fused=True or predictor=..., not both")
     device = torch.device(device)
     model.to(device)
     idx = range(len(dataset)) if indices is None else indices
@@ -898,6 +906,9 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
         from .infer import TopologicalPredictor
         predictor = TopologicalPredictor(model)
         fwd = lambda _model, data, out_dim: (predictor(data), data.y.view(-1, out_dim))      # noqa: E731
+    elif predictor is not None:
+        kind_fwd, call = _KINDS[kind], predictor
+        fwd = lambda _model, data, out_dim: kind_fwd(call, data, out_dim)                   # noqa: E731
     loader = GraphLoader(dataset, batch_size, shuffle=False, device=device,
                          batches=_local_batches(idx, batch_size, rank, world, _graph_costs(dataset, idx)))
     kept, skipped = [], 0
@@ -925,8 +936,9 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
                 continue
             try:
                 out, y = fwd(model, data, output_dim)
-            except ValueError:
-                if fused:                             # outside the predictor's envelope: an error, not a LUT-less batch
+            except ValueError as err:
+                from .infer import EnvelopeError
+                if fused or isinstance(err, EnvelopeError):     # outside a predictor's envelope: not a LUT-less batch
                     raise
                 skipped += data.num_graphs            # lightpath_training/test.py:82-85
                 continue

@@ -1,9 +1,11 @@
-"""Single-launch inference for ``TopologicalGNN``: ``TopologicalPredictor`` (``csrc/infer.hip``).
+"""Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``) and ``LightpathPredictor``
+(``csrc/infer_lightpath.hip``).
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
-TransformerConv, the NNConv forward and the read-out kernel, each behind an autograd wrapper.  That is host-bound for one
-graph or a handful -- the case of a planning tool that scores one candidate after another.  The predictor runs the same
-function as ONE kernel launch per call, one workgroup per graph, and touches autograd nowhere.
+TransformerConv, the NNConv forward and the read-out kernel (``LightpathGNN``: the self-looped graph index, the GAT walk
+over all nodes, BatchNorm rows and the head), each behind an autograd wrapper.  That is host-bound for one graph or a
+handful -- the case of a planning tool that scores one candidate after another.  A predictor runs the same function as ONE
+kernel launch per call and touches autograd nowhere.
 """
 from __future__ import annotations
 
@@ -37,6 +39,50 @@ def wcat_index(h: int, k: int, device) -> torch.Tensor:
 def edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
     """Most edges a graph may have beside ``n_max`` nodes (the kernel's LDS budget, asked of the library); -1: none."""
     return int(_lib.load().qot_topological_infer_max_edges(int(n_max), int(hidden), int(edge_dim)))
+
+
+def _i64(t, dev):
+    if t.dtype != torch.int64 or t.device != dev:
+        t = t.to(device=dev, dtype=torch.int64)
+    return t.contiguous()
+
+
+def graph_slices(data, ei, N, dev, who):
+    """``(node_ptr, edge_ptr, B, n_max, max_e, exact)`` of a block-diagonal batch of ``N`` nodes with the int64
+    ``edge_index`` ``ei`` on ``dev``.  A batch that carries ``ptr`` / ``edge_ptr`` / ``graph_sizes`` (ours do) costs no
+    device read; otherwise the slices come from ``data.batch`` with device-side torch ops (and ``n_max`` / ``max_e`` with one
+    read).  Edges not grouped by graph raise ``ValueError``.  ``exact()`` reads the true largest node / edge count (the
+    carried sizes are bounds: a shard inherits its parent's).  ``who`` prefixes the error messages."""
+    E = ei.shape[1]
+    ptr, eptr, sizes = getattr(data, "ptr", None), getattr(data, "edge_ptr", None), getattr(data, "graph_sizes", None)
+    if ptr is None:
+        batch = _i64(data.batch, dev)
+        B = getattr(data, "num_graphs", None)
+        B = int(B) if B is not None else (int(batch.max()) + 1 if N else 0)
+        ptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        ptr[1:] = torch.cumsum(torch.bincount(batch, minlength=B), 0)
+        sizes = None
+    ptr = _i64(ptr, dev)
+    B = ptr.numel() - 1
+    if eptr is None:
+        # edges of a collated batch are grouped by graph: the slices follow from the graph of every edge's target
+        batch = torch.repeat_interleave(torch.arange(B, device=dev), ptr[1:] - ptr[:-1])
+        eb = batch[ei[1]]
+        if E > 1 and not bool((eb[1:] >= eb[:-1]).all()):
+            raise ValueError(f"{who}: the edges of the batch are not grouped by graph")
+        eptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        eptr[1:] = torch.cumsum(torch.bincount(eb, minlength=B), 0)
+        sizes = None
+    eptr = _i64(eptr, dev)
+    if eptr.numel() != B + 1:
+        raise ValueError(f"{who}: ptr and edge_ptr disagree on the number of graphs")
+
+    def exact():
+        if B == 0:
+            return 0, 0
+        return int((ptr[1:] - ptr[:-1]).max()), int((eptr[1:] - eptr[:-1]).max())
+    n_max, max_e = (int(sizes[0]), int(sizes[1])) if sizes is not None else exact()
+    return ptr, eptr, B, n_max, max_e, exact
 
 
 class TopologicalPredictor:
@@ -126,12 +172,6 @@ class TopologicalPredictor:
         return self._tables
 
     # ------------------------------------------------------------------ the batch
-    @staticmethod
-    def _i64(t, dev):
-        if t.dtype != torch.int64 or t.device != dev:
-            t = t.to(device=dev, dtype=torch.int64)
-        return t.contiguous()
-
     def _slices(self, data, dev):
         """``(node_ids, edge_index, node_ptr, edge_ptr, n_max, max_e, B)``, remembered on the batch object.  A batch that
         carries ``ptr`` / ``edge_ptr`` / ``graph_sizes`` (ours do) costs no device read; otherwise the slices come from
@@ -143,36 +183,8 @@ class TopologicalPredictor:
         c = _cache(data)
         if c is not None and "infer" in c and c["infer"][0] == tag:
             return c["infer"][1]
-        ids, ei = self._i64(ids, dev), self._i64(ei, dev)
-        N, E = ids.shape[0], ei.shape[1]
-        ptr, eptr, sizes = getattr(data, "ptr", None), getattr(data, "edge_ptr", None), getattr(data, "graph_sizes", None)
-        if ptr is None:
-            batch = self._i64(data.batch, dev)
-            B = getattr(data, "num_graphs", None)
-            B = int(B) if B is not None else (int(batch.max()) + 1 if N else 0)
-            ptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-            ptr[1:] = torch.cumsum(torch.bincount(batch, minlength=B), 0)
-            sizes = None
-        ptr = self._i64(ptr, dev)
-        B = ptr.numel() - 1
-        if eptr is None:
-            # edges of a collated batch are grouped by graph: the slices follow from the graph of every edge's target
-            batch = torch.repeat_interleave(torch.arange(B, device=dev), ptr[1:] - ptr[:-1])
-            eb = batch[ei[1]]
-            if E > 1 and not bool((eb[1:] >= eb[:-1]).all()):
-                raise ValueError("TopologicalPredictor: the edges of the batch are not grouped by graph")
-            eptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-            eptr[1:] = torch.cumsum(torch.bincount(eb, minlength=B), 0)
-            sizes = None
-        eptr = self._i64(eptr, dev)
-        if eptr.numel() != B + 1:
-            raise ValueError("TopologicalPredictor: ptr and edge_ptr disagree on the number of graphs")
-
-        def exact():
-            if B == 0:
-                return 0, 0
-            return int((ptr[1:] - ptr[:-1]).max()), int((eptr[1:] - eptr[:-1]).max())
-        n_max, max_e = (int(sizes[0]), int(sizes[1])) if sizes is not None else exact()
+        ids, ei = _i64(ids, dev), _i64(ei, dev)
+        ptr, eptr, B, n_max, max_e, exact = graph_slices(data, ei, ids.shape[0], dev, "TopologicalPredictor")
         res = (ids, ei, ptr, eptr, n_max, max_e, B, exact)
         if c is not None:
             c["infer"] = (tag, res)
@@ -240,3 +252,135 @@ class TopologicalPredictor:
         if code:
             raise _lib.QotError(f"qot_topological_infer flagged the batch (status {code}): bit 0 an edge leaves its "
                                 "graph's node range, bit 1 slices outside the arrays, bit 2 a node id outside the table")
+
+
+# ====================================================================== LightpathGNN
+LP_MAX_FEATURES = 16            # csrc/infer_lightpath.hip: kLpMaxF
+LP_MAX_HIDDEN = 256             # kLpMaxC
+LP_MAX_OUTPUTS = 8              # kLpMaxO
+
+
+class EnvelopeError(ValueError):
+    """A model or a batch outside what ``LightpathPredictor`` runs; there is no other path behind it.  (A LUT-less batch is
+    NOT one: that is the model's own ``ValueError``.)"""
+
+
+class LightpathPredictor:
+    """``predict = LightpathPredictor(model)``: the EVAL-MODE forward of a one-layer ``LightpathGNN`` as one kernel launch
+    that computes the LUT rows only (one wavefront per row, no graph index, no other node's row).
+
+    ``predict(data) -> (out [L, O], lut_batch [L])``: the contract of ``model.eval()(data)``.  The LUT rows are the model's
+    (``model._lut_rows``: cached on the batch object, one host read on the first visit of a batch); a LUT-less batch raises
+    the model's ``ValueError("No LUT node found in the batch.")``, or gives zero rows when ``model.allow_empty_lut`` is set.
+
+    ``predict.per_graph(data) -> (out [B, O], count [B] int32)``: one row per GRAPH, found on the device: ``count[g]`` LUT
+    nodes in graph ``g``, ``out[g]`` the row of the lowest-numbered one, NaN when there is none.  No host synchronisation;
+    legal inside ``torch.cuda.graph`` capture when the batch carries ``ptr`` / ``edge_ptr`` (ours do) or has been through
+    one call before (the derived slices are remembered on the batch object).
+
+    Both: ``model.training`` does not matter (eval-mode function: running statistics, no dropout), buffers are never
+    written, the result carries no ``grad_fn``.  Parameters and buffers are read by the kernel at call time, in place: an
+    in-place optimizer step, ``load_state_dict`` or running statistics moved by a train-mode forward are seen by the next
+    call with no bookkeeping.  A row is bitwise reproducible, independent of the other graphs of the batch and the same
+    from either call; against ``model.eval()(data)`` it agrees to fp32 rounding.  A model whose width the engine runs
+    zero-padded (e.g. C = 20) is supported: the kernel reads its real parameters.
+
+    Envelope -- ``EnvelopeError`` naming the condition otherwise: a model on the GPU with ``num_layers == 1``, 1 ... 16 input
+    features, hidden width 1 ... 256, 1 ... 8 outputs; ``data.x`` of shape ``[N, F]``.  No cap on in-degree, graph size or
+    batch size.  Edges must be grouped by graph (``ValueError`` otherwise); an edge that leaves its graph's node range makes
+    the rows of that graph NaN and ``check_status()`` raise.
+    """
+
+    def __init__(self, model):
+        self.model = model
+        self._status = None
+        self._check_model()
+
+    def _check_model(self):
+        m = self.model
+        if getattr(m, "num_layers", None) != 1 or not hasattr(m, "conv1") or not hasattr(m, "norm1"):
+            raise EnvelopeError(f"LightpathPredictor: num_layers must be 1 (the reference architecture: one GATConv), got "
+                                f"{getattr(m, 'num_layers', None)}")
+        conv = m.conv1
+        F, C, O = conv.in_channels, conv.out_channels, m.mlp[3].out_features
+        if conv.heads != 4:
+            raise EnvelopeError(f"LightpathPredictor: heads {conv.heads} is not supported; it must be 4")
+        if not 1 <= F <= LP_MAX_FEATURES:
+            raise EnvelopeError(f"LightpathPredictor: in_channels {F} is not supported; it must be 1 ... {LP_MAX_FEATURES}")
+        if not 1 <= C <= LP_MAX_HIDDEN:
+            raise EnvelopeError(f"LightpathPredictor: hidden_channels {C} is not supported; it must be 1 ... {LP_MAX_HIDDEN}")
+        if not 1 <= O <= LP_MAX_OUTPUTS:
+            raise EnvelopeError(f"LightpathPredictor: output_dim {O} is not supported; it must be 1 ... {LP_MAX_OUTPUTS}")
+        if not 0 <= int(m.is_lut_index) < F:
+            raise EnvelopeError(f"LightpathPredictor: is_lut_index {m.is_lut_index} is not a column of {F} features")
+        if not conv.bias.is_cuda:
+            raise EnvelopeError("LightpathPredictor: the model is on the CPU; move it to the GPU first (model.to('cuda'))")
+        return F, C, O
+
+    def _batch(self, data, F, dev):
+        """``(x, edge_index, node_ptr, edge_ptr, B)`` on ``dev``; the slices are remembered on the batch object."""
+        x = getattr(data, "x", None)
+        if x is None or x.dim() != 2 or x.shape[1] != F:
+            raise EnvelopeError(f"LightpathPredictor: data.x must be [N, {F}], got "
+                                f"{None if x is None else tuple(x.shape)}")
+        x = _f32c(x if x.device == dev else x.to(dev))
+        ei = data.edge_index
+        tag = (x.shape[0], ei.data_ptr(), ei._version, tuple(ei.shape))
+        c = _cache(data)
+        if c is not None and "infer_lp" in c and c["infer_lp"][0] == tag:
+            return (x,) + c["infer_lp"][1]
+        ei = _i64(ei, dev)
+        ptr, eptr, B, _, _, _ = graph_slices(data, ei, x.shape[0], dev, "LightpathPredictor")
+        res = (ei, ptr, eptr, B)
+        if c is not None:
+            c["infer_lp"] = (tag, res)
+        return (x,) + res
+
+    def _launch(self, x, ei, batch, ptr, eptr, lut_idx, B, out, count, F, C, O):
+        m = self.model
+        conv, bn, l0, l3 = m.conv1, m.norm1.module, m.mlp[0], m.mlp[3]
+        dev = out.device
+        if self._status is None or self._status.device != dev:
+            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        p = [_f32c(t.detach()) for t in (conv.lin.weight, conv.att_src, conv.att_dst, conv.bias, bn.weight, bn.bias,
+                                         bn.running_mean, bn.running_var, l0.weight, l0.bias, l3.weight, l3.bias)]
+        _lib.call("qot_lightpath_infer", x, ei, batch, ptr, eptr, lut_idx, 0 if lut_idx is None else lut_idx.shape[0],
+                  x.shape[0], ei.shape[1], B, p[0], p[1], p[2], p[3], float(conv.negative_slope), p[4], p[5], p[6], p[7],
+                  float(bn.eps), p[8], p[9], p[10], p[11], float(m.mlp[1].negative_slope), out, count, F, C, O,
+                  int(conv.heads), int(m.is_lut_index), self._status)
+
+    @torch.no_grad()
+    def __call__(self, data):
+        F, C, O = self._check_model()
+        m = self.model
+        dev = m.conv1.bias.device
+        x, ei, ptr, eptr, B = self._batch(data, F, dev)
+        idx = m._lut_rows(data)                     # the model's ValueError for a LUT-less batch
+        batch = _i64(data.batch, dev)
+        idx = _i64(idx, dev)
+        out = torch.empty(idx.shape[0], O, dtype=torch.float32, device=dev)
+        if idx.shape[0] == 0:                       # only with allow_empty_lut
+            return out, batch[:0]
+        self._launch(x, ei, batch, ptr, eptr, idx, B, out, None, F, C, O)
+        return out, batch.index_select(0, idx)
+
+    @torch.no_grad()
+    def per_graph(self, data):
+        F, C, O = self._check_model()
+        dev = self.model.conv1.bias.device
+        x, ei, ptr, eptr, B = self._batch(data, F, dev)
+        out = torch.empty(B, O, dtype=torch.float32, device=dev)
+        count = torch.empty(B, dtype=torch.int32, device=dev)
+        self._launch(x, ei, None, ptr, eptr, None, B, out, count, F, C, O)
+        return out, count
+
+    def check_status(self):
+        """Reads the kernel's status word (one device synchronisation): raises when a batch since the last check had an
+        edge outside its graph's node range or indices / slices that disagree with its arrays (such rows are NaN)."""
+        if self._status is None:
+            return
+        code = int(self._status.item())
+        self._status.zero_()
+        if code:
+            raise _lib.QotError(f"qot_lightpath_infer flagged the batch (status {code}): bit 0 an edge leaves its "
+                                "graph's node range, bit 1 a LUT index, graph number or slice outside the arrays")

@@ -36,7 +36,8 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=512)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--fused", action="store_true",
-                    help="topological only: single-launch inference kernel per batch (harness.evaluate(fused=True))")
+                    help="single-launch inference kernel per batch: harness.evaluate(fused=True) for topological, "
+                         "harness.evaluate(predictor=LightpathPredictor(model)) for lightpath")
     ap.add_argument("--is-lut-index", type=int, default=None, help="default: from the dataset (lightpath test.py:59)")
     args = ap.parse_args(argv)
 
@@ -61,9 +62,15 @@ def main(argv=None):
     model.load_state_dict(state, strict=True)
     print(f"Model loaded from {path}")
     _, _, test_idx = harness.split_ranges(len(dataset))
+    how = {}
+    if args.fused and kind == "topological":
+        how = {"fused": True}
+    elif args.fused:
+        from .infer import LightpathPredictor
+        how = {"predictor": LightpathPredictor(model.to(device))}
     metrics, y_true, y_pred, skipped = harness.evaluate(model, dataset, test_idx, kind=kind, batch_size=args.batch_size,
                                                         output_dim=params["output_dim"], device=device,
-                                                        return_predictions=True, **({"fused": True} if args.fused else {}))
+                                                        return_predictions=True, **how)
     print(f"Test R2 Score per output: {[m['R2'] for m in metrics.values()]}")
     print(f"Test MSE per output: {[m['Test_MSE'] for m in metrics.values()]}")
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")

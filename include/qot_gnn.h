@@ -811,6 +811,40 @@ int qot_topological_infer(const int64_t* node_ids, const int64_t* edge_index, co
                           const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
                           float slope_head, float* out, int H, int D, int O, int32_t* status, qot_stream_t stream);
 
+/* ---- single-launch inference: the eval-mode LightpathGNN forward of the LUT rows ------------------------------------
+ * lightpath_training/models.py:7-45 with dropout off, reference architecture (ONE GATConv(heads = 4) -> BatchNorm on the
+ * running statistics -> ReLU -> LUT rows -> Linear -> LeakyReLU -> Linear), for a block-diagonal batch in ONE launch, one
+ * wavefront per output row.  A row depends on the one-hop in-neighbourhood of its LUT node only: the wave scans its graph's
+ * edge slice for the messages into that node (dst == i and src != i, plus exactly one self loop: PyG's remove_self_loops
+ * + add_self_loops; repeated edges are separate messages), forms the logits as leaky_relu(s_h . x_j + d_h . x_i) with
+ * s_h = W_h^T att_src_h, d_h = W_h^T att_dst_h, takes the softmax per head (max subtraction, + 1e-16), and applies W_h to
+ * u_h = sum_e alpha_e x_j.  No graph index is built and no other node's row is computed.  Every sum runs in one fixed order
+ * given by the edge's offset inside its graph's slice (the messages one after the other by rising offset, the self loop
+ * last): a row is bitwise reproducible and does not depend on the other graphs of the launch or on the mode.  fp32 FMA.
+ *
+ * The batch (device): x [N, F] raw features, edge_index [2, E] int64 (row 0 = source, row 1 = target, offset by the graph's
+ * first node), node_ptr [B+1] / edge_ptr [B+1] int64 (the edges of a graph are one slice).
+ *   rows mode   (lut_idx != NULL): lut_idx [L] int64 node numbers, batch [N] int64 (graph of every node); out [L, O].
+ *   graphs mode (lut_idx == NULL): one row per graph; the wave tests x[n, lut_col] == 1.0f (exact) over the graph's nodes,
+ *               writes count[g] (int32 [B]: LUT nodes found) and out[g, :] for the lowest-numbered one, NaN when there is
+ *               none; out [B, O].  `batch` and L are not read.
+ * The model's own parameters, read in place: w [4C, F] (conv1.lin.weight), att_src / att_dst [4, C], conv_bias [4C],
+ * slope_att (conv1.negative_slope); bn_weight / bn_bias / bn_mean / bn_var [4C] and bn_eps (norm1.module, running
+ * statistics); w0 [C, 4C] / b0 [C] (mlp.0), w3 [O, C] / b3 [O] (mlp.3), slope_head (mlp.1).
+ *
+ * Envelope (QOT_ERR_UNSUPPORTED outside it): 1 <= F <= 16, 1 <= C <= 256, 1 <= O <= 8, heads == 4, 0 <= lut_col < F.  No
+ * cap on in-degree, graph size or batch size.
+ * status (optional, device int32, caller-zeroed): bit 0 = an edge of the row's graph slice has an end outside the graph's
+ * node range, bit 1 = a LUT index, graph number or slice outside the arrays; such rows are written as NaN and nothing is
+ * read through the offending index. */
+int qot_lightpath_infer(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                        const int64_t* edge_ptr, const int64_t* lut_idx, int64_t L, int64_t N, int64_t E, int64_t B,
+                        const float* w, const float* att_src, const float* att_dst, const float* conv_bias, float slope_att,
+                        const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var,
+                        float bn_eps, const float* w0, const float* b0, const float* w3, const float* b3, float slope_head,
+                        float* out, int32_t* count, int F, int C, int O, int heads, int lut_col, int32_t* status,
+                        qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,15 @@ two device synchronisations; the figure is the median over the rounds (min and m
 per shape, and a markdown table at the end; ``--out FILE`` also writes the JSON lines there.
 
     python tools/bench_infer.py [--rounds 50] [--warmup 10] [--out prof_out/bench_infer.jsonl]
+
+``--kind lightpath``: ``LightpathPredictor`` (csrc/infer_lightpath.hip) instead -- milliseconds per call of ``predict(data)``,
+``predict.per_graph(data)`` and the eager eval ``model(data)`` under ``torch.no_grad()``, alternating in one process, on
+``synthetic.lightpath_batch`` graphs at C = 32, F = 5 and B = 1, 8, 512 and 65 536 (64 distinct graphs, tiled).  Every call
+sees the same batch object, so the LUT rows of ``predict`` and of the model are the cached ones (no host read inside the
+timed calls).  Per way the median and the interquartile range; a difference of two medians that does not exceed the larger
+of the two interquartile ranges is reported as no difference.
+
+    python tools/bench_infer.py --kind lightpath [--out profiles/bench_infer_lightpath.jsonl]
 """
 import argparse
 import json
@@ -97,11 +106,83 @@ def measure(shape, device, rounds, warmup):
     return res
 
 
+LIGHTPATH_SIZES = (1, 8, 512, 65536)
+
+
+def measure_lightpath(B, device, rounds, warmup):
+    torch.manual_seed(0)
+    model = q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval()
+    distinct = min(B, 64)
+    data = S.tile_batch(S.lightpath_batch(distinct), B // distinct).to(device)
+    predict = q.LightpathPredictor(model)
+
+    def eager():
+        with torch.no_grad():
+            return model(data)
+
+    for _ in range(3):
+        want, want_b = eager()
+    got, got_b = predict(data)
+    per, count = predict.per_graph(data)
+    torch.cuda.synchronize()
+    predict.check_status()
+    scale = want.double().abs().max()
+    err = float((got.double() - want.double()).abs().max() / scale)
+    err_per = float((per.double() - want.double()).abs().max() / scale)       # (one LUT node per graph, graph order)
+    assert torch.equal(got_b, want_b) and bool((count == 1).all()) and err <= 1e-4 and err_per <= 1e-4, (B, err, err_per)
+
+    ways = {"predict": lambda: predict(data), "per_graph": lambda: predict.per_graph(data), "eager": eager}
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed(fn))
+    res = dict(shape=f"lightpath B={B}", kind="lightpath", B=B, C=32, F=5, N=int(data.x.shape[0]),
+               E=int(data.edge_index.shape[1]), rounds=rounds, rel_err=err, rel_err_per_graph=err_per)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def verdict(r, way):
+    """``way`` against the eager forward: the ratio of the medians, or "no difference" (module docstring)."""
+    a, b = r[f"{way}_ms"], r["eager_ms"]
+    if abs(a - b) <= max(r[f"{way}_iqr_ms"], r["eager_iqr_ms"]):
+        return "no difference"
+    return f"{b / a:.2f}x"
+
+
+def main_lightpath(args, device, commit):
+    rows = []
+    for B in LIGHTPATH_SIZES:
+        res = measure_lightpath(B, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| B (nodes, edges) | predict ms (IQR) | per_graph ms (IQR) | eager ms (IQR) | eager / predict | eager / per_graph |")
+    print("|---|---|---|---|---|---|")
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['B']} ({r['N']}, {r['E']}) | {cell('predict')} | {cell('per_graph')} | {cell('eager')} | "
+              f"{verdict(r, 'predict')} | {verdict(r, 'per_graph')} |")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rounds", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kind", choices=["topological", "lightpath"], default="topological")
     args = ap.parse_args()
     if args.rounds < 20:
         raise SystemExit("--rounds: at least 20 timed calls per way")
@@ -109,6 +190,8 @@ def main():
         raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    if args.kind == "lightpath":
+        return main_lightpath(args, device, commit)
     rows = []
     for shape in SHAPES:
         res = measure(shape, device, args.rounds, args.warmup)
