@@ -173,6 +173,11 @@ SIGNATURES = {
                                      _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _int, _int, _int, _p, _p]),
     "qot_lightpath_infer": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f,
                                    _p, _p, _p, _p, _f, _p, _p, _int, _int, _int, _int, _int, _p, _p]),
+    "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),
+    "qot_status_graph_count": (_int, [_p, _p, _p, _i64, _i64, _int, _i64, _i64, _int, _int, _int, C.c_double, _int, _p, _sz, _p,
+                                      _p]),
+    "qot_status_graph_fill": (_int, [_p, _p, _p, _i64, _i64, _int, _i64, _i64, _int, _int, _int, _int, _p, _int, _p, _int, _p,
+                                     _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
 }
 
 MAX_ROLES = 12           # include/qot_gnn.h: QOT_MAX_ROLES

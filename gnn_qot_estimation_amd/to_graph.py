@@ -25,6 +25,11 @@ the reference).  The pair test is one vectorised comparison per link.
 Both return ``networkx.Graph`` objects that pickle into the ``.gpickle`` files ``dataset.TopologicalDataset`` /
 ``LightpathDataset`` (and the reference's own dataset classes) read; ``store_graphs`` writes them, ``build_shard``
 skips the files and packs ``Data`` objects straight into a ``PackedGraphs`` shard.
+
+Device form (DESIGN.md section 4.14): ``NetworkStatus.to_device`` keeps a chunk of samples in HBM (``DeviceStatus``);
+``build_shard(..., device=...)`` / ``device_batch`` run ``csrc/status_graph.hip`` over it -- one workgroup per sample, no
+``networkx`` -- and return a resident ``PackedGraphs`` / ``Batch``.  Its directed links are in the canonical order
+(source, target) inside each graph; ``canonical_link_order`` brings a host-built shard into the same order.
 """
 from __future__ import annotations
 
@@ -80,6 +85,43 @@ class NetworkStatus:
                 ds.close()
         z = np.load(path, allow_pickle=False)
         return cls(z["data"], z["target"], z["lp_feat"], z["metric"], z["link"], z["freq"])
+
+    def to_device(self, device="cuda", samples: Optional[Sequence[int]] = None) -> "DeviceStatus":
+        """The chosen samples (default: all) as fp64 tensors on ``device``, with the coordinate names: the input of the
+        device builder.  The reference's whole dataset does not fit in HBM as a dense array, so a chunk is the unit."""
+        import torch
+        pick = slice(None) if samples is None else np.asarray(list(samples), dtype=np.int64)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+        return DeviceStatus(up(np.asarray(self.data)[pick]), up(np.asarray(self.target)[pick]), up(self.freq),
+                            self.lp_feat, self.metric, np.asarray(self.link))
+
+
+class DeviceStatus:
+    """A chunk of network-status samples resident on the GPU: ``data [sample, lp_feat, link, freq]``, ``target [sample,
+    metric]`` and ``freq [freq]`` as contiguous fp64 tensors, plus the coordinate names (``NetworkStatus.to_device``)."""
+
+    def __init__(self, data, target, freq, lp_feat: Sequence[str], metric: Sequence[str], link=None):
+        import torch
+        for name, t, nd in (("data", data, 4), ("target", target, 2), ("freq", freq, 1)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != nd:
+                raise ValueError(f"{name} must be a {nd}-d float64 tensor")
+        self.data, self.target, self.freq = data.contiguous(), target.contiguous(), freq.contiguous()
+        self.lp_feat = [str(v) for v in lp_feat]
+        self.metric = [str(v) for v in metric]
+        self.link = link
+        self.feature_indexes = {f: i for i, f in enumerate(self.lp_feat)}
+        if data.shape[1] != len(self.lp_feat) or data.shape[3] != freq.shape[0]:
+            raise ValueError("lp_feat / freq coordinates do not match data")
+        if target.shape[0] != data.shape[0] or target.shape[1] != len(self.metric):
+            raise ValueError("target must be [sample, metric]")
+        self._tables: Dict[tuple, tuple] = {}
+
+    def __len__(self) -> int:
+        return self.data.shape[0]
+
+    @property
+    def device(self):
+        return self.data.device
 
 
 Source = Union[NetworkStatus, str]
@@ -210,10 +252,18 @@ def store_graphs(dataset: Source, representation: str = "lightpath", directory: 
     return directory
 
 
-def build_shard(dataset: Source, representation: str = "lightpath", features_to_consider: Sequence[str] = DEFAULT_FEATURES,
-                samples: Optional[Sequence[int]] = None):
+def build_shard(dataset, representation: str = "lightpath", features_to_consider: Sequence[str] = DEFAULT_FEATURES,
+                samples: Optional[Sequence[int]] = None, device=None, freq_threshold: float = 0.05):
     """Samples -> graphs -> ``Data`` -> one ``PackedGraphs`` shard, without the per-graph files in between; the
-    conversion rules are those of the dataset classes (``dataset.topological_data_from_graph`` / ``lightpath_...``)."""
+    conversion rules are those of the dataset classes (``dataset.topological_data_from_graph`` / ``lightpath_...``).
+
+    With a ``device`` (or a ``DeviceStatus`` as ``dataset``) the shard is built on the GPU and stays there, in the state
+    ``PackedGraphs.to_device`` leaves one; its directed links are in canonical order (``canonical_link_order``)."""
+    if isinstance(dataset, DeviceStatus):
+        return _device_build(dataset, representation, features_to_consider, samples, freq_threshold)
+    if device is not None:
+        status = _source(dataset).to_device(device, samples)
+        return _device_build(status, representation, features_to_consider, None, freq_threshold)
     from .dataset import lightpath_data_from_graph, topological_data_from_graph
     from .loader import PackedGraphs
     ds = _source(dataset)
@@ -221,11 +271,157 @@ def build_shard(dataset: Source, representation: str = "lightpath", features_to_
     out = []
     for i in (range(len(ds)) if samples is None else samples):
         if representation == "lightpath":
-            out.append(lightpath_data_from_graph(create_lightpath_graph(i, list(features_to_consider), ds),
+            out.append(lightpath_data_from_graph(create_lightpath_graph(i, list(features_to_consider), ds, freq_threshold),
                                                  sorted(feats + ["is_lut"])))
         else:
             out.append(topological_data_from_graph(create_topological_graph(i, list(features_to_consider), ds), feats))
     return PackedGraphs.from_data_list(out)
+
+
+# ------------------------------------------------------------------------------------------ device builder
+# caps and status bits of csrc/status_graph.hip (include/qot_gnn.h: QOT_SG_*)
+MAX_FREQS, MAX_LIGHTPATHS = 1024, 256
+SG_BAD_CONN, SG_TOO_MANY, SG_BAD_ENDPOINT, SG_BAD_SAMPLE = 1, 2, 4, 8
+_SG_CAUSES = (
+    (SG_BAD_CONN, "a conn_id is not finite or lies beyond +-2^53"),
+    (SG_TOO_MANY, f"a sample holds more than {MAX_LIGHTPATHS} lightpaths (the cap of the device builder)"),
+    (SG_BAD_ENDPOINT, f"a src_id / dst_id is not an integer in 1 .. {NUM_TOPOLOGY_NODES}"),
+    (SG_BAD_SAMPLE, "a sample number lies outside the status chunk"),
+)
+
+
+def _column_tables(st: DeviceStatus, representation: str, features_to_consider: Sequence[str]):
+    """The two column tables of ``qot_status_graph_fill`` on the device: one row ``(lp_feat row, min, max - min,
+    has_range)`` per output column in sorted name order (``is_lut``: row -1), and the same over ``target``."""
+    import torch
+    from .dataset import FEATURE_RANGES, TARGET_KEYS, TARGET_RANGES
+    key = (representation, tuple(features_to_consider))
+    if key not in st._tables:
+        feats = sorted(features_to_consider)
+        names = sorted(feats + ["is_lut"]) if representation == "lightpath" else feats
+        fi = st.feature_indexes
+
+        def row(index, r):
+            if r is None:
+                return [float(index), 0.0, 1.0, 0.0]
+            return [float(index), float(r["min"]), float(r["max"] - r["min"]), 1.0]
+
+        cols = [row(-1, None) if (n == "is_lut" and representation == "lightpath") else row(fi[n], FEATURE_RANGES.get(n))
+                for n in names]
+        tcols = [row(st.metric.index(k) if k in st.metric else -1, TARGET_RANGES[k]) for k in TARGET_KEYS]
+        up = lambda rows: torch.tensor(rows, dtype=torch.float64).reshape(len(rows), 4).to(st.device)
+        st._tables[key] = (up(cols), up(tcols), len(names))
+    return st._tables[key]
+
+
+def _device_build(st: DeviceStatus, representation: str, features_to_consider: Sequence[str],
+                  samples: Optional[Sequence[int]], freq_threshold: float):
+    """``csrc/status_graph.hip`` over the samples of a resident chunk: count launch, ONE host read (status word, self-loop
+    flag, per-graph node and link counts), fill launch.  There is no CPU form of this path."""
+    import torch
+    from . import _lib
+    from .loader import PackedGraphs
+    if representation not in ("lightpath", "topological"):
+        raise ValueError("representation must be 'lightpath' or 'topological'")
+    _lib.load()
+    if not st.data.is_cuda:
+        raise _lib.QotError("the device graph builder needs a status chunk on the GPU, got CPU tensors: there is no CPU "
+                            "form of it (the host path is build_shard(..., device=None))")
+    dev = st.device
+    S, P, L, Q = (int(v) for v in st.data.shape)
+    fi = st.feature_indexes
+    lightpath = representation == "lightpath"
+    rep = 0 if lightpath else 1
+    conn_row = fi["conn_id"]
+    src_row, dst_row = (-1, -1) if lightpath else (fi["src_id"], fi["dst_id"])
+    osnr_row, snr_row, ber_row = (fi["osnr"], fi["snr"], fi["ber"]) if lightpath else (-1, -1, -1)
+    cols, tcols, ncol = _column_tables(st, representation, list(features_to_consider))
+    if Q > MAX_FREQS:
+        raise _lib.QotError(f"the device graph builder takes at most {MAX_FREQS} frequency slots per link, got {Q}")
+    with torch.cuda.device(dev):
+        if samples is None:
+            G, picks = S, None
+        else:
+            picks = torch.tensor([int(v) for v in samples], dtype=torch.long).to(dev)
+            G = int(picks.numel())
+        info = torch.zeros(2 + 2 * G, dtype=torch.int32, device=dev)
+        nbytes = int(_lib.load().qot_status_graph_scratch_bytes(G, L, Q, rep))
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        _lib.call("qot_status_graph_count", st.data, st.freq, picks, G, S, P, L, Q, conn_row, src_row, dst_row,
+                  float(freq_threshold), rep, scratch, nbytes, info)
+        host = info.cpu()                                    # the one device -> host read of the call
+        code = int(host[0])
+        if code:
+            raise _lib.QotError("qot_status_graph: " + "; ".join(t for bit, t in _SG_CAUSES if code & bit) +
+                                ": no graph was built")
+        counts = host[2:].view(G, 2).to(torch.long)
+        zero = torch.zeros(1, dtype=torch.long)
+        node_ptr = torch.cat([zero, counts[:, 0].cumsum(0)])
+        edge_ptr = torch.cat([zero, counts[:, 1].cumsum(0)])
+        N, E = int(node_ptr[-1]), int(edge_ptr[-1])
+        dcounts = info[2:].view(G, 2).to(torch.long)
+        dzero = torch.zeros(1, dtype=torch.long, device=dev)
+        node_ptr_dev = torch.cat([dzero, dcounts[:, 0].cumsum(0)])
+        edge_ptr_dev = torch.cat([dzero, dcounts[:, 1].cumsum(0)])
+        edge_index = torch.empty(2, E, dtype=torch.long, device=dev)
+        feat = torch.empty(N if lightpath else E, ncol, dtype=torch.float32, device=dev)
+        node_ids = None if lightpath else torch.empty(N, dtype=torch.long, device=dev)
+        y = torch.empty(G, 3, dtype=torch.float32, device=dev)
+        _lib.call("qot_status_graph_fill", st.data, st.target, picks, G, S, P, L, Q, int(st.target.shape[1]), osnr_row,
+                  snr_row, ber_row, cols, ncol, tcols, rep, scratch, info, node_ptr_dev, edge_ptr_dev, N, E, edge_index,
+                  feat, node_ids, y)
+        if lightpath:
+            out = PackedGraphs(node_ptr, edge_ptr, edge_index, None, None, feat, y, None)
+        else:
+            out = PackedGraphs(node_ptr, edge_ptr, edge_index, feat, node_ids, None, y.view(-1),
+                               NUM_TOPOLOGY_NODES if G else None)
+        out.has_self_loops = bool(host[1])
+        out.graph_of_node = torch.repeat_interleave(torch.arange(G, device=dev), dcounts[:, 0], output_size=N)
+        out.node_ptr_dev, out.edge_ptr_dev = node_ptr_dev, edge_ptr_dev
+        out.device = dev
+        out._batch_cache = {}
+    return out
+
+
+def device_batch(status: DeviceStatus, representation: str, features_to_consider: Sequence[str] = DEFAULT_FEATURES,
+                 samples: Optional[Sequence[int]] = None, freq_threshold: float = 0.05):
+    """The chosen samples of a resident chunk as one ``Batch`` on the device, with the fields ``PackedGraphs.device_batch``
+    sets: what the models and the single-launch predictors take."""
+    if not isinstance(status, DeviceStatus):
+        raise TypeError("device_batch takes a DeviceStatus (NetworkStatus.to_device)")
+    shard = _device_build(status, representation, features_to_consider, samples, freq_threshold)
+    return shard.device_batch(0, len(shard))
+
+
+def canonical_link_order(edge_index, edge_ptr, edge_attr=None):
+    """The directed links of a shard in the device builder's order: graphs as they are, inside a graph ascending by
+    ``(edge_index[0], edge_index[1])``.  The host builder's order inside a graph follows networkx's adjacency (grouped by
+    source, targets in insertion order); this keeps the grouping by graph and by source.  Returns the reordered
+    ``edge_index``, or ``(edge_index, edge_attr)`` when ``edge_attr`` is given (its rows follow their links).  Pure host
+    function; the inputs are not modified."""
+    import torch
+    E = edge_index.shape[1]
+    counts = (edge_ptr[1:] - edge_ptr[:-1]).to(torch.long)
+    if int(edge_ptr[-1]) - int(edge_ptr[0]) != E:
+        raise ValueError("edge_ptr does not cover edge_index")
+    graph = torch.repeat_interleave(torch.arange(counts.numel()), counts)
+    perm = torch.argsort(edge_index[1], stable=True)
+    perm = perm[torch.argsort(edge_index[0][perm], stable=True)]
+    perm = perm[torch.argsort(graph[perm], stable=True)]
+    ei = edge_index[:, perm].contiguous()
+    if edge_attr is None:
+        return ei
+    return ei, edge_attr[perm].contiguous()
+
+
+def canonical_shard(shard):
+    """A host shard with its links in canonical order (``canonical_link_order``); everything else is shared."""
+    from .loader import PackedGraphs
+    if shard.edge_attr is None:
+        ei, ea = canonical_link_order(shard.edge_index, shard.edge_ptr), None
+    else:
+        ei, ea = canonical_link_order(shard.edge_index, shard.edge_ptr, shard.edge_attr)
+    return PackedGraphs(shard.node_ptr, shard.edge_ptr, ei, ea, shard.node_ids, shard.x, shard.y, shard.uniform_node_ids)
 
 
 # ------------------------------------------------------------------------------------------ .nc-free sample generator
@@ -282,7 +478,15 @@ def main(argv=None):
     ap.add_argument("--representation", default="lightpath", choices=["lightpath", "topological"])
     ap.add_argument("--storage_type", default="pickle", choices=["pickle", "gexf"])
     ap.add_argument("--directory", default=None)
+    ap.add_argument("--shard", default=None, help="write one PackedGraphs shard file (dataset.save_shard) instead of graph files")
+    ap.add_argument("--device", default=None, help="with --shard: build the shard on this device (e.g. cuda)")
     args = ap.parse_args(argv)
+    if args.shard is not None:
+        from .dataset import save_shard
+        shard = build_shard(args.dataset, args.representation, device=args.device)
+        save_shard(args.shard, shard, {"representation": args.representation, "features": sorted(DEFAULT_FEATURES)})
+        print(f"Shard of {len(shard)} graphs stored in {args.shard}")
+        return
     d = store_graphs(args.dataset, args.representation, args.directory, storage_type=args.storage_type)
     print(f"Graphs stored in {d}")
 

@@ -845,6 +845,54 @@ int qot_lightpath_infer(const float* x, const int64_t* edge_index, const int64_t
                         float* out, int32_t* count, int F, int C, int O, int heads, int lut_col, int32_t* status,
                         qot_stream_t stream);
 
+/* ---- graph construction from network-status samples (csrc/status_graph.hip) ----------------
+ * data [S, P, L, Q] fp64 (sample, lp_feat, link, freq), target [S, M] fp64, freq [Q] fp64, all on the device.  samples
+ * [G] int64 picks the samples of the call, in order, repeats allowed (NULL: samples 0 .. G-1).  One workgroup per
+ * sample.  A channel (l, q) is occupied when any of its P values != 0 (a NaN counts); scan order is l * Q + q; the
+ * lightpaths are the distinct trunc(conn_id) values, attributes from the first occupied channel of each.
+ *
+ *   QOT_SG_LIGHTPATH    nodes = lightpaths in first-seen order; a -- b when a link that carries at least two lightpaths
+ *                       has an occupied channel of each with 0 < |freq[q1] - freq[q2]| < freq_threshold (fp64); a == b
+ *                       gives one self loop.
+ *   QOT_SG_TOPOLOGICAL  75 nodes; one link per unordered {src_id - 1, dst_id - 1} pair, carrying the features of the
+ *                       lightpath with the largest conn of the pair.
+ * Directed links of a graph are sorted by (source, target); both directions of a link, a self loop once.
+ *
+ * qot_status_graph_count writes info [2 + 2 G] int32 (caller-zeroed): info[0] the status word (QOT_SG_BAD_*, OR-ed over
+ * the samples), info[1] != 0 when some graph has a self loop, info[2 + 2 g] / info[3 + 2 g] nodes / directed links of
+ * graph g; and the scratch (qot_status_graph_scratch_bytes, 16-byte aligned) that qot_status_graph_fill reads.  The host
+ * reads info once, forms the exclusive prefix sums node_ptr / edge_ptr [G + 1] int64 (device copies are passed to fill)
+ * and allocates the outputs.  Nothing read from data is used as an index unchecked; fill writes nothing for a graph
+ * whose offsets do not match info.
+ *
+ * qot_status_graph_fill: cols [ncol, 4] fp64, one row per output column: (lp_feat row, min, max - min, has_range); row
+ * -1 (lightpath only) is the is_lut column, 1.0f iff osnr == snr == ber == -1 on the first channel.  tcols [3, 4]
+ * likewise over the columns of target (-1: absent, reads 0.0).  A column is ((v - min) / (max - min)) in fp64 rounded
+ * once to fp32, or v rounded to fp32 without a range.  Outputs: edge_index [2, e_total] int64 (shard numbering), feat =
+ * x [n_total, ncol] (lightpath) or edge_attr [e_total, ncol] (topological), node_ids [n_total] int64 (topological
+ * only), y [G, 3].
+ *
+ * Envelope: any L, P, S with L * Q < 2^31; Q <= QOT_SG_MAX_FREQS (QOT_ERR_UNSUPPORTED above); at most
+ * QOT_SG_MAX_LIGHTPATHS lightpaths per sample (QOT_SG_TOO_MANY in the status word above). */
+#define QOT_SG_LIGHTPATH 0
+#define QOT_SG_TOPOLOGICAL 1
+#define QOT_SG_MAX_FREQS 1024
+#define QOT_SG_MAX_LIGHTPATHS 256
+#define QOT_SG_NODES 75
+#define QOT_SG_BAD_CONN 1      /* conn_id not finite or beyond +-2^53 */
+#define QOT_SG_TOO_MANY 2      /* more than QOT_SG_MAX_LIGHTPATHS lightpaths in a sample */
+#define QOT_SG_BAD_ENDPOINT 4  /* topological: src_id / dst_id outside 1 .. 75 or not integral */
+#define QOT_SG_BAD_SAMPLE 8    /* sample number outside [0, S) */
+size_t qot_status_graph_scratch_bytes(int64_t G, int64_t L, int64_t Q, int representation);
+int qot_status_graph_count(const double* data, const double* freq, const int64_t* samples, int64_t G, int64_t S, int P,
+                           int64_t L, int64_t Q, int conn_row, int src_row, int dst_row, double freq_threshold,
+                           int representation, void* scratch, size_t scratch_bytes, int32_t* info, qot_stream_t stream);
+int qot_status_graph_fill(const double* data, const double* target, const int64_t* samples, int64_t G, int64_t S, int P,
+                          int64_t L, int64_t Q, int M, int osnr_row, int snr_row, int ber_row, const double* cols, int ncol,
+                          const double* tcols, int representation, const void* scratch, const int32_t* info,
+                          const int64_t* node_ptr, const int64_t* edge_ptr, int64_t n_total, int64_t e_total,
+                          int64_t* edge_index, float* feat, int64_t* node_ids, float* y, qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
