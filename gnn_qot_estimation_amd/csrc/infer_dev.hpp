@@ -1,0 +1,320 @@
+// Device pieces of the single-launch TopologicalGNN forward, shared by the eval kernel (infer.hip) and
+// the Monte-Carlo dropout kernel (infer_mc.hip): the LDS layout, the argument block and the two halves of
+// a workgroup's work on ONE graph --
+//   infer_phases12: index, edge MLP hidden layer, TransformerConv + leaky_relu -> the undropped x1 in LDS
+//   infer_phases34: NNConv (mean) in row tiles + leaky_relu, pooled on the fly, mean pool, read-out MLP -> one output row
+// The second half is a template on MC: false compiles the eval forward (no dropout code at all), true applies the engine's
+// counter-based dropout (common.hpp: act_hash64) behind conv2's leaky_relu and inside the read-out; conv1's dropout is a
+// masked copy of x1 the caller hands in as `xin`.  Every sum runs in the same order in both.
+#pragma once
+#include "graph_prep_dev.hpp"
+
+namespace qot {
+
+constexpr int kInferThreads = 256;
+constexpr int kInferMaxN = 128;                       // local node ids are packed 16 + 16 bits; one softmax thread per row
+constexpr size_t kInferLdsMax = 160 * 1024 - 2048;    // the CU's LDS less the static words of the block scan and flags
+
+__host__ __device__ constexpr int infer_rpt(int H) { return H == 64 ? 4 : 2; }                 // rows per thread of A Wcat
+__host__ __device__ constexpr int infer_tile_rows(int H) { return infer_rpt(H) * (kInferThreads / H); }
+__host__ __device__ constexpr int infer_pad4(int v) { return (v + 3) & ~3; }
+
+// 4-byte word offsets of the LDS image for graphs of at most cap_n nodes / cap_m edges: the ONE statement of the budget
+// (the kernels, the entry points and qot_topological_infer[_mc]_supported all read it).  mc: the Monte-Carlo kernel's
+// variant -- the eval image, unchanged, followed by x1d, the sample's masked copy of x1 (cap_n * H more words).
+struct InferLds {
+    int atile, x1, ea, he, alpha, ends, key, cin, rp, lnid, part, pooled, h1, x1d, words;
+};
+__host__ __device__ inline InferLds infer_lds(int cap_n, int cap_m, int H, int D, bool mc = false) {
+    const int K = 2 * D;
+    InferLds L;
+    int o = 0;
+    L.atile = o;  o += infer_tile_rows(H) * (K + 2) * H;       // [R][(K + 2) H], rows 16-byte aligned
+    L.x1 = o;     o += infer_pad4(cap_n * H);                  // first convolution's output
+    L.ea = o;     o += infer_pad4(cap_m * D);                  // edge features, edge order
+    L.he = o;     o += infer_pad4(cap_m * K);                  // edge MLP hidden layer, edge order
+    L.alpha = o;  o += cap_m;                                  // placement rank, then logits / attention weights per slot
+    L.ends = o;   o += cap_m;                                  // local source << 16 | local destination, edge order
+    L.key = o;    o += cap_m;                                  // edge of every slot
+    L.cin = o;    o += cap_n;
+    L.rp = o;     o += cap_n + 1;
+    L.lnid = o;   o += cap_n;
+    o = infer_pad4(o);
+    L.part = o;   o += kInferThreads;                          // pool shares of the row groups
+    L.pooled = o; o += H;
+    L.h1 = o;     o += H;
+    L.x1d = o;    if (mc) o += infer_pad4(cap_n * H);          // 16-byte aligned: everything above ends on a multiple of 4
+    L.words = o;
+    return L;
+}
+
+struct InferArgs {
+    const int64_t* node_ids; const int64_t* ei; const float* edge_attr; const int64_t* node_ptr; const int64_t* edge_ptr;
+    int64_t N, E, B;
+    int cap_n, cap_m;
+    const float* t4; int ld4; const float* M; int ldm; const float* P; int V;
+    const float* w_edge; const float* w1; const float* b1; const float* wcat; const float* bias2;
+    const float* w0; const float* b0; const float* w3; const float* b3;
+    float slope_conv, slope_head;
+    float* out; int O;
+    int32_t* status;
+};
+
+// the dropout of one Monte-Carlo sample (include/qot_gnn.h: keep = hash(site seed, step, flat element) >= thr16)
+struct InferDrop {
+    uint64_t seed_conv2, seed_head, step;
+    uint32_t thr_conv, thr_head;        // 0: that site keeps everything and multiplies nothing
+    float scale_conv, scale_head;       // 1 / (1 - p) in fp32
+    uint64_t row0, graph;               // the graph's first row in the batch's [N, H] activation; its row of [B, H]
+};
+
+__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : slope * v; }
+
+// dropout of the already activated value y, element `flat` of its activation: act_apply1's rule (common.hpp)
+__device__ __forceinline__ float infer_drop1(float y, uint64_t seed, uint64_t step, uint64_t flat, uint32_t thr16,
+                                             float scale) {
+    if (thr16) {
+        const uint64_t z = act_hash64(seed, step, flat >> 2);
+        const bool keep = ((uint32_t)(z >> (16 * (flat & 3))) & 0xFFFFu) >= thr16;
+        y = keep ? y * scale : 0.f;
+    }
+    return y;
+}
+
+// the graph's slices lie inside the arrays and inside the LDS image the host sized
+__device__ __forceinline__ bool infer_slices_ok(const InferArgs& a, int64_t n0, int64_t e0, int64_t nn, int64_t mm) {
+    return !(nn < 0 || mm < 0 || nn > a.cap_n || mm > a.cap_m || n0 < 0 || e0 < 0 || n0 + nn > a.N || e0 + mm > a.E);
+}
+
+// ---- phases 1 and 2 of graph [n0, n0 + n) / [e0, e0 + m): returns 0 with x1, he, rp, key, ends in LDS, or the status bits
+// of a breach (uniform over the workgroup; the image is then unusable and the caller writes NaN)
+template <int H, int D>
+__device__ __forceinline__ int infer_phases12(const InferArgs& a, float* lds, const InferLds& L, int64_t n0, int64_t e0,
+                                              int n, int m) {
+    constexpr int NT = kInferThreads;
+    constexpr int K = 2 * D;
+    __shared__ int s_bad;
+    const int tid = threadIdx.x;
+    float* x1 = lds + L.x1;
+    float* ea = lds + L.ea;
+    float* he = lds + L.he;
+    float* alpha = lds + L.alpha;
+    int* rank = reinterpret_cast<int*>(lds + L.alpha);
+    unsigned int* ends = reinterpret_cast<unsigned int*>(lds + L.ends);
+    int* key = reinterpret_cast<int*>(lds + L.key);
+    int* cin = reinterpret_cast<int*>(lds + L.cin);
+    int* rp = reinterpret_cast<int*>(lds + L.rp);
+    int* lnid = reinterpret_cast<int*>(lds + L.lnid);
+
+    // ---- phase 1: the graph's image and index ----
+    if (tid == 0) s_bad = 0;
+    int bad = 0;
+    for (int t = tid; t < n; t += NT) {
+        int64_t id = a.node_ids[n0 + t];
+        if (id < 0 || id >= a.V) { bad |= 4; id = 0; }
+        lnid[t] = (int)id;
+        cin[t] = 0;
+    }
+    for (int c = tid; c < m * D; c += NT) ea[c] = a.edge_attr[e0 * D + c];
+    __syncthreads();
+    for (int e = tid; e < m; e += NT) {
+        int j = (int)(a.ei[e0 + e] - n0), i = (int)(a.ei[a.E + e0 + e] - n0);
+        if (i < 0 || i >= n || j < 0 || j >= n) { bad |= 1; continue; }      // (the workgroup leaves below: nothing reads it)
+        ends[e] = ((unsigned int)j << 16) | (unsigned int)i;
+        rank[e] = atomicAdd(&cin[i], 1);
+        float f[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) f[d] = ea[e * D + d];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float h = a.b1[k];
+#pragma unroll
+            for (int d = 0; d < D; ++d) h = fmaf(a.w1[k * D + d], f[d], h);
+            he[e * K + k] = h > 0.f ? h : 0.f;
+        }
+    }
+    if (bad) atomicOr(&s_bad, bad);
+    __syncthreads();
+    if (s_bad) return s_bad;                                          // (uniform: every thread reads the same word)
+    block_scan_into<NT>(cin, rp, n);
+    for (int e = tid; e < m; e += NT) key[rp[ends[e] & 0xFFFFu] + rank[e]] = e;
+    __syncthreads();
+    for (int r = tid; r < n; r += NT) sort_row_keys(key, rp[r], rp[r + 1]);
+    __syncthreads();
+
+    // ---- phase 2: TransformerConv + leaky_relu ----
+    for (int p = tid; p < m; p += NT) {
+        const int e = key[p];
+        const unsigned int ji = ends[e];
+        const int idi = lnid[ji & 0xFFFFu], idj = lnid[ji >> 16];
+        float l = a.M[(int64_t)idi * a.ldm + idj];
+#pragma unroll
+        for (int d = 0; d < D; ++d) l = fmaf(a.P[(int64_t)idi * D + d], ea[e * D + d], l);
+        alpha[p] = l;
+    }
+    __syncthreads();
+    for (int r = tid; r < n; r += NT) {
+        const int beg = rp[r], end = rp[r + 1];
+        if (beg == end) continue;
+        float mx = alpha[beg];
+        for (int p = beg + 1; p < end; ++p) mx = fmaxf(mx, alpha[p]);
+        float s = 0.f;
+        for (int p = beg; p < end; ++p) {
+            const float ex = expf(alpha[p] - mx);
+            alpha[p] = ex;
+            s += ex;
+        }
+        s += 1e-16f;
+        for (int p = beg; p < end; ++p) alpha[p] = alpha[p] / s;
+    }
+    __syncthreads();
+    {
+        const float* tv = a.t4 + 2 * H;
+        const float* ts = a.t4 + 3 * H;
+        for (int idx = tid; idx < n * H; idx += NT) {
+            const int r = idx / H, c = idx % H;
+            const int beg = rp[r], end = rp[r + 1];
+            float acc = 0.f;
+            float aa[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) aa[d] = 0.f;
+#pragma unroll 4
+            for (int p = beg; p < end; ++p) {
+                const int e = key[p];
+                const float al = alpha[p];
+                acc = fmaf(al, tv[(int64_t)lnid[ends[e] >> 16] * a.ld4 + c], acc);
+#pragma unroll
+                for (int d = 0; d < D; ++d) aa[d] = fmaf(al, ea[e * D + d], aa[d]);
+            }
+#pragma unroll
+            for (int d = 0; d < D; ++d) acc = fmaf(a.w_edge[c * D + d], aa[d], acc);
+            acc += ts[(int64_t)lnid[r] * a.ld4 + c];
+            x1[idx] = leaky(acc, a.slope_conv);
+        }
+    }
+    __syncthreads();
+    return 0;
+}
+
+// ---- phases 3 and 4 on the first convolution's output `xin` [n, H] (LDS: x1 itself, or a sample's masked copy of it):
+// writes orow[0 .. O).  Ends without a barrier; the LDS it wrote last (h1) is not written again before three barriers of
+// the next call.
+template <int H, int D, bool MC>
+__device__ __forceinline__ void infer_phases34(const InferArgs& a, float* lds, const InferLds& L, int n, const float* xin,
+                                               float* orow, const InferDrop& dr) {
+    constexpr int NT = kInferThreads;
+    constexpr int K = 2 * D, KT = (K + 2) * H;
+    constexpr int RPT = infer_rpt(H), R = infer_tile_rows(H);
+    const int tid = threadIdx.x;
+    float* atile = lds + L.atile;
+    const float* he = lds + L.he;
+    const unsigned int* ends = reinterpret_cast<const unsigned int*>(lds + L.ends);
+    const int* key = reinterpret_cast<const int*>(lds + L.key);
+    const int* rp = reinterpret_cast<const int*>(lds + L.rp);
+    float* part = lds + L.part;
+    float* pooled = lds + L.pooled;
+    float* h1 = lds + L.h1;
+
+    // ---- phase 3: NNConv (mean) + leaky_relu, pooled on the fly ----
+    const int o = tid % H, rg = tid / H;
+    const float bias_o = a.bias2[o];
+    float pool = 0.f;
+    for (int r0 = 0; r0 < n; r0 += R) {
+        for (int idx = tid; idx < R * (K + 1) * H; idx += NT) {
+            const int rr = idx / ((K + 1) * H), rem = idx % ((K + 1) * H);
+            const int k = rem / H, c = rem % H;
+            const int r = r0 + rr;
+            float v = 0.f;
+            if (r < n) {
+                const int beg = rp[r], end = rp[r + 1];
+                for (int p = beg; p < end; ++p) {
+                    const int e = key[p];
+                    const float xj = xin[(ends[e] >> 16) * H + c];
+                    v = k < K ? fmaf(he[e * K + k], xj, v) : v + xj;
+                }
+                if (end - beg > 1) v = v / (float)(end - beg);
+            }
+            atile[rr * KT + rem] = v;
+        }
+        for (int idx = tid; idx < R * H; idx += NT) {
+            const int rr = idx / H, c = idx % H;
+            atile[rr * KT + (K + 1) * H + c] = r0 + rr < n ? xin[(r0 + rr) * H + c] : 0.f;
+        }
+        __syncthreads();
+        float acc[RPT];
+#pragma unroll
+        for (int u = 0; u < RPT; ++u) acc[u] = 0.f;
+        const float* arow = atile + rg * RPT * KT;
+        const float* wcol = a.wcat + o;
+#pragma unroll 2
+        for (int kk = 0; kk < KT; kk += 4) {
+            const float w0 = wcol[(kk + 0) * H], w1 = wcol[(kk + 1) * H], w2 = wcol[(kk + 2) * H], w3 = wcol[(kk + 3) * H];
+#pragma unroll
+            for (int u = 0; u < RPT; ++u) {
+                const float4 av = *reinterpret_cast<const float4*>(arow + u * KT + kk);
+                acc[u] = fmaf(av.x, w0, acc[u]);
+                acc[u] = fmaf(av.y, w1, acc[u]);
+                acc[u] = fmaf(av.z, w2, acc[u]);
+                acc[u] = fmaf(av.w, w3, acc[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RPT; ++u)
+            if (r0 + rg * RPT + u < n) {
+                float y = leaky(acc[u] + bias_o, a.slope_conv);
+                if constexpr (MC)
+                    y = infer_drop1(y, dr.seed_conv2, dr.step, (dr.row0 + (uint64_t)(r0 + rg * RPT + u)) * H + o, dr.thr_conv,
+                                    dr.scale_conv);
+                pool += y;
+            }
+        __syncthreads();
+    }
+
+    // ---- phase 4: mean pool and the read-out MLP ----
+    part[tid] = pool;                                   // [rg][o]
+    __syncthreads();
+    if (tid < H) {
+        float s = 0.f;
+#pragma unroll
+        for (int g = 0; g < NT / H; ++g) s += part[g * H + tid];
+        pooled[tid] = n > 0 ? s / (float)n : 0.f;
+    }
+    __syncthreads();
+    if (tid < H) {
+        float s = a.b0[tid];
+        const float* w = a.w0 + tid * H;
+#pragma unroll 8
+        for (int c = 0; c < H; ++c) s = fmaf(w[c], pooled[c], s);
+        float y = leaky(s, a.slope_head);
+        if constexpr (MC) y = infer_drop1(y, dr.seed_head, dr.step, dr.graph * H + tid, dr.thr_head, dr.scale_head);
+        h1[tid] = y;
+    }
+    __syncthreads();
+    if (tid < a.O) {
+        float s = a.b3[tid];
+        const float* w = a.w3 + tid * H;
+#pragma unroll 8
+        for (int c = 0; c < H; ++c) s = fmaf(w[c], h1[c], s);
+        orow[tid] = s;
+    }
+}
+
+static inline bool infer_shape_ok(int H, int D, int O) {
+    return (H == 16 || H == 32 || H == 64) && D >= 1 && D <= 4 && O >= 1 && O <= 8;
+}
+
+// the pointer / size checks both entry points make (QOT_OK or the error to return)
+static inline int infer_args_check(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                                   const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, const float* t4,
+                                   int ld4, const float* M, int ldm, const float* P, int V, const float* w_edge,
+                                   const float* w1, const float* b1, const float* wcat, const float* bias2, const float* w0,
+                                   const float* b0, const float* w3, const float* b3, const float* out, int H) {
+    if (ld4 < 4 * H || (ld4 & 3) || ldm < V) return QOT_ERR_BADARG;
+    if (!node_ptr || !edge_ptr || !t4 || !M || !P || !w_edge || !w1 || !b1 || !wcat || !bias2 || !w0 || !b0 || !w3 || !b3 ||
+        !out)
+        return QOT_ERR_BADARG;
+    if ((N > 0 && !node_ids) || (E > 0 && (!edge_index || !edge_attr))) return QOT_ERR_BADARG;
+    return QOT_OK;
+}
+
+}  // namespace qot

@@ -870,7 +870,8 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
              batch_size: int = 512, output_dim: int = 3, device="cuda",
              output_keys: Sequence[str] = ("osnr", "snr", "ber"),
              target_ranges: Dict[str, Dict[str, float]] = TARGET_RANGES, return_predictions: bool = False,
-             fused: bool = False, predictor: Optional[Callable] = None):
+             fused: bool = False, predictor: Optional[Callable] = None, mc_samples: Optional[int] = None,
+             mc_p=None, mc_seed: Optional[int] = None):
     """test.py's metric block: per-output R2 and MSE on min-max descaled values (test.py:76-121).
 
     ``fused=True`` (opt-in, ``kind="topological"`` on one process; ``ValueError`` otherwise or when the model or a batch
@@ -886,8 +887,16 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
 
     ``return_predictions``: also return ``(y_true_descaled, y_pred_descaled, skipped_graphs)`` -- the arrays test.py
     writes to ``y_true_descaled.json`` / ``y_pred_descaled.json`` (test.py:92-103,129-136), in dataset order; they stay
-    on the device until the loop is over (one host copy)."""
+    on the device until the loop is over (one host copy).
+
+    ``mc_samples=T`` (with ``fused=True`` only, ``ValueError`` otherwise): every batch additionally runs
+    ``TopologicalPredictor.sample(data, T, p=mc_p, seed=mc_seed)`` (Monte-Carlo dropout) and the result
+    gains a LAST element ``y_pred_std_descaled [graphs, outputs]``: the per-graph standard deviation of the draws times
+    ``max - min`` of the output (a spread: no offset), in dataset order.  The predictions and metrics stay the eval-mode
+    ones.  ``mc_p=None``: the model's own dropout probabilities (a model rebuilt for testing has 0: say 0.5)."""
     rank, world = _rank_world()
+    if mc_samples is not None and not fused:
+        raise ValueError("evaluate(mc_samples=...) needs fused=True (TopologicalPredictor.sample)")
     if fused and kind != "topological":
         raise ValueError(f"evaluate(fused=True) is for kind='topological' only, got kind={kind!r}")
     if fused and world > 1:
@@ -906,12 +915,13 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
         from .infer import TopologicalPredictor
         predictor = TopologicalPredictor(model)
         fwd = lambda _model, data, out_dim: (predictor(data), data.y.view(-1, out_dim))      # noqa: E731
+        sampler = predictor
     elif predictor is not None:
         kind_fwd, call = _KINDS[kind], predictor
         fwd = lambda _model, data, out_dim: kind_fwd(call, data, out_dim)                   # noqa: E731
     loader = GraphLoader(dataset, batch_size, shuffle=False, device=device,
                          batches=_local_batches(idx, batch_size, rank, world, _graph_costs(dataset, idx)))
-    kept, skipped = [], 0
+    kept, skipped, stds = [], 0, []
     # Under data parallelism a rank sees only its share of every global batch.  The reference decides "no LUT node in the
     # batch" (lightpath_training/test.py:82-85) on the WHOLE batch, so a share without LUT rows contributes zero rows
     # (allow_empty_lut) and the skip is decided afterwards from the row counts of all ranks, per global batch.
@@ -945,6 +955,8 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
             stats.update(y, out)
             if return_predictions:
                 kept.append((b, y.detach().clone(), out.detach().clone()))
+            if mc_samples is not None:
+                stds.append(sampler.sample(data, mc_samples, p=mc_p, seed=mc_seed)[1])
     if sharded_lut:
         everyone = [None] * world
         dist.all_gather_object(everyone, shares)
@@ -960,8 +972,12 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
     scale = torch.tensor([target_ranges[k]["max"] - target_ranges[k]["min"] for k in keys], dtype=torch.float64)
     res = stats.result(scale)
     metrics = {k.upper(): {"R2": res["r2_raw"][i], "Test_MSE": res["mse_raw"][i]} for i, k in enumerate(keys)}
+    extra = ()
+    if mc_samples is not None:
+        std = torch.cat([t.cpu().double() for t in stds]) if stds else torch.zeros(0, output_dim, dtype=torch.float64)
+        extra = (std * scale,)                            # a spread descales by the range alone
     if not return_predictions:
-        return metrics
+        return (metrics,) + extra if extra else metrics
     parts = [(b, rank, y.cpu(), o.cpu()) for b, y, o in kept]
     if world > 1:
         gathered = [None] * world
@@ -972,7 +988,7 @@ def evaluate(model, dataset, indices: Optional[Sequence[int]] = None, *, kind: s
     cat = lambda j: (torch.cat([p[j].double() for p in parts]) if parts else torch.zeros(0, output_dim, dtype=torch.float64))
     y_true = cat(2) * scale + lo                      # min_max_descale (test.py:12-13)
     y_pred = cat(3) * scale + lo
-    return metrics, y_true, y_pred, skipped
+    return (metrics, y_true, y_pred, skipped) + extra
 
 
 def next_model_path(root_dir: str) -> Tuple[str, int]:

@@ -1,5 +1,5 @@
-"""Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``) and ``LightpathPredictor``
-(``csrc/infer_lightpath.hip``).
+"""Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``; its Monte-Carlo dropout
+``sample``: ``csrc/infer_mc.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``).
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
 TransformerConv, the NNConv forward and the read-out kernel (``LightpathGNN``: the self-looped graph index, the GAT walk
@@ -39,6 +39,57 @@ def wcat_index(h: int, k: int, device) -> torch.Tensor:
 def edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
     """Most edges a graph may have beside ``n_max`` nodes (the kernel's LDS budget, asked of the library); -1: none."""
     return int(_lib.load().qot_topological_infer_max_edges(int(n_max), int(hidden), int(edge_dim)))
+
+
+def mc_edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
+    """``edge_cap`` of the sampling kernel (``TopologicalPredictor.sample``): lower, its LDS image also holds the sample's
+    masked copy of the first convolution's output; -1: none."""
+    return int(_lib.load().qot_topological_infer_mc_max_edges(int(n_max), int(hidden), int(edge_dim)))
+
+
+MC_MAX_SAMPLES = 4096           # csrc/infer_mc.hip: T
+
+
+def mc_chunk(num_graphs: int, samples: int, compute_units: int) -> int:
+    """Samples per workgroup of ``qot_topological_infer_mc``'s grid ``(B, ceil(T / chunk))``.  The grid is that of the
+    largest chunk for which ``B * ceil(T / chunk)`` workgroups still reach the device's compute-unit count (a larger chunk
+    shares phases 1 - 2 among more samples, but leaves units idle); the chunk returned is the smallest with that many
+    workgroups, so that they carry equal shares (T = 32 over 4 workgroups: 8 each, not 10, 10, 10, 2).  1 when no chunk
+    reaches the device.  Pure host arithmetic."""
+    B, T, cus = int(num_graphs), int(samples), int(compute_units)
+    if T < 1:
+        raise ValueError(f"mc_chunk: samples must be >= 1, got {T}")
+    if B < 1 or B * T < cus:
+        return 1
+    need = -(-cus // B)                                    # workgroups per graph that reach the device
+    largest = T if need <= 1 else (T - 1) // (need - 1)    # largest chunk with ceil(T / chunk) >= need
+    chunks = -(-T // largest)
+    return -(-T // chunks)
+
+
+def mc_args(samples, p, chunk, first_step, model_p=(0.0, 0.0)):
+    """The argument checks of ``TopologicalPredictor.sample`` that need no device: returns ``(T, p_conv, p_head, chunk or
+    None, first_step)`` or raises the named ``ValueError``.  ``model_p``: the model's ``(conv, head)`` probabilities, used
+    when ``p`` is ``None``."""
+    who = "TopologicalPredictor.sample"
+    if isinstance(samples, bool) or not isinstance(samples, int) or not 2 <= samples <= MC_MAX_SAMPLES:
+        raise ValueError(f"{who}: samples must be an integer in 2 ... {MC_MAX_SAMPLES}, got {samples!r}")
+    if p is None:
+        pc, ph = model_p
+    elif isinstance(p, (tuple, list)):
+        if len(p) != 2:
+            raise ValueError(f"{who}: p must be a probability or a (conv, head) pair, got {p!r}")
+        pc, ph = p
+    else:
+        pc = ph = p
+    for name, v in (("the convolutions'", pc), ("the read-out's", ph)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) < 1.0:
+            raise ValueError(f"{who}: p must lie in [0, 1), got {v!r} for {name} dropout")
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= samples):
+        raise ValueError(f"{who}: chunk must be an integer in 1 ... samples = {samples}, got {chunk!r}")
+    if isinstance(first_step, bool) or not isinstance(first_step, int) or first_step < 0 or first_step + samples > 1 << 63:
+        raise ValueError(f"{who}: first_step must be an integer >= 0 with first_step + samples <= 2^63, got {first_step!r}")
+    return samples, float(pc), float(ph), chunk, first_step
 
 
 def _i64(t, dev):
@@ -101,6 +152,8 @@ class TopologicalPredictor:
     ``num_layers == 2``, hidden width 16 / 32 / 64 (not a zero-padded one), ``edge_dim <= 4``, at most 8 outputs; a batch
     in table mode (``data.x`` ``None`` or empty) whose graphs have at most 128 nodes and at most ``edge_cap(n_max,
     hidden, edge_dim)`` edges each.  ``node_ids`` outside the embedding table raise ``IndexError`` as the model does.
+
+    ``predictor.sample(data, samples)``: Monte-Carlo dropout, ``samples`` stochastic forwards in one launch (see there).
     """
 
     def __init__(self, model):
@@ -208,8 +261,9 @@ class TopologicalPredictor:
             c["infer_ids_ok"] = tag
 
     # ------------------------------------------------------------------ the call
-    @torch.no_grad()
-    def __call__(self, data):
+    def _prepare(self, data, mc=False):
+        """Everything a launch needs, checked: ``(H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, tables)``.  ``mc``:
+        the envelope of the sampling kernel (``qot_topological_infer_mc``) instead of the eval kernel's."""
         H, D, O = self._check_model()
         m = self.model
         if data.x is not None and data.x.numel():
@@ -218,14 +272,15 @@ class TopologicalPredictor:
         dev = m.node_embeddings.weight.device
         ids, ei, ptr, eptr, n_max, max_e, B, exact = self._slices(data, dev)
         lib = _lib.load()
-        if n_max > MAX_NODES or not lib.qot_topological_infer_supported(n_max, max_e, H, D, O):
+        supported = lib.qot_topological_infer_mc_supported if mc else lib.qot_topological_infer_supported
+        if n_max > MAX_NODES or not supported(n_max, max_e, H, D, O):
             n_max, max_e = exact()          # the carried sizes are bounds (a shard inherits its parent's): look once
             if n_max > MAX_NODES:
                 raise ValueError(f"TopologicalPredictor: a graph of {n_max} nodes; at most {MAX_NODES} nodes per graph")
-            cap = edge_cap(n_max, H, D)
+            cap = (mc_edge_cap if mc else edge_cap)(n_max, H, D)
             if max_e > cap:
-                raise ValueError(f"TopologicalPredictor: a graph of {max_e} edges is above the edge cap {cap} for graphs of "
-                                 f"up to {n_max} nodes at hidden width {H}, edge_dim {D}")
+                raise ValueError(f"TopologicalPredictor: a graph of {max_e} edges is above the {'sampling ' if mc else ''}"
+                                 f"edge cap {cap} for graphs of up to {n_max} nodes at hidden width {H}, edge_dim {D}")
         ea = data.edge_attr
         E = ei.shape[1]
         if ea is None or tuple(ea.shape) != (E, D):
@@ -236,11 +291,55 @@ class TopologicalPredictor:
         self._check_ids(data, ids, t["V"], n_max)
         if self._status is None or self._status.device != dev:
             self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        return H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t
+
+    @torch.no_grad()
+    def __call__(self, data):
+        H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t = self._prepare(data)
         out = torch.empty(B, O, dtype=torch.float32, device=dev)
-        _lib.call("qot_topological_infer", ids, ei, ea, ptr, eptr, ids.shape[0], E, B, n_max, max_e, t["t4"], 4 * H, t["M"],
-                  t["ldm"], t["P"], t["V"], t["we"], t["w1"], t["b1"], t["wcat"], t["bias2"], t["w0"], t["b0"], t["w3"],
-                  t["b3"], 0.01, float(m.mlp[1].negative_slope), out, H, D, O, self._status)
+        _lib.call("qot_topological_infer", ids, ei, ea, ptr, eptr, ids.shape[0], ei.shape[1], B, n_max, max_e, t["t4"], 4 * H,
+                  t["M"], t["ldm"], t["P"], t["V"], t["we"], t["w1"], t["b1"], t["wcat"], t["bias2"], t["w0"], t["b0"], t["w3"],
+                  t["b3"], 0.01, float(self.model.mlp[1].negative_slope), out, H, D, O, self._status)
         return out
+
+    @torch.no_grad()
+    def sample(self, data, samples, *, p=None, seed=None, first_step=0, chunk=None, return_samples=False):
+        """Monte-Carlo dropout: ``samples`` (T) stochastic forwards of the batch in ONE kernel launch; returns ``(mean [B,
+        O], std [B, O])`` over the draws (``std`` unbiased), with ``return_samples=True`` also ``draws [T, B, O]``.
+
+        Draw ``t`` is, by construction, the output of a train-mode forward of the engine on this batch at dropout step
+        ``first_step + t`` with base seed ``seed``: the masks are the engine's pure function of ``(site seed, step, flat
+        element index)`` (``include/qot_gnn.h``; ``oracle/dropout.py`` restates it), nothing is drawn from a generator.  A
+        given ``(batch, seed, first_step, t)`` is therefore bitwise reproducible and does not depend on ``samples`` or
+        ``chunk``.  The element index runs over the BATCH's activations, so a graph's draws depend on its row offset in the
+        batch, as in training: ``__call__``'s batch independence does NOT extend to ``sample``.  With ``p == 0`` every draw
+        equals ``self(data)`` bit for bit.
+
+        ``p``: dropout probability of all three sites, or a ``(convolutions, read-out)`` pair; ``None`` takes
+        ``model.dropout.p`` and ``model.mlp[2].p`` (a model built for testing has 0 there).  ``seed``: ``None`` takes the
+        model's base seed.  ``chunk``: samples per workgroup (grid ``(B, ceil(T / chunk))``); ``None`` asks ``mc_chunk`` with
+        the device's compute-unit count.
+
+        Pure: ``model.training``, the model's dropout counter, its parameters and the tables ``__call__`` relies on are not
+        touched; parameter updates are followed as ``__call__`` follows them.  Refusals (``ValueError`` naming the condition):
+        everything ``__call__`` refuses, ``p`` outside ``[0, 1)``, ``samples`` outside ``2 ... 4096``, ``chunk`` outside ``1 ...
+        samples``, ``first_step < 0`` or ``first_step + samples > 2^63``, a graph above ``mc_edge_cap`` (lower than the eval
+        kernel's: DESIGN.md 4.15).  ``IndexError`` and ``check_status()`` as ``__call__``."""
+        m = self.model
+        T, p_conv, p_head, chunk, first_step = mc_args(samples, p, chunk, first_step,
+                                                        (getattr(getattr(m, "dropout", None), "p", 0.0),
+                                                         getattr(m.mlp[2], "p", 0.0) if hasattr(m, "mlp") else 0.0))
+        H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t = self._prepare(data, mc=True)
+        base = (m._seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+        if chunk is None:
+            chunk = mc_chunk(B, T, torch.cuda.get_device_properties(dev).multi_processor_count)
+        draws = torch.empty(T, B, O, dtype=torch.float32, device=dev)
+        _lib.call("qot_topological_infer_mc", ids, ei, ea, ptr, eptr, ids.shape[0], ei.shape[1], B, n_max, max_e, t["t4"],
+                  4 * H, t["M"], t["ldm"], t["P"], t["V"], t["we"], t["w1"], t["b1"], t["wcat"], t["bias2"], t["w0"], t["b0"],
+                  t["w3"], t["b3"], 0.01, float(m.mlp[1].negative_slope), draws, H, D, O, self._status, T, first_step, base,
+                  p_conv, p_head, chunk)
+        mean, std = draws.mean(0), draws.std(0, unbiased=True)
+        return (mean, std, draws) if return_samples else (mean, std)
 
     def check_status(self):
         """Reads the kernel's status word (one device synchronisation): raises when a batch since the last check had an

@@ -6,6 +6,10 @@ Loads the latest ``<root>/models/model_<k>.pth`` (ours or the reference's: same 
 MSE on descaled values and writes the reference's three JSON files: ``results_metrics.json`` (topological,
 test.py:126-127; ``results.json`` for lightpath, lightpath test.py:137), ``y_true_descaled.json``,
 ``y_pred_descaled.json`` into ``<root>/results/results_<timestamp>[_model_<k>]``.
+
+``--kind topological --fused --mc-samples T [--mc-p P]``: additionally writes ``y_pred_std_descaled.json``, the per-graph
+standard deviation of T Monte-Carlo dropout forwards (``TopologicalPredictor.sample``) times the output's range.  The
+scored predictions stay the eval-mode ones; without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -38,8 +42,15 @@ def main(argv=None):
     ap.add_argument("--fused", action="store_true",
                     help="single-launch inference kernel per batch: harness.evaluate(fused=True) for topological, "
                          "harness.evaluate(predictor=LightpathPredictor(model)) for lightpath")
+    ap.add_argument("--mc-samples", type=int, default=None,
+                    help="topological with --fused: Monte-Carlo dropout forwards per graph; writes y_pred_std_descaled.json")
+    ap.add_argument("--mc-p", type=float, default=0.5,
+                    help="dropout probability of the Monte-Carlo forwards (the model is rebuilt with dropout_p = 0.0; "
+                         "the reference trains with 0.5)")
     ap.add_argument("--is-lut-index", type=int, default=None, help="default: from the dataset (lightpath test.py:59)")
     args = ap.parse_args(argv)
+    if args.mc_samples is not None and not (args.fused and args.kind == "topological"):
+        ap.error("--mc-samples needs --kind topological --fused")
 
     from . import LightpathGNN, TopologicalGNN
     kind = args.kind
@@ -65,12 +76,15 @@ def main(argv=None):
     how = {}
     if args.fused and kind == "topological":
         how = {"fused": True}
+        if args.mc_samples is not None:
+            how.update(mc_samples=args.mc_samples, mc_p=args.mc_p)
     elif args.fused:
         from .infer import LightpathPredictor
         how = {"predictor": LightpathPredictor(model.to(device))}
-    metrics, y_true, y_pred, skipped = harness.evaluate(model, dataset, test_idx, kind=kind, batch_size=args.batch_size,
-                                                        output_dim=params["output_dim"], device=device,
-                                                        return_predictions=True, **how)
+    metrics, y_true, y_pred, skipped, *y_std = harness.evaluate(model, dataset, test_idx, kind=kind,
+                                                                batch_size=args.batch_size,
+                                                                output_dim=params["output_dim"], device=device,
+                                                                return_predictions=True, **how)
     print(f"Test R2 Score per output: {[m['R2'] for m in metrics.values()]}")
     print(f"Test MSE per output: {[m['Test_MSE'] for m in metrics.values()]}")
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -86,6 +100,9 @@ def main(argv=None):
         json.dump(y_true.tolist(), f)
     with open(os.path.join(folder, "y_pred_descaled.json"), "w") as f:
         json.dump(y_pred.tolist(), f)
+    if y_std:
+        with open(os.path.join(folder, "y_pred_std_descaled.json"), "w") as f:
+            json.dump(y_std[0].tolist(), f)
     print(f"Results saved to {folder}")
     return folder
 

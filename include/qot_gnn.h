@@ -811,6 +811,33 @@ int qot_topological_infer(const int64_t* node_ids, const int64_t* edge_index, co
                           const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
                           float slope_head, float* out, int H, int D, int O, int32_t* status, qot_stream_t stream);
 
+/* ---- Monte-Carlo dropout in one launch: T stochastic forwards of the same model and batch -------------------------
+ * samples[t, b, 0..O) (fp32, [T, B, O]) is the output of a TRAIN-MODE forward of the engine on this batch at dropout step
+ * first_step + t with base seed base_seed: leaky_relu + Dropout(p_conv) behind both convolutions, Dropout(p_head) inside
+ * the read-out, masks by the rule at the top of this header -- keep = 16 bits of hash(site seed, step, flat / 4) >= thr16,
+ * site seed = base_seed + 0x9E3779B97F4A7C15 * site (mod 2^64) with site 1 behind conv1, 2 behind conv2, 97 in the
+ * read-out; flat = (node_ptr[b] + j) * H + c over the batch's [N, H] at the conv sites, b * H + c over [B, H] in the
+ * read-out; kept values times 1 / (1 - p) in fp32.  A graph's draw therefore depends on its row offset in the batch (as in
+ * training); a given (batch, seed, first_step, t) is bitwise reproducible and independent of T and chunk.  With p_conv ==
+ * p_head == 0 every sample equals qot_topological_infer's row bit for bit (same sums in the same order, no multiply taken).
+ *
+ * Grid (B, ceil(T / chunk)): a workgroup builds its graph's index and the first convolution ONCE (nothing before conv1's
+ * activation depends on the draw) and then runs NNConv, pool and read-out for chunk samples.  Everything else -- batch
+ * layout, tables, status bits (all T rows of a flagged graph are NaN) -- as qot_topological_infer.  Envelope: that of
+ * qot_topological_infer with a lower edge cap (the LDS image holds a masked copy of conv1's output: n_max * H more words);
+ * qot_topological_infer_mc_supported / _max_edges answer from the kernel's own layout.  1 <= T <= 4096, 1 <= chunk <= T,
+ * else QOT_ERR_UNSUPPORTED; first_step < 0 or a probability outside [0, 1): QOT_ERR_BADARG. */
+int qot_topological_infer_mc_supported(int n_max, int max_e, int H, int D, int O);
+int qot_topological_infer_mc_max_edges(int n_max, int H, int D);
+int qot_topological_infer_mc(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                             const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t B, int n_max,
+                             int max_e, const float* t4, int ld4, const float* M, int ldm, const float* P, int V,
+                             const float* w_edge, const float* w1, const float* b1, const float* wcat, const float* bias2,
+                             const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
+                             float slope_head, float* samples, int H, int D, int O, int32_t* status, int T,
+                             int64_t first_step, uint64_t base_seed, float p_conv, float p_head, int chunk,
+                             qot_stream_t stream);
+
 /* ---- single-launch inference: the eval-mode LightpathGNN forward of the LUT rows ------------------------------------
  * lightpath_training/models.py:7-45 with dropout off, reference architecture (ONE GATConv(heads = 4) -> BatchNorm on the
  * running statistics -> ReLU -> LUT rows -> Linear -> LeakyReLU -> Linear), for a block-diagonal batch in ONE launch, one

@@ -1,0 +1,153 @@
+"""CPU-side checks of the Monte-Carlo dropout path (``csrc/infer_mc.hip``, ``TopologicalPredictor.sample``): the entry
+points are declared, bound and exported; the envelope answers; ``infer.mc_chunk``; the argument checks of ``sample`` that
+come before any device use; and the fixture the GPU tests lean on -- ``oracle.dropout.topological_masks`` at ``p = 0``
+leaves the oracle's eval output unchanged."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+import gnn_qot_estimation_amd as q
+from gnn_qot_estimation_amd import _lib, harness, infer
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("qot_topological_infer_mc", "qot_topological_infer_mc_supported", "qot_topological_infer_mc_max_edges")
+
+
+def test_symbols_declared_bound_and_exported():
+    hdr = open(os.path.join(ROOT, "include", "qot_gnn.h")).read()
+    declared = set(re.findall(r"\b(qot_[a-z0-9_]+)\s*\(", hdr))
+    assert os.path.exists(_lib.LIB_PATH), "run __graft_entry__.build() first"
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in NAMES:
+        assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name), name
+        decl = re.search(r"int %s\(([^;]*)\);" % name, hdr).group(1)
+        assert len(_lib.SIGNATURES[name][1]) == decl.count(",") + 1, name
+    # everything qot_topological_infer takes, then T, first_step, base_seed, p_conv, p_head, chunk; the stream comes last
+    ev, mc = _lib.SIGNATURES["qot_topological_infer"][1], _lib.SIGNATURES["qot_topological_infer_mc"][1]
+    assert mc[:len(ev) - 1] == ev[:-1] and mc[-1] is ctypes.c_void_p
+    assert mc[len(ev) - 1:-1] == [ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_int]
+    assert hasattr(q.TopologicalPredictor, "sample")
+
+
+@pytest.mark.parametrize("n,H,D", [(75, 16, 4), (100, 64, 4), (128, 64, 4), (128, 32, 1), (2, 16, 2)])
+def test_edge_cap_is_the_eval_cap_less_the_masked_copy(n, H, D):
+    lib = _lib.load()
+    cap, eval_cap = lib.qot_topological_infer_mc_max_edges(n, H, D), lib.qot_topological_infer_max_edges(n, H, D)
+    assert cap == infer.mc_edge_cap(n, H, D) and 0 < cap < eval_cap
+    assert lib.qot_topological_infer_mc_supported(n, cap, H, D, 3) == 1
+    assert lib.qot_topological_infer_mc_supported(n, cap + 1, H, D, 3) == 0
+    # the copy is ceil4(n * H) words; an edge costs D + 2D + 3 words (up to the padding of the two feature arrays)
+    lost = eval_cap - cap
+    words = (n * H + 3) // 4 * 4
+    assert abs(lost - words / (3 * D + 3)) <= 2, (lost, words)
+    assert lib.qot_topological_infer_mc_max_edges(129, H, D) == -1 and lib.qot_topological_infer_mc_max_edges(n, 48, D) == -1
+    assert lib.qot_topological_infer_mc_supported(n, 10, H, 5, 3) == 0 and lib.qot_topological_infer_mc_supported(n, 10, H, D, 9) == 0
+
+
+def test_entry_point_refuses_before_any_launch():
+    fn = _lib.load().qot_topological_infer_mc
+    one = ctypes.c_void_p(1)                                 # never dereferenced: every call below is refused first
+
+    def call(T=4, first_step=0, p_conv=0.5, p_head=0.5, chunk=1, H=16, max_e=10):
+        return fn(one, one, one, one, one, 10, 10, 1, 10, max_e, one, 4 * H, one, 16, one, 16, one, one, one, one, one, one, one,
+                  one, one, 0.01, 0.01, one, H, 4, 3, None, T, first_step, 0, p_conv, p_head, chunk, None)
+    UNSUPPORTED, BADARG = -1, -2                             # include/qot_gnn.h: QOT_ERR_UNSUPPORTED, QOT_ERR_BADARG
+    for kw in (dict(T=0), dict(T=4097), dict(chunk=0), dict(chunk=5), dict(H=48), dict(max_e=1 << 21)):
+        assert call(**kw) == UNSUPPORTED, kw
+    for kw in (dict(first_step=-1), dict(p_conv=1.0), dict(p_head=-0.5), dict(p_conv=float("nan"))):
+        assert call(**kw) == BADARG, kw
+
+
+def test_mc_chunk():
+    table = [  # (B, T, CUs) -> chunk
+        ((256, 32, 256), 32), ((512, 32, 256), 32), ((1000, 2, 256), 2),         # B >= CUs: one workgroup per graph
+        ((1, 32, 256), 1), ((7, 32, 256), 1),                                    # no chunk reaches the device: 1
+        ((8, 32, 256), 1),                                                       # exactly B * T workgroups
+        ((64, 32, 256), 8),             # largest chunk reaching 256 is 10 (4 workgroups per graph): 4 equal shares of 8
+        ((128, 32, 256), 16),           # ... 31 (2 per graph): 16 + 16, not 31 + 1
+        ((100, 32, 256), 11), ((1, 4096, 256), 16), ((3, 100, 256), 1), ((3, 1000, 256), 11),
+        ((0, 32, 256), 1), ((1, 2, 1), 2),
+    ]
+    for (B, T, cus), want in table:
+        got = infer.mc_chunk(B, T, cus)
+        assert got == want, ((B, T, cus), got, want)
+    for B in (0, 1, 2, 5, 31, 255, 256, 257, 5000):
+        for T in (1, 2, 3, 5, 32, 33, 1000, 4096):
+            for cus in (1, 64, 256, 304):
+                c = infer.mc_chunk(B, T, cus)
+                assert 1 <= c <= T
+                # the rule, by exhaustion: the largest chunk whose grid reaches the device, then equal shares
+                reaching = [k for k in range(1, T + 1) if B * -(-T // k) >= cus]
+                if not reaching:
+                    assert c == 1
+                    continue
+                chunks = -(-T // max(reaching))
+                assert c == -(-T // chunks) and -(-T // c) == chunks, (B, T, cus, c)
+                if B >= cus:
+                    assert c == T
+    with pytest.raises(ValueError):
+        infer.mc_chunk(1, 0, 256)
+
+
+def test_sample_argument_checks_need_no_device():
+    assert infer.mc_args(32, None, None, 0, (0.5, 0.25)) == (32, 0.5, 0.25, None, 0)
+    assert infer.mc_args(2, 0.0, 2, 2 ** 63 - 2) == (2, 0.0, 0.0, 2, 2 ** 63 - 2)
+    assert infer.mc_args(4096, (0.0, 0.5), 1, 5) == (4096, 0.0, 0.5, 1, 5)
+    for bad in (1, 0, -3, 4097, 2.0, "4", None, True):
+        with pytest.raises(ValueError, match="samples must be an integer in 2 ... 4096"):
+            infer.mc_args(bad, 0.5, None, 0)
+    for bad in (1.0, -0.1, 1.5, float("nan"), "0.5", (0.5, 1.0), (0.5,), True):
+        with pytest.raises(ValueError, match="p must"):
+            infer.mc_args(4, bad, None, 0)
+    with pytest.raises(ValueError, match=r"p must lie in \[0, 1\)"):
+        infer.mc_args(4, None, None, 0, (0.5, 1.0))          # the model's own probability is checked too
+    for bad in (0, 5, -1, 1.0, True):
+        with pytest.raises(ValueError, match="chunk must be an integer in 1 ... samples = 4"):
+            infer.mc_args(4, 0.5, bad, 0)
+    for bad in (-1, 2 ** 63 - 3, 2 ** 63, 0.0, True):
+        with pytest.raises(ValueError, match="first_step must be"):
+            infer.mc_args(4, 0.5, None, bad)
+
+
+def test_sample_checks_its_arguments_before_the_model_and_the_batch():
+    """A predictor cannot be built on a CPU model; one whose model has since moved to the CPU still names a bad argument
+    first, then the CPU model -- and reads nothing of the batch for either."""
+    pred = q.TopologicalPredictor.__new__(q.TopologicalPredictor)
+    pred.model, pred._tables, pred._tag, pred._status = q.TopologicalGNN(14, 32, 3, 4), None, None, None
+    with pytest.raises(ValueError, match="samples must be"):
+        pred.sample(None, 1)
+    with pytest.raises(ValueError, match="chunk must be"):
+        pred.sample(None, 4, chunk=9)
+    with pytest.raises(ValueError, match="CPU"):
+        pred.sample(None, 4)
+    assert pred.model.training and int(pred.model._qot_step) == 0
+
+
+def test_evaluate_mc_needs_the_fused_path():
+    m = q.TopologicalGNN(14, 16, 3, 4)
+    with pytest.raises(ValueError, match="needs fused=True"):
+        harness.evaluate(m, [], kind="topological", device="cpu", mc_samples=4)
+
+
+def test_masks_at_p_zero_leave_the_oracles_eval_output_unchanged():
+    import dropout_cases as DC
+    from gnn_qot_estimation_amd import synthetic as S
+    from oracle import dropout as OD, sparse as Osp
+    torch.manual_seed(0)
+    batch = S.topological_batch(2, 3, n=9, e=20)
+    for p_model in (0.0, 0.5):
+        ref = Osp.TopologicalGNN(9, 16, 3, 4, dropout_p=p_model).eval()
+        keep = OD.topological_masks(DC.SEED, 2 ** 33 + 1, 0.0, batch.num_nodes, batch.num_graphs, 16)
+        assert set(keep) == {"conv1", "conv2", "head"} and all(bool(k.all()) for k in keep.values())
+        with torch.no_grad():
+            want = ref(batch)
+            ref.dropout.p = ref.mlp[2].p = 0.0               # (the injected scale is 1 / (1 - module.p))
+            assert torch.equal(ref(batch, keep=keep), want)
+    # ... and a real mask changes it (the injection is live)
+    ref = Osp.TopologicalGNN(9, 16, 3, 4, dropout_p=0.5).eval()
+    keep = OD.topological_masks(DC.SEED, 2 ** 33 + 1, 0.5, batch.num_nodes, batch.num_graphs, 16)
+    with torch.no_grad():
+        assert not torch.equal(ref(batch, keep=keep), ref(batch))

@@ -21,6 +21,16 @@ timed calls).  Per way the median and the interquartile range; a difference of t
 of the two interquartile ranges is reported as no difference.
 
     python tools/bench_infer.py --kind lightpath [--out profiles/bench_infer_lightpath.jsonl]
+
+``--mc T``: Monte-Carlo dropout (csrc/infer_mc.hip) -- milliseconds per call of ``predict.sample(data, T)``
+(one launch for the T draws, two small torch launches for mean and std) against the only other way to T stochastic
+forwards: ``model.train()`` and T calls of ``model(data)`` under ``torch.no_grad()`` (the stack of their outputs is not
+reduced: the eager side is charged less than it would cost).  p = 0.5 at all three sites; the reference shape at B = 1, 8
+and 512 and the headline shape at B = 1.  The draws of both ways are compared first (draw t of ``sample(first_step=1)`` is
+the train-mode forward at dropout step 1 + t); then both alternate in one process, median and interquartile range as for
+``--kind lightpath``.
+
+    python tools/bench_infer.py --mc 32 [--out profiles/bench_infer_mc.jsonl]
 """
 import argparse
 import json
@@ -106,6 +116,69 @@ def measure(shape, device, rounds, warmup):
     return res
 
 
+MC_SHAPES = [SHAPES[0], SHAPES[1], SHAPES[2], SHAPES[3]]
+
+
+def measure_mc(shape, T, device, rounds, warmup):
+    torch.manual_seed(0)
+    model = q.TopologicalGNN(shape["V"], shape["H"], 3, 4, dropout_p=0.5).to(device).train()
+    data = batch_for(shape, device)
+    predict = q.TopologicalPredictor(model)
+
+    def eager():
+        with torch.no_grad():
+            return [model(data) for _ in range(T)]
+
+    eager()
+    model._qot_step.zero_()
+    want = torch.stack(eager())                            # dropout steps 1 ... T
+    got = predict.sample(data, T, first_step=1, return_samples=True)[2]
+    torch.cuda.synchronize()
+    predict.check_status()
+    err = float((got.double() - want.double()).abs().max() / want.double().abs().max())
+    assert err <= 1e-4, (shape["name"], err)
+    assert not torch.equal(got[0], got[1])
+
+    ways = {"sample": lambda: predict.sample(data, T), "eager": eager}
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed(fn))
+    from gnn_qot_estimation_amd import infer
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    res = dict(shape=shape["name"], kind="mc", T=T, p=0.5, chunk=infer.mc_chunk(shape["B"], T, cus), compute_units=cus,
+               **{k: shape[k] for k in ("V", "n", "e", "H", "B")}, rounds=rounds, rel_err=err)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_mc(args, device, commit):
+    rows = []
+    for shape in MC_SHAPES:
+        res = measure_mc(shape, args.mc, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print(f"\n| shape | chunk | sample(T={args.mc}) ms (IQR) | {args.mc} train-mode forwards ms (IQR) | eager / sample |")
+    print("|---|---|---|---|---|")
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['shape']} (n={r['n']}, e={r['e']}, H={r['H']}) | {r['chunk']} | {cell('sample')} | {cell('eager')} | "
+              f"{verdict(r, 'sample')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -183,7 +256,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--kind", choices=["topological", "lightpath"], default="topological")
+    ap.add_argument("--mc", type=int, default=None, metavar="T",
+                    help="Monte-Carlo dropout: predict.sample(data, T) against T train-mode forwards")
     args = ap.parse_args()
+    if args.mc is not None and args.kind != "topological":
+        raise SystemExit("--mc is for the topological model")
     if args.rounds < 20:
         raise SystemExit("--rounds: at least 20 timed calls per way")
     if not torch.cuda.is_available():
@@ -192,6 +269,8 @@ def main():
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     if args.kind == "lightpath":
         return main_lightpath(args, device, commit)
+    if args.mc is not None:
+        return main_mc(args, device, commit)
     rows = []
     for shape in SHAPES:
         res = measure(shape, device, args.rounds, args.warmup)
