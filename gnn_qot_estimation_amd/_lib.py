@@ -176,6 +176,11 @@ SIGNATURES = {
     "qot_topological_infer_mc": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _int, _p, _int, _p, _int, _p, _p,
                                         _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _int, _int, _int, _p, _int, _i64, _u64, _f, _f,
                                         _int, _p]),
+    "qot_topological_infer_grad_supported": (_int, [_int, _int, _int, _int, _int]),
+    "qot_topological_infer_grad_max_edges": (_int, [_int, _int, _int]),
+    "qot_topological_infer_grad": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _int, _p, _int, _p, _int, _p,
+                                          _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _int, _int, _int, _p, _p, _int, _p, _p,
+                                          _p]),
     "qot_lightpath_infer": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f,
                                    _p, _p, _p, _p, _f, _p, _p, _int, _int, _int, _int, _int, _p, _p]),
     "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),

@@ -1,11 +1,12 @@
-// Device pieces of the single-launch TopologicalGNN forward, shared by the eval kernel (infer.hip) and
-// the Monte-Carlo dropout kernel (infer_mc.hip): the LDS layout, the argument block and the two halves of
-// a workgroup's work on ONE graph --
+// Device pieces of the single-launch TopologicalGNN forward, shared by the eval kernel (infer.hip), the
+// Monte-Carlo dropout kernel (infer_mc.hip) and the sensitivity kernel (infer_grad.hip):
+// the LDS layout, the argument block and the two halves of a workgroup's work on ONE graph --
 //   infer_phases12: index, edge MLP hidden layer, TransformerConv + leaky_relu -> the undropped x1 in LDS
 //   infer_phases34: NNConv (mean) in row tiles + leaky_relu, pooled on the fly, mean pool, read-out MLP -> one output row
 // The second half is a template on MC: false compiles the eval forward (no dropout code at all), true applies the engine's
 // counter-based dropout (common.hpp: act_hash64) behind conv2's leaky_relu and inside the read-out; conv1's dropout is a
-// masked copy of x1 the caller hands in as `xin`.  Every sum runs in the same order in both.
+// masked copy of x1 the caller hands in as `xin`.  Every sum runs in the same order in both.  GRAD (the sensitivity
+// kernel) keeps the branches the two leaky_relus took -- nothing else changes, the sums are the eval forward's.
 #pragma once
 #include "graph_prep_dev.hpp"
 
@@ -20,12 +21,17 @@ __host__ __device__ constexpr int infer_tile_rows(int H) { return infer_rpt(H) *
 __host__ __device__ constexpr int infer_pad4(int v) { return (v + 3) & ~3; }
 
 // 4-byte word offsets of the LDS image for graphs of at most cap_n nodes / cap_m edges: the ONE statement of the budget
-// (the kernels, the entry points and qot_topological_infer[_mc]_supported all read it).  mc: the Monte-Carlo kernel's
-// variant -- the eval image, unchanged, followed by x1d, the sample's masked copy of x1 (cap_n * H more words).
+// (the kernels, the entry points and qot_topological_infer[_mc|_grad]_supported all read it).  Variants: the eval image,
+// unchanged, followed by
+//   kInferMc    x1d, the sample's masked copy of x1 (cap_n * H words)
+//   kInferGrad  gx1 [cap_n, H] (the adjoint of x1, then of conv1's pre-activation), gy [R, H] (a row tile of conv2's
+//               adjoint), dh [cap_m, K] (per edge: the adjoint of the edge MLP's hidden layer, later the edge's partial
+//               result) and gs / gpool [H] (the read-out's adjoints)
+enum InferVariant { kInferEval = 0, kInferMc = 1, kInferGrad = 2 };
 struct InferLds {
-    int atile, x1, ea, he, alpha, ends, key, cin, rp, lnid, part, pooled, h1, x1d, words;
+    int atile, x1, ea, he, alpha, ends, key, cin, rp, lnid, part, pooled, h1, x1d, gx1, gy, dh, gs, gpool, words;
 };
-__host__ __device__ inline InferLds infer_lds(int cap_n, int cap_m, int H, int D, bool mc = false) {
+__host__ __device__ inline InferLds infer_lds(int cap_n, int cap_m, int H, int D, InferVariant var = kInferEval) {
     const int K = 2 * D;
     InferLds L;
     int o = 0;
@@ -43,7 +49,15 @@ __host__ __device__ inline InferLds infer_lds(int cap_n, int cap_m, int H, int D
     L.part = o;   o += kInferThreads;                          // pool shares of the row groups
     L.pooled = o; o += H;
     L.h1 = o;     o += H;
-    L.x1d = o;    if (mc) o += infer_pad4(cap_n * H);          // 16-byte aligned: everything above ends on a multiple of 4
+    L.x1d = o;    if (var == kInferMc) o += infer_pad4(cap_n * H);   // 16-byte aligned: all above ends on a multiple of 4
+    L.gx1 = L.gy = L.dh = L.gs = L.gpool = o;
+    if (var == kInferGrad) {
+        L.gx1 = o;    o += infer_pad4(cap_n * H);
+        L.gy = o;     o += infer_tile_rows(H) * H;
+        L.dh = o;     o += infer_pad4(cap_m * K);
+        L.gs = o;     o += H;
+        L.gpool = o;  o += H;
+    }
     L.words = o;
     return L;
 }
@@ -198,10 +212,12 @@ __device__ __forceinline__ int infer_phases12(const InferArgs& a, float* lds, co
 
 // ---- phases 3 and 4 on the first convolution's output `xin` [n, H] (LDS: x1 itself, or a sample's masked copy of it):
 // writes orow[0 .. O).  Ends without a barrier; the LDS it wrote last (h1) is not written again before three barriers of
-// the next call.
-template <int H, int D, bool MC>
+// the next call.  GRAD: *ybits gets one bit per row of this thread, (tile number) * RPT + u, set where conv2's
+// pre-activation of (that row, column tid % H) is positive (at most 128 / R * RPT = 32 rows per thread), and part[c]
+// (c < H) keeps the read-out's pre-activation s.
+template <int H, int D, bool MC, bool GRAD = false>
 __device__ __forceinline__ void infer_phases34(const InferArgs& a, float* lds, const InferLds& L, int n, const float* xin,
-                                               float* orow, const InferDrop& dr) {
+                                               float* orow, const InferDrop& dr, unsigned int* ybits = nullptr) {
     constexpr int NT = kInferThreads;
     constexpr int K = 2 * D, KT = (K + 2) * H;
     constexpr int RPT = infer_rpt(H), R = infer_tile_rows(H);
@@ -219,6 +235,7 @@ __device__ __forceinline__ void infer_phases34(const InferArgs& a, float* lds, c
     const int o = tid % H, rg = tid / H;
     const float bias_o = a.bias2[o];
     float pool = 0.f;
+    unsigned int ypos = 0;
     for (int r0 = 0; r0 < n; r0 += R) {
         for (int idx = tid; idx < R * (K + 1) * H; idx += NT) {
             const int rr = idx / ((K + 1) * H), rem = idx % ((K + 1) * H);
@@ -262,6 +279,7 @@ __device__ __forceinline__ void infer_phases34(const InferArgs& a, float* lds, c
         for (int u = 0; u < RPT; ++u)
             if (r0 + rg * RPT + u < n) {
                 float y = leaky(acc[u] + bias_o, a.slope_conv);
+                if constexpr (GRAD) ypos |= (acc[u] + bias_o > 0.f ? 1u : 0u) << ((r0 / R) * RPT + u);
                 if constexpr (MC)
                     y = infer_drop1(y, dr.seed_conv2, dr.step, (dr.row0 + (uint64_t)(r0 + rg * RPT + u)) * H + o, dr.thr_conv,
                                     dr.scale_conv);
@@ -288,7 +306,9 @@ __device__ __forceinline__ void infer_phases34(const InferArgs& a, float* lds, c
         float y = leaky(s, a.slope_head);
         if constexpr (MC) y = infer_drop1(y, dr.seed_head, dr.step, dr.graph * H + tid, dr.thr_head, dr.scale_head);
         h1[tid] = y;
+        if constexpr (GRAD) part[tid] = s;              // (the row groups' shares were read before the last barrier)
     }
+    if constexpr (GRAD) *ybits = ypos;
     __syncthreads();
     if (tid < a.O) {
         float s = a.b3[tid];

@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_mc_kernel(con
     const int64_t n0 = a.node_ptr[b], e0 = a.edge_ptr[b];
     const int64_t nn = a.node_ptr[b + 1] - n0, mm = a.edge_ptr[b + 1] - e0;
     int bad = infer_slices_ok(a, n0, e0, nn, mm) ? 0 : 2;
-    const InferLds L = infer_lds(a.cap_n, a.cap_m, H, D, true);
+    const InferLds L = infer_lds(a.cap_n, a.cap_m, H, D, kInferMc);
     const int n = (int)nn, m = (int)mm;
     if (!bad) bad = infer_phases12<H, D>(a, lds, L, n0, e0, n, m);
     if (bad) {                                                         // as the eval kernel: flag, NaN rows, nothing else
@@ -91,7 +91,7 @@ using namespace qot;
 extern "C" int qot_topological_infer_mc_supported(int n_max, int max_e, int H, int D, int O) {
     if (!infer_shape_ok(H, D, O) || n_max < 0 || n_max > kInferMaxN || max_e < 0) return 0;
     if (max_e > (1 << 20)) return 0;                   // (keeps the word count below 2^31)
-    return (size_t)infer_lds(n_max, max_e, H, D, true).words * 4 <= kInferLdsMax ? 1 : 0;
+    return (size_t)infer_lds(n_max, max_e, H, D, kInferMc).words * 4 <= kInferLdsMax ? 1 : 0;
 }
 
 extern "C" int qot_topological_infer_mc_max_edges(int n_max, int H, int D) {
@@ -132,7 +132,7 @@ extern "C" int qot_topological_infer_mc(const int64_t* node_ids, const int64_t* 
     mc.seed_conv1 = base_seed + golden * 1; mc.seed_conv2 = base_seed + golden * 2; mc.seed_head = base_seed + golden * 97;
     mc_threshold(p_conv, &mc.thr_conv, &mc.scale_conv);
     mc_threshold(p_head, &mc.thr_head, &mc.scale_head);
-    const size_t lds = (size_t)infer_lds(n_max, max_e, H, D, true).words * 4;
+    const size_t lds = (size_t)infer_lds(n_max, max_e, H, D, kInferMc).words * 4;
     const dim3 grid((unsigned)B, (unsigned)chunks);
 #define QOT_INFER_MC_CASE(HH, DD)                                                                                         \
     case HH * 8 + DD: {                                                                                                   \

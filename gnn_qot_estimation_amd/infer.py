@@ -1,5 +1,6 @@
 """Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``; its Monte-Carlo dropout
-``sample``: ``csrc/infer_mc.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``).
+``sample``: ``csrc/infer_mc.hip``; its per-link ``sensitivity``: ``csrc/infer_grad.hip``, DESIGN.md
+4.16) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``).
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
 TransformerConv, the NNConv forward and the read-out kernel (``LightpathGNN``: the self-looped graph index, the GAT walk
@@ -45,6 +46,30 @@ def mc_edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
     """``edge_cap`` of the sampling kernel (``TopologicalPredictor.sample``): lower, its LDS image also holds the sample's
     masked copy of the first convolution's output; -1: none."""
     return int(_lib.load().qot_topological_infer_mc_max_edges(int(n_max), int(hidden), int(edge_dim)))
+
+
+def grad_edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
+    """``edge_cap`` of the sensitivity kernel (``TopologicalPredictor.sensitivity``): lower, its LDS image also holds the
+    adjoint of the first convolution's output and ``2 * edge_dim`` more words per edge; -1: none."""
+    return int(_lib.load().qot_topological_infer_grad_max_edges(int(n_max), int(hidden), int(edge_dim)))
+
+
+def grad_outputs(outputs, num_outputs: int):
+    """The ``outputs`` argument of ``TopologicalPredictor.sensitivity``, checked without a device: ``None`` (every output,
+    in order) or a non-empty list / tuple of distinct integers in ``0 ... num_outputs - 1``; returns the list or raises the
+    named ``ValueError``."""
+    who = "TopologicalPredictor.sensitivity"
+    O = int(num_outputs)
+    if outputs is None:
+        return list(range(O))
+    if not isinstance(outputs, (list, tuple)) or len(outputs) == 0:
+        raise ValueError(f"{who}: outputs must be None or a non-empty list of output indices, got {outputs!r}")
+    for o in outputs:
+        if isinstance(o, bool) or not isinstance(o, int) or not 0 <= o < O:
+            raise ValueError(f"{who}: outputs must be integers in 0 ... {O - 1}, got {o!r}")
+    if len(set(outputs)) != len(outputs):
+        raise ValueError(f"{who}: outputs must be distinct, got {list(outputs)!r}")
+    return list(outputs)
 
 
 MC_MAX_SAMPLES = 4096           # csrc/infer_mc.hip: T
@@ -154,6 +179,7 @@ class TopologicalPredictor:
     hidden, edge_dim)`` edges each.  ``node_ids`` outside the embedding table raise ``IndexError`` as the model does.
 
     ``predictor.sample(data, samples)``: Monte-Carlo dropout, ``samples`` stochastic forwards in one launch (see there).
+    ``predictor.sensitivity(data)``: the output together with its Jacobian wrt the edge features, in one launch.
     """
 
     def __init__(self, model):
@@ -164,7 +190,7 @@ class TopologicalPredictor:
         self._check_model()
 
     # ------------------------------------------------------------------ envelope
-    def _check_model(self):
+    def _check_model(self, on_gpu=True):
         m = self.model
         if getattr(m, "num_layers", None) != 2 or not hasattr(m, "conv2") or not hasattr(m, "node_embeddings"):
             raise ValueError(f"TopologicalPredictor: num_layers must be 2 (TransformerConv + NNConv), got "
@@ -181,7 +207,7 @@ class TopologicalPredictor:
         O = m.mlp[3].out_features
         if not 1 <= O <= MAX_OUTPUTS or m.mlp[0].out_features != H:
             raise ValueError(f"TopologicalPredictor: out_channels {O} is not supported; it must be 1 ... {MAX_OUTPUTS}")
-        if not m.node_embeddings.weight.is_cuda:
+        if on_gpu and not m.node_embeddings.weight.is_cuda:
             raise ValueError("TopologicalPredictor: the model is on the CPU; move it to the GPU first (model.to('cuda'))")
         return H, D, O
 
@@ -261,9 +287,10 @@ class TopologicalPredictor:
             c["infer_ids_ok"] = tag
 
     # ------------------------------------------------------------------ the call
-    def _prepare(self, data, mc=False):
-        """Everything a launch needs, checked: ``(H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, tables)``.  ``mc``:
-        the envelope of the sampling kernel (``qot_topological_infer_mc``) instead of the eval kernel's."""
+    def _prepare(self, data, mc=False, grad=False):
+        """Everything a launch needs, checked: ``(H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, tables)``.  ``mc``
+        / ``grad``: the envelope of the sampling kernel (``qot_topological_infer_mc``) / of the sensitivity kernel
+        (``qot_topological_infer_grad``) instead of the eval kernel's."""
         H, D, O = self._check_model()
         m = self.model
         if data.x is not None and data.x.numel():
@@ -272,14 +299,16 @@ class TopologicalPredictor:
         dev = m.node_embeddings.weight.device
         ids, ei, ptr, eptr, n_max, max_e, B, exact = self._slices(data, dev)
         lib = _lib.load()
-        supported = lib.qot_topological_infer_mc_supported if mc else lib.qot_topological_infer_supported
+        supported = (lib.qot_topological_infer_grad_supported if grad else
+                     lib.qot_topological_infer_mc_supported if mc else lib.qot_topological_infer_supported)
         if n_max > MAX_NODES or not supported(n_max, max_e, H, D, O):
             n_max, max_e = exact()          # the carried sizes are bounds (a shard inherits its parent's): look once
             if n_max > MAX_NODES:
                 raise ValueError(f"TopologicalPredictor: a graph of {n_max} nodes; at most {MAX_NODES} nodes per graph")
-            cap = (mc_edge_cap if mc else edge_cap)(n_max, H, D)
+            cap = (grad_edge_cap if grad else mc_edge_cap if mc else edge_cap)(n_max, H, D)
             if max_e > cap:
-                raise ValueError(f"TopologicalPredictor: a graph of {max_e} edges is above the {'sampling ' if mc else ''}"
+                which = "sensitivity " if grad else "sampling " if mc else ""
+                raise ValueError(f"TopologicalPredictor: a graph of {max_e} edges is above the {which}"
                                  f"edge cap {cap} for graphs of up to {n_max} nodes at hidden width {H}, edge_dim {D}")
         ea = data.edge_attr
         E = ei.shape[1]
@@ -340,6 +369,41 @@ class TopologicalPredictor:
                   p_conv, p_head, chunk)
         mean, std = draws.mean(0), draws.std(0, unbiased=True)
         return (mean, std, draws) if return_samples else (mean, std)
+
+    @torch.no_grad()
+    def sensitivity(self, data, outputs=None, *, return_attention_weights=False):
+        """The per-link sensitivity of the prediction in ONE kernel launch: returns ``(out [B, O], jac [Q, E, D])`` with
+        ``jac[q, e, :] = d out[graph(e), outputs[q]] / d edge_attr[e, :]`` of the EVAL-MODE function -- what
+        ``model.eval()(data)[:, o].sum().backward()`` leaves in ``edge_attr.grad``, for every requested output at once
+        (graphs are block-diagonal: this is the whole Jacobian).  ``out`` is ``self(data)`` bit for bit.
+
+        ``outputs``: ``None`` (all, in order) or a non-empty list of distinct integers in ``0 ... O - 1``.
+        ``return_attention_weights=True``: also ``(edge_index, alpha [E, 1])``, conv1's softmax weights in the order of
+        ``data.edge_index`` -- what ``model(data, return_attention_weights=True)`` returns.
+
+        Plain tensors without ``grad_fn``, bitwise reproducible; a graph's slices of ``jac`` and ``alpha`` do not depend on
+        the other graphs of the batch (no atomics: every sum has one owner and a fixed order).  The derivative of
+        ``leaky_relu`` / ``relu`` at 0 is torch's.  Pure: no model state is touched; parameter updates are followed as
+        ``__call__`` follows them.  Refusals, ``IndexError`` and ``check_status()`` as ``__call__`` (a flagged graph has NaN in
+        its ``out`` row, its ``jac`` slice and its ``alpha`` slice), with a lower edge cap: ``grad_edge_cap`` (DESIGN.md
+        4.16)."""
+        # the model's shape, then the argument, are named before the model's device and the batch are looked at
+        sel = grad_outputs(outputs, self._check_model(on_gpu=False)[2])
+        H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t = self._prepare(data, grad=True)
+        E, Q = ei.shape[1], len(sel)
+        out = torch.empty(B, O, dtype=torch.float32, device=dev)
+        jac = torch.empty(Q, E, D, dtype=torch.float32, device=dev)
+        alpha = torch.empty(E, 1, dtype=torch.float32, device=dev) if return_attention_weights else None
+        cache = self.__dict__.setdefault("_outputs_dev", {})     # one upload per selection: the call stays ONE launch
+        osel = cache.get((tuple(sel), dev))
+        if osel is None:
+            osel = cache[(tuple(sel), dev)] = torch.tensor(sel, dtype=torch.int32, device=dev)
+        _lib.call("qot_topological_infer_grad", ids, ei, ea, ptr, eptr, ids.shape[0], E, B, n_max, max_e, t["t4"], 4 * H,
+                  t["M"], t["ldm"], t["P"], t["V"], t["we"], t["w1"], t["b1"], t["wcat"], t["bias2"], t["w0"], t["b0"], t["w3"],
+                  t["b3"], 0.01, float(self.model.mlp[1].negative_slope), out, H, D, O, self._status, osel, Q, jac, alpha)
+        if return_attention_weights:
+            return out, jac, (data.edge_index, alpha)
+        return out, jac
 
     def check_status(self):
         """Reads the kernel's status word (one device synchronisation): raises when a batch since the last check had an

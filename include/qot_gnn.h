@@ -838,6 +838,32 @@ int qot_topological_infer_mc(const int64_t* node_ids, const int64_t* edge_index,
                              int64_t first_step, uint64_t base_seed, float p_conv, float p_head, int chunk,
                              qot_stream_t stream);
 
+/* ---- per-link sensitivity in one launch (TopologicalPredictor.sensitivity) --------------------------
+ * The eval-mode forward of qot_topological_infer -- the same sums in the same order: `out` is that entry's row bit for bit
+ * -- followed, inside the graph's workgroup, by one back pass per requested output to the edge features:
+ *   jac[q, e, d] = d out[graph(e), outputs[q]] / d edge_attr[e, d],   jac [Q, E, D] row-major, outputs [Q] device int32,
+ * distinct values in 0 ... O - 1 (the caller checks the contents; 1 <= Q <= O is checked here).  Graphs are block-diagonal,
+ * so this is the whole Jacobian.  The derivative of leaky_relu / relu at 0 is the forward's own branch (v > 0 ? 1 : slope;
+ * relu: 0), torch's rule.  alpha (optional, [E]): TransformerConv's softmax weights in the order of edge_index.
+ * No parameter or embedding gradient is formed and there is no float atomic anywhere: every element of jac, alpha and
+ * every intermediate sum has one owning thread and a fixed order, so the result is bitwise reproducible and a graph's
+ * slices do not depend on the other graphs of the batch.  Every jac / alpha element of a graph with edges is written once
+ * (no zero fill needed).  Batch layout, tables and status bits as qot_topological_infer; a flagged graph gets NaN in its
+ * out row, its jac slices and its alpha slice.
+ * Envelope: that of qot_topological_infer with a lower edge cap (the LDS image also holds the adjoint of conv1's output,
+ * one row tile of conv2's adjoint and 2 D words per edge); qot_topological_infer_grad_supported / _max_edges answer from
+ * the kernel's own layout.  QOT_ERR_UNSUPPORTED: outside the envelope, Q outside 1 ... O, slope_conv <= 0 (conv1's branch
+ * is read off the sign of its output); QOT_ERR_BADARG: a null required pointer. */
+int qot_topological_infer_grad_supported(int n_max, int max_e, int H, int D, int O);
+int qot_topological_infer_grad_max_edges(int n_max, int H, int D);
+int qot_topological_infer_grad(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                               const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t B, int n_max,
+                               int max_e, const float* t4, int ld4, const float* M, int ldm, const float* P, int V,
+                               const float* w_edge, const float* w1, const float* b1, const float* wcat, const float* bias2,
+                               const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
+                               float slope_head, float* out, int H, int D, int O, int32_t* status, const int32_t* outputs,
+                               int Q, float* jac, float* alpha, qot_stream_t stream);
+
 /* ---- single-launch inference: the eval-mode LightpathGNN forward of the LUT rows ------------------------------------
  * lightpath_training/models.py:7-45 with dropout off, reference architecture (ONE GATConv(heads = 4) -> BatchNorm on the
  * running statistics -> ReLU -> LUT rows -> Linear -> LeakyReLU -> Linear), for a block-diagonal batch in ONE launch, one

@@ -31,6 +31,15 @@ the train-mode forward at dropout step 1 + t); then both alternate in one proces
 ``--kind lightpath``.
 
     python tools/bench_infer.py --mc 32 [--out profiles/bench_infer_mc.jsonl]
+
+``--grad``: per-link sensitivity (csrc/infer_grad.hip) -- milliseconds per call of
+``predict.sensitivity(data)`` (output and the whole Jacobian wrt the edge features, one launch) against the other route to
+the same numbers: ``model.eval()`` forward with ``edge_attr.requires_grad_()``, parameters frozen, one
+``backward(retain_graph=True)`` per output.  The reference shape at B = 1 and 512 and the headline shape at B = 1; the two
+Jacobians are compared first; then both alternate in one process, each call between two ``torch.cuda.Event``s, median and
+interquartile range as above.
+
+    python tools/bench_infer.py --grad [--out profiles/bench_infer_grad.jsonl]
 """
 import argparse
 import json
@@ -179,6 +188,86 @@ def main_mc(args, device, commit):
               f"{verdict(r, 'sample')} |")
 
 
+GRAD_SHAPES = [SHAPES[0], SHAPES[2], SHAPES[3]]
+
+
+def timed_event(fn):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end)
+
+
+def measure_grad(shape, device, rounds, warmup):
+    torch.manual_seed(0)
+    model = q.TopologicalGNN(shape["V"], shape["H"], 3, 4, dropout_p=0.0).to(device).eval()
+    for p in model.parameters():
+        p.requires_grad_(False)
+    data = batch_for(shape, device)
+    predict = q.TopologicalPredictor(model)
+    leaf = batch_for(shape, device)
+    leaf.edge_attr = leaf.edge_attr.detach().clone().requires_grad_()
+
+    def autograd():
+        out = model(leaf)
+        jac = []
+        for o in range(out.shape[1]):
+            leaf.edge_attr.grad = None
+            out[:, o].sum().backward(retain_graph=True)
+            jac.append(leaf.edge_attr.grad)
+        return out, jac
+
+    for _ in range(3):
+        want_out, want = autograd()
+    want = torch.stack(want)
+    out, got = predict.sensitivity(data)
+    torch.cuda.synchronize()
+    predict.check_status()
+    err = float((got.double() - want.double()).abs().max() / want.double().abs().max())
+    err_out = float((out.double() - want_out.double()).abs().max() / want_out.double().abs().max())
+    assert err <= 1e-4 and err_out <= 1e-4, (shape["name"], err, err_out)
+
+    ways = {"sensitivity": lambda: predict.sensitivity(data), "eager": autograd}
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed_event(fn))
+    res = dict(shape=shape["name"], kind="grad", outputs=3, **{k: shape[k] for k in ("V", "n", "e", "H", "B")}, rounds=rounds,
+               rel_err=err)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_grad(args, device, commit):
+    rows = []
+    for shape in GRAD_SHAPES:
+        res = measure_grad(shape, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| shape | sensitivity ms (IQR) | forward + 3 backward ms (IQR) | autograd / sensitivity |")
+    print("|---|---|---|---|")
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['shape']} (n={r['n']}, e={r['e']}, H={r['H']}) | {cell('sensitivity')} | {cell('eager')} | "
+              f"{verdict(r, 'sensitivity')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -258,9 +347,13 @@ def main():
     ap.add_argument("--kind", choices=["topological", "lightpath"], default="topological")
     ap.add_argument("--mc", type=int, default=None, metavar="T",
                     help="Monte-Carlo dropout: predict.sample(data, T) against T train-mode forwards")
+    ap.add_argument("--grad", action="store_true",
+                    help="per-link sensitivity: predict.sensitivity(data) against eval forward + one backward per output")
     args = ap.parse_args()
-    if args.mc is not None and args.kind != "topological":
-        raise SystemExit("--mc is for the topological model")
+    if (args.mc is not None or args.grad) and args.kind != "topological":
+        raise SystemExit("--mc and --grad are for the topological model")
+    if args.mc is not None and args.grad:
+        raise SystemExit("--mc and --grad are separate runs")
     if args.rounds < 20:
         raise SystemExit("--rounds: at least 20 timed calls per way")
     if not torch.cuda.is_available():
@@ -271,6 +364,8 @@ def main():
         return main_lightpath(args, device, commit)
     if args.mc is not None:
         return main_mc(args, device, commit)
+    if args.grad:
+        return main_grad(args, device, commit)
     rows = []
     for shape in SHAPES:
         res = measure(shape, device, args.rounds, args.warmup)
