@@ -28,6 +28,10 @@ _sz = C.c_size_t
 # name -> (restype, argtypes); must list every symbol include/qot_gnn.h declares
 ABI_VERSION = 13         # include/qot_gnn.h: QOT_ABI_VERSION
 
+# what qot_topological_infer, _mc and _grad take alike, up to the status word; each adds its own arguments and the stream
+_INFER_COMMON = ([_p] * 5 + [_i64] * 3 + [_int, _int, _p, _int, _p, _int, _p, _int] + [_p] * 9
+                 + [_f, _f, _p, _int, _int, _int, _p])
+
 SIGNATURES = {
     "qot_abi_version": (_int, []),
     "qot_error_string": (C.c_char_p, [_int]),
@@ -167,20 +171,11 @@ SIGNATURES = {
     "qot_run_roles": (_int, [_p, _int, _p]),
     "qot_rows_gather": (_int, [_p, _p, _p, _i64, _int, _p]),
     "qot_rows_scatter": (_int, [_p, _p, _p, _i64, _int, _p]),
-    "qot_topological_infer_supported": (_int, [_int, _int, _int, _int, _int]),
-    "qot_topological_infer_max_edges": (_int, [_int, _int, _int]),
-    "qot_topological_infer": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _int, _p, _int, _p, _int, _p, _p,
-                                     _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _int, _int, _int, _p, _p]),
-    "qot_topological_infer_mc_supported": (_int, [_int, _int, _int, _int, _int]),
-    "qot_topological_infer_mc_max_edges": (_int, [_int, _int, _int]),
-    "qot_topological_infer_mc": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _int, _p, _int, _p, _int, _p, _p,
-                                        _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _int, _int, _int, _p, _int, _i64, _u64, _f, _f,
-                                        _int, _p]),
-    "qot_topological_infer_grad_supported": (_int, [_int, _int, _int, _int, _int]),
-    "qot_topological_infer_grad_max_edges": (_int, [_int, _int, _int]),
-    "qot_topological_infer_grad": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _int, _p, _int, _p, _int, _p,
-                                          _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _int, _int, _int, _p, _p, _int, _p, _p,
-                                          _p]),
+    **{f"qot_topological_infer{k}_supported": (_int, [_int] * 5) for k in ("", "_mc", "_grad")},
+    **{f"qot_topological_infer{k}_max_edges": (_int, [_int] * 3) for k in ("", "_mc", "_grad")},
+    "qot_topological_infer": (_int, _INFER_COMMON + [_p]),
+    "qot_topological_infer_mc": (_int, _INFER_COMMON + [_int, _i64, _u64, _f, _f, _int, _p]),
+    "qot_topological_infer_grad": (_int, _INFER_COMMON + [_p, _int, _p, _p, _p]),
     "qot_lightpath_infer": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f,
                                    _p, _p, _p, _p, _f, _p, _p, _int, _int, _int, _int, _int, _p, _p]),
     "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),

@@ -185,14 +185,22 @@ __device__ __forceinline__ float4 act_apply4s(float4 v, const ActParams& a, uint
     return make_float4(r[0], r[1], r[2], r[3]);
 }
 
+// the constants of a dropout probability p: thr16 = round(p * 65536) clamped to 65535 and 1 / (1 - p) in fp32; p <= 0
+// gives 0 and 1 (no dropout)
+inline void dropout_consts(float p, uint32_t* thr16, float* keep_scale) {
+    *thr16 = 0;
+    *keep_scale = 1.0f;
+    if (p > 0.f) {
+        const uint32_t thr = (uint32_t)(p * 65536.0f + 0.5f);
+        *thr16 = thr > 65535u ? 65535u : thr;
+        *keep_scale = 1.0f / (1.0f - p);
+    }
+}
+
 inline ActParams make_act(int act, float slope, float p, uint64_t seed, const int64_t* step) {
     ActParams a;
     a.enabled = act; a.slope = slope; a.thr16 = 0; a.keep_scale = 1.0f; a.seed = seed; a.step = step;
-    if (act && p > 0.f && step) {
-        uint32_t thr = (uint32_t)(p * 65536.0f + 0.5f);
-        a.thr16 = thr > 65535u ? 65535u : thr;
-        a.keep_scale = 1.0f / (1.0f - p);
-    }
+    if (act && step) dropout_consts(p, &a.thr16, &a.keep_scale);
     return a;
 }
 

@@ -30,27 +30,15 @@ template <int H, int D>
 __global__ __launch_bounds__(kInferThreads) void topological_infer_kernel(const InferArgs a) {
     extern __shared__ float4 infer_lds_raw[];
     float* lds = reinterpret_cast<float*>(infer_lds_raw);
-    const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    float* orow = a.out + b * a.O;
-
-    const int64_t n0 = a.node_ptr[b], e0 = a.edge_ptr[b];
-    const int64_t nn = a.node_ptr[b + 1] - n0, mm = a.edge_ptr[b + 1] - e0;
-    // host-side size bound violated, or slices that do not lie inside the arrays: flag, write NaN, touch nothing else
-    if (!infer_slices_ok(a, n0, e0, nn, mm)) {
-        if (tid == 0 && a.status) atomicOr(a.status, 2);
-        if (tid < a.O) orow[tid] = __builtin_nanf("");
+    const InferGraph g = infer_prologue<H, D, kInferEval>(a, lds);
+    float* orow = a.out + (int64_t)blockIdx.x * a.O;
+    if (g.bad) {                                        // flag, a NaN row, nothing else
+        infer_refuse(a, g.bad, orow);
         return;
     }
-    const int n = (int)nn, m = (int)mm;
+    // (the layout restated behind the check, not g.L: two SGPRs fewer at D = 3, which is an occupancy step there)
     const InferLds L = infer_lds(a.cap_n, a.cap_m, H, D);
-    const int bad = infer_phases12<H, D>(a, lds, L, n0, e0, n, m);
-    if (bad) {
-        if (tid == 0 && a.status) atomicOr(a.status, bad);
-        if (tid < a.O) orow[tid] = __builtin_nanf("");
-        return;
-    }
-    infer_phases34<H, D, false>(a, lds, L, n, lds + L.x1, orow, InferDrop{});
+    infer_phases34<H, D, false>(a, lds, L, (int)g.n, lds + L.x1, orow, InferDrop{});
 }
 
 }  // namespace qot
@@ -58,20 +46,10 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_kernel(const 
 using namespace qot;
 
 extern "C" int qot_topological_infer_supported(int n_max, int max_e, int H, int D, int O) {
-    if (!infer_shape_ok(H, D, O) || n_max < 0 || n_max > kInferMaxN || max_e < 0) return 0;
-    if (max_e > (1 << 20)) return 0;                   // (keeps the word count below 2^31)
-    return (size_t)infer_lds(n_max, max_e, H, D).words * 4 <= kInferLdsMax ? 1 : 0;
+    return infer_supported(kInferEval, n_max, max_e, H, D, O);
 }
 
-extern "C" int qot_topological_infer_max_edges(int n_max, int H, int D) {
-    if (!qot_topological_infer_supported(n_max, 0, H, D, 1)) return -1;
-    int lo = 0, hi = 1 << 20;                          // the layout grows with max_e: largest accepted value by bisection
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (qot_topological_infer_supported(n_max, mid, H, D, 1)) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+extern "C" int qot_topological_infer_max_edges(int n_max, int H, int D) { return infer_max_edges(kInferEval, n_max, H, D); }
 
 extern "C" int qot_topological_infer(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
                                      const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t B,
@@ -80,31 +58,13 @@ extern "C" int qot_topological_infer(const int64_t* node_ids, const int64_t* edg
                                      const float* bias2, const float* w0, const float* b0, const float* w3, const float* b3,
                                      float slope_conv, float slope_head, float* out, int H, int D, int O, int32_t* status,
                                      qot_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (N < 0 || E < 0 || B < 0 || n_max < 0 || max_e < 0 || V <= 0) return QOT_ERR_BADARG;
-    if (!qot_topological_infer_supported(n_max, max_e, H, D, O)) return QOT_ERR_UNSUPPORTED;
-    if (B == 0) return QOT_OK;
-    if (B > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
-    const int arc = infer_args_check(node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, t4, ld4, M, ldm, P, V, w_edge,
-                                     w1, b1, wcat, bias2, w0, b0, w3, b3, out, H);
-    if (arc != QOT_OK) return arc;
-    const InferArgs a{node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, B, n_max, max_e, t4, ld4, M, ldm, P, V,
-                      w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, O, status};
-    const size_t lds = (size_t)infer_lds(n_max, max_e, H, D).words * 4;
-#define QOT_INFER_CASE(HH, DD)                                                                                         \
-    case HH * 8 + DD: {                                                                                                \
-        static size_t allowed[kMaxDevices];                                                                            \
-        const int lrc = ensure_dyn_lds(reinterpret_cast<const void*>(topological_infer_kernel<HH, DD>), lds, allowed); \
-        if (lrc != QOT_OK) return lrc;                                                                                 \
-        topological_infer_kernel<HH, DD><<<(int)B, kInferThreads, lds, stream>>>(a);                                   \
-    } break;
-    switch (H * 8 + D) {
-        QOT_INFER_CASE(16, 1) QOT_INFER_CASE(16, 2) QOT_INFER_CASE(16, 3) QOT_INFER_CASE(16, 4)
-        QOT_INFER_CASE(32, 1) QOT_INFER_CASE(32, 2) QOT_INFER_CASE(32, 3) QOT_INFER_CASE(32, 4)
-        QOT_INFER_CASE(64, 1) QOT_INFER_CASE(64, 2) QOT_INFER_CASE(64, 3) QOT_INFER_CASE(64, 4)
-        default: return QOT_ERR_UNSUPPORTED;
-    }
-#undef QOT_INFER_CASE
-    QOT_LAUNCH_CHECK();
-    return QOT_OK;
+    if (!infer_sizes_ok(N, E, B, n_max, max_e, V)) return QOT_ERR_BADARG;
+    if (!infer_supported(kInferEval, n_max, max_e, H, D, O)) return QOT_ERR_UNSUPPORTED;
+    InferArgs a;
+    const int rc = infer_make_args(&a, node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, B, n_max, max_e, t4, ld4, M,
+                                   ldm, P, V, w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, H, O,
+                                   status);
+    if (rc != QOT_OK || B == 0) return rc;
+    QOT_INFER_DISPATCH(topological_infer_kernel, H, D, dim3((unsigned)B), infer_lds_bytes(kInferEval, n_max, max_e, H, D),
+                       (hipStream_t)stream_, a)
 }

@@ -7,6 +7,8 @@
 // counter-based dropout (common.hpp: act_hash64) behind conv2's leaky_relu and inside the read-out; conv1's dropout is a
 // masked copy of x1 the caller hands in as `xin`.  Every sum runs in the same order in both.  GRAD (the sensitivity
 // kernel) keeps the branches the two leaky_relus took -- nothing else changes, the sums are the eval forward's.
+// Around the phases, stated once for the three: a kernel's first steps (infer_prologue, infer_refuse) and, at the end of
+// this file, the host path of an entry point -- the envelope answers, the argument checks, the dispatch over (H, D).
 #pragma once
 #include "graph_prep_dev.hpp"
 
@@ -210,6 +212,36 @@ __device__ __forceinline__ int infer_phases12(const InferArgs& a, float* lds, co
     return 0;
 }
 
+// ---- a kernel's first steps on graph blockIdx.x: its slices as the arrays state them, checked, then phases 1 and 2.
+// bad: 0, or the status bits of the breach (uniform); n and m fit an int when it is 0
+struct InferGraph {
+    int64_t n0, e0, n, m;
+    int bad;
+    InferLds L;                         // the variant's image for the launch's caps
+};
+template <int H, int D, InferVariant VAR>
+__device__ __forceinline__ InferGraph infer_prologue(const InferArgs& a, float* lds) {
+    const int64_t b = blockIdx.x;
+    InferGraph g;
+    g.n0 = a.node_ptr[b];
+    g.e0 = a.edge_ptr[b];
+    g.n = a.node_ptr[b + 1] - g.n0;
+    g.m = a.edge_ptr[b + 1] - g.e0;
+    // host-side size bound violated, or slices that do not lie inside the arrays: nothing else is touched
+    g.bad = infer_slices_ok(a, g.n0, g.e0, g.n, g.m) ? 0 : 2;
+    g.L = infer_lds(a.cap_n, a.cap_m, H, D, VAR);
+    if (g.bad) return g;
+    g.bad = infer_phases12<H, D>(a, lds, g.L, g.n0, g.e0, (int)g.n, (int)g.m);
+    return g;
+}
+
+// a refused graph: flag the launch's status word, NaN in one output row
+__device__ __forceinline__ void infer_refuse(const InferArgs& a, int bad, float* row) {
+    const int tid = threadIdx.x;
+    if (tid == 0 && a.status) atomicOr(a.status, bad);
+    if (tid < a.O) row[tid] = __builtin_nanf("");
+}
+
 // ---- phases 3 and 4 on the first convolution's output `xin` [n, H] (LDS: x1 itself, or a sample's masked copy of it):
 // writes orow[0 .. O).  Ends without a barrier; the LDS it wrote last (h1) is not written again before three barriers of
 // the next call.  GRAD: *ybits gets one bit per row of this thread, (tile number) * RPT + u, set where conv2's
@@ -319,22 +351,78 @@ __device__ __forceinline__ void infer_phases34(const InferArgs& a, float* lds, c
     }
 }
 
-static inline bool infer_shape_ok(int H, int D, int O) {
-    return (H == 16 || H == 32 || H == 64) && D >= 1 && D <= 4 && O >= 1 && O <= 8;
+// ====================================================================== the host path of an entry point
+// qot_topological_infer[_mc|_grad]_supported / _max_edges: one layout, one answer per variant
+inline size_t infer_lds_bytes(InferVariant var, int n_max, int max_e, int H, int D) {
+    return (size_t)infer_lds(n_max, max_e, H, D, var).words * 4;
 }
 
-// the pointer / size checks both entry points make (QOT_OK or the error to return)
-static inline int infer_args_check(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
-                                   const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, const float* t4,
-                                   int ld4, const float* M, int ldm, const float* P, int V, const float* w_edge,
-                                   const float* w1, const float* b1, const float* wcat, const float* bias2, const float* w0,
-                                   const float* b0, const float* w3, const float* b3, const float* out, int H) {
+inline int infer_supported(InferVariant var, int n_max, int max_e, int H, int D, int O) {
+    const bool shape_ok = (H == 16 || H == 32 || H == 64) && D >= 1 && D <= 4 && O >= 1 && O <= 8;
+    if (!shape_ok || n_max < 0 || n_max > kInferMaxN || max_e < 0) return 0;
+    if (max_e > (1 << 20)) return 0;                   // (keeps the word count below 2^31)
+    return infer_lds_bytes(var, n_max, max_e, H, D) <= kInferLdsMax ? 1 : 0;
+}
+
+inline int infer_max_edges(InferVariant var, int n_max, int H, int D) {
+    if (!infer_supported(var, n_max, 0, H, D, 1)) return -1;
+    int lo = 0, hi = 1 << 20;                          // the layout grows with max_e: largest accepted value by bisection
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (infer_supported(var, n_max, mid, H, D, 1)) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// An entry point checks in this order: infer_sizes_ok (else QOT_ERR_BADARG), its own arguments and its variant's
+// infer_supported, then infer_make_args.
+inline bool infer_sizes_ok(int64_t N, int64_t E, int64_t B, int n_max, int max_e, int V) {
+    return !(N < 0 || E < 0 || B < 0 || n_max < 0 || max_e < 0 || V <= 0);
+}
+
+// The common arguments of an entry point, in the ABI's order (edge_dim is not needed here): QOT_OK with *a filled, or
+// the error to return.  B == 0 is QOT_OK before any pointer is looked at; the caller launches nothing then.
+inline int infer_make_args(InferArgs* a, const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                           const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t B, int n_max,
+                           int max_e, const float* t4, int ld4, const float* M, int ldm, const float* P, int V,
+                           const float* w_edge, const float* w1, const float* b1, const float* wcat, const float* bias2,
+                           const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
+                           float slope_head, float* out, int H, int O, int32_t* status) {
+    if (B == 0) return QOT_OK;
+    if (B > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
     if (ld4 < 4 * H || (ld4 & 3) || ldm < V) return QOT_ERR_BADARG;
     if (!node_ptr || !edge_ptr || !t4 || !M || !P || !w_edge || !w1 || !b1 || !wcat || !bias2 || !w0 || !b0 || !w3 || !b3 ||
         !out)
         return QOT_ERR_BADARG;
     if ((N > 0 && !node_ids) || (E > 0 && (!edge_index || !edge_attr))) return QOT_ERR_BADARG;
+    *a = InferArgs{node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, B, n_max, max_e, t4, ld4, M, ldm, P, V,
+                   w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, O, status};
+    return QOT_OK;
+}
+
+// One launch of kernel instantiation Kernel, 256 threads per workgroup; more than 64 KB of dynamic LDS is allowed first
+// (the attribute is per kernel and per device: every instantiation has its own table).
+template <auto Kernel, class... Args>
+inline int infer_launch(dim3 grid, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+    static size_t allowed[kMaxDevices];
+    const int lrc = ensure_dyn_lds(reinterpret_cast<const void*>(Kernel), lds_bytes, allowed);
+    if (lrc != QOT_OK) return lrc;
+    Kernel<<<grid, kInferThreads, lds_bytes, stream>>>(args...);
+    QOT_LAUNCH_CHECK();
     return QOT_OK;
 }
 
 }  // namespace qot
+
+// The (H, D) switch of the three entry points: returns infer_launch<KERNEL<H, D>>(grid, lds_bytes, stream, args...) from
+// the calling function, QOT_ERR_UNSUPPORTED outside {16, 32, 64} x {1 .. 4}.
+#define QOT_INFER_CASE(KERNEL, HH, DD, ...) \
+    case HH * 8 + DD: return qot::infer_launch<KERNEL<HH, DD>>(__VA_ARGS__);
+#define QOT_INFER_ROW(KERNEL, HH, ...) \
+    QOT_INFER_CASE(KERNEL, HH, 1, __VA_ARGS__) QOT_INFER_CASE(KERNEL, HH, 2, __VA_ARGS__) \
+    QOT_INFER_CASE(KERNEL, HH, 3, __VA_ARGS__) QOT_INFER_CASE(KERNEL, HH, 4, __VA_ARGS__)
+#define QOT_INFER_DISPATCH(KERNEL, H, D, ...)                                                                       \
+    switch ((H) * 8 + (D)) {                                                                                        \
+        QOT_INFER_ROW(KERNEL, 16, __VA_ARGS__) QOT_INFER_ROW(KERNEL, 32, __VA_ARGS__) QOT_INFER_ROW(KERNEL, 64, __VA_ARGS__) \
+        default: return QOT_ERR_UNSUPPORTED;                                                                        \
+    }

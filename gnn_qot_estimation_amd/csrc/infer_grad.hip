@@ -44,17 +44,13 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_grad_kernel(c
     const int64_t b = blockIdx.x;
     float* orow = a.out + b * a.O;
 
-    const int64_t n0 = a.node_ptr[b], e0 = a.edge_ptr[b];
-    const int64_t nn = a.node_ptr[b + 1] - n0, mm = a.edge_ptr[b + 1] - e0;
-    int bad = infer_slices_ok(a, n0, e0, nn, mm) ? 0 : 2;
-    const InferLds L = infer_lds(a.cap_n, a.cap_m, H, D, kInferGrad);
-    const int n = (int)nn, m = (int)mm;
-    if (!bad) bad = infer_phases12<H, D>(a, lds, L, n0, e0, n, m);
-    if (bad) {                                          // flag, NaN in all three outputs of the graph, nothing else
-        if (tid == 0 && a.status) atomicOr(a.status, bad);
-        if (tid < a.O) orow[tid] = __builtin_nanf("");
+    const InferGraph g = infer_prologue<H, D, kInferGrad>(a, lds);
+    const InferLds& L = g.L;
+    const int64_t e0 = g.e0;
+    if (g.bad) {                                        // flag, NaN in all three outputs of the graph, nothing else
+        infer_refuse(a, g.bad, orow);
         // (slices that leave the arrays: the part of the edge range that lies inside them)
-        const int64_t lo = e0 < 0 ? 0 : e0, hi = mm < 0 ? lo : (e0 + mm > a.E ? a.E : e0 + mm);
+        const int64_t lo = e0 < 0 ? 0 : e0, hi = g.m < 0 ? lo : (e0 + g.m > a.E ? a.E : e0 + g.m);
         for (int64_t e = lo + tid; e < hi; e += NT) {
             if (ga.alpha) ga.alpha[e] = __builtin_nanf("");
             for (int q = 0; q < ga.Q; ++q)
@@ -62,6 +58,7 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_grad_kernel(c
         }
         return;
     }
+    const int n = (int)g.n, m = (int)g.m;
     unsigned int ybits = 0;
     infer_phases34<H, D, false, true>(a, lds, L, n, lds + L.x1, orow, InferDrop{}, &ybits);
     if (m == 0) return;                                 // (uniform) no edge: nothing to differentiate
@@ -242,19 +239,11 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_grad_kernel(c
 using namespace qot;
 
 extern "C" int qot_topological_infer_grad_supported(int n_max, int max_e, int H, int D, int O) {
-    if (!infer_shape_ok(H, D, O) || n_max < 0 || n_max > kInferMaxN || max_e < 0) return 0;
-    if (max_e > (1 << 20)) return 0;                   // (keeps the word count below 2^31)
-    return (size_t)infer_lds(n_max, max_e, H, D, kInferGrad).words * 4 <= kInferLdsMax ? 1 : 0;
+    return infer_supported(kInferGrad, n_max, max_e, H, D, O);
 }
 
 extern "C" int qot_topological_infer_grad_max_edges(int n_max, int H, int D) {
-    if (!qot_topological_infer_grad_supported(n_max, 0, H, D, 1)) return -1;
-    int lo = 0, hi = 1 << 20;                          // the layout grows with max_e: largest accepted value by bisection
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (qot_topological_infer_grad_supported(n_max, mid, H, D, 1)) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+    return infer_max_edges(kInferGrad, n_max, H, D);
 }
 
 extern "C" int qot_topological_infer_grad(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
@@ -265,35 +254,17 @@ extern "C" int qot_topological_infer_grad(const int64_t* node_ids, const int64_t
                                           const float* w3, const float* b3, float slope_conv, float slope_head, float* out,
                                           int H, int D, int O, int32_t* status, const int32_t* outputs, int Q, float* jac,
                                           float* alpha, qot_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (N < 0 || E < 0 || B < 0 || n_max < 0 || max_e < 0 || V <= 0) return QOT_ERR_BADARG;
-    if (!qot_topological_infer_grad_supported(n_max, max_e, H, D, O)) return QOT_ERR_UNSUPPORTED;
+    if (!infer_sizes_ok(N, E, B, n_max, max_e, V)) return QOT_ERR_BADARG;
+    if (!infer_supported(kInferGrad, n_max, max_e, H, D, O)) return QOT_ERR_UNSUPPORTED;
     if (Q < 1 || Q > O) return QOT_ERR_UNSUPPORTED;
     if (!(slope_conv > 0.f)) return QOT_ERR_UNSUPPORTED;    // conv1's branch is read off the sign of its OUTPUT
     if (!outputs || (E > 0 && !jac)) return QOT_ERR_BADARG;
-    if (B == 0) return QOT_OK;
-    if (B > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
-    const int arc = infer_args_check(node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, t4, ld4, M, ldm, P, V, w_edge,
-                                     w1, b1, wcat, bias2, w0, b0, w3, b3, out, H);
-    if (arc != QOT_OK) return arc;
-    const InferArgs a{node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, B, n_max, max_e, t4, ld4, M, ldm, P, V,
-                      w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, O, status};
+    InferArgs a;
+    const int rc = infer_make_args(&a, node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, B, n_max, max_e, t4, ld4, M,
+                                   ldm, P, V, w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, H, O,
+                                   status);
+    if (rc != QOT_OK || B == 0) return rc;
     const InferGradArgs ga{outputs, Q, jac, alpha};
-    const size_t lds = (size_t)infer_lds(n_max, max_e, H, D, kInferGrad).words * 4;
-#define QOT_INFER_GRAD_CASE(HH, DD)                                                                                         \
-    case HH * 8 + DD: {                                                                                                     \
-        static size_t allowed[kMaxDevices];                                                                                 \
-        const int lrc = ensure_dyn_lds(reinterpret_cast<const void*>(topological_infer_grad_kernel<HH, DD>), lds, allowed); \
-        if (lrc != QOT_OK) return lrc;                                                                                      \
-        topological_infer_grad_kernel<HH, DD><<<(int)B, kInferThreads, lds, stream>>>(a, ga);                               \
-    } break;
-    switch (H * 8 + D) {
-        QOT_INFER_GRAD_CASE(16, 1) QOT_INFER_GRAD_CASE(16, 2) QOT_INFER_GRAD_CASE(16, 3) QOT_INFER_GRAD_CASE(16, 4)
-        QOT_INFER_GRAD_CASE(32, 1) QOT_INFER_GRAD_CASE(32, 2) QOT_INFER_GRAD_CASE(32, 3) QOT_INFER_GRAD_CASE(32, 4)
-        QOT_INFER_GRAD_CASE(64, 1) QOT_INFER_GRAD_CASE(64, 2) QOT_INFER_GRAD_CASE(64, 3) QOT_INFER_GRAD_CASE(64, 4)
-        default: return QOT_ERR_UNSUPPORTED;
-    }
-#undef QOT_INFER_GRAD_CASE
-    QOT_LAUNCH_CHECK();
-    return QOT_OK;
+    QOT_INFER_DISPATCH(topological_infer_grad_kernel, H, D, dim3((unsigned)B), infer_lds_bytes(kInferGrad, n_max, max_e, H, D),
+                       (hipStream_t)stream_, a, ga)
 }

@@ -34,18 +34,14 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_mc_kernel(con
     const int64_t tstride = a.B * a.O;
     float* orow = mc.samples + b * a.O;                                // + t * tstride: sample t's row of this graph
 
-    const int64_t n0 = a.node_ptr[b], e0 = a.edge_ptr[b];
-    const int64_t nn = a.node_ptr[b + 1] - n0, mm = a.edge_ptr[b + 1] - e0;
-    int bad = infer_slices_ok(a, n0, e0, nn, mm) ? 0 : 2;
-    const InferLds L = infer_lds(a.cap_n, a.cap_m, H, D, kInferMc);
-    const int n = (int)nn, m = (int)mm;
-    if (!bad) bad = infer_phases12<H, D>(a, lds, L, n0, e0, n, m);
-    if (bad) {                                                         // as the eval kernel: flag, NaN rows, nothing else
-        if (tid == 0 && a.status) atomicOr(a.status, bad);
-        if (tid < a.O)
-            for (int t = t0; t < t1; ++t) orow[t * tstride + tid] = __builtin_nanf("");
+    const InferGraph g = infer_prologue<H, D, kInferMc>(a, lds);
+    const InferLds& L = g.L;
+    if (g.bad) {                                                       // as the eval kernel: flag, NaN rows, nothing else
+        for (int t = t0; t < t1; ++t) infer_refuse(a, g.bad, orow + t * tstride);
         return;
     }
+    const int64_t n0 = g.n0;
+    const int n = (int)g.n;
     const float4* x1 = reinterpret_cast<const float4*>(lds + L.x1);
     float4* x1d = reinterpret_cast<float4*>(lds + L.x1d);
     const uint64_t q0 = ((uint64_t)n0 * H) >> 2;                       // first float4 of the graph's rows in [N, H]
@@ -73,36 +69,15 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_mc_kernel(con
     }
 }
 
-// round(p * 65536) clamped to 65535 and 1 / (1 - p) in fp32, as make_act (common.hpp) states them
-static void mc_threshold(float p, uint32_t* thr16, float* scale) {
-    *thr16 = 0;
-    *scale = 1.0f;
-    if (p > 0.f) {
-        const uint32_t thr = (uint32_t)(p * 65536.0f + 0.5f);
-        *thr16 = thr > 65535u ? 65535u : thr;
-        *scale = 1.0f / (1.0f - p);
-    }
-}
-
 }  // namespace qot
 
 using namespace qot;
 
 extern "C" int qot_topological_infer_mc_supported(int n_max, int max_e, int H, int D, int O) {
-    if (!infer_shape_ok(H, D, O) || n_max < 0 || n_max > kInferMaxN || max_e < 0) return 0;
-    if (max_e > (1 << 20)) return 0;                   // (keeps the word count below 2^31)
-    return (size_t)infer_lds(n_max, max_e, H, D, kInferMc).words * 4 <= kInferLdsMax ? 1 : 0;
+    return infer_supported(kInferMc, n_max, max_e, H, D, O);
 }
 
-extern "C" int qot_topological_infer_mc_max_edges(int n_max, int H, int D) {
-    if (!qot_topological_infer_mc_supported(n_max, 0, H, D, 1)) return -1;
-    int lo = 0, hi = 1 << 20;                          // the layout grows with max_e: largest accepted value by bisection
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (qot_topological_infer_mc_supported(n_max, mid, H, D, 1)) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+extern "C" int qot_topological_infer_mc_max_edges(int n_max, int H, int D) { return infer_max_edges(kInferMc, n_max, H, D); }
 
 extern "C" int qot_topological_infer_mc(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
                                         const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t B,
@@ -112,42 +87,23 @@ extern "C" int qot_topological_infer_mc(const int64_t* node_ids, const int64_t* 
                                         const float* w3, const float* b3, float slope_conv, float slope_head, float* samples,
                                         int H, int D, int O, int32_t* status, int T, int64_t first_step, uint64_t base_seed,
                                         float p_conv, float p_head, int chunk, qot_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (N < 0 || E < 0 || B < 0 || n_max < 0 || max_e < 0 || V <= 0 || first_step < 0) return QOT_ERR_BADARG;
+    if (!infer_sizes_ok(N, E, B, n_max, max_e, V) || first_step < 0) return QOT_ERR_BADARG;
     if (!(p_conv >= 0.f && p_conv < 1.f) || !(p_head >= 0.f && p_head < 1.f)) return QOT_ERR_BADARG;
     if (T < 1 || T > 4096 || chunk < 1 || chunk > T) return QOT_ERR_UNSUPPORTED;
     const int chunks = (T + chunk - 1) / chunk;
     if (chunks > 65535) return QOT_ERR_UNSUPPORTED;
-    if (!qot_topological_infer_mc_supported(n_max, max_e, H, D, O)) return QOT_ERR_UNSUPPORTED;
-    if (B == 0) return QOT_OK;
-    if (B > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
-    const int arc = infer_args_check(node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, t4, ld4, M, ldm, P, V, w_edge,
-                                     w1, b1, wcat, bias2, w0, b0, w3, b3, samples, H);
-    if (arc != QOT_OK) return arc;
-    const InferArgs a{node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, B, n_max, max_e, t4, ld4, M, ldm, P, V,
-                      w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, nullptr, O, status};
+    if (!infer_supported(kInferMc, n_max, max_e, H, D, O)) return QOT_ERR_UNSUPPORTED;
+    InferArgs a;                                       // (a.out = samples: the kernel writes through mc.samples)
+    const int rc = infer_make_args(&a, node_ids, edge_index, edge_attr, node_ptr, edge_ptr, N, E, B, n_max, max_e, t4, ld4, M,
+                                   ldm, P, V, w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, samples, H,
+                                   O, status);
+    if (rc != QOT_OK || B == 0) return rc;
     const uint64_t golden = 0x9E3779B97F4A7C15ull;     // TopologicalGNN._act: site seed = base + golden * site (mod 2^64)
     InferMcArgs mc;
     mc.samples = samples; mc.T = T; mc.chunk = chunk; mc.first_step = (uint64_t)first_step;
     mc.seed_conv1 = base_seed + golden * 1; mc.seed_conv2 = base_seed + golden * 2; mc.seed_head = base_seed + golden * 97;
-    mc_threshold(p_conv, &mc.thr_conv, &mc.scale_conv);
-    mc_threshold(p_head, &mc.thr_head, &mc.scale_head);
-    const size_t lds = (size_t)infer_lds(n_max, max_e, H, D, kInferMc).words * 4;
-    const dim3 grid((unsigned)B, (unsigned)chunks);
-#define QOT_INFER_MC_CASE(HH, DD)                                                                                         \
-    case HH * 8 + DD: {                                                                                                   \
-        static size_t allowed[kMaxDevices];                                                                               \
-        const int lrc = ensure_dyn_lds(reinterpret_cast<const void*>(topological_infer_mc_kernel<HH, DD>), lds, allowed); \
-        if (lrc != QOT_OK) return lrc;                                                                                    \
-        topological_infer_mc_kernel<HH, DD><<<grid, kInferThreads, lds, stream>>>(a, mc);                                 \
-    } break;
-    switch (H * 8 + D) {
-        QOT_INFER_MC_CASE(16, 1) QOT_INFER_MC_CASE(16, 2) QOT_INFER_MC_CASE(16, 3) QOT_INFER_MC_CASE(16, 4)
-        QOT_INFER_MC_CASE(32, 1) QOT_INFER_MC_CASE(32, 2) QOT_INFER_MC_CASE(32, 3) QOT_INFER_MC_CASE(32, 4)
-        QOT_INFER_MC_CASE(64, 1) QOT_INFER_MC_CASE(64, 2) QOT_INFER_MC_CASE(64, 3) QOT_INFER_MC_CASE(64, 4)
-        default: return QOT_ERR_UNSUPPORTED;
-    }
-#undef QOT_INFER_MC_CASE
-    QOT_LAUNCH_CHECK();
-    return QOT_OK;
+    dropout_consts(p_conv, &mc.thr_conv, &mc.scale_conv);
+    dropout_consts(p_head, &mc.thr_head, &mc.scale_head);
+    QOT_INFER_DISPATCH(topological_infer_mc_kernel, H, D, dim3((unsigned)B, (unsigned)chunks),
+                       infer_lds_bytes(kInferMc, n_max, max_e, H, D), (hipStream_t)stream_, a, mc)
 }

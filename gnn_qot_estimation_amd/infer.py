@@ -10,6 +10,8 @@ kernel launch per call and touches autograd nowhere.
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 
 from . import _lib
@@ -37,21 +39,33 @@ def wcat_index(h: int, k: int, device) -> torch.Tensor:
     return _WCAT_IDX[key]
 
 
+# kind -> (the envelope's symbol, the edge cap's symbol, the word the error message puts before "edge cap")
+_KINDS = {
+    "eval": ("qot_topological_infer_supported", "qot_topological_infer_max_edges", ""),
+    "mc": ("qot_topological_infer_mc_supported", "qot_topological_infer_mc_max_edges", "sampling "),
+    "grad": ("qot_topological_infer_grad_supported", "qot_topological_infer_grad_max_edges", "sensitivity "),
+}
+
+
+def _edge_cap(kind, n_max, hidden, edge_dim):
+    return int(getattr(_lib.load(), _KINDS[kind][1])(int(n_max), int(hidden), int(edge_dim)))
+
+
 def edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
     """Most edges a graph may have beside ``n_max`` nodes (the kernel's LDS budget, asked of the library); -1: none."""
-    return int(_lib.load().qot_topological_infer_max_edges(int(n_max), int(hidden), int(edge_dim)))
+    return _edge_cap("eval", n_max, hidden, edge_dim)
 
 
 def mc_edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
     """``edge_cap`` of the sampling kernel (``TopologicalPredictor.sample``): lower, its LDS image also holds the sample's
     masked copy of the first convolution's output; -1: none."""
-    return int(_lib.load().qot_topological_infer_mc_max_edges(int(n_max), int(hidden), int(edge_dim)))
+    return _edge_cap("mc", n_max, hidden, edge_dim)
 
 
 def grad_edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
     """``edge_cap`` of the sensitivity kernel (``TopologicalPredictor.sensitivity``): lower, its LDS image also holds the
     adjoint of the first convolution's output and ``2 * edge_dim`` more words per edge; -1: none."""
-    return int(_lib.load().qot_topological_infer_grad_max_edges(int(n_max), int(hidden), int(edge_dim)))
+    return _edge_cap("grad", n_max, hidden, edge_dim)
 
 
 def grad_outputs(outputs, num_outputs: int):
@@ -159,6 +173,10 @@ def graph_slices(data, ei, N, dev, who):
         return int((ptr[1:] - ptr[:-1]).max()), int((eptr[1:] - eptr[:-1]).max())
     n_max, max_e = (int(sizes[0]), int(sizes[1])) if sizes is not None else exact()
     return ptr, eptr, B, n_max, max_e, exact
+
+
+# what TopologicalPredictor._prepare hands to _launch: the model's shape, the batch on dev, its size bounds, the tables
+_Prepared = namedtuple("_Prepared", "H D O dev ids ei ea ptr eptr n_max max_e B tables")
 
 
 class TopologicalPredictor:
@@ -287,10 +305,9 @@ class TopologicalPredictor:
             c["infer_ids_ok"] = tag
 
     # ------------------------------------------------------------------ the call
-    def _prepare(self, data, mc=False, grad=False):
-        """Everything a launch needs, checked: ``(H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, tables)``.  ``mc``
-        / ``grad``: the envelope of the sampling kernel (``qot_topological_infer_mc``) / of the sensitivity kernel
-        (``qot_topological_infer_grad``) instead of the eval kernel's."""
+    def _prepare(self, data, kind="eval"):
+        """Everything a launch needs, checked, as a ``_Prepared``.  ``kind``: whose envelope holds -- the eval kernel's, the
+        sampling kernel's (``"mc"``) or the sensitivity kernel's (``"grad"``); see ``_KINDS``."""
         H, D, O = self._check_model()
         m = self.model
         if data.x is not None and data.x.numel():
@@ -298,16 +315,13 @@ class TopologicalPredictor:
                              "table) is supported")
         dev = m.node_embeddings.weight.device
         ids, ei, ptr, eptr, n_max, max_e, B, exact = self._slices(data, dev)
-        lib = _lib.load()
-        supported = (lib.qot_topological_infer_grad_supported if grad else
-                     lib.qot_topological_infer_mc_supported if mc else lib.qot_topological_infer_supported)
-        if n_max > MAX_NODES or not supported(n_max, max_e, H, D, O):
+        supported, _, which = _KINDS[kind]
+        if n_max > MAX_NODES or not getattr(_lib.load(), supported)(n_max, max_e, H, D, O):
             n_max, max_e = exact()          # the carried sizes are bounds (a shard inherits its parent's): look once
             if n_max > MAX_NODES:
                 raise ValueError(f"TopologicalPredictor: a graph of {n_max} nodes; at most {MAX_NODES} nodes per graph")
-            cap = (grad_edge_cap if grad else mc_edge_cap if mc else edge_cap)(n_max, H, D)
+            cap = _edge_cap(kind, n_max, H, D)
             if max_e > cap:
-                which = "sensitivity " if grad else "sampling " if mc else ""
                 raise ValueError(f"TopologicalPredictor: a graph of {max_e} edges is above the {which}"
                                  f"edge cap {cap} for graphs of up to {n_max} nodes at hidden width {H}, edge_dim {D}")
         ea = data.edge_attr
@@ -320,15 +334,20 @@ class TopologicalPredictor:
         self._check_ids(data, ids, t["V"], n_max)
         if self._status is None or self._status.device != dev:
             self._status = torch.zeros(1, dtype=torch.int32, device=dev)
-        return H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t
+        return _Prepared(H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t)
+
+    def _launch(self, name, p, out, *extra):
+        """One launch of entry point ``name``: the arguments the three kernels share (``out`` among them), then ``extra``."""
+        t = p.tables
+        _lib.call(name, p.ids, p.ei, p.ea, p.ptr, p.eptr, p.ids.shape[0], p.ei.shape[1], p.B, p.n_max, p.max_e, t["t4"],
+                  4 * p.H, t["M"], t["ldm"], t["P"], t["V"], t["we"], t["w1"], t["b1"], t["wcat"], t["bias2"], t["w0"], t["b0"],
+                  t["w3"], t["b3"], 0.01, float(self.model.mlp[1].negative_slope), out, p.H, p.D, p.O, self._status, *extra)
 
     @torch.no_grad()
     def __call__(self, data):
-        H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t = self._prepare(data)
-        out = torch.empty(B, O, dtype=torch.float32, device=dev)
-        _lib.call("qot_topological_infer", ids, ei, ea, ptr, eptr, ids.shape[0], ei.shape[1], B, n_max, max_e, t["t4"], 4 * H,
-                  t["M"], t["ldm"], t["P"], t["V"], t["we"], t["w1"], t["b1"], t["wcat"], t["bias2"], t["w0"], t["b0"], t["w3"],
-                  t["b3"], 0.01, float(self.model.mlp[1].negative_slope), out, H, D, O, self._status)
+        p = self._prepare(data)
+        out = torch.empty(p.B, p.O, dtype=torch.float32, device=p.dev)
+        self._launch("qot_topological_infer", p, out)
         return out
 
     @torch.no_grad()
@@ -358,15 +377,12 @@ class TopologicalPredictor:
         T, p_conv, p_head, chunk, first_step = mc_args(samples, p, chunk, first_step,
                                                         (getattr(getattr(m, "dropout", None), "p", 0.0),
                                                          getattr(m.mlp[2], "p", 0.0) if hasattr(m, "mlp") else 0.0))
-        H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t = self._prepare(data, mc=True)
+        prep = self._prepare(data, "mc")
         base = (m._seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
         if chunk is None:
-            chunk = mc_chunk(B, T, torch.cuda.get_device_properties(dev).multi_processor_count)
-        draws = torch.empty(T, B, O, dtype=torch.float32, device=dev)
-        _lib.call("qot_topological_infer_mc", ids, ei, ea, ptr, eptr, ids.shape[0], ei.shape[1], B, n_max, max_e, t["t4"],
-                  4 * H, t["M"], t["ldm"], t["P"], t["V"], t["we"], t["w1"], t["b1"], t["wcat"], t["bias2"], t["w0"], t["b0"],
-                  t["w3"], t["b3"], 0.01, float(m.mlp[1].negative_slope), draws, H, D, O, self._status, T, first_step, base,
-                  p_conv, p_head, chunk)
+            chunk = mc_chunk(prep.B, T, torch.cuda.get_device_properties(prep.dev).multi_processor_count)
+        draws = torch.empty(T, prep.B, prep.O, dtype=torch.float32, device=prep.dev)
+        self._launch("qot_topological_infer_mc", prep, draws, T, first_step, base, p_conv, p_head, chunk)
         mean, std = draws.mean(0), draws.std(0, unbiased=True)
         return (mean, std, draws) if return_samples else (mean, std)
 
@@ -389,18 +405,16 @@ class TopologicalPredictor:
         4.16)."""
         # the model's shape, then the argument, are named before the model's device and the batch are looked at
         sel = grad_outputs(outputs, self._check_model(on_gpu=False)[2])
-        H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t = self._prepare(data, grad=True)
-        E, Q = ei.shape[1], len(sel)
-        out = torch.empty(B, O, dtype=torch.float32, device=dev)
-        jac = torch.empty(Q, E, D, dtype=torch.float32, device=dev)
+        p = self._prepare(data, "grad")
+        E, Q, dev = p.ei.shape[1], len(sel), p.dev
+        out = torch.empty(p.B, p.O, dtype=torch.float32, device=dev)
+        jac = torch.empty(Q, E, p.D, dtype=torch.float32, device=dev)
         alpha = torch.empty(E, 1, dtype=torch.float32, device=dev) if return_attention_weights else None
         cache = self.__dict__.setdefault("_outputs_dev", {})     # one upload per selection: the call stays ONE launch
         osel = cache.get((tuple(sel), dev))
         if osel is None:
             osel = cache[(tuple(sel), dev)] = torch.tensor(sel, dtype=torch.int32, device=dev)
-        _lib.call("qot_topological_infer_grad", ids, ei, ea, ptr, eptr, ids.shape[0], E, B, n_max, max_e, t["t4"], 4 * H,
-                  t["M"], t["ldm"], t["P"], t["V"], t["we"], t["w1"], t["b1"], t["wcat"], t["bias2"], t["w0"], t["b0"], t["w3"],
-                  t["b3"], 0.01, float(self.model.mlp[1].negative_slope), out, H, D, O, self._status, osel, Q, jac, alpha)
+        self._launch("qot_topological_infer_grad", p, out, osel, Q, jac, alpha)
         if return_attention_weights:
             return out, jac, (data.edge_index, alpha)
         return out, jac

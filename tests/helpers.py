@@ -224,3 +224,35 @@ def oracle_trajectory(case, dtype, **kw):
     res = train_loop.train(model, trajectory_graphs(case), case["kind"], dtype=dtype, **case["fit"], **kw)
     res["param_names"] = [n for n, p in model.named_parameters() if p.requires_grad]
     return res
+
+
+def infer_common_args(H=16, D=4, O=3, **kw):
+    """The arguments ``qot_topological_infer``, ``_mc`` and ``_grad`` share, up to the status word, for calls that are
+    refused (or, with ``B = 0``, answered) before any pointer is read: every pointer is 1 unless ``kw`` names it."""
+    import ctypes
+    a = dict(node_ids=1, edge_index=1, edge_attr=1, node_ptr=1, edge_ptr=1, N=10, E=10, B=1, n_max=10, max_e=10, t4=1,
+             ld4=4 * H, M=1, ldm=16, P=1, V=16, w_edge=1, w1=1, b1=1, wcat=1, bias2=1, w0=1, b0=1, w3=1, b3=1,
+             slope_conv=0.01, slope_head=0.01, out=1, H=H, D=D, O=O, status=None)
+    assert set(kw) <= set(a), set(kw) - set(a)
+    a.update(kw)
+    pointers = ("node_ids", "edge_index", "edge_attr", "node_ptr", "edge_ptr", "t4", "M", "P", "w_edge", "w1", "b1", "wcat",
+                "bias2", "w0", "b0", "w3", "b3", "out", "status")
+    return [ctypes.c_void_p(v) if k in pointers else v for k, v in a.items()]
+
+
+# the returns every entry point of the single-launch family makes before its own checks are over, by the argument that
+# provokes them: (kwargs of infer_common_args, QOT_OK 0 / QOT_ERR_UNSUPPORTED -1 / QOT_ERR_BADARG -2)
+INFER_COMMON_REFUSALS = [
+    (dict(N=-1), -2), (dict(E=-1), -2), (dict(B=-1), -2), (dict(n_max=-1), -2), (dict(max_e=-1), -2), (dict(V=0), -2),
+    (dict(H=48), -1), (dict(D=5), -1), (dict(O=9), -1), (dict(n_max=129), -1), (dict(max_e=1 << 21), -1),
+    (dict(B=0), 0), (dict(B=1 << 31), -1),
+    (dict(ld4=60), -2), (dict(ld4=66), -2), (dict(ldm=15), -2),
+    (dict(node_ptr=None), -2), (dict(t4=None), -2), (dict(b3=None), -2), (dict(out=None), -2),
+    (dict(node_ids=None), -2), (dict(edge_attr=None), -2),
+    # two at once: the earlier check of the source order wins
+    (dict(V=0, H=48), -2),                      # sizes before the envelope
+    (dict(H=48, B=0), -1),                      # the envelope before the empty batch
+    (dict(B=0, out=None, ld4=0), 0),            # an empty batch before the leading dimensions and the pointers
+    (dict(B=1 << 31, out=None), -1),            # the batch bound before the pointers
+    (dict(N=0, E=0, node_ids=None, edge_index=None, edge_attr=None, B=1 << 31), -1),   # (legal nulls, then the bound)
+]

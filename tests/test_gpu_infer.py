@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import gnn_qot_estimation_amd as q
-from gnn_qot_estimation_amd import harness, infer, synthetic as S
+from gnn_qot_estimation_amd import _lib, harness, infer, synthetic as S
 from helpers import TOL, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -241,3 +241,61 @@ def test_shipped_checkpoint(cuda_device):
     pred.check_status()
     assert rel_err(out, fx["expected"]) <= TOL
     assert rel_err(out, fx["expected_dense64"]) <= TOL
+
+
+# ------------------------------------------------------------------ refusals inside the kernels
+def _ring(n, seed):
+    """Both directions of a ring of ``n`` nodes, ``edge_dim`` 1."""
+    fwd, nxt = list(range(n)), [(v + 1) % n for v in range(n)]
+    return _custom(n, fwd + nxt, nxt + fwd, D=1, seed=seed)
+
+
+def test_edge_outside_its_graph_is_flagged_and_its_row_nan(cuda_device):
+    _, hip = _models(cuda_device, 8, 16, O=1, D=1)
+    pred = q.TopologicalPredictor(hip)
+    graphs = [_ring(4, 1), _ring(3, 2)]
+    want = pred(q.Batch.from_data_list(graphs).to(cuda_device))
+    pred.check_status()
+    bad = q.Batch.from_data_list(graphs)
+    bad.edge_index[0, int(bad.edge_ptr[1])] = int(bad.ptr[1]) - 1      # a node of graph 0: inside [0, N), outside graph 1
+    got = pred(bad.to(cuda_device))
+    with pytest.raises(_lib.QotError, match="status 1"):
+        pred.check_status()
+    pred.check_status()                                  # (read and cleared)
+    assert torch.isnan(got[1]).all() and torch.equal(got[0], want[0])
+
+
+@pytest.mark.parametrize("kind", ["eval", "mc", "grad"])
+def test_understated_node_bound_is_refused_by_the_kernel(cuda_device, kind):
+    """A launch whose ``n_max`` is below a graph's node count: the kernel compares before it touches its LDS image, flags
+    status 2 and writes NaN to everything of that graph; the other graph's results are those of the honest launch."""
+    _, hip = _models(cuda_device, 8, 16, O=1, D=1)
+    pred = q.TopologicalPredictor(hip)
+    db = q.Batch.from_data_list([_ring(4, 1), _ring(3, 2)]).to(cuda_device)
+    prep = pred._prepare(db, kind)
+    E, e1 = prep.ei.shape[1], int(db.edge_ptr[1])
+    assert (prep.n_max, prep.B, e1, E) == (4, 2, 8, 14)
+
+    def run(p):
+        new = lambda *shape: torch.full(shape, 7.0, device=cuda_device)
+        if kind == "eval":
+            out = new(2, 1)
+            pred._launch("qot_topological_infer", p, out)
+            return [(out[0], out[1])]
+        if kind == "mc":
+            draws = new(2, 2, 1)                         # T = 2 samples in one chunk
+            pred._launch("qot_topological_infer_mc", p, draws, 2, 0, 1234, 0.1, 0.1, 2)
+            return [(draws[:, 0], draws[:, 1])]
+        out, jac, alpha = new(2, 1), new(1, E, 1), new(E, 1)
+        sel = torch.zeros(1, dtype=torch.int32, device=cuda_device)
+        pred._launch("qot_topological_infer_grad", p, out, sel, 1, jac, alpha)
+        return [(out[0], out[1]), (jac[:, :e1], jac[:, e1:]), (alpha[:e1], alpha[e1:])]
+    want = run(prep)
+    pred.check_status()
+    got = run(prep._replace(n_max=3))                    # the 4-node graph is above it
+    with pytest.raises(_lib.QotError, match="status 2"):
+        pred.check_status()
+    pred.check_status()
+    for (g0, g1), (w0, w1) in zip(got, want):
+        assert not torch.isnan(w0).any() and not (w1 == 7.0).any()
+        assert torch.isnan(g0).all() and torch.equal(g1, w1)

@@ -10,6 +10,7 @@ import torch
 
 import gnn_qot_estimation_amd as q
 from gnn_qot_estimation_amd import _lib, harness, infer
+from helpers import INFER_COMMON_REFUSALS, infer_common_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("qot_topological_infer", "qot_topological_infer_supported", "qot_topological_infer_max_edges")
@@ -58,6 +59,24 @@ def test_supported_is_monotone_in_edges_up_to_its_cap(n, H, D):
     assert lib.qot_topological_infer_max_edges(128, H, D) <= cap
     assert lib.qot_topological_infer_max_edges(n, 64, D) <= cap
     assert lib.qot_topological_infer_max_edges(129, H, D) == -1 and lib.qot_topological_infer_max_edges(n, 48, D) == -1
+
+
+# qot_topological_infer{,_mc,_grad}_max_edges at (n, H, D), as the library answered before the three envelopes were one
+# function (1541 / 1114 / 677 at the headline shape also follow from infer_lds by hand)
+PINNED_CAPS = {(100, 64, 4): (1541, 1114, 677), (75, 16, 4): (2240, 2160, 1385), (128, 32, 1): (5599, 4916, 3615)}
+
+
+def test_edge_caps_are_pinned():
+    lib = _lib.load()
+    for shape, want in PINNED_CAPS.items():
+        got = tuple(getattr(lib, f"qot_topological_infer{k}_max_edges")(*shape) for k in ("", "_mc", "_grad"))
+        assert got == want, (shape, got, want)
+        assert (infer.edge_cap(*shape), infer.mc_edge_cap(*shape), infer.grad_edge_cap(*shape)) == want
+
+
+@pytest.mark.parametrize("kw,code", INFER_COMMON_REFUSALS)
+def test_entry_point_return_codes_before_any_launch(kw, code):
+    assert _lib.load().qot_topological_infer(*infer_common_args(**kw), None) == code
 
 
 def test_predictor_refuses_a_cpu_model():

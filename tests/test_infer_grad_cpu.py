@@ -13,7 +13,7 @@ import torch
 import gnn_qot_estimation_amd as q
 from gnn_qot_estimation_amd import _lib, infer
 import infer_grad_cases as C
-from helpers import TOL, rel_err
+from helpers import INFER_COMMON_REFUSALS, TOL, infer_common_args, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("qot_topological_infer_grad", "qot_topological_infer_grad_supported", "qot_topological_infer_grad_max_edges")
@@ -71,6 +71,24 @@ def test_entry_point_refuses_before_any_launch():
         assert call(**kw) == UNSUPPORTED, kw
     for kw in (dict(jac=None), dict(outputs=None)):
         assert call(**kw) == BADARG, kw
+
+
+def _grad_call(Q=1, outputs=1, jac=1, alpha=None, **kw):
+    p = ctypes.c_void_p
+    return _lib.load().qot_topological_infer_grad(*infer_common_args(**kw), p(outputs), Q, p(jac), p(alpha), None)
+
+
+@pytest.mark.parametrize("kw,code", INFER_COMMON_REFUSALS + [
+    # the entry point's own checks, in its source order: the envelope, Q, slope_conv, outputs / jac
+    (dict(Q=0), -1), (dict(Q=4), -1), (dict(Q=2, O=1), -1), (dict(slope_conv=0.0), -1), (dict(slope_conv=float("nan")), -1),
+    (dict(outputs=None), -2), (dict(jac=None), -2), (dict(jac=None, E=0, B=0), 0),
+    # two at once
+    (dict(Q=0, outputs=None), -1), (dict(slope_conv=-1.0, jac=None), -1), (dict(H=48, outputs=None), -1),
+    (dict(V=0, Q=0), -2), (dict(outputs=None, B=0), -2), (dict(Q=0, B=0), -1), (dict(slope_conv=0.0, B=0), -1),
+    (dict(outputs=None, B=1 << 31), -2), (dict(Q=9, O=9), -1),
+])
+def test_entry_point_return_codes_before_any_launch(kw, code):
+    assert _grad_call(**kw) == code
 
 
 def test_outputs_argument_check_needs_no_device():

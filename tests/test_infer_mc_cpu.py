@@ -11,6 +11,7 @@ import torch
 
 import gnn_qot_estimation_amd as q
 from gnn_qot_estimation_amd import _lib, harness, infer
+from helpers import INFER_COMMON_REFUSALS, infer_common_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("qot_topological_infer_mc", "qot_topological_infer_mc_supported", "qot_topological_infer_mc_max_edges")
@@ -59,6 +60,24 @@ def test_entry_point_refuses_before_any_launch():
         assert call(**kw) == UNSUPPORTED, kw
     for kw in (dict(first_step=-1), dict(p_conv=1.0), dict(p_head=-0.5), dict(p_conv=float("nan"))):
         assert call(**kw) == BADARG, kw
+
+
+def _mc_call(T=4, first_step=0, p_conv=0.5, p_head=0.5, chunk=1, **kw):
+    return _lib.load().qot_topological_infer_mc(*infer_common_args(**kw), T, first_step, 0, p_conv, p_head, chunk, None)
+
+
+@pytest.mark.parametrize("kw,code", INFER_COMMON_REFUSALS + [
+    # the entry point's own checks, in its source order: first_step with the sizes, the probabilities, T / chunk, the envelope
+    (dict(first_step=-1), -2), (dict(p_conv=1.0), -2), (dict(p_head=-0.5), -2), (dict(p_head=float("nan")), -2),
+    (dict(T=0), -1), (dict(T=4097), -1), (dict(chunk=0), -1), (dict(chunk=5), -1),
+    (dict(T=4096, chunk=1, B=0), 0),            # (4096 chunks: the grid's y bound is not reached)
+    # two at once
+    (dict(first_step=-1, T=0), -2), (dict(p_conv=1.0, T=0), -2), (dict(p_head=2.0, H=48), -2),
+    (dict(T=0, V=0), -2), (dict(T=0, out=None), -1), (dict(T=0, B=0), -1), (dict(chunk=5, ld4=0), -1),
+    (dict(H=48, ld4=0), -1), (dict(first_step=-1, B=0), -2), (dict(p_conv=1.0, B=0), -2),
+])
+def test_entry_point_return_codes_before_any_launch(kw, code):
+    assert _mc_call(**kw) == code
 
 
 def test_mc_chunk():
