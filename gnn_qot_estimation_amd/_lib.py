@@ -178,6 +178,10 @@ SIGNATURES = {
     "qot_topological_infer_grad": (_int, _INFER_COMMON + [_p, _int, _p, _p, _p]),
     "qot_lightpath_infer": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f,
                                    _p, _p, _p, _p, _f, _p, _p, _int, _int, _int, _int, _int, _p, _p]),
+    # qot_lightpath_infer's arguments up to the status word, then outputs, Q, jac_self, jac_edge, alpha_self, alpha_edge
+    "qot_lightpath_infer_grad": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f, _p, _p, _p, _p,
+                                        _f, _p, _p, _p, _p, _f, _p, _p, _int, _int, _int, _int, _int, _p, _p, _int, _p, _p, _p,
+                                        _p, _p]),
     "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "qot_status_graph_count": (_int, [_p, _p, _p, _i64, _i64, _int, _i64, _i64, _int, _int, _int, C.c_double, _int, _p, _sz, _p,
                                       _p]),

@@ -1,286 +1,21 @@
 // Single-launch inference for LightpathGNN: the eval-mode forward (lightpath_training/models.py:7-45, dropout off) of the
-// LUT rows only, ONE wavefront (a workgroup of 64 threads) per output row.
-//
-// The reference architecture is GATConv(heads = 4) -> BatchNorm (running statistics) -> ReLU -> LUT rows -> MLP, so an output
-// row depends on nothing but the one-hop in-neighbourhood of its LUT node: no graph index, no other node's row.  Because
-// z_j = W x_j, the aggregate of head h factors as out_i[h] = W_h u_h with u_h = sum_e alpha_e x_{j_e} (F numbers per head
-// instead of C), and the logit of a message is leaky_relu(s_h . x_j + d_h . x_i) with s_h = W_h^T att_src_h and
-// d_h = W_h^T att_dst_h.
-//
-// Steps of a row (destination i of graph g; a workgroup barrier between them, which for one wave is a wait on its own
-// LDS traffic):
-//   0  s_h, d_h [4][F]: lane (h, f) walks the C channels of its head; x_i -> LDS; a_dst_h = d_h . x_i and the self loop's logit
-//   1  scan of the graph's edge slice, 64 edges per chunk, lane = offset mod 64: every edge's ends are checked against the
-//      graph's node range; the messages (dst == i, src != i: PyG's remove_self_loops) give the per-head maximum
-//   2  second scan: a message's lane leaves its weights exp(logit - max) and its source row in LDS; then lane (h, f) adds
-//      the chunk's messages to its denominator and to u[h][f] ONE AFTER THE OTHER in slice order; the self loop (PyG's
-//      add_self_loops: exactly one, appended) comes last, then u /= (denominator + 1e-16)
-//   3  lane-strided over the 4C channels: W_h u_h + bias, BatchNorm on running statistics, ReLU -> LDS
-//   4  Linear(4C -> C) + leaky_relu, Linear(C -> O): lanes stride the inner dimension (coalesced rows of the weight), the
-//      64 partial sums of an output go through LDS and are added in lane order by one lane
-// Every sum has one fixed order that depends on the edge's offset inside its graph's slice and on nothing else: a row is
-// bitwise reproducible, and independent of the other graphs of the launch and of the mode that asked for it.  Widths are run
-// time values (loops stride them by lane); the parameters are read in place, nothing is tabulated or cached.
-#include "common.hpp"
+// LUT rows only, ONE wavefront (a workgroup of 64 threads) per output row.  The row itself -- its steps,
+// the order of its sums -- is infer_lightpath_dev.hpp's lp_row, shared with the sensitivity kernel
+// (infer_lightpath_grad.hip).
+#include "infer_lightpath_dev.hpp"
 
 namespace qot {
 namespace {
-
-constexpr int kLpMaxF = 16, kLpMaxC = 256, kLpMaxO = 8, kLpHeads = 4;
-constexpr int kLpXs = kLpMaxF + 1;      // row stride of the staged source rows (odd: lanes of a chunk hit different banks)
-constexpr int kLpTile = 32;             // outputs of a dense layer per pass
-constexpr int kLpPs = kWave + 1;        // row stride of their partial sums
-
-struct LpLds {
-    float s[kLpHeads * kLpMaxF];        // s_h[f]
-    float d[kLpHeads * kLpMaxF];        // d_h[f]
-    float xi[kLpMaxF];                  // the destination's features
-    float ps[kLpHeads];                 // the self loop's weight exp(logit - max)
-    float u[kLpHeads * kLpMaxF];
-    float pw[kLpHeads * kWave];         // a chunk's message weights [h][lane]
-    float xs[kWave * kLpXs];            // a chunk's source rows [lane][f]
-    float y[kLpHeads * kLpMaxC];        // relu(norm(conv)) of the row
-    float h1[kLpMaxC];
-    float part[kLpTile * kLpPs];
-};
-
-struct LpArgs {
-    const float* x; const int64_t* ei; const int64_t* batch; const int64_t* node_ptr; const int64_t* edge_ptr;
-    const int64_t* lut_idx;
-    int64_t L, N, E, B;
-    const float* w; const float* att_src; const float* att_dst; const float* conv_bias; float slope_att;
-    const float* bn_w; const float* bn_b; const float* bn_mean; const float* bn_var; float eps;
-    const float* w0; const float* b0; const float* w3; const float* b3; float slope_head;
-    float* out; int32_t* count;
-    int F, C, O, lut_col;
-    int32_t* status;
-};
-
-__device__ __forceinline__ float lp_leaky(float v, float slope) { return v > 0.f ? v : slope * v; }
-
-__device__ __forceinline__ void lp_refuse(const LpArgs& a, float* orow, int lane, int bit) {
-    if (lane == 0 && a.status) atomicOr(a.status, bit);
-    if (lane < a.O) orow[lane] = __builtin_nanf("");
-}
-
-// dst[o] = sum_q w[o, q] in[q] + b[o] for o < M (leaky_relu behind it when `act`); `in` holds K floats in LDS
-__device__ __forceinline__ void lp_dense(const float* __restrict__ w, const float* __restrict__ b, const float* in, int K, int M,
-                                         bool act, float slope, float* dst, float* part, int lane) {
-    for (int c0 = 0; c0 < M; c0 += kLpTile) {
-        const int nt = M - c0 < kLpTile ? M - c0 : kLpTile;
-        for (int t = 0; t < nt; ++t) {
-            const float* wr = w + (int64_t)(c0 + t) * K;
-            float p = 0.f;
-            for (int q = lane; q < K; q += kWave) p = fmaf(wr[q], in[q], p);
-            part[t * kLpPs + lane] = p;
-        }
-        __syncthreads();
-        if (lane < nt) {
-            float sum = 0.f;
-#pragma unroll 16
-            for (int k = 0; k < kWave; ++k) sum += part[lane * kLpPs + k];
-            sum += b[c0 + lane];
-            dst[c0 + lane] = act ? lp_leaky(sum, slope) : sum;
-        }
-        __syncthreads();
-    }
-}
-
-// the messages of a chunk: lane `lane` looks at the edge at offset base + lane of the slice.  Returns 0 (no message),
-// 1 (a message from `src`) or 2 (an edge that leaves the graph's node range: nothing is read through it)
-__device__ __forceinline__ int lp_edge(const LpArgs& a, int64_t e0, int64_t m, int64_t k, int64_t n0, int64_t n1, int64_t i,
-                                       int64_t& src) {
-    if (k >= m) return 0;
-    const int64_t s = a.ei[e0 + k], d = a.ei[a.E + e0 + k];
-    if (s < n0 || s >= n1 || d < n0 || d >= n1) return 2;
-    src = s;
-    return (d == i && s != i) ? 1 : 0;
-}
-
-// the output row of node i of graph g (0 <= i < N and 0 <= g < B are the caller's)
-__device__ __forceinline__ void lp_row(const LpArgs& a, LpLds& L, int64_t i, int64_t g, float* orow, int lane) {
-    const int F = a.F, C = a.C;
-    const int64_t n0 = a.node_ptr[g], n1 = a.node_ptr[g + 1], e0 = a.edge_ptr[g], e1 = a.edge_ptr[g + 1];
-    if (n0 < 0 || n1 > a.N || i < n0 || i >= n1 || e0 < 0 || e1 < e0 || e1 > a.E) {
-        lp_refuse(a, orow, lane, 2);
-        return;
-    }
-    const int64_t m = e1 - e0;
-
-    // ---- step 0: s_h, d_h, the destination's row ----
-    const int h = lane / F, f = lane - h * F;                  // lanes below 4F own the pair (h, f)
-    if (lane < kLpHeads * F) {
-        const float* w = a.w + (int64_t)h * C * F + f;
-        const float* as = a.att_src + h * C;
-        const float* ad = a.att_dst + h * C;
-        float s = 0.f, d = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float wv = w[c * F];
-            s = fmaf(wv, as[c], s);
-            d = fmaf(wv, ad[c], d);
-        }
-        L.s[h * kLpMaxF + f] = s;
-        L.d[h * kLpMaxF + f] = d;
-    }
-    if (lane < F) L.xi[lane] = a.x[i * F + lane];
-    __syncthreads();
-    float4 adst = f4zero(), lself = f4zero();
-    for (int t = 0; t < F; ++t) {
-        const float xv = L.xi[t];
-        adst.x = fmaf(L.d[0 * kLpMaxF + t], xv, adst.x);
-        adst.y = fmaf(L.d[1 * kLpMaxF + t], xv, adst.y);
-        adst.z = fmaf(L.d[2 * kLpMaxF + t], xv, adst.z);
-        adst.w = fmaf(L.d[3 * kLpMaxF + t], xv, adst.w);
-        lself.x = fmaf(L.s[0 * kLpMaxF + t], xv, lself.x);
-        lself.y = fmaf(L.s[1 * kLpMaxF + t], xv, lself.y);
-        lself.z = fmaf(L.s[2 * kLpMaxF + t], xv, lself.z);
-        lself.w = fmaf(L.s[3 * kLpMaxF + t], xv, lself.w);
-    }
-    lself.x = lp_leaky(lself.x + adst.x, a.slope_att);
-    lself.y = lp_leaky(lself.y + adst.y, a.slope_att);
-    lself.z = lp_leaky(lself.z + adst.z, a.slope_att);
-    lself.w = lp_leaky(lself.w + adst.w, a.slope_att);
-
-    // ---- step 1: range check of the slice, per-head maximum over the messages and the self loop ----
-    float4 mx = lself;
-    bool bad = false;
-    for (int64_t base = 0; base < m; base += kWave) {
-        int64_t src = 0;
-        const int kind = lp_edge(a, e0, m, base + lane, n0, n1, i, src);
-        bad = bad || kind == 2;
-        if (kind == 1) {
-            const float* xj = a.x + src * F;
-            float4 l = f4zero();
-            for (int t = 0; t < F; ++t) {
-                const float xv = xj[t];
-                l.x = fmaf(L.s[0 * kLpMaxF + t], xv, l.x);
-                l.y = fmaf(L.s[1 * kLpMaxF + t], xv, l.y);
-                l.z = fmaf(L.s[2 * kLpMaxF + t], xv, l.z);
-                l.w = fmaf(L.s[3 * kLpMaxF + t], xv, l.w);
-            }
-            mx.x = fmaxf(mx.x, lp_leaky(l.x + adst.x, a.slope_att));
-            mx.y = fmaxf(mx.y, lp_leaky(l.y + adst.y, a.slope_att));
-            mx.z = fmaxf(mx.z, lp_leaky(l.z + adst.z, a.slope_att));
-            mx.w = fmaxf(mx.w, lp_leaky(l.w + adst.w, a.slope_att));
-        }
-    }
-    if (__any(bad)) {                                          // (wave-uniform)
-        lp_refuse(a, orow, lane, 1);
-        return;
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {                  // (a maximum: exact in any order)
-        mx.x = fmaxf(mx.x, __shfl_xor(mx.x, o));
-        mx.y = fmaxf(mx.y, __shfl_xor(mx.y, o));
-        mx.z = fmaxf(mx.z, __shfl_xor(mx.z, o));
-        mx.w = fmaxf(mx.w, __shfl_xor(mx.w, o));
-    }
-    if (lane == 0) {
-        L.ps[0] = expf(lself.x - mx.x); L.ps[1] = expf(lself.y - mx.y);
-        L.ps[2] = expf(lself.z - mx.z); L.ps[3] = expf(lself.w - mx.w);
-    }
-
-    // ---- step 2: weights and source rows of a chunk -> LDS, then the sums in slice order ----
-    float den = 0.f, u = 0.f;
-    for (int64_t base = 0; base < m; base += kWave) {
-        int64_t src = 0;
-        const bool msg = lp_edge(a, e0, m, base + lane, n0, n1, i, src) == 1;
-        if (msg) {
-            const float* xj = a.x + src * F;
-            float4 l = f4zero();
-            for (int t = 0; t < F; ++t) {
-                const float xv = xj[t];
-                L.xs[lane * kLpXs + t] = xv;
-                l.x = fmaf(L.s[0 * kLpMaxF + t], xv, l.x);
-                l.y = fmaf(L.s[1 * kLpMaxF + t], xv, l.y);
-                l.z = fmaf(L.s[2 * kLpMaxF + t], xv, l.z);
-                l.w = fmaf(L.s[3 * kLpMaxF + t], xv, l.w);
-            }
-            L.pw[0 * kWave + lane] = expf(lp_leaky(l.x + adst.x, a.slope_att) - mx.x);
-            L.pw[1 * kWave + lane] = expf(lp_leaky(l.y + adst.y, a.slope_att) - mx.y);
-            L.pw[2 * kWave + lane] = expf(lp_leaky(l.z + adst.z, a.slope_att) - mx.z);
-            L.pw[3 * kWave + lane] = expf(lp_leaky(l.w + adst.w, a.slope_att) - mx.w);
-        }
-        unsigned long long mask = __ballot(msg);
-        __syncthreads();
-        if (lane < kLpHeads * F) {
-            while (mask) {                                     // (wave-uniform: the chunk's messages by rising offset)
-                const int k = __builtin_ctzll(mask);
-                mask &= mask - 1;
-                const float p = L.pw[h * kWave + k];
-                den += p;
-                u = fmaf(p, L.xs[k * kLpXs + f], u);
-            }
-        }
-        __syncthreads();
-    }
-    __syncthreads();                                           // (L.ps of lane 0, when the slice is empty)
-    if (lane < kLpHeads * F) {
-        const float p = L.ps[h];
-        den += p;
-        u = fmaf(p, L.xi[f], u);
-        L.u[h * kLpMaxF + f] = u / (den + 1e-16f);
-    }
-    __syncthreads();
-
-    // ---- step 3: W_h u_h + bias, BatchNorm (running statistics), ReLU ----
-    for (int q = lane; q < kLpHeads * C; q += kWave) {
-        const float* wr = a.w + (int64_t)q * F;
-        const float* uh = L.u + (q / C) * kLpMaxF;
-        float v = 0.f;
-        for (int t = 0; t < F; ++t) v = fmaf(wr[t], uh[t], v);
-        v += a.conv_bias[q];
-        v = (v - a.bn_mean[q]) / sqrtf(a.bn_var[q] + a.eps) * a.bn_w[q] + a.bn_b[q];
-        L.y[q] = v > 0.f ? v : 0.f;
-    }
-    __syncthreads();
-
-    // ---- step 4: the head ----
-    lp_dense(a.w0, a.b0, L.y, kLpHeads * C, C, true, a.slope_head, L.h1, L.part, lane);
-    lp_dense(a.w3, a.b3, L.h1, C, a.O, false, 0.f, orow, L.part, lane);
-}
 
 __global__ __launch_bounds__(kWave) void lightpath_infer_kernel(const LpArgs a) {
     __shared__ LpLds L;
     const int lane = threadIdx.x;
     const int64_t r = blockIdx.x;
     float* orow = a.out + r * a.O;
-    if (a.lut_idx) {                                           // rows mode: one wave per entry of lut_idx
-        const int64_t i = a.lut_idx[r];
-        if (i < 0 || i >= a.N) {
-            lp_refuse(a, orow, lane, 2);
-            return;
-        }
-        const int64_t g = a.batch[i];
-        if (g < 0 || g >= a.B) {
-            lp_refuse(a, orow, lane, 2);
-            return;
-        }
-        lp_row(a, L, i, g, orow, lane);
-        return;
-    }
-    // graphs mode: one wave per graph; its LUT nodes are counted, the lowest-indexed one gives the row
-    const int64_t n0 = a.node_ptr[r], n1 = a.node_ptr[r + 1];
-    if (n0 < 0 || n1 < n0 || n1 > a.N) {
-        if (lane == 0) a.count[r] = 0;
-        lp_refuse(a, orow, lane, 2);
-        return;
-    }
-    int cnt = 0;
-    int64_t first = -1;
-    for (int64_t base = n0; base < n1; base += kWave) {
-        const int64_t k = base + lane;
-        const bool hit = k < n1 && a.x[k * a.F + a.lut_col] == 1.0f;
-        const unsigned long long mask = __ballot(hit);
-        cnt += __popcll(mask);
-        if (first < 0 && mask) first = base + __builtin_ctzll(mask);
-    }
-    if (lane == 0) a.count[r] = cnt;
-    if (first < 0) {
-        if (lane < a.O) orow[lane] = __builtin_nanf("");
-        return;
-    }
-    lp_row(a, L, first, r, orow, lane);
+    int64_t i = 0, g = 0;
+    if (!lp_locate(a, r, orow, lane, i, g)) return;
+    LpRowRegs R;
+    lp_row<false>(a, L, nullptr, i, g, orow, lane, R);
 }
 
 }  // namespace
@@ -296,20 +31,10 @@ extern "C" int qot_lightpath_infer(const float* x, const int64_t* edge_index, co
                                    const float* b3, float slope_head, float* out, int32_t* count, int F, int C, int O,
                                    int heads, int lut_col, int32_t* status, qot_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (N < 0 || E < 0 || B < 0 || L < 0) return QOT_ERR_BADARG;
-    if (F < 1 || F > kLpMaxF) return QOT_ERR_UNSUPPORTED;
-    if (C < 1 || C > kLpMaxC) return QOT_ERR_UNSUPPORTED;
-    if (O < 1 || O > kLpMaxO) return QOT_ERR_UNSUPPORTED;
-    if (heads != kLpHeads) return QOT_ERR_UNSUPPORTED;
-    if (lut_col < 0 || lut_col >= F) return QOT_ERR_UNSUPPORTED;
-    const int64_t rows = lut_idx ? L : B;
-    if (rows == 0) return QOT_OK;
-    if (rows > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
-    if (!node_ptr || !edge_ptr || !w || !att_src || !att_dst || !conv_bias || !bn_weight || !bn_bias || !bn_mean || !bn_var ||
-        !w0 || !b0 || !w3 || !b3 || !out)
-        return QOT_ERR_BADARG;
-    if ((N > 0 && !x) || (E > 0 && !edge_index)) return QOT_ERR_BADARG;
-    if (lut_idx ? !batch : !count) return QOT_ERR_BADARG;
+    int64_t rows = 0;
+    const int rc = lp_check(x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias,
+                            bn_weight, bn_bias, bn_mean, bn_var, w0, b0, w3, b3, out, count, F, C, O, heads, lut_col, 1, &rows);
+    if (rc != QOT_OK || rows == 0) return rc;
     const LpArgs a{x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias, slope_att,
                    bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, count, F, C, O, lut_col,
                    status};

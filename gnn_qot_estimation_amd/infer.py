@@ -1,6 +1,7 @@
 """Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``; its Monte-Carlo dropout
 ``sample``: ``csrc/infer_mc.hip``; its per-link ``sensitivity``: ``csrc/infer_grad.hip``, DESIGN.md
-4.16) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``).
+4.16) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
+``csrc/infer_lightpath_grad.hip``).
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
 TransformerConv, the NNConv forward and the read-out kernel (``LightpathGNN``: the self-looped graph index, the GAT walk
@@ -68,11 +69,10 @@ def grad_edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
     return _edge_cap("grad", n_max, hidden, edge_dim)
 
 
-def grad_outputs(outputs, num_outputs: int):
-    """The ``outputs`` argument of ``TopologicalPredictor.sensitivity``, checked without a device: ``None`` (every output,
-    in order) or a non-empty list / tuple of distinct integers in ``0 ... num_outputs - 1``; returns the list or raises the
-    named ``ValueError``."""
-    who = "TopologicalPredictor.sensitivity"
+def grad_outputs(outputs, num_outputs: int, who: str = "TopologicalPredictor.sensitivity"):
+    """The ``outputs`` argument of ``TopologicalPredictor.sensitivity`` (and of ``LightpathPredictor.sensitivity``: ``who``
+    names the caller in the message), checked without a device: ``None`` (every output, in order) or a non-empty list /
+    tuple of distinct integers in ``0 ... num_outputs - 1``; returns the list or raises the named ``ValueError``."""
     O = int(num_outputs)
     if outputs is None:
         return list(range(O))
@@ -432,9 +432,10 @@ class TopologicalPredictor:
 
 
 # ====================================================================== LightpathGNN
-LP_MAX_FEATURES = 16            # csrc/infer_lightpath.hip: kLpMaxF
+LP_MAX_FEATURES = 16            # csrc/infer_lightpath_dev.hpp: kLpMaxF (both kernels)
 LP_MAX_HIDDEN = 256             # kLpMaxC
-LP_MAX_OUTPUTS = 8              # kLpMaxO
+LP_MAX_OUTPUTS = 8              # kLpMaxO; also the most outputs one sensitivity call differentiates (Q <= O)
+LP_HEADS = 4                    # kLpHeads: the columns of alpha_self / alpha_edge
 
 
 class EnvelopeError(ValueError):
@@ -462,6 +463,9 @@ class LightpathPredictor:
     from either call; against ``model.eval()(data)`` it agrees to fp32 rounding.  A model whose width the engine runs
     zero-padded (e.g. C = 20) is supported: the kernel reads its real parameters.
 
+    ``predict.sensitivity(data)``: the rows together with their Jacobian wrt the node features of each row's one-hop
+    in-neighbourhood, in one launch (see there).
+
     Envelope -- ``EnvelopeError`` naming the condition otherwise: a model on the GPU with ``num_layers == 1``, 1 ... 16 input
     features, hidden width 1 ... 256, 1 ... 8 outputs; ``data.x`` of shape ``[N, F]``.  No cap on in-degree, graph size or
     batch size.  Edges must be grouped by graph (``ValueError`` otherwise); an edge that leaves its graph's node range makes
@@ -471,9 +475,11 @@ class LightpathPredictor:
     def __init__(self, model):
         self.model = model
         self._status = None
-        self._check_model()
+        self._outputs_dev = {}
+        F, C, O = self._check_model()
+        self._outputs(list(range(O)), model.conv1.bias.device)      # the default selection is uploaded here, not in a call
 
-    def _check_model(self):
+    def _check_model(self, on_gpu=True):
         m = self.model
         if getattr(m, "num_layers", None) != 1 or not hasattr(m, "conv1") or not hasattr(m, "norm1"):
             raise EnvelopeError(f"LightpathPredictor: num_layers must be 1 (the reference architecture: one GATConv), got "
@@ -490,7 +496,7 @@ class LightpathPredictor:
             raise EnvelopeError(f"LightpathPredictor: output_dim {O} is not supported; it must be 1 ... {LP_MAX_OUTPUTS}")
         if not 0 <= int(m.is_lut_index) < F:
             raise EnvelopeError(f"LightpathPredictor: is_lut_index {m.is_lut_index} is not a column of {F} features")
-        if not conv.bias.is_cuda:
+        if on_gpu and not conv.bias.is_cuda:
             raise EnvelopeError("LightpathPredictor: the model is on the CPU; move it to the GPU first (model.to('cuda'))")
         return F, C, O
 
@@ -513,7 +519,15 @@ class LightpathPredictor:
             c["infer_lp"] = (tag, res)
         return (x,) + res
 
-    def _launch(self, x, ei, batch, ptr, eptr, lut_idx, B, out, count, F, C, O):
+    def _outputs(self, sel, dev):
+        """``sel`` as a device int32 tensor: one upload per selection and device, none in later calls."""
+        t = self._outputs_dev.get((tuple(sel), dev))
+        if t is None:
+            t = self._outputs_dev[(tuple(sel), dev)] = torch.tensor(sel, dtype=torch.int32, device=dev)
+        return t
+
+    def _launch(self, x, ei, batch, ptr, eptr, lut_idx, B, out, count, F, C, O, name="qot_lightpath_infer", extra=()):
+        """One launch of entry point ``name``: the arguments the two kernels share, then ``extra``."""
         m = self.model
         conv, bn, l0, l3 = m.conv1, m.norm1.module, m.mlp[0], m.mlp[3]
         dev = out.device
@@ -521,10 +535,10 @@ class LightpathPredictor:
             self._status = torch.zeros(1, dtype=torch.int32, device=dev)
         p = [_f32c(t.detach()) for t in (conv.lin.weight, conv.att_src, conv.att_dst, conv.bias, bn.weight, bn.bias,
                                          bn.running_mean, bn.running_var, l0.weight, l0.bias, l3.weight, l3.bias)]
-        _lib.call("qot_lightpath_infer", x, ei, batch, ptr, eptr, lut_idx, 0 if lut_idx is None else lut_idx.shape[0],
+        _lib.call(name, x, ei, batch, ptr, eptr, lut_idx, 0 if lut_idx is None else lut_idx.shape[0],
                   x.shape[0], ei.shape[1], B, p[0], p[1], p[2], p[3], float(conv.negative_slope), p[4], p[5], p[6], p[7],
                   float(bn.eps), p[8], p[9], p[10], p[11], float(m.mlp[1].negative_slope), out, count, F, C, O,
-                  int(conv.heads), int(m.is_lut_index), self._status)
+                  int(conv.heads), int(m.is_lut_index), self._status, *extra)
 
     @torch.no_grad()
     def __call__(self, data):
@@ -551,9 +565,74 @@ class LightpathPredictor:
         self._launch(x, ei, None, ptr, eptr, None, B, out, count, F, C, O)
         return out, count
 
+    @torch.no_grad()
+    def sensitivity(self, data, outputs=None, *, per_graph=False, return_attention_weights=False):
+        """The rows of ``predict(data)`` together with their Jacobian wrt the node features of each row's one-hop
+        in-neighbourhood, in ONE kernel launch: returns ``(out [L, O], lut_batch [L], jac_self [Q, L, F], jac_edge [Q, E,
+        F])``; with ``per_graph=True`` ``(out [B, O], count [B], jac_self [Q, B, F], jac_edge)`` -- the rows of
+        ``predict.per_graph(data)``.  ``out`` and ``lut_batch`` / ``count`` are those calls' results bit for bit.
+
+        ``jac_edge[q, e, :]``, in the order of ``data.edge_index``: for an edge ``e`` that is a message into a computed row
+        ``r`` (``dst(e)`` is the row's node and ``src(e) != dst(e)``), ``d out[r, outputs[q]] / d x[src(e), :]`` through that
+        message; repeated edges are separate messages with a share each.  Every other edge holds exactly 0: input self
+        loops (PyG removes them), edges into non-LUT nodes and, with ``per_graph=True``, edges into the LUT nodes behind a
+        graph's first.  ``jac_self[q, r, :]``: the derivative wrt the row's own features -- the appended self loop's
+        message and logit, and the destination term of every message's logit.  Together they are ``x.grad``: with
+        ``J = zeros(N, F)``, ``J.index_add_(0, edge_index[0], jac_edge[q]); J[lut_idx] += jac_self[q]`` is what
+        ``model.eval()(data)[0][:, outputs[q]].sum().backward()`` leaves in ``data.x.grad`` (the LUT selection is a
+        constant: the ``is_lut`` column gets its plain derivative; ``leaky_relu`` / ``relu`` at 0 as torch).
+
+        ``outputs``: ``None`` (all, in order) or a non-empty list of distinct integers in ``0 ... O - 1``; ``Q`` of them.
+        ``return_attention_weights=True``: also ``(alpha_self [L or B, 4], alpha_edge [E, 4])``, conv1's softmax weights of
+        each row's self loop and of the message edges (0 on every other edge): the values ``model(data,
+        return_attention_weights=True)`` gives those ``(source, target)`` pairs.
+
+        Plain tensors without ``grad_fn``; pure (no model state is touched); parameters and running statistics are read
+        at call time.  No atomics: every element has one owning wave and every sum a fixed order, so the result is
+        bitwise reproducible and a row's slices do not depend on the other graphs of the batch or on the mode.  The
+        kernel writes only the message edges: the zeros elsewhere are ``torch.zeros`` allocations of ``jac_edge`` (and
+        ``alpha_edge``), ONE FILL EACH in front of the one kernel launch.  With ``per_graph=True`` there is no host read,
+        and the call is legal inside ``torch.cuda.graph`` capture under ``per_graph``'s condition (single stream); a graph
+        without a LUT node has ``count == 0``, NaN in its ``out`` and ``jac_self`` rows and zeros in its ``jac_edge``
+        slice.  (A selection other than ``None`` is uploaded once, on its first call: make that call before capturing.)
+
+        Refusals as ``__call__`` (``EnvelopeError``; the LUT-less ``ValueError`` / ``allow_empty_lut`` in rows mode).  A
+        flagged row (``check_status()`` raises) has NaN in its ``out`` and ``jac_self`` rows and, its graph's edge slice
+        being valid, over that slice of ``jac_edge`` / ``alpha_edge``."""
+        # the model's shape, then the argument, are named before the model's device and the batch are looked at
+        sel = grad_outputs(outputs, self._check_model(on_gpu=False)[2], "LightpathPredictor.sensitivity")
+        F, C, O = self._check_model()
+        m = self.model
+        dev = m.conv1.bias.device
+        x, ei, ptr, eptr, B = self._batch(data, F, dev)
+        E, Q = ei.shape[1], len(sel)
+        if per_graph:
+            idx = batch = None
+            rows = B
+            second = torch.empty(B, dtype=torch.int32, device=dev)
+        else:
+            idx = m._lut_rows(data)                 # the model's ValueError for a LUT-less batch
+            batch, idx = _i64(data.batch, dev), _i64(idx, dev)
+            rows = idx.shape[0]
+            second = batch.index_select(0, idx) if rows else batch[:0]
+        out = torch.empty(rows, O, dtype=torch.float32, device=dev)
+        jac_self = torch.empty(Q, rows, F, dtype=torch.float32, device=dev)
+        jac_edge = torch.zeros(Q, E, F, dtype=torch.float32, device=dev)
+        alpha = None
+        if return_attention_weights:
+            alpha = (torch.empty(rows, LP_HEADS, dtype=torch.float32, device=dev),
+                     torch.zeros(E, LP_HEADS, dtype=torch.float32, device=dev))
+        if rows:                                    # (0 rows: only with allow_empty_lut, or an empty batch)
+            self._launch(x, ei, batch, ptr, eptr, idx, B, out, second if per_graph else None, F, C, O,
+                         "qot_lightpath_infer_grad", (self._outputs(sel, dev), Q, jac_self, jac_edge,
+                                                      None if alpha is None else alpha[0],
+                                                      None if alpha is None else alpha[1]))
+        res = (out, second, jac_self, jac_edge)
+        return res + (alpha,) if return_attention_weights else res
+
     def check_status(self):
-        """Reads the kernel's status word (one device synchronisation): raises when a batch since the last check had an
-        edge outside its graph's node range or indices / slices that disagree with its arrays (such rows are NaN)."""
+        """Reads the status word of both kernels (one device synchronisation): raises when a batch since the last check had
+        an edge outside its graph's node range or indices / slices that disagree with its arrays (such rows are NaN)."""
         if self._status is None:
             return
         code = int(self._status.item())

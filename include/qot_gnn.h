@@ -898,6 +898,37 @@ int qot_lightpath_infer(const float* x, const int64_t* edge_index, const int64_t
                         float* out, int32_t* count, int F, int C, int O, int heads, int lut_col, int32_t* status,
                         qot_stream_t stream);
 
+/* ---- per-neighbour sensitivity of the LUT rows in one launch (LightpathPredictor.sensitivity) --------
+ * The forward of qot_lightpath_infer -- the same sums in the same order: `out` (and `count`) are that entry's, bit for bit
+ * -- followed, inside the row's wavefront, by the Jacobian of Q requested outputs wrt the node features of the row's
+ * one-hop in-neighbourhood.  outputs [Q] device int32, distinct values in 0 ... O - 1 (the caller checks the contents; a
+ * value outside that range gives NaN, nothing is read through it).  R = L (rows mode) or B (graphs mode) rows.
+ *   jac_edge [Q, E, F]  for an edge e that is a message into computed row r (dst(e) is the row's node, src(e) != dst(e)):
+ *                       d out[r, outputs[q]] / d x[src(e), :] THROUGH THAT MESSAGE (repeated edges are separate messages).
+ *                       Every other edge is NOT WRITTEN: the caller zero-fills the array.
+ *   jac_self [Q, R, F]  the derivative wrt the row's own features: the appended self loop's message and logit, and the
+ *                       d_h . x_i term of every message's logit.
+ *   alpha_self [R, 4], alpha_edge [E, 4] (optional, both may be NULL): conv1's softmax weights of the self loop and of the
+ *                       message edges; alpha_edge is caller-zeroed like jac_edge.
+ * With J[q] = zeros(N, F): J[q].index_add_(0, src, jac_edge[q]); J[q][row nodes] += jac_self[q] is x.grad of
+ * out[:, outputs[q]].sum() -- the LUT selection taken as constant.  leaky_relu' / relu' at 0 as torch (v > 0 ? 1 : slope;
+ * relu: 0).  No float atomics: an edge has one destination, so every element has at most one owning wave, and every sum
+ * has one order (the destination-side sums run over the messages by rising offset in the graph's slice): bitwise
+ * reproducible, independent of the other graphs of the launch and of the mode.
+ * A row that is not computed (flagged as in qot_lightpath_infer, or a graph without a LUT node in graphs mode) has NaN in
+ * its out, jac_self and alpha_self rows; a flagged row whose graph's edge slice lies inside the edge array also writes NaN
+ * over that slice of jac_edge / alpha_edge.
+ * Envelope and return codes of qot_lightpath_infer, plus QOT_ERR_UNSUPPORTED for Q outside 1 ... O, and -- when there are
+ * rows -- QOT_ERR_BADARG for a NULL outputs, jac_self or (E > 0) jac_edge. */
+int qot_lightpath_infer_grad(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                             const int64_t* edge_ptr, const int64_t* lut_idx, int64_t L, int64_t N, int64_t E, int64_t B,
+                             const float* w, const float* att_src, const float* att_dst, const float* conv_bias,
+                             float slope_att, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                             const float* bn_var, float bn_eps, const float* w0, const float* b0, const float* w3,
+                             const float* b3, float slope_head, float* out, int32_t* count, int F, int C, int O, int heads,
+                             int lut_col, int32_t* status, const int32_t* outputs, int Q, float* jac_self, float* jac_edge,
+                             float* alpha_self, float* alpha_edge, qot_stream_t stream);
+
 /* ---- graph construction from network-status samples (csrc/status_graph.hip) ----------------
  * data [S, P, L, Q] fp64 (sample, lp_feat, link, freq), target [S, M] fp64, freq [Q] fp64, all on the device.  samples
  * [G] int64 picks the samples of the call, in order, repeats allowed (NULL: samples 0 .. G-1).  One workgroup per

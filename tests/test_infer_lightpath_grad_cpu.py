@@ -1,0 +1,149 @@
+"""CPU-side checks of LightpathGNN's sensitivity path (``csrc/infer_lightpath_grad.hip``,
+``LightpathPredictor.sensitivity``): the entry point is declared, bound and exported; it answers its envelope before any
+launch; the ``outputs`` argument is checked before the device is looked at; and the soundness of the fixtures the GPU tests
+lean on -- the oracle's ``x.grad`` in fp32 and in fp64 must agree per output to ``TOL / 10`` on every batch of
+``lightpath_grad_cases.py`` (a gradient jumps at a leaky_relu / relu kink: inputs on which the reference's own two
+precisions disagree cannot judge a kernel)."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+import gnn_qot_estimation_amd as q
+from gnn_qot_estimation_amd import _lib, infer
+import lightpath_grad_cases as C
+from helpers import TOL, rel_err
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAME = "qot_lightpath_infer_grad"
+
+
+def test_symbol_declared_bound_and_exported():
+    hdr = open(os.path.join(ROOT, "include", "qot_gnn.h")).read()
+    declared = set(re.findall(r"\b(qot_[a-z0-9_]+)\s*\(", hdr))
+    assert os.path.exists(_lib.LIB_PATH), "run __graft_entry__.build() first"
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    assert NAME in declared and NAME in _lib.SIGNATURES and hasattr(lib, NAME)
+    decl = re.search(r"int %s\(([^;]*)\);" % NAME, hdr).group(1)
+    assert len(_lib.SIGNATURES[NAME][1]) == decl.count(",") + 1
+    # everything qot_lightpath_infer takes, then outputs, Q, jac_self, jac_edge, alpha_self, alpha_edge; the stream last
+    ev, gr = _lib.SIGNATURES["qot_lightpath_infer"][1], _lib.SIGNATURES[NAME][1]
+    p = ctypes.c_void_p
+    assert gr[:len(ev) - 1] == ev[:-1] and gr[-1] is p
+    assert gr[len(ev) - 1:-1] == [p, ctypes.c_int, p, p, p, p]
+    assert hasattr(q.LightpathPredictor, "sensitivity")
+
+
+def test_entry_refuses_shapes_outside_the_envelope_before_any_launch():
+    fn = getattr(_lib.load(), NAME)
+
+    def rc(F=5, C=32, O=3, heads=4, lut_col=1, B=0, Q=1, outputs=None, jac_self=None):
+        # no arrays: the envelope is answered first, and an empty batch (B = 0 in graphs mode) launches nothing
+        return fn(None, None, None, None, None, None, 0, 0, 0, B, None, None, None, None, 0.2, None, None, None, None, 1e-5,
+                  None, None, None, None, 0.01, None, None, F, C, O, heads, lut_col, None, outputs, Q, jac_self, None, None,
+                  None, None)
+
+    assert rc() == 0 and rc(Q=3) == 0
+    assert rc(F=16, C=256, O=8, lut_col=15, Q=8) == 0 and rc(F=1, C=1, O=1, lut_col=0) == 0
+    for bad in (dict(F=0), dict(F=17), dict(C=0), dict(C=257), dict(O=0), dict(O=9), dict(heads=1), dict(heads=8),
+                dict(lut_col=-1), dict(lut_col=5), dict(Q=0), dict(Q=-1), dict(Q=4), dict(Q=2, O=1), dict(Q=9, O=8)):
+        assert rc(**bad) == -1, bad                     # QOT_ERR_UNSUPPORTED
+    assert rc(B=-1) == -2 and rc(B=3) == -2             # QOT_ERR_BADARG: negative size; rows to compute but no arrays
+    assert rc(B=3, Q=0) == -1                           # the envelope is answered before the arrays are looked at
+    one = ctypes.c_void_p(1)                            # never dereferenced: refused for the other arrays first
+    assert rc(B=3, outputs=one, jac_self=one) == -2
+
+
+def _bare(model):
+    pred = q.LightpathPredictor.__new__(q.LightpathPredictor)
+    pred.model, pred._status, pred._outputs_dev = model, None, {}
+    return pred
+
+
+def test_predictor_refuses_a_cpu_model():
+    model = q.LightpathGNN(5, 32, 3, 1)
+    with pytest.raises(infer.EnvelopeError, match="CPU"):
+        q.LightpathPredictor(model)
+    with pytest.raises(infer.EnvelopeError, match="CPU"):
+        _bare(model).sensitivity(None)
+    with pytest.raises(infer.EnvelopeError, match="CPU"):
+        _bare(model).sensitivity(None, per_graph=True, return_attention_weights=True)
+    assert model.training
+
+
+def test_outputs_are_checked_before_the_device_is_looked_at():
+    pred = _bare(q.LightpathGNN(5, 32, 3, 1))           # a CPU model: the argument's error comes first
+    for bad in ([], [3], [-1], [0, 0], [True], "0", 0, [0.0], ["0"], (), [0, 1, 2, 0]):
+        with pytest.raises(ValueError, match="LightpathPredictor.sensitivity: outputs must be") as err:
+            pred.sensitivity(None, outputs=bad)
+        assert not isinstance(err.value, infer.EnvelopeError)
+    for good in (None, [2, 0], (1,)):
+        with pytest.raises(infer.EnvelopeError, match="CPU"):
+            pred.sensitivity(None, outputs=good)
+    # the messages are infer.grad_outputs's, under the caller's name
+    assert infer.grad_outputs([2, 0], 3, "LightpathPredictor.sensitivity") == [2, 0]
+    with pytest.raises(ValueError, match="TopologicalPredictor.sensitivity: outputs must be distinct"):
+        infer.grad_outputs([1, 1], 3)
+    # a model outside the envelope is named before the argument
+    with pytest.raises(infer.EnvelopeError, match="num_layers"):
+        _bare(q.LightpathGNN(5, 8, 3, 1, num_layers=2)).sensitivity(None, outputs=[3])
+
+
+def _sound(ref, batch, grad64):
+    _, grad32 = C.oracle_xgrad(ref, batch, dtype=torch.float32)
+    worst = 0.0
+    for k in range(grad64.shape[0]):
+        e = rel_err(grad32[k], grad64[k])
+        worst = max(worst, e)
+        assert e <= TOL / 10, (k, e)
+    return worst
+
+
+@pytest.mark.parametrize("C_,F,O", C.PARITY)
+def test_parity_fixtures_are_sound(C_, F, O):
+    for lut in C.lut_columns(F):
+        ref, batch, out64, grad64 = C.parity_case(C_, F, O, lut)
+        assert batch.num_graphs == 16 and tuple(grad64.shape) == (O, batch.x.shape[0], F)
+        assert batch.x.shape[0] == 394 + 6 + 5 and batch.edge_index.shape[1] == 456 + 10 + 5
+        assert out64.shape[0] == 14 + 2 + 1 and float(grad64.abs().max()) > 0
+        print(f"C {C_} F {F} O {O} lut {lut}: oracle fp32 vs fp64 x.grad {_sound(ref, batch, grad64):.3e}")
+
+
+def test_the_unrolled_graph_restates_the_triple_edge():
+    """The unrolled copy gives the triple-edge graph's output, and the gradient of each copy is a third of the gradient of
+    the shared source -- the oracle's own statement that the copies' gradients are the per-edge shares."""
+    ref, batch, out64, grad64 = C.parity_case(32, 5, 3, 1)
+    rows = C.lut_rows(batch, 1)
+    lb = batch.batch[rows].tolist()
+    assert torch.allclose(out64[lb.index(C.TRIPLE)], out64[lb.index(15)], rtol=1e-12, atol=0)
+    n = C.slices(batch.ptr)
+    src = n[C.TRIPLE][0] + 1
+    shares = grad64[:, [n[15][0] + k for k in C.UNROLLED_NODES]]                # [O, 3, F]
+    assert torch.allclose(shares.sum(1), grad64[:, src], rtol=1e-10, atol=1e-14)
+    e0 = C.slices(batch.edge_ptr)[C.TRIPLE][0]
+    for k in C.TRIPLE_EDGES:
+        assert batch.edge_index[:, e0 + k].tolist() == [src, src - 1]
+    s0 = C.slices(batch.edge_ptr)[C.SELF_LOOP][0]
+    assert batch.edge_index[0, s0 + 1] == batch.edge_index[1, s0 + 1]
+
+
+def test_independence_capture_and_tracking_fixtures_are_sound():
+    ref = C.oracle_model()
+    g, others = C.independence_graphs()
+    for graphs in ([g], others + [g]):
+        batch = q.Batch.from_data_list(graphs)
+        _sound(ref, batch, C.oracle_xgrad(ref, batch)[1])
+    batch = C.relabelled()
+    _sound(ref, batch, C.oracle_xgrad(ref, batch)[1])
+    only, first, has = C.first_lut_only(batch)
+    assert torch.equal(C.lut_rows(only, 1), first) and 1 < len(has) < batch.num_graphs
+    _sound(ref, only, C.oracle_xgrad(ref, only)[1])
+    batch, refs, deltas = C.tracking_case()
+    grads = []
+    for r in refs:
+        grads.append(C.oracle_xgrad(r, batch)[1])
+        _sound(r, batch, grads[-1])
+    assert rel_err(grads[1], grads[0]) > TOL            # the step moves the Jacobian by more than the comparison allows
+    assert set(deltas) == set(dict(refs[0].named_parameters()))

@@ -40,6 +40,16 @@ Jacobians are compared first; then both alternate in one process, each call betw
 interquartile range as above.
 
     python tools/bench_infer.py --grad [--out profiles/bench_infer_grad.jsonl]
+
+``--kind lightpath --grad``: per-neighbour sensitivity of the LUT rows (csrc/infer_lightpath_grad.hip) --
+milliseconds per call of ``predict.sensitivity(data)`` (the rows and their Jacobian wrt the node features of every row's
+in-neighbourhood: two fills and one launch) against the other route to the same numbers: ``x.requires_grad_()``, the eval
+``model(data)``, parameters frozen, one ``backward(retain_graph=True)`` per output.  ``synthetic.lightpath_batch`` chains at
+C = 32, F = 5, O = 3 and B = 1, 8 and 512; ``jac_self`` / ``jac_edge`` are put together by the index-add identity and
+compared with autograd's ``x.grad`` first; then both alternate in one process, each call between two
+``torch.cuda.Event``s, median and interquartile range as above.
+
+    python tools/bench_infer.py --kind lightpath --grad [--out profiles/bench_infer_lightpath_grad.jsonl]
 """
 import argparse
 import json
@@ -310,6 +320,82 @@ def measure_lightpath(B, device, rounds, warmup):
     return res
 
 
+LIGHTPATH_GRAD_SIZES = (1, 8, 512)
+
+
+def measure_lightpath_grad(B, device, rounds, warmup):
+    torch.manual_seed(0)
+    model = q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval()
+    for p in model.parameters():
+        p.requires_grad_(False)
+    distinct = min(B, 64)
+    data = S.tile_batch(S.lightpath_batch(distinct), B // distinct).to(device)
+    leaf = S.tile_batch(S.lightpath_batch(distinct), B // distinct).to(device)
+    leaf.x = leaf.x.detach().clone().requires_grad_()
+    predict = q.LightpathPredictor(model)
+
+    def autograd():
+        out, lb = model(leaf)
+        jac = []
+        for o in range(out.shape[1]):
+            leaf.x.grad = None
+            out[:, o].sum().backward(retain_graph=True)
+            jac.append(leaf.x.grad)
+        return out, jac
+
+    for _ in range(3):
+        want_out, want = autograd()
+    want = torch.stack(want).double()
+    out, lb, jac_self, jac_edge = predict.sensitivity(data)
+    torch.cuda.synchronize()
+    predict.check_status()
+    rows = model._lut_rows(data)
+    got = torch.zeros_like(want)                           # the identity: J.index_add_(0, src, jac_edge); J[lut] += jac_self
+    for k in range(got.shape[0]):
+        got[k].index_add_(0, data.edge_index[0], jac_edge[k].double())
+        got[k][rows] += jac_self[k].double()
+    err = float((got - want).abs().max() / want.abs().max())
+    want_out = want_out.detach().double()
+    err_out = float((out.double() - want_out).abs().max() / want_out.abs().max())
+    assert err <= 1e-4 and err_out <= 1e-4, (B, err, err_out)
+
+    ways = {"sensitivity": lambda: predict.sensitivity(data), "eager": autograd}
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed_event(fn))
+    res = dict(shape=f"lightpath B={B}", kind="lightpath_grad", outputs=3, B=B, C=32, F=5, N=int(data.x.shape[0]),
+               E=int(data.edge_index.shape[1]), rows=int(rows.numel()), rounds=rounds, rel_err=err, rel_err_out=err_out)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_lightpath_grad(args, device, commit):
+    rows = []
+    for B in LIGHTPATH_GRAD_SIZES:
+        res = measure_lightpath_grad(B, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| B (nodes, edges) | sensitivity ms (IQR) | forward + 3 backward ms (IQR) | autograd / sensitivity |")
+    print("|---|---|---|---|")
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['B']} ({r['N']}, {r['E']}) | {cell('sensitivity')} | {cell('eager')} | {verdict(r, 'sensitivity')} |")
+
+
 def verdict(r, way):
     """``way`` against the eager forward: the ratio of the medians, or "no difference" (module docstring)."""
     a, b = r[f"{way}_ms"], r["eager_ms"]
@@ -348,10 +434,11 @@ def main():
     ap.add_argument("--mc", type=int, default=None, metavar="T",
                     help="Monte-Carlo dropout: predict.sample(data, T) against T train-mode forwards")
     ap.add_argument("--grad", action="store_true",
-                    help="per-link sensitivity: predict.sensitivity(data) against eval forward + one backward per output")
+                    help="sensitivity: predict.sensitivity(data) against eval forward + one backward per output "
+                         "(with --kind lightpath: LightpathPredictor's)")
     args = ap.parse_args()
-    if (args.mc is not None or args.grad) and args.kind != "topological":
-        raise SystemExit("--mc and --grad are for the topological model")
+    if args.mc is not None and args.kind != "topological":
+        raise SystemExit("--mc is for the topological model")
     if args.mc is not None and args.grad:
         raise SystemExit("--mc and --grad are separate runs")
     if args.rounds < 20:
@@ -361,7 +448,7 @@ def main():
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     if args.kind == "lightpath":
-        return main_lightpath(args, device, commit)
+        return (main_lightpath_grad if args.grad else main_lightpath)(args, device, commit)
     if args.mc is not None:
         return main_mc(args, device, commit)
     if args.grad:
