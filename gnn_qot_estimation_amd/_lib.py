@@ -31,6 +31,8 @@ ABI_VERSION = 13         # include/qot_gnn.h: QOT_ABI_VERSION
 # what qot_topological_infer, _mc and _grad take alike, up to the status word; each adds its own arguments and the stream
 _INFER_COMMON = ([_p] * 5 + [_i64] * 3 + [_int, _int, _p, _int, _p, _int, _p, _int] + [_p] * 9
                  + [_f, _f, _p, _int, _int, _int, _p])
+# ... and qot_lightpath_infer and _grad, likewise
+_LP_COMMON = ([_p] * 6 + [_i64] * 4 + [_p] * 4 + [_f] + [_p] * 4 + [_f] + [_p] * 4 + [_f, _p, _p] + [_int] * 5 + [_p])
 
 SIGNATURES = {
     "qot_abi_version": (_int, []),
@@ -176,12 +178,8 @@ SIGNATURES = {
     "qot_topological_infer": (_int, _INFER_COMMON + [_p]),
     "qot_topological_infer_mc": (_int, _INFER_COMMON + [_int, _i64, _u64, _f, _f, _int, _p]),
     "qot_topological_infer_grad": (_int, _INFER_COMMON + [_p, _int, _p, _p, _p]),
-    "qot_lightpath_infer": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f, _p, _p, _p, _p, _f,
-                                   _p, _p, _p, _p, _f, _p, _p, _int, _int, _int, _int, _int, _p, _p]),
-    # qot_lightpath_infer's arguments up to the status word, then outputs, Q, jac_self, jac_edge, alpha_self, alpha_edge
-    "qot_lightpath_infer_grad": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _f, _p, _p, _p, _p,
-                                        _f, _p, _p, _p, _p, _f, _p, _p, _int, _int, _int, _int, _int, _p, _p, _int, _p, _p, _p,
-                                        _p, _p]),
+    "qot_lightpath_infer": (_int, _LP_COMMON + [_p]),
+    "qot_lightpath_infer_grad": (_int, _LP_COMMON + [_p, _int, _p, _p, _p, _p, _p]),
     "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "qot_status_graph_count": (_int, [_p, _p, _p, _i64, _i64, _int, _i64, _i64, _int, _int, _int, C.c_double, _int, _p, _sz, _p,
                                       _p]),

@@ -31,13 +31,12 @@ extern "C" int qot_lightpath_infer(const float* x, const int64_t* edge_index, co
                                    const float* b3, float slope_head, float* out, int32_t* count, int F, int C, int O,
                                    int heads, int lut_col, int32_t* status, qot_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    LpArgs a;
     int64_t rows = 0;
-    const int rc = lp_check(x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias,
-                            bn_weight, bn_bias, bn_mean, bn_var, w0, b0, w3, b3, out, count, F, C, O, heads, lut_col, 1, &rows);
+    const int rc = lp_args(x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias,
+                           slope_att, bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, count, F, C,
+                           O, heads, lut_col, status, 1, a, rows);
     if (rc != QOT_OK || rows == 0) return rc;
-    const LpArgs a{x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias, slope_att,
-                   bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, count, F, C, O, lut_col,
-                   status};
     lightpath_infer_kernel<<<(int)rows, kWave, 0, stream>>>(a);
     QOT_LAUNCH_CHECK();
     return QOT_OK;

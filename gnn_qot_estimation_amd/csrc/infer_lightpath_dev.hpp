@@ -1,6 +1,9 @@
 // The eval-mode forward of one LightpathGNN output row by one wavefront, shared by the single-launch inference kernel
 // (infer_lightpath.hip) and the sensitivity kernel (infer_lightpath_grad.hip): both run
-// lp_locate + lp_row, so the row they write is the same sums in the same order, bit for bit.
+// lp_locate + lp_row, so the row they write is the same sums in the same order, bit for bit.  Stated once here for both:
+// lp_dot4 (the four per-head dot products of a logit; per-head values live in float[kLpHeads], indexed by unrolled loops
+// only), LpRowRegs (what a row leaves in registers for the adjoint) and lp_args (the entry points' envelope, argument
+// checks and LpArgs block).
 //
 // The reference architecture is GATConv(heads = 4) -> BatchNorm (running statistics) -> ReLU -> LUT rows -> MLP, so an output
 // row depends on nothing but the one-hop in-neighbourhood of its LUT node: no graph index, no other node's row.  Because
@@ -53,7 +56,7 @@ struct LpKeep {
 
 // ... and registers, the same in every lane
 struct LpRowRegs {
-    float4 mx, adst, rself;             // per head: the maximum logit, d_h . x_i, the self loop's logit before leaky_relu
+    float mx[kLpHeads], adst[kLpHeads], rself[kLpHeads];    // the maximum logit, d_h . x_i, the self loop's raw logit
     int64_t n0, n1, e0, m;              // the graph's node range, the first edge and the length of its edge slice
 };
 
@@ -70,6 +73,17 @@ struct LpArgs {
 };
 
 __device__ __forceinline__ float lp_leaky(float v, float slope) { return v > 0.f ? v : slope * v; }
+
+// acc[h] += sum_t v[h][t] x[t] for the four heads, t rising, one accumulator per head (v: [4][kLpMaxF] in LDS).  `stage`
+// (may be null) receives a copy of x[0 .. F).  The loops over h are unrolled: acc stays in registers.
+__device__ __forceinline__ void lp_dot4(const float* v, const float* x, int F, float (&acc)[kLpHeads], float* stage = nullptr) {
+    for (int t = 0; t < F; ++t) {
+        const float xv = x[t];
+        if (stage) stage[t] = xv;
+#pragma unroll
+        for (int h = 0; h < kLpHeads; ++h) acc[h] = fmaf(v[h * kLpMaxF + t], xv, acc[h]);
+    }
+}
 
 __device__ __forceinline__ void lp_refuse(const LpArgs& a, float* orow, int lane, int bit) {
     if (lane == 0 && a.status) atomicOr(a.status, bit);
@@ -145,46 +159,36 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
     }
     if (lane < F) L.xi[lane] = a.x[i * F + lane];
     __syncthreads();
-    float4 adst = f4zero(), lself = f4zero();
-    for (int t = 0; t < F; ++t) {
+    float adst[kLpHeads] = {}, lself[kLpHeads] = {};
+    for (int t = 0; t < F; ++t) {                              // (two lp_dot4 in one pass over x_i: one LDS wait per t)
         const float xv = L.xi[t];
-        adst.x = fmaf(L.d[0 * kLpMaxF + t], xv, adst.x);
-        adst.y = fmaf(L.d[1 * kLpMaxF + t], xv, adst.y);
-        adst.z = fmaf(L.d[2 * kLpMaxF + t], xv, adst.z);
-        adst.w = fmaf(L.d[3 * kLpMaxF + t], xv, adst.w);
-        lself.x = fmaf(L.s[0 * kLpMaxF + t], xv, lself.x);
-        lself.y = fmaf(L.s[1 * kLpMaxF + t], xv, lself.y);
-        lself.z = fmaf(L.s[2 * kLpMaxF + t], xv, lself.z);
-        lself.w = fmaf(L.s[3 * kLpMaxF + t], xv, lself.w);
+#pragma unroll
+        for (int hh = 0; hh < kLpHeads; ++hh) {
+            adst[hh] = fmaf(L.d[hh * kLpMaxF + t], xv, adst[hh]);
+            lself[hh] = fmaf(L.s[hh * kLpMaxF + t], xv, lself[hh]);
+        }
     }
-    R.adst = adst;
-    R.rself = add4(lself, adst);
-    lself.x = lp_leaky(lself.x + adst.x, a.slope_att);
-    lself.y = lp_leaky(lself.y + adst.y, a.slope_att);
-    lself.z = lp_leaky(lself.z + adst.z, a.slope_att);
-    lself.w = lp_leaky(lself.w + adst.w, a.slope_att);
+#pragma unroll
+    for (int hh = 0; hh < kLpHeads; ++hh) {
+        R.adst[hh] = adst[hh];
+        R.rself[hh] = lself[hh] + adst[hh];
+        lself[hh] = lp_leaky(R.rself[hh], a.slope_att);
+    }
 
     // ---- step 1: range check of the slice, per-head maximum over the messages and the self loop ----
-    float4 mx = lself;
+    float mx[kLpHeads];
+#pragma unroll
+    for (int hh = 0; hh < kLpHeads; ++hh) mx[hh] = lself[hh];
     bool bad = false;
     for (int64_t base = 0; base < m; base += kWave) {
         int64_t src = 0;
         const int kind = lp_edge(a, e0, m, base + lane, n0, n1, i, src);
         bad = bad || kind == 2;
         if (kind == 1) {
-            const float* xj = a.x + src * F;
-            float4 l = f4zero();
-            for (int t = 0; t < F; ++t) {
-                const float xv = xj[t];
-                l.x = fmaf(L.s[0 * kLpMaxF + t], xv, l.x);
-                l.y = fmaf(L.s[1 * kLpMaxF + t], xv, l.y);
-                l.z = fmaf(L.s[2 * kLpMaxF + t], xv, l.z);
-                l.w = fmaf(L.s[3 * kLpMaxF + t], xv, l.w);
-            }
-            mx.x = fmaxf(mx.x, lp_leaky(l.x + adst.x, a.slope_att));
-            mx.y = fmaxf(mx.y, lp_leaky(l.y + adst.y, a.slope_att));
-            mx.z = fmaxf(mx.z, lp_leaky(l.z + adst.z, a.slope_att));
-            mx.w = fmaxf(mx.w, lp_leaky(l.w + adst.w, a.slope_att));
+            float l[kLpHeads] = {};
+            lp_dot4(L.s, a.x + src * F, F, l);
+#pragma unroll
+            for (int hh = 0; hh < kLpHeads; ++hh) mx[hh] = fmaxf(mx[hh], lp_leaky(l[hh] + adst[hh], a.slope_att));
         }
     }
     if (__any(bad)) {                                          // (wave-uniform)
@@ -193,15 +197,13 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
     }
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) {                  // (a maximum: exact in any order)
-        mx.x = fmaxf(mx.x, __shfl_xor(mx.x, o));
-        mx.y = fmaxf(mx.y, __shfl_xor(mx.y, o));
-        mx.z = fmaxf(mx.z, __shfl_xor(mx.z, o));
-        mx.w = fmaxf(mx.w, __shfl_xor(mx.w, o));
+#pragma unroll
+        for (int hh = 0; hh < kLpHeads; ++hh) mx[hh] = fmaxf(mx[hh], __shfl_xor(mx[hh], o));
     }
-    R.mx = mx;
-    if (lane == 0) {
-        L.ps[0] = expf(lself.x - mx.x); L.ps[1] = expf(lself.y - mx.y);
-        L.ps[2] = expf(lself.z - mx.z); L.ps[3] = expf(lself.w - mx.w);
+#pragma unroll
+    for (int hh = 0; hh < kLpHeads; ++hh) {
+        R.mx[hh] = mx[hh];
+        if (lane == 0) L.ps[hh] = expf(lself[hh] - mx[hh]);
     }
 
     // ---- step 2: weights and source rows of a chunk -> LDS, then the sums in slice order ----
@@ -210,20 +212,11 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
         int64_t src = 0;
         const bool msg = lp_edge(a, e0, m, base + lane, n0, n1, i, src) == 1;
         if (msg) {
-            const float* xj = a.x + src * F;
-            float4 l = f4zero();
-            for (int t = 0; t < F; ++t) {
-                const float xv = xj[t];
-                L.xs[lane * kLpXs + t] = xv;
-                l.x = fmaf(L.s[0 * kLpMaxF + t], xv, l.x);
-                l.y = fmaf(L.s[1 * kLpMaxF + t], xv, l.y);
-                l.z = fmaf(L.s[2 * kLpMaxF + t], xv, l.z);
-                l.w = fmaf(L.s[3 * kLpMaxF + t], xv, l.w);
-            }
-            L.pw[0 * kWave + lane] = expf(lp_leaky(l.x + adst.x, a.slope_att) - mx.x);
-            L.pw[1 * kWave + lane] = expf(lp_leaky(l.y + adst.y, a.slope_att) - mx.y);
-            L.pw[2 * kWave + lane] = expf(lp_leaky(l.z + adst.z, a.slope_att) - mx.z);
-            L.pw[3 * kWave + lane] = expf(lp_leaky(l.w + adst.w, a.slope_att) - mx.w);
+            float l[kLpHeads] = {};
+            lp_dot4(L.s, a.x + src * F, F, l, L.xs + lane * kLpXs);
+#pragma unroll
+            for (int hh = 0; hh < kLpHeads; ++hh)
+                L.pw[hh * kWave + lane] = expf(lp_leaky(l[hh] + adst[hh], a.slope_att) - mx[hh]);
         }
         unsigned long long mask = __ballot(msg);
         __syncthreads();
@@ -309,32 +302,34 @@ __device__ __forceinline__ bool lp_locate(const LpArgs& a, int64_t r, float* oro
     return true;
 }
 
-// the checks of qot_lightpath_infer that its sensitivity variant shares, in one place: returns QOT_OK and `rows` (0: an
-// empty batch, nothing to launch), or the error.  Sizes first, then the envelope, then -- when there are rows -- the
-// pointers every row reads through.
-inline int lp_check(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
-                    const int64_t* edge_ptr, const int64_t* lut_idx, int64_t L, int64_t N, int64_t E, int64_t B, const float* w,
-                    const float* att_src, const float* att_dst, const float* conv_bias, const float* bn_weight,
-                    const float* bn_bias, const float* bn_mean, const float* bn_var, const float* w0, const float* b0,
-                    const float* w3, const float* b3, const float* out, const int32_t* count, int F, int C, int O, int heads,
-                    int lut_col, int Q, int64_t* rows_) {
-    *rows_ = 0;
+// What both entry points do with the arguments they share, passed on in the ABI's order (Q: the eval entry passes 1):
+// sizes first, then the envelope, then -- when there are rows -- the pointers every row reads through.  Returns QOT_OK
+// with `a` and `rows` filled (rows == 0: an empty batch, nothing to launch), or the error.
+inline int lp_args(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                   const int64_t* edge_ptr, const int64_t* lut_idx, int64_t L, int64_t N, int64_t E, int64_t B, const float* w,
+                   const float* att_src, const float* att_dst, const float* conv_bias, float slope_att, const float* bn_weight,
+                   const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps, const float* w0,
+                   const float* b0, const float* w3, const float* b3, float slope_head, float* out, int32_t* count, int F, int C,
+                   int O, int heads, int lut_col, int32_t* status, int Q, LpArgs& a, int64_t& rows) {
+    rows = 0;
     if (N < 0 || E < 0 || B < 0 || L < 0) return QOT_ERR_BADARG;
     if (F < 1 || F > kLpMaxF) return QOT_ERR_UNSUPPORTED;
     if (C < 1 || C > kLpMaxC) return QOT_ERR_UNSUPPORTED;
     if (O < 1 || O > kLpMaxO) return QOT_ERR_UNSUPPORTED;
     if (heads != kLpHeads) return QOT_ERR_UNSUPPORTED;
     if (lut_col < 0 || lut_col >= F) return QOT_ERR_UNSUPPORTED;
-    if (Q < 1 || Q > O) return QOT_ERR_UNSUPPORTED;           // (the eval entry passes Q = 1)
-    const int64_t rows = lut_idx ? L : B;
-    if (rows == 0) return QOT_OK;
-    if (rows > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
+    if (Q < 1 || Q > O) return QOT_ERR_UNSUPPORTED;
+    const int64_t n = lut_idx ? L : B;
+    if (n == 0) return QOT_OK;
+    if (n > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
     if (!node_ptr || !edge_ptr || !w || !att_src || !att_dst || !conv_bias || !bn_weight || !bn_bias || !bn_mean || !bn_var ||
         !w0 || !b0 || !w3 || !b3 || !out)
         return QOT_ERR_BADARG;
     if ((N > 0 && !x) || (E > 0 && !edge_index)) return QOT_ERR_BADARG;
     if (lut_idx ? !batch : !count) return QOT_ERR_BADARG;
-    *rows_ = rows;
+    a = LpArgs{x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias, slope_att,
+               bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, count, F, C, O, lut_col, status};
+    rows = n;
     return QOT_OK;
 }
 

@@ -120,10 +120,9 @@ __global__ __launch_bounds__(kWave) void lightpath_infer_grad_kernel(const LpArg
 
     // ---- phase B: third scan of the edge slice ----
     const float sl = a.slope_att;
-    const float mx[kLpHeads] = {R.mx.x, R.mx.y, R.mx.z, R.mx.w};
-    const float adst[kLpHeads] = {R.adst.x, R.adst.y, R.adst.z, R.adst.w};
-    const float den[kLpHeads] = {G.keep.den[0] + 1e-16f, G.keep.den[1] + 1e-16f, G.keep.den[2] + 1e-16f,
-                                 G.keep.den[3] + 1e-16f};
+    float den[kLpHeads];
+#pragma unroll
+    for (int hh = 0; hh < kLpHeads; ++hh) den[hh] = G.keep.den[hh] + 1e-16f;
     float* bq = L.part;                                        // a chunk's b [q * 4 + h][lane]
     float dsum = 0.f;
     for (int64_t base = 0; base < R.m; base += kWave) {
@@ -131,32 +130,21 @@ __global__ __launch_bounds__(kWave) void lightpath_infer_grad_kernel(const LpArg
         const bool msg = lp_edge(a, R.e0, R.m, base + lane, R.n0, R.n1, i, src) == 1;
         if (msg) {
             const int64_t e = R.e0 + base + lane;
-            const float* xj = a.x + src * F;
             float* xs = L.xs + lane * kLpXs;                   // (this lane's own row: no barrier needed)
-            float l[kLpHeads] = {0.f, 0.f, 0.f, 0.f};
-            for (int t = 0; t < F; ++t) {
-                const float xv = xj[t];
-                xs[t] = xv;
-#pragma unroll
-                for (int hh = 0; hh < kLpHeads; ++hh) l[hh] = fmaf(L.s[hh * kLpMaxF + t], xv, l[hh]);
-            }
+            float l[kLpHeads] = {};
+            lp_dot4(L.s, a.x + src * F, F, l, xs);
             float al[kLpHeads], dk[kLpHeads];
 #pragma unroll
             for (int hh = 0; hh < kLpHeads; ++hh) {
-                const float raw = l[hh] + adst[hh];
-                al[hh] = expf(lp_leaky(raw, sl) - mx[hh]) / den[hh];
+                const float raw = l[hh] + R.adst[hh];
+                al[hh] = expf(lp_leaky(raw, sl) - R.mx[hh]) / den[hh];
                 dk[hh] = raw > 0.f ? 1.f : sl;
                 if (ga.alpha_edge) ga.alpha_edge[e * kLpHeads + hh] = al[hh];
             }
             for (int q = 0; q < Q; ++q) {
                 const float* gu = G.gu + q * kLpGu;
-                float dt[kLpHeads] = {0.f, 0.f, 0.f, 0.f};
-                for (int t = 0; t < F; ++t) {
-                    const float xv = xs[t];
-#pragma unroll
-                    for (int hh = 0; hh < kLpHeads; ++hh) dt[hh] = fmaf(gu[hh * kLpMaxF + t], xv, dt[hh]);
-                }
-                float b[kLpHeads];
+                float dt[kLpHeads] = {}, b[kLpHeads];
+                lp_dot4(gu, xs, F, dt);
 #pragma unroll
                 for (int hh = 0; hh < kLpHeads; ++hh) {
                     b[hh] = al[hh] * (dt[hh] - G.gud[q * kLpHeads + hh]) * dk[hh];
@@ -189,22 +177,17 @@ __global__ __launch_bounds__(kWave) void lightpath_infer_grad_kernel(const LpArg
     __syncthreads();
 
     // ---- phase C: the self loop and the destination's own row ----
-    const float rself[kLpHeads] = {R.rself.x, R.rself.y, R.rself.z, R.rself.w};
     float as[kLpHeads], dks[kLpHeads];
 #pragma unroll
     for (int hh = 0; hh < kLpHeads; ++hh) {
         as[hh] = L.ps[hh] / den[hh];
-        dks[hh] = rself[hh] > 0.f ? 1.f : sl;
+        dks[hh] = R.rself[hh] > 0.f ? 1.f : sl;
         if (ga.alpha_self && lane == hh) ga.alpha_self[r * kLpHeads + hh] = as[hh];
     }
     for (int q = 0; q < Q; ++q) {
         const float* gu = G.gu + q * kLpGu;
-        float dt[kLpHeads] = {0.f, 0.f, 0.f, 0.f};
-        for (int t = 0; t < F; ++t) {
-            const float xv = L.xi[t];
-#pragma unroll
-            for (int hh = 0; hh < kLpHeads; ++hh) dt[hh] = fmaf(gu[hh * kLpMaxF + t], xv, dt[hh]);
-        }
+        float dt[kLpHeads] = {};
+        lp_dot4(gu, L.xi, F, dt);
         if (lane < F) {
             float v = 0.f;
 #pragma unroll
@@ -234,14 +217,13 @@ extern "C" int qot_lightpath_infer_grad(const float* x, const int64_t* edge_inde
                                         int32_t* status, const int32_t* outputs, int Q, float* jac_self, float* jac_edge,
                                         float* alpha_self, float* alpha_edge, qot_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    LpArgs a;
     int64_t rows = 0;
-    const int rc = lp_check(x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias,
-                            bn_weight, bn_bias, bn_mean, bn_var, w0, b0, w3, b3, out, count, F, C, O, heads, lut_col, Q, &rows);
+    const int rc = lp_args(x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias,
+                           slope_att, bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, count, F, C,
+                           O, heads, lut_col, status, Q, a, rows);
     if (rc != QOT_OK || rows == 0) return rc;
     if (!outputs || !jac_self || (E > 0 && !jac_edge)) return QOT_ERR_BADARG;
-    const LpArgs a{x, edge_index, batch, node_ptr, edge_ptr, lut_idx, L, N, E, B, w, att_src, att_dst, conv_bias, slope_att,
-                   bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, count, F, C, O, lut_col,
-                   status};
     const LpGradArgs ga{outputs, Q, jac_self, jac_edge, alpha_self, alpha_edge};
     lightpath_infer_grad_kernel<<<(int)rows, kWave, 0, stream>>>(a, ga);
     QOT_LAUNCH_CHECK();

@@ -175,11 +175,41 @@ def graph_slices(data, ei, N, dev, who):
     return ptr, eptr, B, n_max, max_e, exact
 
 
+class _DeviceState:
+    """What both predictors keep on the device beside the model: the status word their kernels flag a batch in and the
+    ``outputs`` selections of ``sensitivity``.  ``_FLAGS`` of a predictor: its kernel's name, the meaning of the status bits."""
+
+    def __init__(self):
+        self._status = None
+        self._outputs_dev = {}
+
+    def _status_on(self, dev):
+        if self._status is None or self._status.device != dev:
+            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _outputs(self, sel, dev):
+        """``sel`` as a device int32 tensor: one upload per selection and device, none in later calls."""
+        t = self._outputs_dev.get((tuple(sel), dev))
+        if t is None:
+            t = self._outputs_dev[(tuple(sel), dev)] = torch.tensor(sel, dtype=torch.int32, device=dev)
+        return t
+
+    def check_status(self):
+        """Reads the kernels' status word (one device synchronisation): raises when a batch since the last check had an
+        edge outside its graph's node range or indices / slices that disagree with its arrays (such rows are NaN)."""
+        if self._status is None:
+            return
+        code = int(self._status.item())
+        self._status.zero_()
+        if code:
+            raise _lib.QotError("%s flagged the batch (status %d): %s" % (self._FLAGS[0], code, self._FLAGS[1]))
+
+
 # what TopologicalPredictor._prepare hands to _launch: the model's shape, the batch on dev, its size bounds, the tables
 _Prepared = namedtuple("_Prepared", "H D O dev ids ei ea ptr eptr n_max max_e B tables")
 
 
-class TopologicalPredictor:
+class TopologicalPredictor(_DeviceState):
     """``predictor(data) -> out [B, O]``: the EVAL-MODE forward of a two-layer ``TopologicalGNN`` as one kernel launch.
 
     ``model.training`` does not matter: the predictor always computes the eval-mode function (no dropout).  The result
@@ -200,11 +230,14 @@ class TopologicalPredictor:
     ``predictor.sensitivity(data)``: the output together with its Jacobian wrt the edge features, in one launch.
     """
 
+    _FLAGS = ("qot_topological_infer", "bit 0 an edge leaves its graph's node range, bit 1 slices outside the arrays, "
+                                       "bit 2 a node id outside the table")
+
     def __init__(self, model):
+        super().__init__()
         self.model = model
         self._tables = None
         self._tag = None
-        self._status = None
         self._check_model()
 
     # ------------------------------------------------------------------ envelope
@@ -332,8 +365,7 @@ class TopologicalPredictor:
         ea = _f32c(ea if ea.device == dev else ea.to(dev))
         t = self._refresh(H, D)
         self._check_ids(data, ids, t["V"], n_max)
-        if self._status is None or self._status.device != dev:
-            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._status_on(dev)
         return _Prepared(H, D, O, dev, ids, ei, ea, ptr, eptr, n_max, max_e, B, t)
 
     def _launch(self, name, p, out, *extra):
@@ -410,25 +442,10 @@ class TopologicalPredictor:
         out = torch.empty(p.B, p.O, dtype=torch.float32, device=dev)
         jac = torch.empty(Q, E, p.D, dtype=torch.float32, device=dev)
         alpha = torch.empty(E, 1, dtype=torch.float32, device=dev) if return_attention_weights else None
-        cache = self.__dict__.setdefault("_outputs_dev", {})     # one upload per selection: the call stays ONE launch
-        osel = cache.get((tuple(sel), dev))
-        if osel is None:
-            osel = cache[(tuple(sel), dev)] = torch.tensor(sel, dtype=torch.int32, device=dev)
-        self._launch("qot_topological_infer_grad", p, out, osel, Q, jac, alpha)
+        self._launch("qot_topological_infer_grad", p, out, self._outputs(sel, dev), Q, jac, alpha)
         if return_attention_weights:
             return out, jac, (data.edge_index, alpha)
         return out, jac
-
-    def check_status(self):
-        """Reads the kernel's status word (one device synchronisation): raises when a batch since the last check had an
-        edge outside its graph's node range or slices that disagree with its arrays (such graphs' rows are NaN)."""
-        if self._status is None:
-            return
-        code = int(self._status.item())
-        self._status.zero_()
-        if code:
-            raise _lib.QotError(f"qot_topological_infer flagged the batch (status {code}): bit 0 an edge leaves its "
-                                "graph's node range, bit 1 slices outside the arrays, bit 2 a node id outside the table")
 
 
 # ====================================================================== LightpathGNN
@@ -443,7 +460,12 @@ class EnvelopeError(ValueError):
     NOT one: that is the model's own ``ValueError``.)"""
 
 
-class LightpathPredictor:
+# what LightpathPredictor._prepare hands to _launch: the model's shape, the batch on dev, which rows (rows mode: batch,
+# idx; graphs mode: a fresh count) and how many
+_LpPrepared = namedtuple("_LpPrepared", "F C O dev x ei batch ptr eptr idx B rows count")
+
+
+class LightpathPredictor(_DeviceState):
     """``predict = LightpathPredictor(model)``: the EVAL-MODE forward of a one-layer ``LightpathGNN`` as one kernel launch
     that computes the LUT rows only (one wavefront per row, no graph index, no other node's row).
 
@@ -472,14 +494,16 @@ class LightpathPredictor:
     the rows of that graph NaN and ``check_status()`` raise.
     """
 
-    def __init__(self, model):
-        self.model = model
-        self._status = None
-        self._outputs_dev = {}
-        F, C, O = self._check_model()
-        self._outputs(list(range(O)), model.conv1.bias.device)      # the default selection is uploaded here, not in a call
+    _FLAGS = ("qot_lightpath_infer", "bit 0 an edge leaves its graph's node range, bit 1 a LUT index, graph number or slice "
+                                     "outside the arrays")
 
-    def _check_model(self, on_gpu=True):
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+        F, C, O = self._check_model()
+        self._outputs(list(range(O)), self._device())               # the default selection is uploaded here, not in a call
+
+    def _check_model(self):
         m = self.model
         if getattr(m, "num_layers", None) != 1 or not hasattr(m, "conv1") or not hasattr(m, "norm1"):
             raise EnvelopeError(f"LightpathPredictor: num_layers must be 1 (the reference architecture: one GATConv), got "
@@ -496,9 +520,13 @@ class LightpathPredictor:
             raise EnvelopeError(f"LightpathPredictor: output_dim {O} is not supported; it must be 1 ... {LP_MAX_OUTPUTS}")
         if not 0 <= int(m.is_lut_index) < F:
             raise EnvelopeError(f"LightpathPredictor: is_lut_index {m.is_lut_index} is not a column of {F} features")
-        if on_gpu and not conv.bias.is_cuda:
-            raise EnvelopeError("LightpathPredictor: the model is on the CPU; move it to the GPU first (model.to('cuda'))")
         return F, C, O
+
+    def _device(self):
+        bias = self.model.conv1.bias
+        if not bias.is_cuda:
+            raise EnvelopeError("LightpathPredictor: the model is on the CPU; move it to the GPU first (model.to('cuda'))")
+        return bias.device
 
     def _batch(self, data, F, dev):
         """``(x, edge_index, node_ptr, edge_ptr, B)`` on ``dev``; the slices are remembered on the batch object."""
@@ -519,51 +547,50 @@ class LightpathPredictor:
             c["infer_lp"] = (tag, res)
         return (x,) + res
 
-    def _outputs(self, sel, dev):
-        """``sel`` as a device int32 tensor: one upload per selection and device, none in later calls."""
-        t = self._outputs_dev.get((tuple(sel), dev))
-        if t is None:
-            t = self._outputs_dev[(tuple(sel), dev)] = torch.tensor(sel, dtype=torch.int32, device=dev)
-        return t
+    def _prepare(self, data, per_graph, shape=None):
+        """Everything a launch needs, checked, as an ``_LpPrepared``.  ``per_graph``: one row per graph, found on the device,
+        instead of the model's LUT rows.  ``shape``: ``_check_model()``'s answer, when the caller has asked already."""
+        F, C, O = shape or self._check_model()
+        dev = self._device()
+        x, ei, ptr, eptr, B = self._batch(data, F, dev)
+        if per_graph:
+            idx = batch = None
+            rows, count = B, torch.empty(B, dtype=torch.int32, device=dev)
+        else:
+            idx = self.model._lut_rows(data)        # the model's ValueError for a LUT-less batch
+            batch, idx = _i64(data.batch, dev), _i64(idx, dev)
+            rows, count = idx.shape[0], None
+        self._status_on(dev)
+        return _LpPrepared(F, C, O, dev, x, ei, batch, ptr, eptr, idx, B, rows, count)
 
-    def _launch(self, x, ei, batch, ptr, eptr, lut_idx, B, out, count, F, C, O, name="qot_lightpath_infer", extra=()):
-        """One launch of entry point ``name``: the arguments the two kernels share, then ``extra``."""
-        m = self.model
-        conv, bn, l0, l3 = m.conv1, m.norm1.module, m.mlp[0], m.mlp[3]
-        dev = out.device
-        if self._status is None or self._status.device != dev:
-            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
-        p = [_f32c(t.detach()) for t in (conv.lin.weight, conv.att_src, conv.att_dst, conv.bias, bn.weight, bn.bias,
-                                         bn.running_mean, bn.running_var, l0.weight, l0.bias, l3.weight, l3.bias)]
-        _lib.call(name, x, ei, batch, ptr, eptr, lut_idx, 0 if lut_idx is None else lut_idx.shape[0],
-                  x.shape[0], ei.shape[1], B, p[0], p[1], p[2], p[3], float(conv.negative_slope), p[4], p[5], p[6], p[7],
-                  float(bn.eps), p[8], p[9], p[10], p[11], float(m.mlp[1].negative_slope), out, count, F, C, O,
-                  int(conv.heads), int(m.is_lut_index), self._status, *extra)
+    def _launch(self, name, p, out, *extra):
+        """One launch of entry point ``name``: the arguments the two kernels share (``out`` among them), then ``extra``;
+        none for 0 rows (only with ``allow_empty_lut``, or an empty batch).  Returns what the call hands back beside its
+        rows: ``count``, or ``lut_batch`` -- gathered behind the launch, so that the kernel is not queued after it."""
+        F, C, O, _, x, ei, batch, ptr, eptr, idx, B, rows, count = p
+        if rows:
+            m = self.model
+            conv, bn, l0, l3 = m.conv1, m.norm1.module, m.mlp[0], m.mlp[3]
+            w = [_f32c(t.detach()) for t in (conv.lin.weight, conv.att_src, conv.att_dst, conv.bias, bn.weight, bn.bias,
+                                             bn.running_mean, bn.running_var, l0.weight, l0.bias, l3.weight, l3.bias)]
+            _lib.call(name, x, ei, batch, ptr, eptr, idx, 0 if idx is None else rows, x.shape[0], ei.shape[1], B, *w[:4],
+                      float(conv.negative_slope), *w[4:8], float(bn.eps), *w[8:], float(m.mlp[1].negative_slope), out, count,
+                      F, C, O, int(conv.heads), int(m.is_lut_index), self._status, *extra)
+        if idx is None:
+            return count
+        return batch.index_select(0, idx) if rows else batch[:0]
 
     @torch.no_grad()
     def __call__(self, data):
-        F, C, O = self._check_model()
-        m = self.model
-        dev = m.conv1.bias.device
-        x, ei, ptr, eptr, B = self._batch(data, F, dev)
-        idx = m._lut_rows(data)                     # the model's ValueError for a LUT-less batch
-        batch = _i64(data.batch, dev)
-        idx = _i64(idx, dev)
-        out = torch.empty(idx.shape[0], O, dtype=torch.float32, device=dev)
-        if idx.shape[0] == 0:                       # only with allow_empty_lut
-            return out, batch[:0]
-        self._launch(x, ei, batch, ptr, eptr, idx, B, out, None, F, C, O)
-        return out, batch.index_select(0, idx)
+        p = self._prepare(data, False)
+        out = torch.empty(p.rows, p.O, dtype=torch.float32, device=p.dev)
+        return out, self._launch("qot_lightpath_infer", p, out)
 
     @torch.no_grad()
     def per_graph(self, data):
-        F, C, O = self._check_model()
-        dev = self.model.conv1.bias.device
-        x, ei, ptr, eptr, B = self._batch(data, F, dev)
-        out = torch.empty(B, O, dtype=torch.float32, device=dev)
-        count = torch.empty(B, dtype=torch.int32, device=dev)
-        self._launch(x, ei, None, ptr, eptr, None, B, out, count, F, C, O)
-        return out, count
+        p = self._prepare(data, True)
+        out = torch.empty(p.rows, p.O, dtype=torch.float32, device=p.dev)
+        return out, self._launch("qot_lightpath_infer", p, out)
 
     @torch.no_grad()
     def sensitivity(self, data, outputs=None, *, per_graph=False, return_attention_weights=False):
@@ -600,43 +627,17 @@ class LightpathPredictor:
         flagged row (``check_status()`` raises) has NaN in its ``out`` and ``jac_self`` rows and, its graph's edge slice
         being valid, over that slice of ``jac_edge`` / ``alpha_edge``."""
         # the model's shape, then the argument, are named before the model's device and the batch are looked at
-        sel = grad_outputs(outputs, self._check_model(on_gpu=False)[2], "LightpathPredictor.sensitivity")
-        F, C, O = self._check_model()
-        m = self.model
-        dev = m.conv1.bias.device
-        x, ei, ptr, eptr, B = self._batch(data, F, dev)
-        E, Q = ei.shape[1], len(sel)
-        if per_graph:
-            idx = batch = None
-            rows = B
-            second = torch.empty(B, dtype=torch.int32, device=dev)
-        else:
-            idx = m._lut_rows(data)                 # the model's ValueError for a LUT-less batch
-            batch, idx = _i64(data.batch, dev), _i64(idx, dev)
-            rows = idx.shape[0]
-            second = batch.index_select(0, idx) if rows else batch[:0]
-        out = torch.empty(rows, O, dtype=torch.float32, device=dev)
-        jac_self = torch.empty(Q, rows, F, dtype=torch.float32, device=dev)
-        jac_edge = torch.zeros(Q, E, F, dtype=torch.float32, device=dev)
-        alpha = None
+        shape = self._check_model()
+        sel = grad_outputs(outputs, shape[2], "LightpathPredictor.sensitivity")
+        p = self._prepare(data, per_graph, shape)
+        E, Q, rows, dev = p.ei.shape[1], len(sel), p.rows, p.dev
+        out = torch.empty(rows, p.O, dtype=torch.float32, device=dev)
+        jac_self = torch.empty(Q, rows, p.F, dtype=torch.float32, device=dev)
+        jac_edge = torch.zeros(Q, E, p.F, dtype=torch.float32, device=dev)
+        alpha = (None, None)
         if return_attention_weights:
             alpha = (torch.empty(rows, LP_HEADS, dtype=torch.float32, device=dev),
                      torch.zeros(E, LP_HEADS, dtype=torch.float32, device=dev))
-        if rows:                                    # (0 rows: only with allow_empty_lut, or an empty batch)
-            self._launch(x, ei, batch, ptr, eptr, idx, B, out, second if per_graph else None, F, C, O,
-                         "qot_lightpath_infer_grad", (self._outputs(sel, dev), Q, jac_self, jac_edge,
-                                                      None if alpha is None else alpha[0],
-                                                      None if alpha is None else alpha[1]))
+        second = self._launch("qot_lightpath_infer_grad", p, out, self._outputs(sel, dev), Q, jac_self, jac_edge, *alpha)
         res = (out, second, jac_self, jac_edge)
         return res + (alpha,) if return_attention_weights else res
-
-    def check_status(self):
-        """Reads the status word of both kernels (one device synchronisation): raises when a batch since the last check had
-        an edge outside its graph's node range or indices / slices that disagree with its arrays (such rows are NaN)."""
-        if self._status is None:
-            return
-        code = int(self._status.item())
-        self._status.zero_()
-        if code:
-            raise _lib.QotError(f"qot_lightpath_infer flagged the batch (status {code}): bit 0 an edge leaves its "
-                                "graph's node range, bit 1 a LUT index, graph number or slice outside the arrays")

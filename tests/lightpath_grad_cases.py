@@ -128,6 +128,21 @@ def parity_case(C, F, O, lut):
     return ref, batch, out64, grad64
 
 
+EDGE_SHAPES = ((1, 1, 1), (16, 256, 8))   # (F, C, O): only lanes 0 - 3 own an (h, f) pair; all 64 lanes do
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(F, C, O):
+    """``(ref, batch, out64, grad64)`` at the ends of the envelope's widths (LUT column 0), three graphs with one LUT node
+    each: in-degree 65 (messages at slice offsets 0, 63 and 64: across the chunk boundary of the scan), in-degree 129
+    (three chunks) and in-degree 0 (only the appended self loop).  Model seed 0: the oracle's fp32 and fp64 ``x.grad``
+    agree to ``TOL / 10`` on every graph's own slice, and no graph's gradient vanishes for any output."""
+    ref = oracle_model(F, C, O, 0)
+    batch = q.Batch.from_data_list([_star(65, F, 0, 60), _star(129, F, 0, 61), _graph(3, [0, 1], [1, 2], (0,), F, 0, 62)])
+    out64, grad64 = oracle_xgrad(ref, batch)
+    return ref, batch, out64, grad64
+
+
 def independence_graphs(F=5, lut=1):
     """``(g, others)`` of the bitwise-independence test: a 150-star with back edges, and six other graphs (the sixth has
     two LUT nodes)."""

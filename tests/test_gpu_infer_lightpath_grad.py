@@ -78,6 +78,40 @@ def test_parity_mixed_batch(cuda_device, Cw, F, O):
         _parity(cuda_device, Cw, F, O, lut)
 
 
+# ------------------------------------------------------------------ 1b. the ends of the widths, the chunk boundary
+@pytest.mark.parametrize("F,Cw,O", C.EDGE_SHAPES)
+def test_chunk_boundaries_and_a_lone_self_loop_at_the_ends_of_the_widths(cuda_device, F, Cw, O):
+    """In-degree 65, in-degree 129 and a LUT node with only its self loop, at ``(F, C, O) = (1, 1, 1)`` (lanes 0 - 3 own an
+    ``(h, f)`` pair) and ``(16, 256, 8)`` (all 64 do): ``predict``, ``per_graph`` and ``sensitivity`` in both modes against
+    the fp64 oracle, each graph on its own slice; the three calls' ``out`` bit for bit."""
+    ref, batch, out64, grad64 = C.edge_case(F, Cw, O)
+    pred = q.LightpathPredictor(C.engine_model(ref, cuda_device))
+    db = batch.to(cuda_device)
+    rows, N = C.lut_rows(batch, 0), batch.x.shape[0]
+    out, lb = pred(db)
+    per, count = pred.per_graph(db)
+    assert lb.tolist() == [0, 1, 2] and count.tolist() == [1, 1, 1]
+    assert torch.equal(per, out)
+    for g in range(3):
+        e = rel_err(out[g], out64[g])
+        print(f"F {F} C {Cw} O {O} graph {g}: out vs oracle {e:.3e}")
+        assert e <= TOL, (g, e)
+    for per_graph in (False, True):
+        s_out, second, js, je, (a_self, a_edge) = pred.sensitivity(db, per_graph=per_graph, return_attention_weights=True)
+        assert torch.equal(s_out, out) and torch.equal(second, count if per_graph else lb)
+        assert tuple(js.shape) == (O, 3, F) and tuple(je.shape) == (O, batch.edge_index.shape[1], F)
+        J = C.assemble(js, je, batch.edge_index, rows, N)
+        for g, (n0, n1) in enumerate(C.slices(batch.ptr)):
+            for k in range(O):
+                e = rel_err(J[k, n0:n1], grad64[k, n0:n1])
+                print(f"F {F} C {Cw} O {O} per_graph {per_graph} graph {g} output {k}: vs oracle {e:.3e}")
+                assert e <= TOL, (per_graph, g, k, e)
+        total = a_self.double().cpu()
+        total.index_add_(0, batch.batch[batch.edge_index[1]], a_edge.double().cpu())     # (non-messages hold 0)
+        assert float((total - 1.0).abs().max()) <= 1e-5
+    pred.check_status()
+
+
 # ------------------------------------------------------------------ 2. edge level
 def test_repeated_edges_get_their_own_share_and_an_input_self_loop_none(cuda_device):
     ref, batch, hip, pred, (out, lb, js, je), grad64 = _parity(cuda_device, 32, 5, 3, 1)

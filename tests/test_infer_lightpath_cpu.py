@@ -61,3 +61,4 @@ def test_entry_refuses_shapes_outside_the_envelope_before_any_launch():
                 dict(lut_col=-1), dict(lut_col=5)):
         assert rc(**bad) == -1, bad                     # QOT_ERR_UNSUPPORTED
     assert rc(B=-1) == -2 and rc(B=3) == -2             # QOT_ERR_BADARG: negative size; rows to compute but no arrays
+    assert rc(B=3, F=0) == -1                           # the envelope is answered before the arrays are looked at

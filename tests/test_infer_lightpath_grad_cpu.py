@@ -33,6 +33,11 @@ def test_symbol_declared_bound_and_exported():
     p = ctypes.c_void_p
     assert gr[:len(ev) - 1] == ev[:-1] and gr[-1] is p
     assert gr[len(ev) - 1:-1] == [p, ctypes.c_int, p, p, p, p]
+    # both rows are built from the shared list, which ends with the status word
+    common = _lib._LP_COMMON
+    assert ev == common + [p] and gr == common + [p, ctypes.c_int, p, p, p, p, p] and common[-1] is p
+    ev_decl = re.search(r"int qot_lightpath_infer\(([^;]*)\);", hdr).group(1)
+    assert len(ev) == ev_decl.count(",") + 1 and ev_decl.split(",")[len(common) - 1].split()[-1] == "status"
     assert hasattr(q.LightpathPredictor, "sensitivity")
 
 
@@ -109,6 +114,22 @@ def test_parity_fixtures_are_sound(C_, F, O):
         assert batch.x.shape[0] == 394 + 6 + 5 and batch.edge_index.shape[1] == 456 + 10 + 5
         assert out64.shape[0] == 14 + 2 + 1 and float(grad64.abs().max()) > 0
         print(f"C {C_} F {F} O {O} lut {lut}: oracle fp32 vs fp64 x.grad {_sound(ref, batch, grad64):.3e}")
+
+
+@pytest.mark.parametrize("F,C_,O", C.EDGE_SHAPES)
+def test_edge_case_fixture_is_sound(F, C_, O):
+    ref, batch, out64, grad64 = C.edge_case(F, C_, O)
+    rows = C.lut_rows(batch, 0)
+    assert batch.batch[rows].tolist() == [0, 1, 2] and tuple(grad64.shape) == (O, 66 + 130 + 3, F)
+    e0, e1, e2 = C.slices(batch.edge_ptr)
+    assert (e0[1] - e0[0], e1[1] - e1[0]) == (65, 129) and int(C.message_mask(batch, rows)[e2[0]:e2[1]].sum()) == 0
+    assert bool(C.message_mask(batch, rows)[:e1[1]].all())   # every offset of the two stars' slices is a message
+    _, grad32 = C.oracle_xgrad(ref, batch, dtype=torch.float32)
+    for n0, n1 in C.slices(batch.ptr):                        # per graph: the small gradients of a star are judged too
+        for k in range(O):
+            assert float(grad64[k, n0:n1].abs().max()) > 0
+            assert rel_err(grad32[k, n0:n1], grad64[k, n0:n1]) <= TOL / 10, (n0, k)
+    _sound(ref, batch, grad64)
 
 
 def test_the_unrolled_graph_restates_the_triple_edge():
