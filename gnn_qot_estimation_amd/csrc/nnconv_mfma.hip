@@ -426,7 +426,10 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
 
 // VARIANT (diagnostic build only): 0 production; 1 every gathered row read from ONE hot address (no row-load latency);
 // 2 no grad_x loop; 3 no weight-gradient loop; 4 no gather; 5 neither MFMA loop (gather + exchange only)
-template <int D, int VARIANT = 0>
+// SPLIT: the weight-gradient product as split-bf16 MFMAs (the production form; VARIANT builds keep the fp32 loop).  The
+// grad_x product is the fp32 loop either way: its B operand would be bf16 planes of WcatT, which this entry point
+// does not receive.
+template <int D, int VARIANT = 0, bool SPLIT = false>
 __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
     const float* __restrict__ g, int ldg, const float* __restrict__ xf, int ldx, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr_t,
@@ -624,11 +627,35 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
         else { QOT_GIVE(0, 2) QOT_GIVE(1, 2) QOT_GIVE(2, 2) }
 #undef QOT_GIVE
         // ---- weight gradient: gWcat^T[(k,o)][a] += sum_j U[j][(k,o)] x[j][a]
-        // Step s = 4a + b multiplies tile rows 2s, 2s+1.  Software-pipelined by hand: the TPW transposed
+        // fp32 form (the else branch): step s = 4a + b multiplies tile rows 2s, 2s+1.  Software-pipelined by hand: the TPW transposed
         // reads of step s+1 are issued before the TPW MFMAs of step s (left to itself the compiler
         // reused ONE temporary and put `ds_read_b32; s_waitcnt lgkmcnt(0)` in front of every MFMA --
         // half of all MFMAs of this kernel waited for their own LDS read).
-        if (VARIANT != 3 && VARIANT != 5) {
+        if (SPLIT) {
+            // Split form (split_bf16.hpp): both operands are in LDS already, so each is split after its read.  Step s
+            // covers tile rows jj = 8a + 2b + hi with a = 2s + (j >> 2), b = j & 3, j = 0..7: the bf16 MFMA contracts
+            // element j of lane half hi on BOTH operands, so A and B only have to use the same map.  Same 80 transposed
+            // reads of Ut per wave and tile as the fp32 form, at the same addresses; tile rows >= N hold zeros in Ut
+            // and xs, and zero splits to zero.  Rolled, with a sched_barrier per accumulator tile: fully unrolled, D = 4
+            // took 256 VGPRs and spilled.
+#pragma unroll 1
+            for (int s = 0; s < 2; ++s) {
+                float xv[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    xv[j] = xs[(8 * (2 * s + (j >> 2)) + 2 * (j & 3) + hi) * 64 + ah * 32 + r31];
+                const Bf3 xb = split8(make_float4(xv[0], xv[1], xv[2], xv[3]), make_float4(xv[4], xv[5], xv[6], xv[7]));
+#pragma unroll
+                for (int t = 0; t < TPW; ++t) {
+                    float av[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) av[j] = Ut[dwoff[j & 3] + (2 * s + (j >> 2)) * 32 + t * 4096];
+                    dw[t] = mfma_split6(
+                        split8(make_float4(av[0], av[1], av[2], av[3]), make_float4(av[4], av[5], av[6], av[7])), xb, dw[t]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        } else if (VARIANT != 3 && VARIANT != 5) {
             float abuf[2][TPW], xbuf[2];
             const float* xsl = xs + hi * 64 + ah * 32 + r31;          // row 2s + hi -> + 128 s
 #pragma unroll
@@ -1021,11 +1048,22 @@ extern "C" int qot_nnconv_adjoint_dw(const float* grad_out, int ld_g, const floa
         return QOT_OK;
     }
 #endif
+    // The weight-gradient product runs as split-bf16 MFMAs unless QOT_NNCONV_F32_MFMA=1 (the switch
+    // functional.nnconv_split_bf16 reads).  Read per call, not cached: callers flip it inside one process.
+    const char* f32_env = getenv("QOT_NNCONV_F32_MFMA");
+    const bool f32_mfma = f32_env && f32_env[0] == '1' && f32_env[1] == '\0';
     QOT_DISPATCH_D(D, {
-        if (kD <= 4)
-            nnconv_adjoint_dw64_kernel<(kD <= 4 ? kD : 4)><<<grid, 512, 0, stream>>>(
-                grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr_t, col_t, eid_t, invdeg, w_perm, grad_x,
-                workspace, N);
+        if (kD <= 4) {
+            constexpr int kD4 = kD <= 4 ? kD : 4;
+            if (f32_mfma)
+                nnconv_adjoint_dw64_kernel<kD4, 0, false><<<grid, 512, 0, stream>>>(
+                    grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr_t, col_t, eid_t, invdeg, w_perm, grad_x,
+                    workspace, N);
+            else
+                nnconv_adjoint_dw64_kernel<kD4, 0, true><<<grid, 512, 0, stream>>>(
+                    grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr_t, col_t, eid_t, invdeg, w_perm, grad_x,
+                    workspace, N);
+        }
     });
     QOT_LAUNCH_CHECK();
     if (param_layout == 2) return QOT_OK;      // profiling: main kernel only (slabs left unsummed)

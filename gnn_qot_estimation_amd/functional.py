@@ -835,7 +835,8 @@ def nnconv_pack_operands(w2, b2, wroot, k: int):
 
 def nnconv_split_bf16() -> bool:
     """The H = 64 forward and grad-h kernels issue their fp32 products as split-bf16 MFMAs (csrc/split_bf16.hpp) unless
-    ``QOT_NNCONV_F32_MFMA=1``, which selects the fp32-MFMA kernels."""
+    ``QOT_NNCONV_F32_MFMA=1``, which selects the fp32-MFMA kernels.  ``qot_nnconv_adjoint_dw`` reads the same variable
+    itself on every call, for its weight-gradient product (its grad_x product is an fp32 MFMA either way)."""
     return os.environ.get("QOT_NNCONV_F32_MFMA", "0") != "1"
 
 

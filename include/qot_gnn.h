@@ -313,6 +313,8 @@ int qot_gemm_tn(const float* A, int lda, const float* G, int ldg, int64_t N, int
  * [d nn.2.weight [H*H, K] | d nn.2.bias [H*H] | d lin.weight [H, H]] (same total size).
  * param_layout = 2 (profiling only) launches the main kernel alone: per-workgroup slabs stay in the
  * workspace and gwcat_t is not written -- lets bench.py time exactly the kernel rocprofv3 lists.
+ * The X^T U product is issued as split-bf16 MFMAs (csrc/split_bf16.hpp) unless QOT_NNCONV_F32_MFMA=1 is set in the
+ * environment, read on every call; the grad_x product is an fp32 MFMA either way.
  * workspace: qot_nnconv_adjoint_dw_workspace_floats(D) floats. */
 size_t qot_nnconv_adjoint_dw_workspace_floats(int D);
 int qot_nnconv_adjoint_dw(const float* grad_out, int ld_g, const float* x, int ld_x,
