@@ -463,6 +463,33 @@ static void stage_structs(StageShard& s, StageSlot& d, const int64_t* node_ptr, 
     d.B = B; d.N = N; d.E = E; d.max_n = max_nodes; d.max_m = max_edges; d.V = V;
 }
 
+enum StageKind { kExactSlot, kPaddedSlot, kGatherSlot };
+
+// What the three entry points refuse (QOT_ERR_BADARG) before anything is launched, on the structs stage_structs filled.
+// Exact slot: any N >= 0, and the node buffers are needed only when N > 0.  Padded and gather slots: d.max_n is the node
+// count n >= 1 of every graph and P the pad graphs; d.N is not read (the entry point forms B * n once both are bounded).
+// The gather slot takes its scratch `offs` where the others take graph_of_node.
+static bool stage_args_ok(StageKind kind, const int64_t* ctl, int64_t sched_cap, const int32_t* status, const int64_t* offs,
+                          const StageShard& s, const StageSlot& d, int64_t P) {
+    const bool exact = kind == kExactSlot;
+    if (!ctl || !status || !s.node_ptr || !s.edge_ptr || !d.ptr || !d.edge_ptr) return false;
+    if (kind == kGatherSlot ? !offs : !s.graph_of_node) return false;
+    if (sched_cap < 1 || s.G < 1 || s.N_total < 0 || s.E_total < 0 || d.B < 1 || d.E < 0 || d.max_n < 0 || d.max_m < 0 || d.V < 0)
+        return false;
+    if (s.D < 0 || s.F < 0 || s.Y < 0) return false;
+    if (exact && d.N < 0) return false;
+    if (!exact) {
+        if (d.max_n < 1 || P < 0) return false;
+        if (P > 0 && (d.max_n < 2 || d.max_m < 1)) return false;       // a ring over one node is a self loop; no room to pad
+        if (d.B > (INT64_MAX >> 24) || P > (INT64_MAX >> 24) || d.max_n > (1 << 20) || d.max_m > (1 << 20)) return false;
+        if (kind == kGatherSlot && sched_cap > (INT64_MAX >> 4) / d.B) return false;      // sched_cap * B ids
+    }
+    const bool nodes = !exact || d.N > 0;
+    if ((d.E > 0 && (!s.edge_index || !d.edge_index)) || (nodes && !d.batch)) return false;
+    return !((s.edge_attr && d.E > 0 && !d.edge_attr) || (s.node_ids && nodes && !d.node_ids) || (s.x && nodes && !d.x) ||
+             (s.y && !d.y));
+}
+
 // 16-byte units of the whole copy; four per thread, at most 1024 workgroups (4 per CU)
 static int stage_grid(int64_t B, int64_t N, int64_t E, int D, int F, int Y) {
     const int64_t bytes = 16 * E + 4 * E * (int64_t)D + 16 * N + 4 * N * (int64_t)F + 4 * B * (int64_t)Y + 16 * (B + 1);
@@ -479,19 +506,12 @@ extern "C" int qot_shard_stage(int64_t* ctl, int64_t sched_cap, int32_t* status,
                                int64_t E, int64_t max_nodes, int64_t max_edges, int64_t V, int64_t* dst_edge_index,
                                void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x, void* dst_y, int64_t* dst_ptr,
                                int64_t* dst_edge_ptr, int64_t* dst_batch, qot_stream_t stream) {
-    if (!ctl || !status || !node_ptr || !edge_ptr || !graph_of_node || !dst_ptr || !dst_edge_ptr) return QOT_ERR_BADARG;
-    if (sched_cap < 1 || G < 1 || N_total < 0 || E_total < 0 || B < 1 || N < 0 || E < 0 || max_nodes < 0 || max_edges < 0 || V < 0)
-        return QOT_ERR_BADARG;
-    if (D < 0 || F < 0 || Y < 0) return QOT_ERR_BADARG;
-    if ((E > 0 && (!edge_index || !dst_edge_index)) || (N > 0 && !dst_batch)) return QOT_ERR_BADARG;
-    if ((edge_attr && E > 0 && D > 0 && !dst_edge_attr) || (node_ids && N > 0 && !dst_node_ids) || (x && N > 0 && F > 0 && !dst_x) ||
-        (y && Y > 0 && !dst_y))
-        return QOT_ERR_BADARG;
     StageShard s;
     StageSlot d;
     stage_structs(s, d, node_ptr, edge_ptr, graph_of_node, G, N_total, E_total, edge_index, edge_attr, D, node_ids, x, F, y, Y, B,
                   N, E, max_nodes, max_edges, V, dst_edge_index, dst_edge_attr, dst_node_ids, dst_x, dst_y, dst_ptr, dst_edge_ptr,
                   dst_batch);
+    if (!stage_args_ok(kExactSlot, ctl, sched_cap, status, nullptr, s, d, 0)) return QOT_ERR_BADARG;
     hipStream_t st = (hipStream_t)stream;
     stage_plan_kernel<false><<<1, 256, 0, st>>>(ctl, sched_cap, status, node_ptr, edge_ptr, G, N_total, E_total, B, N, E,
                                                 max_nodes, max_edges, 0);
@@ -509,23 +529,15 @@ extern "C" int qot_shard_stage_padded(int64_t* ctl, int64_t sched_cap, int32_t* 
                                       int64_t* dst_edge_index, void* dst_edge_attr, int64_t* dst_node_ids, void* dst_x,
                                       void* dst_y, int64_t* dst_ptr, int64_t* dst_edge_ptr, int64_t* dst_batch,
                                       qot_stream_t stream) {
-    if (!ctl || !status || !node_ptr || !edge_ptr || !graph_of_node || !dst_ptr || !dst_edge_ptr) return QOT_ERR_BADARG;
-    if (sched_cap < 1 || G < 1 || N_total < 0 || E_total < 0 || B < 1 || n < 1 || E_cap < 0 || P < 0 || max_edges < 0 || V < 0)
-        return QOT_ERR_BADARG;
-    if (P > 0 && (n < 2 || max_edges < 1)) return QOT_ERR_BADARG;      // a ring over one node is a self loop; no room to pad
-    if (B > (INT64_MAX >> 24) || P > (INT64_MAX >> 24) || n > (1 << 20) || max_edges > (1 << 20)) return QOT_ERR_BADARG;
-    if (D < 0 || F < 0 || Y < 0) return QOT_ERR_BADARG;
-    if ((E_cap > 0 && (!edge_index || !dst_edge_index)) || !dst_batch) return QOT_ERR_BADARG;
-    if ((edge_attr && E_cap > 0 && D > 0 && !dst_edge_attr) || (node_ids && !dst_node_ids) || (x && F > 0 && !dst_x) ||
-        (y && Y > 0 && !dst_y))
-        return QOT_ERR_BADARG;
     StageShard s;
     StageSlot d;
     stage_structs(s, d, node_ptr, edge_ptr, graph_of_node, G, N_total, E_total, edge_index, edge_attr, D, node_ids, x, F, y, Y, B,
-                  B * n, E_cap, n, max_edges, V, dst_edge_index, dst_edge_attr, dst_node_ids, dst_x, dst_y, dst_ptr, dst_edge_ptr,
+                  0, E_cap, n, max_edges, V, dst_edge_index, dst_edge_attr, dst_node_ids, dst_x, dst_y, dst_ptr, dst_edge_ptr,
                   dst_batch);
+    if (!stage_args_ok(kPaddedSlot, ctl, sched_cap, status, nullptr, s, d, P)) return QOT_ERR_BADARG;
+    d.N = B * n;
     hipStream_t st = (hipStream_t)stream;
-    stage_plan_kernel<true><<<1, 256, 0, st>>>(ctl, sched_cap, status, node_ptr, edge_ptr, G, N_total, E_total, B, B * n, E_cap,
+    stage_plan_kernel<true><<<1, 256, 0, st>>>(ctl, sched_cap, status, node_ptr, edge_ptr, G, N_total, E_total, B, d.N, E_cap,
                                                n, max_edges, P * max_edges);
     QOT_LAUNCH_CHECK();
     stage_copy_padded_kernel<<<stage_grid(B + P, (B + P) * n, E_cap, D, F, Y), 256, 0, st>>>(ctl, status, s, d, P);
@@ -549,22 +561,13 @@ extern "C" int qot_shard_stage_gather(int64_t* ctl, int64_t sched_cap, int32_t* 
                                       int64_t max_edges, int64_t V, int64_t* dst_edge_index, void* dst_edge_attr,
                                       int64_t* dst_node_ids, void* dst_x, void* dst_y, int64_t* dst_ptr, int64_t* dst_edge_ptr,
                                       int64_t* dst_batch, qot_stream_t stream) {
-    if (!ctl || !status || !offs || !node_ptr || !edge_ptr || !dst_ptr || !dst_edge_ptr) return QOT_ERR_BADARG;
-    if (sched_cap < 1 || G < 1 || N_total < 0 || E_total < 0 || B < 1 || n < 1 || E_cap < 0 || P < 0 || max_edges < 0 || V < 0)
-        return QOT_ERR_BADARG;
-    if (P > 0 && (n < 2 || max_edges < 1)) return QOT_ERR_BADARG;      // a ring over one node is a self loop; no room to pad
-    if (B > (INT64_MAX >> 24) || P > (INT64_MAX >> 24) || n > (1 << 20) || max_edges > (1 << 20)) return QOT_ERR_BADARG;
-    if (sched_cap > (INT64_MAX >> 4) / B) return QOT_ERR_BADARG;       // sched_cap * B ids
-    if (D < 0 || F < 0 || Y < 0) return QOT_ERR_BADARG;
-    if ((E_cap > 0 && (!edge_index || !dst_edge_index)) || !dst_batch) return QOT_ERR_BADARG;
-    if ((edge_attr && E_cap > 0 && D > 0 && !dst_edge_attr) || (node_ids && !dst_node_ids) || (x && F > 0 && !dst_x) ||
-        (y && Y > 0 && !dst_y))
-        return QOT_ERR_BADARG;
     StageShard s;
     StageSlot d;
-    stage_structs(s, d, node_ptr, edge_ptr, nullptr, G, N_total, E_total, edge_index, edge_attr, D, node_ids, x, F, y, Y, B, B * n,
+    stage_structs(s, d, node_ptr, edge_ptr, nullptr, G, N_total, E_total, edge_index, edge_attr, D, node_ids, x, F, y, Y, B, 0,
                   E_cap, n, max_edges, V, dst_edge_index, dst_edge_attr, dst_node_ids, dst_x, dst_y, dst_ptr, dst_edge_ptr,
                   dst_batch);
+    if (!stage_args_ok(kGatherSlot, ctl, sched_cap, status, offs, s, d, P)) return QOT_ERR_BADARG;
+    d.N = B * n;
     hipStream_t st = (hipStream_t)stream;
     stage_plan_gather_kernel<<<1, 256, 0, st>>>(ctl, sched_cap, status, offs, node_ptr, edge_ptr, G, N_total, E_total, B, n, E_cap,
                                                 max_edges, P * max_edges);

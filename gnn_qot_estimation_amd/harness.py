@@ -190,6 +190,19 @@ def stream_schedule(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ranges: Sequ
     return out
 
 
+def _plan_of_totals(totals: Dict[int, List[int]], n: int, max_m: int, option: str) -> Dict[int, Dict[str, object]]:
+    """The plan of ``stream_pad_plan`` from the edge totals of every batch, per graph count: ``{B: [edge totals]}`` of graphs
+    of ``n`` nodes and at most ``max_m`` edges; ``option`` names the caller's option in the refusal."""
+    plan: Dict[int, Dict[str, object]] = {}
+    for B, es in totals.items():
+        e_cap, e_min = max(es), min(es)
+        P = 0 if e_cap == e_min else -(-(e_cap - e_min) // max_m)
+        if P and n < 2:
+            raise ValueError(f"{option} needs graphs of at least 2 nodes (a pad graph is a ring without self loops)")
+        plan[B] = {"E_cap": e_cap, "E_min": e_min, "P": P, "shape": (B + P, (B + P) * n, e_cap)}
+    return plan
+
+
 def stream_pad_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ranges: Sequence[Tuple[int, int]],
                     graph_sizes: Tuple[int, int]) -> Dict[int, Dict[str, object]]:
     """Padded slots for the batches ``ranges`` of a shard whose graphs all have ``n`` nodes, per graph count ``B``:
@@ -202,18 +215,10 @@ def stream_pad_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, ranges: Sequ
     if n is None:
         raise ValueError("pad_edges=True needs a shard whose graphs all have the same node count (mixed node counts keep "
                          "stream=True with exact-shape slots)")
-    max_m = int(graph_sizes[1])
     totals: Dict[int, List[int]] = {}
     for lo, hi in ranges:
         totals.setdefault(hi - lo, []).append(int(edge_ptr[hi]) - int(edge_ptr[lo]))
-    plan: Dict[int, Dict[str, object]] = {}
-    for B, es in totals.items():
-        e_cap, e_min = max(es), min(es)
-        P = 0 if e_cap == e_min else -(-(e_cap - e_min) // max_m)
-        if P and n < 2:
-            raise ValueError("pad_edges=True needs graphs of at least 2 nodes (a pad graph is a ring without self loops)")
-        plan[B] = {"E_cap": e_cap, "E_min": e_min, "P": P, "shape": (B + P, (B + P) * n, e_cap)}
-    return plan
+    return _plan_of_totals(totals, n, int(graph_sizes[1]), "pad_edges=True")
 
 
 def epoch_order(indices: range, seed: int, epoch: int) -> List[int]:
@@ -247,7 +252,6 @@ def stream_shuffle_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, chunks: 
     n = uniform_node_count(node_ptr)
     if n is None:
         raise ValueError("shuffle=True on a resident shard needs graphs that all have the same node count")
-    max_m = int(graph_sizes[1])
     counts = (edge_ptr[1:] - edge_ptr[:-1]).tolist()
     totals: Dict[int, List[int]] = {}
     for epoch, chunk in enumerate(chunks):
@@ -255,14 +259,7 @@ def stream_shuffle_plan(node_ptr: torch.Tensor, edge_ptr: torch.Tensor, chunks: 
         for b0 in range(0, len(order), batch_size):
             ids = order[b0:b0 + batch_size]
             totals.setdefault(len(ids), []).append(sum(counts[g] for g in ids))
-    plan: Dict[int, Dict[str, object]] = {}
-    for B, es in totals.items():
-        e_cap, e_min = max(es), min(es)
-        P = 0 if e_cap == e_min else -(-(e_cap - e_min) // max_m)
-        if P and n < 2:
-            raise ValueError("shuffle=True needs graphs of at least 2 nodes (a pad graph is a ring without self loops)")
-        plan[B] = {"E_cap": e_cap, "E_min": e_min, "P": P, "shape": (B + P, (B + P) * n, e_cap)}
-    return plan
+    return _plan_of_totals(totals, n, int(graph_sizes[1]), "shuffle=True")
 
 
 def check_shuffle(dataset, kind: str, world: int, stream, pad_edges) -> None:
@@ -318,14 +315,26 @@ def check_stream(dataset, kind: str, world: int) -> None:
                          "batch (it keeps the per-batch replay)")
 
 
+def _check_options(dataset, kind: str, world: int, stream, pad_edges, shuffle) -> None:
+    """The option checks of ``fit``, ``run_epoch`` and ``StepReplayer``, in their one order: shuffle, then pad_edges (which
+    checks what ``stream=True`` needs itself), else stream."""
+    if shuffle:
+        check_shuffle(dataset, kind, world, stream, pad_edges)
+    if pad_edges:
+        check_pad_edges(dataset, kind, world, stream)
+    elif stream:
+        check_stream(dataset, kind, world)
+
+
 class StepReplayer:
     """HIP-graph replay of whole steps over the cached batches of an HBM-resident shard.
 
     The reference revisits the same unshuffled chunks for 35 epochs (``train.py:79-95``).  With the shard in
     HBM and the batch objects cached, a step's inputs are the SAME device tensors on every visit, so the
     whole step (forward, loss, backward, optimizer update, statistics) is captured once per batch and
-    replayed afterwards: no Python, no launches, no allocation on later visits.  First visit of a batch
-    runs eagerly (it also builds and caches the graph index), the second is captured, later ones replay.
+    replayed afterwards: no Python, no launches, no allocation on later visits.  First visit of a key -- a batch
+    object here, a slot under streamed replay -- runs eagerly (it also builds and caches the graph index), the second
+    is captured, later ones replay (``_cycle``, the one state machine of both).
     All captures share one memory pool (steps never overlap), the learning rate lives in device memory
     (``FusedSGD(device_lr=True)``), dropout draws come from the device-side counter.  Batches whose
     forward raises (``ValueError``: no LUT node) are remembered and skipped; on later visits of such a training batch only
@@ -341,9 +350,8 @@ class StepReplayer:
     through the static slot of its ``(B, N, E, training)`` (``loader.StageSlot``): the captured graph is ``stage + step``,
     the stage launch takes its ``lo`` from the slot's device-side schedule (``begin_epoch`` writes it once per epoch), so
     every batch of a shape -- first visits and single-epoch runs included -- replays the same graph, and the run holds
-    as many graphs, cached indices and pool blocks as it has distinct shapes.  A slot's first use runs eagerly, its
-    second is captured.  CACHE RULE: the stage launch rewrites the slot's tensors through raw pointers, their
-    ``_version`` never moves, and every per-batch cache of ``graph.py`` (``graph_index_for``, ``batch_ptr_for``,
+    as many graphs, cached indices and pool blocks as it has distinct shapes.  CACHE RULE: the stage launch rewrites the
+    slot's tensors through raw pointers, their ``_version`` never moves, and every per-batch cache of ``graph.py`` (``graph_index_for``, ``batch_ptr_for``,
     ``cached_i32``, ``table_maps_for``, the checked node ids) is keyed by ``(data_ptr, _version, shape)``: left alone
     they would serve the PREVIOUS batch's index.  So the slot's ``_qot_cache`` is emptied before the eager visit and
     before the capture; the index build, the int32 narrowing and the table maps are then recorded inside the graph and
@@ -375,14 +383,9 @@ class StepReplayer:
         self.pad_edges = bool(pad_edges)
         self.shuffle, self.seed = bool(shuffle), int(seed)
         self.shuffle_plan: Dict[int, Dict[str, object]] = {}   # per graph count B of the training batches (plan_shuffle)
-        if self.shuffle:
-            check_shuffle(shard, kind, 2 if collective else 1, self.stream, self.pad_edges)
-            if shard is None or shard.device is None:
-                raise ValueError("a StepReplayer shuffles on an HBM-resident shard (a host dataset takes the eager loop)")
-        if self.pad_edges:
-            check_pad_edges(shard, kind, 2 if collective else 1, self.stream)
-        elif self.stream:
-            check_stream(shard, kind, 2 if collective else 1)
+        _check_options(shard, kind, 2 if collective else 1, self.stream, self.pad_edges, self.shuffle)
+        if self.shuffle and (shard is None or shard.device is None):
+            raise ValueError("a StepReplayer shuffles on an HBM-resident shard (a host dataset takes the eager loop)")
         self.shard = shard
         self.pad_plan: Dict[int, Dict[str, object]] = {}       # per graph count B (plan_padding)
         self.slots: Dict[Tuple[int, int, int, bool], StageSlot] = {}
@@ -458,47 +461,74 @@ class StepReplayer:
                     except ValueError:
                         pass
             return False
+        # (a captured collective: thread-local capture mode -- the process group's watchdog thread polls its events meanwhile)
+        mode = dict(capture_error_mode="thread_local") if self.collective else {}
+        how = self._cycle(key, training, lambda: self._step(data, training), skip_on=ValueError, **mode)
+        if how in ("eager", "skipped"):
+            self._keep.append(data)
+        if how == "skipped":
+            self.skip.add(key)
+        return how != "skipped"
+
+    def _cycle(self, key, training: bool, step: Callable[[], None], prepare: Optional[Callable[[], None]] = None,
+               skip_on=(), **capture_mode) -> str:
+        """The eager -> capture -> replay cycle of the graph ``key``, ``step`` performing the visit: a replay when the graph
+        exists; else ``prepare()`` and an eager ``step()`` on the first visit (and while the optimizer has not stepped), a
+        capture of ``step()`` replayed once on the next.  Returns "replayed", "eager", "captured", or "skipped" when the
+        eager ``step()`` raised ``skip_on``."""
         g = self.graphs.get(key)
         if g is not None:
             g.replay()
             self.counts["replayed"] += 1
-            return True
-        seen = self.visits.get(key, 0)
+            return "replayed"
         self.model.train(training)
-        if seen == 0 or (training and self.opt.steps == 0):
+        if prepare is not None:
+            prepare()
+        if self.visits.get(key, 0) == 0 or (training and self.opt.steps == 0):
             try:
-                self._step(data, training)
-            except ValueError:
-                self.skip.add(key)
-                self._keep.append(data)
-                return False
+                step()
+            except skip_on:
+                return "skipped"
             self.visits[key] = 1
-            self._keep.append(data)
             self.counts["eager"] += 1
-            return True
+            return "eager"
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
-        # (a captured collective: thread-local capture mode -- the process group's watchdog thread polls its events meanwhile)
-        mode = dict(capture_error_mode="thread_local") if self.collective else {}
-        with torch.cuda.graph(g, pool=self.pool, **mode):
-            self._step(data, training)
+        with torch.cuda.graph(g, pool=self.pool, **capture_mode):
+            step()
         self.graphs[key] = g
         g.replay()                      # capture records, it does not execute
         self.counts["captured"] += 1
-        return True
+        return "captured"
 
     # ---- streamed replay ------------------------------------------------------------------------------------------
     def replay_counts(self) -> Dict[str, int]:
         return dict(self.counts, graphs=len(self.graphs))
 
-    def _slot(self, shape: Tuple[int, int, int], training: bool) -> StageSlot:
-        key = shape + (bool(training),)
+    def _slot_key(self, lo: int, hi: int, training: bool) -> tuple:
+        """What keys the slot (and the captured graph) of graphs ``[lo, hi)``: the graph count under ``pad_edges``, else
+        the exact shape."""
+        if self.pad_edges:
+            return (hi - lo, bool(training))
+        return batch_shape(self.shard.node_ptr, self.shard.edge_ptr, lo, hi) + (bool(training),)
+
+    def _slot(self, key: tuple) -> StageSlot:
+        """The slot of ``key``, made on first use: an exact slot for ``(B, N, E, training)``; for ``(B, training)`` the
+        padded slot of ``pad_plan`` or, for the training batches of a shuffled run, the gather slot of ``shuffle_plan``."""
         slot = self.slots.get(key)
         if slot is None:
+            *shape, training = key
             emb = getattr(self.model, "node_embeddings", None)
-            slot = self.slots[key] = self.shard.stage_slot(*shape, status=self._stage_status,
-                                                           num_embeddings=0 if emb is None else emb.num_embeddings,
-                                                           capacity=self.schedule_capacity)
+            kw = dict(status=self._stage_status, num_embeddings=0 if emb is None else emb.num_embeddings,
+                      capacity=self.schedule_capacity)
+            if len(shape) == 3:
+                slot = self.shard.stage_slot(*shape, **kw)
+            else:
+                gather = self.shuffle and training
+                plan = (self.shuffle_plan if gather else self.pad_plan)[shape[0]]
+                make = self.shard.gather_stage_slot if gather else self.shard.padded_stage_slot
+                slot = make(shape[0], plan["E_cap"], plan["P"], **kw)
+            self.slots[key] = slot
         return slot
 
     def plan_padding(self, ranges: Sequence[Tuple[int, int]]) -> Dict[int, Dict[str, object]]:
@@ -522,70 +552,55 @@ class StepReplayer:
                                                 self.shard.graph_sizes)
         return self.shuffle_plan
 
-    def _padded_slot(self, B: int, training: bool) -> StageSlot:
-        key = (B, bool(training))
-        slot = self.slots.get(key)
-        if slot is None:
-            gather = self.shuffle and training
-            plan = (self.shuffle_plan if gather else self.pad_plan)[B]
-            emb = getattr(self.model, "node_embeddings", None)
-            make = self.shard.gather_stage_slot if gather else self.shard.padded_stage_slot
-            slot = self.slots[key] = make(B, plan["E_cap"], plan["P"], status=self._stage_status,
-                                          num_embeddings=0 if emb is None else emb.num_embeddings,
-                                          capacity=self.schedule_capacity)
-        return slot
-
     def begin_epoch(self, ranges: Sequence[Tuple[int, int]], training: bool, order: Optional[Sequence[int]] = None) -> None:
         """Write this epoch's schedules: per shape (padded slots: per graph count), the ``lo`` of its batches in visiting
         order.  ``run`` must then be called with exactly ``ranges``, in order.  ``order`` (a shuffled training epoch):
         the graphs to visit instead, batch ``k`` taking as many of them as ``ranges[k]`` holds."""
         G = len(self.shard)
+        gather = self.shuffle and training
         if order is not None:
-            if not (self.shuffle and training):
+            if not gather:
                 raise ValueError("an epoch order belongs to the training epochs of a StepReplayer(shuffle=True)")
             order = [int(g) for g in order]
             if len(order) != sum(hi - lo for lo, hi in ranges):
                 raise ValueError(f"an order of {len(order)} graphs for batches of {sum(hi - lo for lo, hi in ranges)}")
             if any(not 0 <= g < G for g in order):
                 raise IndexError(f"the epoch order names graphs outside a shard of {G} graphs")
+        else:
+            if gather:
+                raise ValueError("a training epoch of a StepReplayer(shuffle=True) needs its order")
+            for lo, hi in ranges:
+                if not 0 <= lo < hi <= G:
+                    raise IndexError(f"graphs [{lo}, {hi}) lie outside a shard of {G} graphs")
+        edge_ptr = self.shard.edge_ptr
+        if not self.pad_edges:
+            schedules = {shape + (bool(training),): los
+                         for shape, los in stream_schedule(self.shard.node_ptr, edge_ptr, ranges).items()}
+        else:
+            plans = self.shuffle_plan if gather else self.pad_plan
             max_m = int(self.shard.graph_sizes[1])
-            counts = self.shard.edge_ptr[1:] - self.shard.edge_ptr[:-1]
-            by_count: Dict[int, List[int]] = {}
+            counts = edge_ptr[1:] - edge_ptr[:-1] if gather else None
+            schedules: Dict[tuple, List[int]] = {}
             at = 0
             for lo, hi in ranges:
-                ids = order[at:at + hi - lo]
-                at += hi - lo
-                plan = self.shuffle_plan.get(hi - lo)
-                e = int(counts[torch.as_tensor(ids, dtype=torch.long)].sum())
+                B = hi - lo
+                if gather:
+                    entry = order[at:at + B]
+                    at += B
+                    e = int(counts[torch.as_tensor(entry, dtype=torch.long)].sum())
+                else:
+                    entry = [lo]
+                    e = int(edge_ptr[hi]) - int(edge_ptr[lo])
+                plan = plans.get(B)
                 if plan is None or not 0 <= plan["E_cap"] - e <= plan["P"] * max_m:
-                    raise ValueError(f"a shuffled batch of {hi - lo} graphs ({e} edges) is not covered by the padding plan "
-                                     f"({'no slot for this graph count' if plan is None else plan}): plan_shuffle takes "
-                                     "every epoch of the run")
-                by_count.setdefault(hi - lo, []).extend(ids)
-            for B, ids in by_count.items():
-                self._padded_slot(B, True).set_schedule(ids)
-            return
-        if self.shuffle and training:
-            raise ValueError("a training epoch of a StepReplayer(shuffle=True) needs its order")
-        for lo, hi in ranges:
-            if not 0 <= lo < hi <= G:
-                raise IndexError(f"graphs [{lo}, {hi}) lie outside a shard of {G} graphs")
-        if self.pad_edges:
-            max_m = int(self.shard.graph_sizes[1])
-            by_count: Dict[int, List[int]] = {}
-            for lo, hi in ranges:
-                plan = self.pad_plan.get(hi - lo)
-                e = int(self.shard.edge_ptr[hi]) - int(self.shard.edge_ptr[lo])
-                if plan is None or not 0 <= plan["E_cap"] - e <= plan["P"] * max_m:
-                    raise ValueError(f"graphs [{lo}, {hi}) ({e} edges) are not covered by the padding plan "
-                                     f"({'no slot for this graph count' if plan is None else plan}): plan_padding takes "
-                                     "every batch of the run")
-                by_count.setdefault(hi - lo, []).append(lo)
-            for B, los in by_count.items():
-                self._padded_slot(B, training).set_schedule(los)
-            return
-        for shape, los in stream_schedule(self.shard.node_ptr, self.shard.edge_ptr, ranges).items():
-            self._slot(shape, training).set_schedule(los)
+                    what = f"a shuffled batch of {B} graphs ({e} edges) is" if gather else f"graphs [{lo}, {hi}) ({e} edges) are"
+                    raise ValueError(f"{what} not covered by the padding plan "
+                                     f"({'no slot for this graph count' if plan is None else plan}): "
+                                     + ("plan_shuffle takes every epoch of the run" if gather else
+                                        "plan_padding takes every batch of the run"))
+                schedules.setdefault(self._slot_key(lo, hi, training), []).extend(entry)
+        for key, entries in schedules.items():
+            self._slot(key).set_schedule(entries)
 
     def end_epoch(self) -> None:
         """Raise what the epoch's device-side checks flagged (two 4-byte reads behind the epoch's host synchronisation)."""
@@ -594,37 +609,20 @@ class StepReplayer:
         check_index_status(self.device)
 
     def _run_streamed(self, rng: Tuple[int, int], training: bool) -> bool:
-        lo, hi = rng
-        if self.pad_edges:
-            key = (hi - lo, bool(training))
-        else:
-            shape = batch_shape(self.shard.node_ptr, self.shard.edge_ptr, lo, hi)
-            key = shape + (bool(training),)
-        g = self.graphs.get(key)
-        if g is not None:
-            g.replay()                  # stage (the schedule's next lo) + step
-            self.counts["replayed"] += 1
-            return True
-        slot = self._padded_slot(hi - lo, training) if self.pad_edges else self._slot(shape, training)
-        self.model.train(training)
-        # the stage launch rewrites the slot's tensors behind torch's back: nothing cached on the batch object may survive
-        # into this visit (class docstring, CACHE RULE)
-        slot.batch._qot_cache = {}
-        if self.visits.get(key, 0) == 0 or (training and self.opt.steps == 0):
-            slot.stage()
+        key = self._slot_key(rng[0], rng[1], training)
+
+        def reset():
+            # the stage launch rewrites the slot's tensors behind torch's back: nothing cached on the batch object may survive
+            # into this visit (class docstring, CACHE RULE)
+            self._slot(key).batch._qot_cache = {}
+
+        def step():
+            slot = self._slot(key)
+            slot.stage()                # the schedule's next entry
             self._step(slot.batch, training)
-            self.visits[key] = 1
-            self.counts["eager"] += 1
-            return True
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self.pool):
-            slot.stage()
-            self._step(slot.batch, training)
-        slot.batch._qot_cache = {}      # what the capture cached lives in the graph's pool: only the graph may use it
-        self.graphs[key] = g
-        g.replay()                      # capture records, it does not execute
-        self.counts["captured"] += 1
+
+        if self._cycle(key, training, step, prepare=reset) == "captured":
+            reset()                     # what the capture cached lives in the graph's pool: only the graph may use it
         return True
 
 
@@ -643,13 +641,9 @@ def run_epoch(model, dataset, indices: range, *, kind: str, batch_size: int, out
     fwd = _KINDS[kind]
     rank, world = _rank_world()
     shuffle = bool(shuffle)
-    if shuffle:
-        check_shuffle(dataset, kind, world, stream, pad_edges)
+    _check_options(dataset, kind, world, stream, pad_edges, shuffle)
     order = epoch_order(indices, seed, epoch) if shuffle and opt is not None else None
-    if pad_edges:
-        check_pad_edges(dataset, kind, world, stream)
     if stream:
-        check_stream(dataset, kind, world)
         if replayer is None or not replayer.stream or replayer.shard is not dataset:
             raise ValueError("stream=True needs a StepReplayer(stream=True, shard=dataset)")
         if bool(pad_edges) != replayer.pad_edges:
@@ -804,12 +798,7 @@ def fit(model, dataset, *, kind: str = "topological", batch_size: int = 512, num
     stream = bool(stream)
     pad_edges = bool(pad_edges)
     shuffle = bool(shuffle)
-    if shuffle:
-        check_shuffle(dataset, kind, _rank_world()[1], stream, pad_edges)
-    if pad_edges:
-        check_pad_edges(dataset, kind, _rank_world()[1], stream)
-    elif stream:
-        check_stream(dataset, kind, _rank_world()[1])
+    _check_options(dataset, kind, _rank_world()[1], stream, pad_edges, shuffle)
     model.to(device)
     tr, va, _ = split_ranges(len(dataset))
     flat = FlatModel(model)

@@ -309,6 +309,11 @@ def check_stage_status(status: torch.Tensor) -> None:
     raise IndexError("index out of range in self")
 
 
+def _resident_shard(shard) -> None:
+    if not isinstance(shard, PackedGraphs) or shard.device is None:
+        raise ValueError("a batch slot stages from an HBM-resident shard (PackedGraphs.to_device)")
+
+
 class StageSlot:
     """Static batch buffers for ONE batch shape ``(B graphs, N nodes, E edges)`` of an HBM-resident shard.
 
@@ -328,10 +333,11 @@ class StageSlot:
     batches of one pass over the shard; the control block is part of the captured launch and never grows).  The schedule holds graph offsets; ``GatherStageSlot``
     is the other schedule format behind the same slot: lists of single graphs (shuffled batches)."""
 
+    _entry = "qot_shard_stage"          # the C entry point stage() calls; subclasses name theirs
+
     def __init__(self, shard: "PackedGraphs", B: int, N: int, E: int, status: Optional[torch.Tensor] = None,
                  num_embeddings: int = 0, capacity: Optional[int] = None):
-        if not isinstance(shard, PackedGraphs) or shard.device is None:
-            raise ValueError("a batch slot stages from an HBM-resident shard (PackedGraphs.to_device)")
+        _resident_shard(shard)
         B, N, E = int(B), int(N), int(E)
         if B < 1 or N < 0 or E < 0:
             raise ValueError("a batch slot needs B >= 1, N >= 0, E >= 0")
@@ -372,13 +378,24 @@ class StageSlot:
         self._words = (0 if shard.edge_attr is None else per(shard.edge_attr), 0 if shard.x is None else per(shard.x),
                        0 if shard.y is None else shard.y_rows * per(shard.y))
 
+    def _write_schedule(self, entries: List[int], batches: int) -> None:
+        if batches > self.capacity:
+            raise ValueError(f"a schedule of {batches} batches exceeds the slot's capacity of {self.capacity}")
+        self.ctl[:4 + len(entries)].copy_(torch.tensor([0, batches, -1, 0] + entries, dtype=torch.long))
+
     def set_schedule(self, los: Sequence[int]) -> None:
         """The ``lo`` values the next ``len(los)`` calls of ``stage()`` take, in order (one small copy to the device,
         ordered on the current stream behind every earlier ``stage()``)."""
         los = [int(v) for v in los]
-        if len(los) > self.capacity:
-            raise ValueError(f"a schedule of {len(los)} batches exceeds the slot's capacity of {self.capacity}")
-        self.ctl[:4 + len(los)].copy_(torch.tensor([0, len(los), -1, 0] + los, dtype=torch.long))
+        self._write_schedule(los, len(los))
+
+    def _index_args(self) -> tuple:
+        """The entry point's arguments between ``status`` and the shard's totals."""
+        return self.shard.node_ptr_dev, self.shard.edge_ptr_dev, self.shard.graph_of_node
+
+    def _shape_args(self) -> tuple:
+        """The entry point's five integers between the shard's fields and ``V``."""
+        return self.B, self.N, self.E, self._totals[3], self._totals[4]
 
     def stage(self, lo: Optional[int] = None) -> Batch:
         """Stage the schedule's next slice (``lo`` given: that slice, as a schedule of one) into ``batch``."""
@@ -387,10 +404,9 @@ class StageSlot:
             self.set_schedule([lo])
         s, b = self.shard, self.batch
         D, F, Y = self._words
-        G, n_total, e_total, max_n, max_m = self._totals
-        _lib.call("qot_shard_stage", self.ctl, self.capacity, self.status, s.node_ptr_dev, s.edge_ptr_dev, s.graph_of_node,
-                  G, n_total, e_total, s.edge_index, s.edge_attr, D, s.node_ids, s.x, F, s.y, Y, self.B, self.N, self.E,
-                  max_n, max_m, self.V, b.edge_index, b.edge_attr, b.node_ids, b.x, b.y, b.ptr, b.edge_ptr, b.batch)
+        _lib.call(self._entry, self.ctl, self.capacity, self.status, *self._index_args(), *self._totals[:3], s.edge_index,
+                  s.edge_attr, D, s.node_ids, s.x, F, s.y, Y, *self._shape_args(), self.V, b.edge_index, b.edge_attr,
+                  b.node_ids, b.x, b.y, b.ptr, b.edge_ptr, b.batch)
         return b
 
 
@@ -414,10 +430,11 @@ class PaddedStageSlot(StageSlot):
     A slice whose spare exceeds ``P * max_m`` (or that holds more than ``E_cap`` edges) stages nothing and sets
     ``STAGE_BAD_SHAPE``.  ``harness.stream_pad_plan`` chooses ``E_cap`` and ``P`` for a run."""
 
+    _entry = "qot_shard_stage_padded"
+
     def __init__(self, shard: "PackedGraphs", B: int, E_cap: int, pad_graphs: int, status: Optional[torch.Tensor] = None,
                  num_embeddings: int = 0, capacity: Optional[int] = None):
-        if not isinstance(shard, PackedGraphs) or shard.device is None:
-            raise ValueError("a batch slot stages from an HBM-resident shard (PackedGraphs.to_device)")
+        _resident_shard(shard)
         B, E_cap, P = int(B), int(E_cap), int(pad_graphs)
         n = uniform_node_count(shard.node_ptr)
         if n is None:
@@ -434,18 +451,8 @@ class PaddedStageSlot(StageSlot):
         if shard.y is not None:
             b.y = torch.zeros((B * shard.y_rows,) + tuple(shard.y.shape[1:]), dtype=shard.y.dtype, device=shard.device)
 
-    def stage(self, lo: Optional[int] = None) -> Batch:
-        from . import _lib
-        if lo is not None:
-            self.set_schedule([lo])
-        s, b = self.shard, self.batch
-        D, F, Y = self._words
-        G, n_total, e_total, _, max_m = self._totals
-        _lib.call("qot_shard_stage_padded", self.ctl, self.capacity, self.status, s.node_ptr_dev, s.edge_ptr_dev,
-                  s.graph_of_node, G, n_total, e_total, s.edge_index, s.edge_attr, D, s.node_ids, s.x, F, s.y, Y,
-                  self.real_graphs, self.n, self.E, self.pad_graphs, max_m, self.V, b.edge_index, b.edge_attr, b.node_ids,
-                  b.x, b.y, b.ptr, b.edge_ptr, b.batch)
-        return b
+    def _shape_args(self) -> tuple:
+        return self.real_graphs, self.n, self.E, self.pad_graphs, self._totals[4]
 
 
 class GatherStageSlot(PaddedStageSlot):
@@ -457,6 +464,8 @@ class GatherStageSlot(PaddedStageSlot):
     the per-graph edge offsets of a batch go through ``offs``, scratch of the slot, so a refused batch leaves
     ``batch.edge_ptr`` alone too.  Cache rule as for every slot.  ``harness.stream_shuffle_plan`` chooses ``E_cap`` and
     ``P`` for a run."""
+
+    _entry = "qot_shard_stage_gather"
 
     def __init__(self, shard: "PackedGraphs", B: int, E_cap: int, pad_graphs: int, status: Optional[torch.Tensor] = None,
                  num_embeddings: int = 0, capacity: Optional[int] = None):
@@ -471,23 +480,16 @@ class GatherStageSlot(PaddedStageSlot):
         B = self.real_graphs
         if len(order) % B:
             raise ValueError(f"a gather schedule holds {B} graph ids per batch, got {len(order)} ids")
-        if len(order) // B > self.capacity:
-            raise ValueError(f"a schedule of {len(order) // B} batches exceeds the slot's capacity of {self.capacity}")
-        self.ctl[:4 + len(order)].copy_(torch.tensor([0, len(order) // B, -1, 0] + order, dtype=torch.long))
+        self._write_schedule(order, len(order) // B)
+
+    def _index_args(self) -> tuple:
+        return self.offs, self.shard.node_ptr_dev, self.shard.edge_ptr_dev
 
     def stage(self, ids: Optional[Sequence[int]] = None) -> Batch:
         """Stage the schedule's next batch (``ids`` given: those ``B`` graphs, as a schedule of one) into ``batch``."""
-        from . import _lib
         if ids is not None:
             self.set_schedule(ids)
-        s, b = self.shard, self.batch
-        D, F, Y = self._words
-        G, n_total, e_total, _, max_m = self._totals
-        _lib.call("qot_shard_stage_gather", self.ctl, self.capacity, self.status, self.offs, s.node_ptr_dev, s.edge_ptr_dev,
-                  G, n_total, e_total, s.edge_index, s.edge_attr, D, s.node_ids, s.x, F, s.y, Y, self.real_graphs, self.n,
-                  self.E, self.pad_graphs, max_m, self.V, b.edge_index, b.edge_attr, b.node_ids, b.x, b.y, b.ptr, b.edge_ptr,
-                  b.batch)
-        return b
+        return super().stage()
 
 
 class GraphLoader:
