@@ -12,7 +12,8 @@ namespace qot {
 //   dL/dh_e[k] = invdeg_i * < GA_i[k,:], x_j > ,  GA_i[k,a] = sum_o g_i[o] * W2[a*64+o, k]
 // The unfused path materialises GA ([N, 512] fp32, a 6.7 GFLOP library GEMM measured at 291 us)
 // and re-reads it per destination.  Here, per tile of 32 destinations:
-//   1. g rows -> LDS in MFMA fragment order (8 KB)
+//   1. g rows -> LDS in MFMA fragment order (fp32 form: 8 KB of fp32; split form: split once per tile by the thread
+//      that loaded them, three bf16 planes in the bf16 MFMA's A-fragment order, 12.4 KB)
 //   2. GA tile [32 x 512] = g_tile @ Bm on the matrix cores (4 waves x 4 column blocks,
 //      128 v_mfma_f32_32x32x2_f32 per wave), accumulators -> LDS row-major (66 KB, padded rows)
 //   3. the tile's edges, staged in LDS at the top of the tile, dealt evenly over the 32 lane groups (r03; r02
@@ -28,9 +29,15 @@ constexpr int kGhCap = 256;   // edges of a tile staged in LDS by the grad-h ker
 
 // VARIANT (diagnostic build only): 0 production; 2 no dot phase; 3 no GA MFMA phase; 5 GA phase with the weight fragments
 // of block 0 reused (no L2 stream)
-// SPLIT: the GA products on the bf16 matrix pipe (split_bf16.hpp): the g tile's fragments split after each read, Bs = Wk^T
-// pre-split into three bf16 planes, each [nb][16-deep step][lane], bs_planes u32x4 apart.
-template <int D, int VARIANT = 0, bool SPLIT = false>
+// SPLIT: the GA products on the bf16 matrix pipe (split_bf16.hpp): Bs = Wk^T pre-split into three bf16 planes, each
+// [nb][16-deep step][lane], bs_planes u32x4 apart.
+// PRESPLIT (split form only): the g tile goes to LDS as three bf16 planes, each [step][lane] u32x4 -- every value split once
+// per tile, an A fragment = three ds_read_b128.  false: the fp32 tile of the fp32 form, every fragment split after its
+// read, by every wave for each of its blocks (16 times per value; kept for comparison, QOT_GRADH_SPLIT_AFTER_READ=1).
+constexpr int kGhPlStep = 66;                // u32x4 per step of a plane: 64 lanes + 32 B, the four steps' stores 8 banks apart
+constexpr int kGhPlLd = 4 * kGhPlStep;       // u32x4 per plane
+
+template <int D, int VARIANT = 0, bool SPLIT = false, bool PRESPLIT = false>
 __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
     const float* __restrict__ g, int ldg, const float* __restrict__ x, int ldx, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr,
@@ -43,11 +50,17 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
     constexpr int NBW = NB / 4;             // per wave
     constexpr int EPG = kGhCap / 32;        // staged edge slots per lane group
     constexpr int EPF = 5;                  // ... of which the source rows are requested in front of the MFMA phase
-    __shared__ __attribute__((aligned(16))) float Gt[8 * 2 * 32 * 4];     // g tile (x 1/deg), fragment-grouped
+    static_assert(SPLIT || !PRESPLIT, "the planes are the split form's");
+    // g tile (x 1/deg): fragment-grouped fp32, or the three bf16 planes
+    __shared__ __attribute__((aligned(16))) float Gt[PRESPLIT ? 3 * kGhPlLd * 4 : 8 * 2 * 32 * 4];
     __shared__ __attribute__((aligned(16))) float GAt[32 * (K * 64 + 4)];  // GA tile, row-major padded
     // the tile's first kGhCap edges, staged once per tile: source row, local destination row, edge features
     __shared__ int sj[kGhCap], sr[kGhCap];
-    __shared__ __attribute__((aligned(16))) float sea[kGhCap * D];
+    // PRESPLIT: the staged edge features live in the planes' storage (written after the MFMA phase, when the planes are
+    // dead, read in the dot phase): 12.4 + 4 KB next to the GA tile would leave no room for two workgroups per CU at D = 4
+    __shared__ __attribute__((aligned(16))) float sea_own[PRESPLIT ? 4 : kGhCap * D];
+    static_assert(!PRESPLIT || kGhCap * D <= 3 * kGhPlLd * 4, "sea fits the planes");
+    float* const sea = PRESPLIT ? Gt : sea_own;
     __shared__ int rp_l[36];
     constexpr int LDGA = K * 64 + 4;
     float4* Gt4 = reinterpret_cast<float4*>(Gt);
@@ -152,8 +165,21 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
                 const int lim = e_t0 + ncap;
                 for (int p = beg + sub; p < end && p < lim; p += 8) sr[p - e_t0] = il;
             }
-            Gt4[at4_slot(sub, 0, il)] = make_float4(g0.x, g0.z, g1.x, g1.z);
-            Gt4[at4_slot(sub, 1, il)] = make_float4(g0.y, g0.w, g1.y, g1.w);
+            if constexpr (PRESPLIT) {
+                // This thread's 8 channels are group sub = 2 s + q of row il: elements 4 q + r of step s, components r of half
+                // hi = 0 (even channels) in words 0-1 of each split plane and of hi = 1 in words 2-3 -- what mfma_split_step
+                // forms from groups 2 s and 2 s + 1.  Six 8-byte stores; rows of absent nodes are zero planes.
+                const Bf3 gs = split8(make_float4(g0.x, g0.z, g1.x, g1.z), make_float4(g0.y, g0.w, g1.y, g1.w));
+                uint2* pl = reinterpret_cast<uint2*>(Gt) + 2 * ((sub >> 1) * kGhPlStep + il) + (sub & 1);
+                const u32x4 ph = __builtin_bit_cast(u32x4, gs.h), pm = __builtin_bit_cast(u32x4, gs.m),
+                            plo = __builtin_bit_cast(u32x4, gs.l);
+                pl[0] = make_uint2(ph[0], ph[1]);                      pl[64] = make_uint2(ph[2], ph[3]);
+                pl[2 * kGhPlLd] = make_uint2(pm[0], pm[1]);            pl[2 * kGhPlLd + 64] = make_uint2(pm[2], pm[3]);
+                pl[4 * kGhPlLd] = make_uint2(plo[0], plo[1]);          pl[4 * kGhPlLd + 64] = make_uint2(plo[2], plo[3]);
+            } else {
+                Gt4[at4_slot(sub, 0, il)] = make_float4(g0.x, g0.z, g1.x, g1.z);
+                Gt4[at4_slot(sub, 1, il)] = make_float4(g0.y, g0.w, g1.y, g1.w);
+            }
         }
         float my_ea[D];
 #pragma unroll
@@ -171,9 +197,10 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
         }
         // 2. GA tile on the matrix cores
         if (SPLIT) {
-            // A fragments split after their ds_read_b128, once per block: a split copy of the g tile in LDS (12 KB instead
-            // of 8) leaves no room for two workgroups per CU, split fragments held across the blocks (48 VGPRs) spill.
+            // A fragments: three ds_read_b128 of the planes per step (PRESPLIT), or the fp32 tile's two, split after the read
+            // once per block; split fragments held across the blocks (48 VGPRs) spill.
             // The block loop is rolled: unrolled, the blocks' MFMA chains were interleaved (four accumulators live).
+            const u32x4* pla = reinterpret_cast<const u32x4*>(Gt) + lane;
 #pragma unroll 1
             for (int t = 0; t < NBW; ++t) {
                 const int nb = wave * NBW + t;
@@ -184,7 +211,8 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
                 for (int s = 0; s < 4; ++s) {
                     const int q = 4 * t + s;                  // step of the wave's sequence (blocks are contiguous in Bs)
                     if (q + SL < 4 * NBW) bsp[(s + SL) % (SL + 1)] = load_split_b(bsw + (q + SL) * 64, bs_planes);
-                    c = mfma_split_step(Gt4, 2 * s, hi, r31, bsp[s], c);
+                    if constexpr (PRESPLIT) c = mfma_split6(load_split_b(pla + s * kGhPlStep, kGhPlLd), bsp[s], c);
+                    else c = mfma_split_step(Gt4, 2 * s, hi, r31, bsp[s], c);
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -222,6 +250,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
                 }
             }
         }
+        if constexpr (PRESPLIT) lds_barrier();       // every wave is through with the planes: sea overwrites them
         if ((int)threadIdx.x < ncap) {
 #pragma unroll
             for (int d = 0; d < D; ++d) sea[threadIdx.x * D + d] = my_ea[d];
@@ -308,11 +337,21 @@ int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, i
 #endif
     (void)variant;
     if (b_split) {
+        // The g tile is split once per tile on its way to LDS unless QOT_GRADH_SPLIT_AFTER_READ=1 (the earlier loop, same
+        // results bit for bit).  Read per call, not cached: callers flip it inside one process.
+        const char* sar_env = getenv("QOT_GRADH_SPLIT_AFTER_READ");
+        const bool presplit = !(sar_env && sar_env[0] == '1' && sar_env[1] == '\0');
         QOT_DISPATCH_D(D, {
-            if (kD <= 4)
-                nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), 0, true><<<grid, 256, 0, stream>>>(
-                    grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
-                    static_cast<const u32x4*>(b_split), split_stride / 8);
+            if (kD <= 4) {
+                if (presplit)
+                    nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), 0, true, true><<<grid, 256, 0, stream>>>(
+                        grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
+                        static_cast<const u32x4*>(b_split), split_stride / 8);
+                else
+                    nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), 0, true><<<grid, 256, 0, stream>>>(
+                        grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
+                        static_cast<const u32x4*>(b_split), split_stride / 8);
+            }
         });
         QOT_LAUNCH_CHECK();
         return QOT_OK;

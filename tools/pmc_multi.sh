@@ -1,10 +1,11 @@
 #!/bin/bash
-# usage: tools/pmc_multi.sh <tag> "<COUNTER COUNTER ...>" [bench args]   (one PMC pass, several counters, per-kernel means)
+# usage: tools/pmc_multi.sh <tag> "<COUNTER COUNTER ...>" [bench args]   (one PMC pass, several counters, per-kernel means;
+# counters only: no tracing rides in the same run)
 tag=$1; ctrs=$2; shift; shift
 R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)      # the repository root
 OUT=${OUT_DIR:-$R/prof_out}; mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd)   # where the records land (OUT_DIR, default prof_out/)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $OUT/$tag -- python3 $R/bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-graph "$@" > $OUT/$tag.log 2>&1
+rocprofv3 --pmc $ctrs --output-format csv -d $OUT/$tag -- python3 $R/bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-graph "$@" > $OUT/$tag.log 2>&1
 python3 - <<PY
 import csv,glob,collections,json
 f=glob.glob("$OUT/$tag/*/*counter_collection.csv")
