@@ -1,5 +1,6 @@
 // Device pieces of the single-launch TopologicalGNN forward, shared by the eval kernel (infer.hip), the
-// Monte-Carlo dropout kernel (infer_mc.hip) and the sensitivity kernel (infer_grad.hip):
+// Monte-Carlo dropout kernel (infer_mc.hip), the sensitivity kernel (infer_grad.hip) and the
+// what-if kernel (infer_whatif.hip, DESIGN.md 4.18: the same phases over an edited edge list, see InferBaseEdges):
 // the LDS layout, the argument block and the two halves of a workgroup's work on ONE graph --
 //   infer_phases12: index, edge MLP hidden layer, TransformerConv + leaky_relu -> the undropped x1 in LDS
 //   infer_phases34: NNConv (mean) in row tiles + leaky_relu, pooled on the fly, mean pool, read-out MLP -> one output row
@@ -102,11 +103,30 @@ __device__ __forceinline__ bool infer_slices_ok(const InferArgs& a, int64_t n0, 
     return !(nn < 0 || mm < 0 || nn > a.cap_n || mm > a.cap_m || n0 < 0 || e0 < 0 || n0 + nn > a.N || e0 + mm > a.E);
 }
 
+// ---- where phase 1 takes the graph's m edges from.  The default: edge e is position e0 + e of the batch's arrays.  Another
+// source (infer_whatif.hip: a base graph's slice less some positions, then edges of a second list) states the same four
+// things; an edge it skips is neither staged nor counted, and keeps its number: the slots stay sorted by edge number.
+struct InferBaseEdges {
+    __device__ __forceinline__ float attr(const InferArgs& a, int64_t e0, int c, int D) const {
+        return a.edge_attr[e0 * D + c];
+    }
+    // true: edge e is left out (its ends and rank were never written)
+    __device__ __forceinline__ bool skips(int e) const { return false; }
+    // the local (source j, target i) of edge e; false: skips(e)
+    __device__ __forceinline__ bool ends_of(const InferArgs& a, int64_t n0, int64_t e0, int n, int e, int& j, int& i) const {
+        j = (int)(a.ei[e0 + e] - n0);
+        i = (int)(a.ei[a.E + e0 + e] - n0);
+        return true;
+    }
+    // slots of the index: m edges, placed slots behind the scan (rp[n]) when some were skipped
+    __device__ __forceinline__ int slots(int m, const int* rp, int n) const { return m; }
+};
+
 // ---- phases 1 and 2 of graph [n0, n0 + n) / [e0, e0 + m): returns 0 with x1, he, rp, key, ends in LDS, or the status bits
 // of a breach (uniform over the workgroup; the image is then unusable and the caller writes NaN)
-template <int H, int D>
+template <int H, int D, class Src = InferBaseEdges>
 __device__ __forceinline__ int infer_phases12(const InferArgs& a, float* lds, const InferLds& L, int64_t n0, int64_t e0,
-                                              int n, int m) {
+                                              int n, int m, const Src& src = Src()) {
     constexpr int NT = kInferThreads;
     constexpr int K = 2 * D;
     __shared__ int s_bad;
@@ -131,10 +151,11 @@ __device__ __forceinline__ int infer_phases12(const InferArgs& a, float* lds, co
         lnid[t] = (int)id;
         cin[t] = 0;
     }
-    for (int c = tid; c < m * D; c += NT) ea[c] = a.edge_attr[e0 * D + c];
+    for (int c = tid; c < m * D; c += NT) ea[c] = src.attr(a, e0, c, D);
     __syncthreads();
     for (int e = tid; e < m; e += NT) {
-        int j = (int)(a.ei[e0 + e] - n0), i = (int)(a.ei[a.E + e0 + e] - n0);
+        int j, i;
+        if (!src.ends_of(a, n0, e0, n, e, j, i)) continue;
         if (i < 0 || i >= n || j < 0 || j >= n) { bad |= 1; continue; }      // (the workgroup leaves below: nothing reads it)
         ends[e] = ((unsigned int)j << 16) | (unsigned int)i;
         rank[e] = atomicAdd(&cin[i], 1);
@@ -153,13 +174,15 @@ __device__ __forceinline__ int infer_phases12(const InferArgs& a, float* lds, co
     __syncthreads();
     if (s_bad) return s_bad;                                          // (uniform: every thread reads the same word)
     block_scan_into<NT>(cin, rp, n);
-    for (int e = tid; e < m; e += NT) key[rp[ends[e] & 0xFFFFu] + rank[e]] = e;
+    for (int e = tid; e < m; e += NT)
+        if (!src.skips(e)) key[rp[ends[e] & 0xFFFFu] + rank[e]] = e;
     __syncthreads();
     for (int r = tid; r < n; r += NT) sort_row_keys(key, rp[r], rp[r + 1]);
     __syncthreads();
 
     // ---- phase 2: TransformerConv + leaky_relu ----
-    for (int p = tid; p < m; p += NT) {
+    const int slots = src.slots(m, rp, n);
+    for (int p = tid; p < slots; p += NT) {
         const int e = key[p];
         const unsigned int ji = ends[e];
         const int idi = lnid[ji & 0xFFFFu], idj = lnid[ji >> 16];

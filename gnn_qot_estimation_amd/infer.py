@@ -1,6 +1,6 @@
 """Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``; its Monte-Carlo dropout
 ``sample``: ``csrc/infer_mc.hip``; its per-link ``sensitivity``: ``csrc/infer_grad.hip``, DESIGN.md
-4.16) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
+4.16; its ``what_if`` over edited graphs: ``csrc/infer_whatif.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
 ``csrc/infer_lightpath_grad.hip``).
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
@@ -45,6 +45,7 @@ _KINDS = {
     "eval": ("qot_topological_infer_supported", "qot_topological_infer_max_edges", ""),
     "mc": ("qot_topological_infer_mc_supported", "qot_topological_infer_mc_max_edges", "sampling "),
     "grad": ("qot_topological_infer_grad_supported", "qot_topological_infer_grad_max_edges", "sensitivity "),
+    "whatif": ("qot_topological_infer_whatif_supported", "qot_topological_infer_whatif_max_edges", "what-if "),
 }
 
 
@@ -67,6 +68,12 @@ def grad_edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
     """``edge_cap`` of the sensitivity kernel (``TopologicalPredictor.sensitivity``): lower, its LDS image also holds the
     adjoint of the first convolution's output and ``2 * edge_dim`` more words per edge; -1: none."""
     return _edge_cap("grad", n_max, hidden, edge_dim)
+
+
+def what_if_edge_cap(n_max: int, hidden: int, edge_dim: int) -> int:
+    """``edge_cap`` of the what-if kernel (``TopologicalPredictor.what_if``): the eval kernel's, its LDS image is the same.
+    It bounds ``edges of a candidate's base graph + the candidate's additions`` (removals are not credited); -1: none."""
+    return _edge_cap("whatif", n_max, hidden, edge_dim)
 
 
 def grad_outputs(outputs, num_outputs: int, who: str = "TopologicalPredictor.sensitivity"):
@@ -175,6 +182,153 @@ def graph_slices(data, ei, N, dev, who):
     return ptr, eptr, B, n_max, max_e, exact
 
 
+WHAT_IF_MAX_DROP = 32           # csrc/infer_whatif.hip: kWhatIfMaxDrop
+
+
+def _host_ptr(p, name, total, who):
+    """A pointer array as an int64 host tensor, checked: non-decreasing from 0 to ``total``.  A device tensor costs one
+    read; a list or a host tensor none."""
+    try:
+        t = torch.as_tensor(p)
+    except (TypeError, ValueError, RuntimeError):
+        t = None
+    if t is None or t.dim() != 1 or t.numel() == 0 or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"{who}: {name} must be a non-empty 1-d sequence of integers, got {p!r}")
+    t = t.to(device="cpu", dtype=torch.int64)
+    if int(t[0]) != 0 or int(t[-1]) != total or (t.numel() > 1 and int(t.diff().min()) < 0):
+        raise ValueError(f"{who}: {name} must be non-decreasing from 0 to {total}, got {t.tolist()!r}")
+    return t
+
+
+_WhatIf = namedtuple("_WhatIf", "K A R add_ptr drop_ptr max_add")
+
+
+def what_if_args(edge_dim, add_edge_index, add_edge_attr, add_ptr, drop=None, drop_ptr=None, graph=None, num_graphs=None,
+                 who="TopologicalPredictor.what_if"):
+    """The argument checks of ``TopologicalPredictor.what_if`` (and of ``materialise_what_if``) that need no device:
+    returns ``(K, A, R, add_ptr, drop_ptr, max_add)`` with the pointer arrays as int64 host tensors (``drop_ptr`` ``None``
+    without removals), or raises the named ``ValueError``.  ``num_graphs``: the base batch's graph count when the caller
+    knows it (``graph=None`` needs exactly one)."""
+    if not isinstance(add_edge_index, torch.Tensor) or add_edge_index.dim() != 2 or add_edge_index.shape[0] != 2 \
+            or add_edge_index.dtype.is_floating_point:
+        raise ValueError(f"{who}: add_edge_index must be an integer tensor [2, A], got "
+                         f"{tuple(add_edge_index.shape) if isinstance(add_edge_index, torch.Tensor) else add_edge_index!r}")
+    A = add_edge_index.shape[1]
+    if not isinstance(add_edge_attr, torch.Tensor) or tuple(add_edge_attr.shape) != (A, int(edge_dim)):
+        raise ValueError(f"{who}: add_edge_attr must be [{A}, {int(edge_dim)}], got "
+                         f"{tuple(add_edge_attr.shape) if isinstance(add_edge_attr, torch.Tensor) else add_edge_attr!r}")
+    if (drop is None) != (drop_ptr is None):
+        raise ValueError(f"{who}: drop and drop_ptr must be given together (got only "
+                         f"{'drop_ptr' if drop is None else 'drop'})")
+    ap = _host_ptr(add_ptr, "add_ptr", A, who)
+    K = ap.numel() - 1
+    R, dp = 0, None
+    if drop is not None:
+        if not isinstance(drop, torch.Tensor) or drop.dim() != 1 or drop.dtype.is_floating_point:
+            raise ValueError(f"{who}: drop must be a 1-d integer tensor of positions into data.edge_index, got {drop!r}")
+        R = drop.shape[0]
+        dp = _host_ptr(drop_ptr, "drop_ptr", R, who)
+        if dp.numel() != K + 1:
+            raise ValueError(f"{who}: add_ptr names {K} candidates, drop_ptr {dp.numel() - 1}")
+        worst = int(dp.diff().max()) if K else 0
+        if worst > WHAT_IF_MAX_DROP:
+            raise ValueError(f"{who}: a candidate removes {worst} edges; at most WHAT_IF_MAX_DROP = {WHAT_IF_MAX_DROP}")
+    if graph is None:
+        if num_graphs is not None and num_graphs != 1:
+            raise ValueError(f"{who}: graph=None needs a base batch of exactly one graph, this one has {num_graphs}")
+    elif not isinstance(graph, torch.Tensor) or tuple(graph.shape) != (K,) or graph.dtype.is_floating_point:
+        raise ValueError(f"{who}: graph must be an integer tensor [{K}] (one base graph per candidate), got "
+                         f"{tuple(graph.shape) if isinstance(graph, torch.Tensor) else graph!r}")
+    return _WhatIf(K, A, R, ap, dp, int(ap.diff().max()) if K else 0)
+
+
+def _num_graphs_hint(data):
+    """The graph count of a batch where it can be told without a device read, else ``None``."""
+    ptr = getattr(data, "ptr", None)
+    if ptr is not None:
+        return ptr.numel() - 1
+    B = getattr(data, "num_graphs", None)
+    return None if B is None else int(B)
+
+
+def materialise_what_if(data, add_edge_index, add_edge_attr, add_ptr, drop=None, drop_ptr=None, graph=None):
+    """The explicit batch of the K edited graphs that ``TopologicalPredictor.what_if`` scores: the DEFINITION of that call
+    (``predict.what_if(...)[k]`` is row ``k`` of ``predict(materialise_what_if(...))`` bit for bit) and what it saves.
+    Pure torch, no kernel of ours; works on CPU tensors as well.
+
+    ``data``: the base batch of B graphs (table mode: ``node_ids``).  Candidate ``k`` names base graph ``graph[k]``
+    (``None``: B == 1, all zeros), removes the edges at positions ``drop[drop_ptr[k]:drop_ptr[k + 1]]`` of
+    ``data.edge_index`` (any order, a repeat counts once; they must lie in that graph's edge slice) and appends the edges
+    ``add_edge_index[:, add_ptr[k]:add_ptr[k + 1]]`` -- ``(source, target)`` in the batch's node numbering, as
+    ``data.edge_index`` -- with the rows of ``add_edge_attr``.  Graph ``k`` of the result holds the base graph's nodes
+    (``node_ids`` copied, ``x`` as the base batch has it: ``None`` in table mode), its surviving edges in their order and
+    the added edges behind them in the order given, node numbers renumbered to the candidate's own block.  The result
+    carries ``batch``, ``ptr``, ``edge_ptr`` and ``graph_sizes``.  Bad arguments, a graph number outside ``0 ... B - 1``, a
+    drop position outside its graph's slice or an added endpoint outside its graph raise ``ValueError``."""
+    from .batch import Batch
+    who = "materialise_what_if"
+    ei = data.edge_index
+    dev = ei.device
+    ea = data.edge_attr
+    if ea is None or ea.dim() != 2 or ea.shape[0] != ei.shape[1]:
+        raise ValueError(f"{who}: data.edge_attr must be [{ei.shape[1]}, D]")
+    ids = data.node_ids
+    if ids is None:
+        raise ValueError(f"{who}: data.node_ids is required (table mode)")
+    N, E = ids.shape[0], ei.shape[1]
+    ei = _i64(ei, dev)
+    ptr, eptr, B, _, _, _ = graph_slices(data, ei, N, dev, who)
+    w = what_if_args(ea.shape[1], add_edge_index, add_edge_attr, add_ptr, drop, drop_ptr, graph, B, who)
+    K = w.K
+    i64 = dict(dtype=torch.int64, device=dev)
+    g = torch.zeros(K, **i64) if graph is None else _i64(graph, dev)
+    if K and (int(g.min()) < 0 or int(g.max()) >= B):
+        raise ValueError(f"{who}: graph must lie in 0 ... {B - 1}")
+    ar = torch.arange(K, **i64)
+    n_k, m_k = (ptr[1:] - ptr[:-1])[g], (eptr[1:] - eptr[:-1])[g]
+    nptr = torch.zeros(K + 1, **i64)
+    nptr[1:] = torch.cumsum(n_k, 0)
+    bptr = torch.zeros(K + 1, **i64)                       # the base edges of every candidate, dropped ones included
+    bptr[1:] = torch.cumsum(m_k, 0)
+    # nodes: candidate c's block is its base graph's rows
+    cn = torch.repeat_interleave(ar, n_k)
+    rows = ptr[g][cn] + (torch.arange(cn.shape[0], **i64) - nptr[cn])
+    shift = nptr[:-1] - ptr[g]                             # batch node number -> the candidate's block
+    # base edges: every position of the base graph's slice, less the dropped ones
+    ce = torch.repeat_interleave(ar, m_k)
+    pos = eptr[g][ce] + (torch.arange(ce.shape[0], **i64) - bptr[ce])
+    if w.R:
+        dpos = _i64(drop, dev)
+        cd = torch.repeat_interleave(ar, w.drop_ptr.to(dev).diff())
+        if bool(((dpos < eptr[g][cd]) | (dpos >= eptr[g + 1][cd])).any()):
+            raise ValueError(f"{who}: a drop position lies outside its candidate's base graph")
+        keep = ~torch.isin(ce * max(E, 1) + pos, cd * max(E, 1) + dpos)
+        ce, pos = ce[keep], pos[keep]
+    # added edges
+    ca = torch.repeat_interleave(ar, w.add_ptr.to(dev).diff())
+    aei = _i64(add_edge_index, dev)
+    if w.A and bool(((aei < ptr[g][ca]) | (aei >= ptr[g + 1][ca])).any()):
+        raise ValueError(f"{who}: an added edge has an endpoint outside its candidate's base graph")
+    cand = torch.cat([ce, ca])
+    order = torch.argsort(cand, stable=True)               # per candidate: survivors in their order, then the additions
+    new_ei = torch.cat([ei[:, pos] + shift[ce], aei + shift[ca]], 1)[:, order]
+    new_ea = torch.cat([ea[pos], add_edge_attr.to(device=dev, dtype=ea.dtype)], 0)[order]
+    out = Batch()
+    out.num_graphs = K
+    out._num_nodes = int(rows.shape[0])
+    out.ptr, out.batch = nptr, cn
+    out.node_ids = ids.to(dev)[rows]
+    out.x = None if data.x is None else data.x.to(dev)[rows]
+    out.uniform_node_ids = None
+    out.edge_index, out.edge_attr = new_ei, new_ea
+    counts = torch.bincount(cand, minlength=K)
+    out.edge_ptr = torch.zeros(K + 1, **i64)
+    out.edge_ptr[1:] = torch.cumsum(counts, 0)
+    out.graph_sizes = (int(n_k.max()), int(counts.max())) if K else (0, 0)
+    out.has_self_loops = None
+    return out
+
+
 class _DeviceState:
     """What both predictors keep on the device beside the model: the status word their kernels flag a batch in and the
     ``outputs`` selections of ``sensitivity``.  ``_FLAGS`` of a predictor: its kernel's name, the meaning of the status bits."""
@@ -228,10 +382,12 @@ class TopologicalPredictor(_DeviceState):
 
     ``predictor.sample(data, samples)``: Monte-Carlo dropout, ``samples`` stochastic forwards in one launch (see there).
     ``predictor.sensitivity(data)``: the output together with its Jacobian wrt the edge features, in one launch.
+    ``predictor.what_if(data, ...)``: K small edits of the batch's graphs (edges added / removed), scored in one launch.
     """
 
     _FLAGS = ("qot_topological_infer", "bit 0 an edge leaves its graph's node range, bit 1 slices outside the arrays, "
-                                       "bit 2 a node id outside the table")
+                                       "bit 2 a node id outside the table (what_if: bit 0 also an added edge, bit 1 also a "
+                                       "graph number or a drop position out of range)")
 
     def __init__(self, model):
         super().__init__()
@@ -446,6 +602,72 @@ class TopologicalPredictor(_DeviceState):
         if return_attention_weights:
             return out, jac, (data.edge_index, alpha)
         return out, jac
+
+    @torch.no_grad()
+    def what_if(self, data, add_edge_index, add_edge_attr, add_ptr, drop=None, drop_ptr=None, graph=None):
+        """"What if": scores K small edits of the batch's graphs in ONE kernel launch, ``out [K, O]``, without building
+        the edited graphs.  ``out[k]`` is, bit for bit, row ``k`` of ``self(materialise_what_if(data, ...))`` -- see there
+        for the definition: candidate ``k`` names base graph ``graph[k]``, removes the edges at positions
+        ``drop[drop_ptr[k]:drop_ptr[k + 1]]`` of ``data.edge_index`` and appends ``add_edge_index[:, add_ptr[k]:add_ptr[k +
+        1]]`` (batch node numbering) with the rows of ``add_edge_attr``; the edited graph holds the base graph's nodes, its
+        surviving edges in their order and the added edges behind them.  A candidate's row does not depend on the other
+        candidates, and one without an edit equals ``self(data)[graph[k]]``.  The graphs are directed: a candidate
+        lightpath of an undirected network graph is its TWO directed edges (set-up: add both; tear-down: drop both; re-route:
+        both).
+
+        ``add_edge_index [2, A]`` int64, ``add_edge_attr [A, D]``, ``add_ptr [K + 1]`` (an empty slice is legal); ``drop [R]``
+        int64 with ``drop_ptr [K + 1]``, both or neither (any order within a candidate, a repeat counts once, at most
+        ``WHAT_IF_MAX_DROP`` = 32 per candidate); ``graph [K]`` int64, ``None`` only for a base batch of one graph.  Hand
+        ``add_ptr`` / ``drop_ptr`` over as lists or host tensors: they are checked on the host, a device tensor costs one read
+        each.  Nothing else is read back from the device.
+
+        Plain tensor without ``grad_fn``; pure (no model state is touched); parameter updates are followed as ``__call__``
+        follows them.  Refusals (``ValueError`` naming the condition, before any launch): everything ``__call__`` refuses,
+        pointer arrays not non-decreasing from 0 to A (R), ``add_edge_attr`` not ``[A, D]``, ``drop`` without ``drop_ptr`` or the
+        reverse, ``graph=None`` with B != 1, more than 32 removals in one candidate, a candidate whose ``edges of its graph +
+        its additions`` exceed ``what_if_edge_cap(n_max, hidden, edge_dim)`` (the eval kernel's cap; removals are not
+        credited.  The bound ``largest graph + most additions`` is tried first; only when that fails are the candidates'
+        own sums read, once).  On the device: an added edge with an endpoint outside its graph (status bit 0), a ``graph[k]``
+        outside ``0 ... B - 1`` or a drop position outside that graph's edge slice (bit 1) give NaN in that candidate's row
+        only, and ``check_status()`` raises."""
+        who = "TopologicalPredictor.what_if"
+        # the arguments are named before the model's device and the batch are looked at
+        H, D, O = self._check_model(on_gpu=False)
+        w = what_if_args(D, add_edge_index, add_edge_attr, add_ptr, drop, drop_ptr, graph, _num_graphs_hint(data), who)
+        p = self._prepare(data)
+        if graph is None and p.B != 1:
+            raise ValueError(f"{who}: graph=None needs a base batch of exactly one graph, this one has {p.B}")
+        dev, K = p.dev, w.K
+        out = torch.empty(K, O, dtype=torch.float32, device=dev)
+        if K == 0:
+            return out
+        if p.B == 0:
+            raise ValueError(f"{who}: {K} candidates, but the base batch has no graph")
+
+        def on_dev(given, host):
+            if isinstance(given, torch.Tensor) and given.device == dev:
+                return _i64(given, dev)
+            return host.to(dev)
+        add_ptr_d = on_dev(add_ptr, w.add_ptr)
+        g = None if graph is None else _i64(graph, dev)
+        max_e, cap = p.max_e, _edge_cap("whatif", p.n_max, H, D)
+        if max_e + w.max_add > cap:
+            # the bound fails: look at the candidates' own sums (one read); a graph number out of range is the kernel's to flag
+            m = p.eptr[1:] - p.eptr[:-1]
+            worst = int((m[g.clamp(0, p.B - 1)] if g is not None else m[:1]).add(add_ptr_d.diff()).max())
+            if worst > cap:
+                raise ValueError(f"{who}: a candidate of {worst} edges (its graph's and its additions; removals are not "
+                                 f"credited) is above the what-if edge cap {cap} for graphs of up to {p.n_max} nodes at "
+                                 f"hidden width {H}, edge_dim {D}")
+            max_e = worst - w.max_add
+        aei = _i64(add_edge_index, dev)
+        aea = _f32c(add_edge_attr if add_edge_attr.device == dev else add_edge_attr.to(dev))
+        dpos = dptr = None
+        if w.R:
+            dpos, dptr = _i64(drop, dev), on_dev(drop_ptr, w.drop_ptr)
+        self._launch("qot_topological_infer_whatif", p._replace(max_e=max_e), out, aei, aea, add_ptr_d, w.A, dpos, dptr, w.R,
+                     g, K, w.max_add)
+        return out
 
 
 # ====================================================================== LightpathGNN

@@ -866,6 +866,34 @@ int qot_topological_infer_grad(const int64_t* node_ids, const int64_t* edge_inde
                                float slope_head, float* out, int H, int D, int O, int32_t* status, const int32_t* outputs,
                                int Q, float* jac, float* alpha, qot_stream_t stream);
 
+/* ---- "what if" in one launch: the eval-mode forward of K edits of the batch's graphs ----------------
+ * Candidate k names base graph graph[k] (null: graph 0 -- legal only with B == 1), removes the edges at positions
+ * drop[drop_ptr[k] .. drop_ptr[k+1]) of edge_index (at most 32 per candidate; any order, a repeat counts once; drop and
+ * drop_ptr null: no removals) and appends the edges add_edge_index[:, add_ptr[k] .. add_ptr[k+1]) ([2, A] int64, batch node
+ * numbering as edge_index) with features add_edge_attr [A, D].  The edited graph holds the base graph's nodes, its
+ * surviving edges in their order and the added edges behind them; out[k, 0..O) ([K, O]) is, bit for bit, the row
+ * qot_topological_infer writes for that graph in any batch: the same code runs the same sums in the same order, and a
+ * candidate's row does not depend on the other candidates.  Grid (K), one workgroup per candidate; the batch is only read.
+ * max_add bounds the additions of one candidate (host-known).  Batch layout and tables as qot_topological_infer.
+ * Envelope: that of qot_topological_infer with max_e + max_add in the place of max_e (the LDS image is the eval kernel's,
+ * sized for a base graph and its additions; removals are not credited); qot_topological_infer_whatif_supported /
+ * _max_edges answer for that sum and equal the eval kernel's.  QOT_ERR_BADARG: negative sizes, max_add > A, R > 0 without
+ * drop / drop_ptr, graph null with B != 1, K > 0 with B == 0, a null required pointer; K == 0: QOT_OK, no launch.
+ * status: bit 0 = an edge, added ones included, leaves its graph's node range; bit 1 = graph[k] outside 0 .. B-1, a drop
+ * position outside that graph's edge slice, more than 32 removals or max_add additions, slices outside the arrays; bit 2
+ * as qot_topological_infer.  Only the flagged candidate's row is NaN. */
+int qot_topological_infer_whatif_supported(int n_max, int max_e, int H, int D, int O);
+int qot_topological_infer_whatif_max_edges(int n_max, int H, int D);
+int qot_topological_infer_whatif(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                                 const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t B, int n_max,
+                                 int max_e, const float* t4, int ld4, const float* M, int ldm, const float* P, int V,
+                                 const float* w_edge, const float* w1, const float* b1, const float* wcat, const float* bias2,
+                                 const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
+                                 float slope_head, float* out, int H, int D, int O, int32_t* status,
+                                 const int64_t* add_edge_index, const float* add_edge_attr, const int64_t* add_ptr, int64_t A,
+                                 const int64_t* drop, const int64_t* drop_ptr, int64_t R, const int64_t* graph, int64_t K,
+                                 int max_add, qot_stream_t stream);
+
 /* ---- single-launch inference: the eval-mode LightpathGNN forward of the LUT rows ------------------------------------
  * lightpath_training/models.py:7-45 with dropout off, reference architecture (ONE GATConv(heads = 4) -> BatchNorm on the
  * running statistics -> ReLU -> LUT rows -> Linear -> LeakyReLU -> Linear), for a block-diagonal batch in ONE launch, one

@@ -50,6 +50,17 @@ compared with autograd's ``x.grad`` first; then both alternate in one process, e
 ``torch.cuda.Event``s, median and interquartile range as above.
 
     python tools/bench_infer.py --kind lightpath --grad [--out profiles/bench_infer_lightpath_grad.jsonl]
+
+``--what-if K [K ...]``: K edits of one network state scored in one launch (csrc/infer_whatif.hip) --
+milliseconds per call of ``predict.what_if(data, ...)`` against (a) ``infer.materialise_what_if(...)`` followed by
+``predict(batch)`` per call, what a caller without ``what_if`` does for every fresh set of candidates, and (b) ``predict``
+alone on a batch materialised beforehand (the same arithmetic: a lower bound for (a), no candidate is ever fresh there).
+One base graph at the reference shape and at the headline shape; each candidate is one lightpath: the two directed edges
+between a seeded pair of nodes.  The edges and their features live on the device, ``add_ptr`` is a host tensor.  The rows of the three ways
+are compared first (equal bits); then they alternate in one process, each call between two ``torch.cuda.Event``s, median
+and interquartile range as above.
+
+    python tools/bench_infer.py --what-if 1 64 1024 [--out profiles/bench_infer_whatif.jsonl]
 """
 import argparse
 import json
@@ -278,6 +289,78 @@ def main_grad(args, device, commit):
               f"{verdict(r, 'sensitivity')} |")
 
 
+WHAT_IF_SHAPES = [SHAPES[0], SHAPES[3]]
+
+
+def measure_what_if(shape, K, device, rounds, warmup):
+    from gnn_qot_estimation_amd import infer
+    torch.manual_seed(0)
+    model = q.TopologicalGNN(shape["V"], shape["H"], 3, 4, dropout_p=0.0).to(device).eval()
+    data = batch_for(shape, device)                        # B = 1: the network state
+    predict = q.TopologicalPredictor(model)
+    gen = torch.Generator().manual_seed(K)
+    u = torch.randint(0, shape["n"], (K,), generator=gen)
+    v = (u + 1 + torch.randint(0, shape["n"] - 1, (K,), generator=gen)) % shape["n"]        # v != u
+    add = torch.stack([torch.stack([u, v], 1).reshape(-1), torch.stack([v, u], 1).reshape(-1)]).to(device)   # u->v, v->u
+    attr = torch.rand(2 * K, 4, generator=gen).to(device)
+    add_ptr = torch.arange(0, 2 * K + 1, 2)                # a host tensor: checked on the host, uploaded per call
+    mat = infer.materialise_what_if(data, add, attr, add_ptr)
+
+    ways = {"what_if": lambda: predict.what_if(data, add, attr, add_ptr),
+            "materialise": lambda: predict(infer.materialise_what_if(data, add, attr, add_ptr)),
+            "prebuilt": lambda: predict(mat)}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    assert torch.equal(got["what_if"], got["prebuilt"]) and torch.equal(got["materialise"], got["prebuilt"]), shape["name"]
+    assert tuple(got["what_if"].shape) == (K, 3) and bool(torch.isfinite(got["what_if"]).all())
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed_event(fn))
+    res = dict(shape=shape["name"], kind="what_if", K=K, added_per_candidate=2,
+               **{k: shape[k] for k in ("V", "n", "e", "H", "B")}, rounds=rounds, equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def versus(r, other):
+    """``other`` against ``what_if``: the ratio of the medians, or "no difference" (module docstring)."""
+    a, b = r["what_if_ms"], r[f"{other}_ms"]
+    if abs(a - b) <= max(r["what_if_iqr_ms"], r[f"{other}_iqr_ms"]):
+        return "no difference"
+    return f"{b / a:.2f}x"
+
+
+def main_what_if(args, device, commit):
+    rows = []
+    for shape in WHAT_IF_SHAPES:
+        for K in args.what_if:
+            res = measure_what_if(shape, K, device, args.rounds, args.warmup)
+            res["commit"] = commit or None
+            res["device"] = torch.cuda.get_device_name(0)
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| shape | K | what_if ms (IQR) | (a) materialise + predict ms (IQR) | (b) predict, prebuilt ms (IQR) | (a) / what_if "
+          "| (b) / what_if |")
+    print("|---|---|---|---|---|---|---|")
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['shape']} (n={r['n']}, e={r['e']}, H={r['H']}) | {r['K']} | {cell('what_if')} | {cell('materialise')} | "
+              f"{cell('prebuilt')} | {versus(r, 'materialise')} | {versus(r, 'prebuilt')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -436,7 +519,13 @@ def main():
     ap.add_argument("--grad", action="store_true",
                     help="sensitivity: predict.sensitivity(data) against eval forward + one backward per output "
                          "(with --kind lightpath: LightpathPredictor's)")
+    ap.add_argument("--what-if", type=int, nargs="+", default=None, metavar="K", dest="what_if",
+                    help="what-if: predict.what_if on K one-lightpath candidates against materialise_what_if + predict and "
+                         "predict on a prebuilt batch")
     args = ap.parse_args()
+    if args.what_if is not None and (args.kind != "topological" or args.mc is not None or args.grad
+                                     or any(k < 1 for k in args.what_if)):
+        raise SystemExit("--what-if K [K ...] (K >= 1) is a run of its own, for the topological model")
     if args.mc is not None and args.kind != "topological":
         raise SystemExit("--mc is for the topological model")
     if args.mc is not None and args.grad:
@@ -449,6 +538,8 @@ def main():
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     if args.kind == "lightpath":
         return (main_lightpath_grad if args.grad else main_lightpath)(args, device, commit)
+    if args.what_if is not None:
+        return main_what_if(args, device, commit)
     if args.mc is not None:
         return main_mc(args, device, commit)
     if args.grad:
