@@ -25,13 +25,6 @@ namespace qot {
 
 constexpr int kGemmBM = 128, kGemmBN = 128, kGemmBK = 32;
 
-#ifdef QOT_DIAG
-__device__ int g_gemm_variant;     // ablation bits of the NT kernel (tools/bench_gemm_k.py): 1 no global loads in the loop,
-#define GEMM_VAR(bit) (gemm_var & (bit))   // 2 no LDS stores, 4 no barrier, 8 no C stores, 16 no fragment reads
-#else
-#define GEMM_VAR(bit) 0
-#endif
-
 // float4 slot of (group g, k parity hi, row) inside one operand stage; the XOR spreads the four groups a quarter-wave
 // writes (NT loader) over all banks, reads of 16 consecutive rows stay a permutation of 16 consecutive slots
 __device__ __forceinline__ int gemm_slot(int g, int hi, int row) { return (2 * g + hi) * 128 + (row ^ ((g & 3) << 2)); }
@@ -65,24 +58,23 @@ __device__ __forceinline__ void gemm_group_mfma(const GemmFrag& f, f32x16 (&c)[2
 // the first fragments of the next stage have been requested: its 16 MFMAs (1024 cycles) cover that LDS round trip.
 template <class Load, class Stash>
 __device__ __forceinline__ void gemm_mainloop(float4 (&lds)[2][2][1024], int64_t nk, int wm, int wn, int hi, int r31,
-                                              f32x16 (&c)[2][2], Load load, Stash stash, int gemm_var = 0) {
+                                              f32x16 (&c)[2][2], Load load, Stash stash) {
     GemmFrag f0, f1;
     if (nk > 0) gemm_read_frag(f0, lds[0][0], lds[0][1], 0, wm, wn, hi, r31);
-    if (GEMM_VAR(16)) f1 = f0;
 #pragma unroll 1
     for (int64_t kt = 0; kt < nk; ++kt) {
         const int cur = (int)(kt & 1);
         const bool more = kt + 1 < nk;
-        if (more && !GEMM_VAR(1)) load(kt + 1);                              // global -> registers, under the MFMAs below
-        if (!GEMM_VAR(16)) gemm_read_frag(f1, lds[cur][0], lds[cur][1], 1, wm, wn, hi, r31);
+        if (more) load(kt + 1);                                              // global -> registers, under the MFMAs below
+        gemm_read_frag(f1, lds[cur][0], lds[cur][1], 1, wm, wn, hi, r31);
         gemm_group_mfma(f0, c);
-        if (!GEMM_VAR(16)) gemm_read_frag(f0, lds[cur][0], lds[cur][1], 2, wm, wn, hi, r31);
+        gemm_read_frag(f0, lds[cur][0], lds[cur][1], 2, wm, wn, hi, r31);
         gemm_group_mfma(f1, c);
-        if (!GEMM_VAR(16)) gemm_read_frag(f1, lds[cur][0], lds[cur][1], 3, wm, wn, hi, r31);
+        gemm_read_frag(f1, lds[cur][0], lds[cur][1], 3, wm, wn, hi, r31);
         gemm_group_mfma(f0, c);
-        if (more && !GEMM_VAR(2)) stash(cur ^ 1);                            // registers -> the other LDS buffer
-        if (!GEMM_VAR(4)) lds_barrier();
-        if (more && !GEMM_VAR(16)) gemm_read_frag(f0, lds[cur ^ 1][0], lds[cur ^ 1][1], 0, wm, wn, hi, r31);
+        if (more) stash(cur ^ 1);                                            // registers -> the other LDS buffer
+        lds_barrier();
+        if (more) gemm_read_frag(f0, lds[cur ^ 1][0], lds[cur ^ 1][1], 0, wm, wn, hi, r31);
         gemm_group_mfma(f1, c);                                              // group 3 of this stage, from registers
     }
 }
@@ -212,12 +204,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const float* __restrict
     load(0);
     stash(0);
     __syncthreads();
-#ifdef QOT_DIAG
-    const int gemm_var = g_gemm_variant;
-#else
-    const int gemm_var = 0;
-#endif
-    gemm_mainloop(lds, nk, wm, wn, hi, r31, c, [&](int64_t kt) { load((int)kt * kGemmBK); }, stash, gemm_var);
+    gemm_mainloop(lds, nk, wm, wn, hi, r31, c, [&](int64_t kt) { load((int)kt * kGemmBK); }, stash);
     // epilogue through LDS: tile row p = output row m0 + p, tile column q = output column n0 + q
     float* tile = reinterpret_cast<float*>(&lds[0][0][0]);
     gemm_tile_to_lds(tile, c, wm, wn, hi, r31);
@@ -231,7 +218,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const float* __restrict
         if (row < M && col < N) {
             float4 v = ld4(tile + pm * 128 + ((4 * q4) ^ ((pm & 7) << 2)));
             if (bias) { const float4 bz = ld4(bias + col); v = add4(v, bz); }
-            if (!GEMM_VAR(8) || v.x == 12345.678f) st4(C + row * ldc + col, v);
+            st4(C + row * ldc + col, v);
         }
     }
     if (LOGITS) {
@@ -606,12 +593,6 @@ extern "C" int qot_gemm256_takes(int64_t M, int N);
 int gemm256_nt_launch(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int N, int K,
                       const float* scale, const float* shift, const float* bias, const float* att_src, const float* att_dst,
                       float* a_src, float* a_dst, hipStream_t stream);
-
-#ifdef QOT_DIAG
-extern "C" int qot_debug_gemm_variant(int v) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(qot::g_gemm_variant), &v, sizeof(int)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 // C[M, N] = A'[M, K] . B[N, K]^T (+ bias[N]);  A' = relu(A * scale[k] + shift[k]) when scale != NULL.
 // K multiple of 32, lda / ldb multiples of 4, 16-byte aligned operands.

@@ -1,7 +1,7 @@
 // The large-M form of gemm.hip's NT product: 256 x 256 x 32 tiles, one 256-thread workgroup per CU, each of the four
 // waves owning a 128 x 128 quarter (4 x 4 MFMA tiles of 32 x 32: 256 accumulator registers per lane, in AGPRs).
 //
-// Why a second tile size (measured, tools/bench_gemm_k.py on the diagnostic build): the 128 x 128 kernel's MFMA stream
+// Why a second tile size (measured with the ablation build since retired): the 128 x 128 kernel's MFMA stream
 // alone runs at 141-147 TFLOP/s, its fragment reads take that to 131-133, the stage's global loads / LDS stores to
 // 124-127 -- not latency (operands from one L2-resident row: no change; barrier removed: no change) but the number of
 // non-MFMA instructions issued per MFMA.  A wave that owns 128 x 128 instead of 64 x 64 issues HALF the ds_read_b128 per
@@ -20,13 +20,6 @@ constexpr int kG2T = 256, kG2BK = 32;
 constexpr int kG2Stage4 = 2048;                          // float4 per operand and stage (256 rows x 32 k)
 constexpr size_t kG2StageBytes = (size_t)2 * 2 * kG2Stage4 * 16;    // two stages x two operands = 128 KB
 constexpr int kG2AttFloats = 2 * 1024;                   // NT: attention vectors of up to 8 heads behind the stages
-
-#ifdef QOT_DIAG
-__device__ int g_gemm256_variant;  // ablation bits of the NT kernel (tools/bench_gemm_k.py): 1 no global loads in the loop,
-#define G2_VAR(bit) (g2_var & (bit))   // 2 no LDS stores, 4 no barrier, 8 no C stores, 16 no fragment reads
-#else
-#define G2_VAR(bit) 0
-#endif
 
 // Fragments of a wave: a[i] (its four 32-row bands), b[2][j] (its four 32-column bands, current and next k group).  A k
 // group's 64 MFMAs run band by band (i-major), so a[i] is dead after its 16 MFMAs and takes the NEXT group's fragment at
@@ -56,19 +49,19 @@ __device__ __forceinline__ void g2_band_mfma(const float4& a, const float4 (&b)[
 }
 
 // k group G (compile-time 0..3) of the stage in (As, Bs): its 64 MFMAs; the fragments of the group after it -- group G + 1
-// of the same stage, or group 0 of (An, Bn) behind group 3 -- are read as registers come free.  SKIP: diagnostic build.
+// of the same stage, or group 0 of (An, Bn) behind group 3 -- are read as registers come free.
 template <int G>
 __device__ __forceinline__ void g2_group(G2Frag& f, const float4* __restrict__ As, const float4* __restrict__ Bs,
                                          const float4* __restrict__ An, const float4* __restrict__ Bn, int wm, int wn, int hi,
-                                         int r31, f32x16 (&c)[4][4], bool skip_reads) {
+                                         int r31, f32x16 (&c)[4][4]) {
     constexpr int NG = (G + 1) & 3;
     const float4* Ar = G == 3 ? An : As;
     const float4* Br = G == 3 ? Bn : Bs;
-    if (!skip_reads) g2_read_b(f.b[(G + 1) & 1], Br, NG, wn, hi, r31);
+    g2_read_b(f.b[(G + 1) & 1], Br, NG, wn, hi, r31);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         g2_band_mfma(f.a[i], f.b[G & 1], c[i]);
-        if (!skip_reads) f.a[i] = g2_read_a(Ar, NG, i, wm, hi, r31);
+        f.a[i] = g2_read_a(Ar, NG, i, wm, hi, r31);
     }
 }
 
@@ -113,7 +106,7 @@ __device__ __forceinline__ void g2_band_out(float* __restrict__ reg, const f32x1
 // refill.  The loop body has no branch: one scheduling region of 192 MFMAs, 24 fragment reads, 16 (20) global loads and
 // 16 LDS stores whose interleave is pinned with sched_group_barrier: with ONE wave per SIMD nothing else fills the matrix
 // pipe while a clump of loads / stores / reads issues (an LDS store takes 13-26 issue cycles; the branchy first version
-// of this kernel had them in clumps of 8 between runs of ~60 MFMAs: 4-7 % on the diagnostic build's ablations, 128 / 125
+// of this kernel had them in clumps of 8 between runs of ~60 MFMAs: 4-7 % in the ablations of the time, 128 / 125
 // TFLOP/s plain / BatchNorm prologue).  The operands come through BUFFER loads (one descriptor per matrix, 32-bit byte
 // offsets, the k offset in the scalar offset field): this compiler's sched_group_barrier VMEM masks do not match
 // global_load (a FLAT instruction) -- with global loads the same pins left them next to the LDS stores that consume them
@@ -208,9 +201,6 @@ __global__ __launch_bounds__(256) void gemm256_nt_kernel(const float* __restrict
         }
     };
     const int nk = K / kG2BK;
-#ifdef QOT_DIAG
-    const int g2_var = g_gemm256_variant;
-#endif
     f32x16 c[4][4];
     G2Frag f;
     point(rb, ct);
@@ -249,14 +239,13 @@ __global__ __launch_bounds__(256) void gemm256_nt_kernel(const float* __restrict
         const float4* Bs = As + kG2Stage4;
         const float4* An = g2lds + (2 * (cur ^ 1)) * kG2Stage4;
         const float4* Bn = An + kG2Stage4;
-        const bool skip = G2_VAR(16);
-        if (!G2_VAR(1)) load_a(kn * kG2BK);
-        g2_group<0>(f, As, Bs, An, Bn, wm, wn, hi, r31, c, skip);
-        if (!G2_VAR(2)) stash_a(cur ^ 1);
-        if (!G2_VAR(1)) load_b(kn * kG2BK);
-        g2_group<1>(f, As, Bs, An, Bn, wm, wn, hi, r31, c, skip);
-        if (!G2_VAR(2)) stash_b(cur ^ 1);
-        g2_group<2>(f, As, Bs, An, Bn, wm, wn, hi, r31, c, skip);
+        load_a(kn * kG2BK);
+        g2_group<0>(f, As, Bs, An, Bn, wm, wn, hi, r31, c);
+        stash_a(cur ^ 1);
+        load_b(kn * kG2BK);
+        g2_group<1>(f, As, Bs, An, Bn, wm, wn, hi, r31, c);
+        stash_b(cur ^ 1);
+        g2_group<2>(f, As, Bs, An, Bn, wm, wn, hi, r31, c);
 #ifndef QOT_G2_NO_PIN
         // group 0: 8 (12) global loads of the A half
         QOT_M(2) QOT_V(1) QOT_M(2) QOT_D(1) QOT_M(2) QOT_V(1) QOT_M(2) QOT_D(1)
@@ -277,8 +266,8 @@ __global__ __launch_bounds__(256) void gemm256_nt_kernel(const float* __restrict
         QOT_M(4) QOT_W(1) QOT_M(4) QOT_W(1) QOT_M(4) QOT_W(1) QOT_M(4) QOT_W(1) QOT_D(1)
         QOT_M(16) QOT_D(1) QOT_M(16) QOT_D(1)
 #endif
-        if (!G2_VAR(4)) lds_barrier();
-        g2_group<3>(f, As, Bs, An, Bn, wm, wn, hi, r31, c, skip);
+        lds_barrier();
+        g2_group<3>(f, As, Bs, An, Bn, wm, wn, hi, r31, c);
 #ifndef QOT_G2_NO_PIN
         QOT_M(4) QOT_D(1) QOT_M(4) QOT_D(1) QOT_M(4) QOT_D(1) QOT_M(4) QOT_D(1) QOT_D(1)
         QOT_M(16) QOT_D(1) QOT_M(16) QOT_D(1) QOT_M(16) QOT_D(1)
@@ -311,7 +300,7 @@ __global__ __launch_bounds__(256) void gemm256_nt_kernel(const float* __restrict
                     const int col = n0 + 4 * q4;
                     if (row < M && col < N) {
                         if (bias) v = add4(v, ld4(bias + col));
-                        if (!G2_VAR(8) || v.x == 12345.678f) st4(C + row * ldc + col, v);
+                        st4(C + row * ldc + col, v);
                     }
                 }
                 if (LOGITS) {
@@ -352,12 +341,6 @@ __global__ __launch_bounds__(256) void gemm256_nt_kernel(const float* __restrict
 }  // namespace qot
 
 using namespace qot;
-
-#ifdef QOT_DIAG
-extern "C" int qot_debug_gemm256_variant(int v) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(qot::g_gemm256_variant), &v, sizeof(int)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 // 1 when the 256 x 256 forms take a product of this size (enough tiles for every CU; narrower N leaves half a tile idle)
 extern "C" int qot_gemm256_takes(int64_t M, int N) {

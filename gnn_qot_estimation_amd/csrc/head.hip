@@ -483,12 +483,6 @@ constexpr int kHeadKeep = 32;            // rows FOUR lane groups per graph woul
 #define QOT_HEAD_THREADS 512       /* measured at cfg2: 256 threads 20.4 us, 512 17.3 us, 1024 23.8 us (64 B/lane of scratch) */
 #endif
 constexpr int kHeadThreads = QOT_HEAD_THREADS;
-#ifdef QOT_DIAG
-__device__ int g_head_variant;           // ablation bits (tools/bench_head.py): 1 no pool backward, 2 no dense phases, 4 no row loads
-#define HD_VAR(bit) (hd_var & (bit))
-#else
-#define HD_VAR(bit) 0
-#endif
 
 template <int H, int NT>
 __global__ __launch_bounds__(NT) void head_train_batched_kernel(
@@ -518,9 +512,6 @@ __global__ __launch_bounds__(NT) void head_train_batched_kernel(
     __shared__ float lrow[GB][8];
     __shared__ int pb[GB + 1];
     const int t = threadIdx.x;
-#ifdef QOT_DIAG
-    const int hd_var = g_head_variant;
-#endif
     const int sub = t % TPR, slot = t / TPR;
     const int gs = slot / SPG, sr = slot % SPG;           // my lane group's graph (of the pass) and its share of the rows
     const int part = t % KS, od = t / KS;                 // dense phases: output od = (g, o), inner-index share `part`
@@ -560,7 +551,7 @@ __global__ __launch_bounds__(NT) void head_train_batched_kernel(
 #pragma unroll
         for (int k = 0; k < KR; ++k) {
             const int r = sr + SPG * k;
-            v[k] = (r < cnt && !HD_VAR(4)) ? ld4(x + (int64_t)(beg + r) * H + 4 * sub) : f4zero();
+            v[k] = (r < cnt) ? ld4(x + (int64_t)(beg + r) * H + 4 * sub) : f4zero();
         }
 #pragma unroll
         for (int k = 0; k < KR; ++k) acc = add4(acc, v[k]);
@@ -581,10 +572,8 @@ __global__ __launch_bounds__(NT) void head_train_batched_kernel(
         float hv = 0.f, dact = 0.f;
         {
             float a0 = 0.f;
-            if (!HD_VAR(2)) {
 #pragma unroll
-                for (int a = part * (H / KS); a < (part + 1) * (H / KS); ++a) a0 = fmaf(w0s[o * HP + a], pp[g][a], a0);
-            }
+            for (int a = part * (H / KS); a < (part + 1) * (H / KS); ++a) a0 = fmaf(w0s[o * HP + a], pp[g][a], a0);
             if (KS >= 2) a0 += dpp_move<0xB1>(a0);
             if (KS >= 4) a0 += dpp_move<0x4E>(a0);
             const float vv = a0 + b0o;
@@ -650,26 +639,22 @@ __global__ __launch_bounds__(NT) void head_train_batched_kernel(
         __syncthreads();
         {
             float a0 = 0.f;
-            if (!HD_VAR(2)) {
 #pragma unroll
-                for (int oo = part * (H / KS); oo < (part + 1) * (H / KS); ++oo) a0 = fmaf(w0s[oo * HP + o], gh[g][oo], a0);
-            }
+            for (int oo = part * (H / KS); oo < (part + 1) * (H / KS); ++oo) a0 = fmaf(w0s[oo * HP + o], gh[g][oo], a0);
             if (KS >= 2) a0 += dpp_move<0xB1>(a0);
             if (KS >= 4) a0 += dpp_move<0x4E>(a0);
             if (part == 0) gp[g][o] = a0;
         }
-        if (!HD_VAR(2)) {
 #pragma unroll
-            for (int gg = 0; gg < GB; ++gg)
+        for (int gg = 0; gg < GB; ++gg)
 #pragma unroll
-                for (int e = 0; e < PER; ++e) {
-                    const int idx = t * PER + e;
-                    aw0[e] = fmaf(gh[gg][idx / H], pp[gg][idx % H], aw0[e]);
-                }
-        }
+            for (int e = 0; e < PER; ++e) {
+                const int idx = t * PER + e;
+                aw0[e] = fmaf(gh[gg][idx / H], pp[gg][idx % H], aw0[e]);
+            }
         __syncthreads();
         // ---- pool backward: my rows get gp / count, through the producer's activation when folded
-        if (cnt > 0 && !HD_VAR(1)) {
+        if (cnt > 0) {
             const float inv = 1.0f / (float)(cnt > 1 ? cnt : 1);
             const float4 gv = make_float4(gp[gs][4 * sub] * inv, gp[gs][4 * sub + 1] * inv, gp[gs][4 * sub + 2] * inv,
                                           gp[gs][4 * sub + 3] * inv);
@@ -844,9 +829,6 @@ extern "C" int qot_head_train_blocks(int64_t B, int H) {
     return B < kHeadBwdBlocks ? (int)B : kHeadBwdBlocks;
 }
 
-#ifdef QOT_DIAG
-extern "C" void qot_debug_head_variant(int v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(qot::g_head_variant), &v, sizeof(int)); }
-#endif
 
 extern "C" int qot_head_fwd_loss(const float* x, const int32_t* ptr, const float* w0, const float* b0,
                                  const float* w3, const float* b3, float* pooled, float* hidden, float* out,

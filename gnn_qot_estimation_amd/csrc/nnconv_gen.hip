@@ -191,9 +191,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
     const float* __restrict__ x, int ldx, const float* __restrict__ ea, const float* __restrict__ w1,
     const float* __restrict__ b1, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const int32_t* __restrict__ eidx, const float* __restrict__ invdeg, const float* __restrict__ Wp,
-    const float* __restrict__ bias, float* __restrict__ out, int64_t N, ActParams act, int variant) {
-    // variant (diagnostic builds only, tools/ablate_gen.py): 1 = no gather (constant operand tile), 2 = weight
-    // fragments loaded once (no L2 stream), 3 = gather only (no MFMA), 4 = 1 + 2
+    const float* __restrict__ bias, float* __restrict__ out, int64_t N, ActParams act) {
     using G = GenW<H>;
     constexpr int K = 2 * D;
     constexpr int CW = G::CW, NP = G::NP, CPL = G::CPL, NCB = G::NCB, CBW = G::CBW, KS = G::KS;
@@ -234,16 +232,6 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
             float root[CPL];
             {
                 float acc[K + 1][CPL];
-#ifdef QOT_DIAG
-                if (variant == 1 || variant == 4) {
-#pragma unroll
-                    for (int kk = 0; kk <= K; ++kk)
-#pragma unroll
-                        for (int c_ = 0; c_ < CPL; ++c_) acc[kk][c_] = 1.0f + kk;
-#pragma unroll
-                    for (int c_ = 0; c_ < CPL; ++c_) root[c_] = 1.0f;
-                } else
-#endif
                 // (the exchange slots of the gather are float4 slots of the operand tile that only this wave's rows map
                 // to -- at4_slot keeps a wave's 8 rows inside its aligned 8 slots of every (group, half) line -- and the
                 // tile is free between the barrier that ended the last MFMA phase and this wave's own frag_store)
@@ -253,11 +241,6 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
                 for (int kk = 0; kk <= K; ++kk) frag_store<CW, CPL>(At, kk, sub, il, acc[kk]);
                 if (ROOT_LDS) frag_store<CW, CPL>(At, K + 1, sub, il, root);
             }
-#ifdef QOT_DIAG
-            const int64_t gstep = (variant == 2 || variant == 4) ? 0 : 1;      // 0: every fragment load hits the same line
-#else
-            constexpr int64_t gstep = 1;
-#endif
             // ---- main part: this wave's groups [ks*GS, (ks+1)*GS) against its column blocks.  The first chunk of weight
             // fragments is requested in FRONT of the barrier that publishes the operand tile, and that barrier orders LDS
             // traffic only: behind a __syncthreads() their L2 round trip was exposed once per pass.
@@ -266,18 +249,15 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
 #pragma unroll
             for (int q = 0; q < CBW; ++q)
 #pragma unroll
-                for (int u = 0; u < CH; ++u) bc[q][u] = wp[((int64_t)q * GALL + u) * 64 * gstep];
+                for (int u = 0; u < CH; ++u) bc[q][u] = wp[((int64_t)q * GALL + u) * 64];
             lds_barrier();
-#ifdef QOT_DIAG
-            if (variant == 3) { lds_barrier(); continue; }
-#endif
             int ch = 0;
 #pragma unroll 1
             for (; ch + 1 < NCH; ch += 2) {
 #pragma unroll
                 for (int q = 0; q < CBW; ++q)
 #pragma unroll
-                    for (int u = 0; u < CH; ++u) bn[q][u] = wp[((int64_t)q * GALL + (ch + 1) * CH + u) * 64 * gstep];
+                    for (int u = 0; u < CH; ++u) bn[q][u] = wp[((int64_t)q * GALL + (ch + 1) * CH + u) * 64];
 #pragma unroll
                 for (int u = 0; u < CH; ++u) {
                     const float4 a = At4[at4_slot(ks * GS + ch * CH + u, hi, r31)];
@@ -293,7 +273,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
 #pragma unroll
                     for (int q = 0; q < CBW; ++q)
 #pragma unroll
-                        for (int u = 0; u < CH; ++u) bc[q][u] = wp[((int64_t)q * GALL + (ch + 2) * CH + u) * 64 * gstep];
+                        for (int u = 0; u < CH; ++u) bc[q][u] = wp[((int64_t)q * GALL + (ch + 2) * CH + u) * 64];
                 }
 #pragma unroll
                 for (int u = 0; u < CH; ++u) {
@@ -439,7 +419,7 @@ __global__ __launch_bounds__(512, 2) void nnconv_dw_gen_kernel(
     const float* __restrict__ x, int ldx, const float* __restrict__ g, int ldg, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const int32_t* __restrict__ eidx, const float* __restrict__ invdeg,
-    float* __restrict__ slabs, int64_t N, int nsplit, int variant) {
+    float* __restrict__ slabs, int64_t N, int nsplit) {
     using W = DwW<H>;
     constexpr int K = 2 * D;
     constexpr int AC = W::AC, NAC = W::NAC, OC = W::OC, OCB = W::OCB, NSLICE = W::NSLICE;
@@ -483,9 +463,6 @@ __global__ __launch_bounds__(512, 2) void nnconv_dw_gen_kernel(
     // The two roles are two separate loops with the same barrier count, so that the consumers' 80 accumulator registers
     // are not live in the producers' code (one loop with a role branch inside spilled 192 B/lane at 128 registers).
     if (producer) {
-#ifdef QOT_DIAG
-        if (variant == 6) __builtin_amdgcn_s_setprio(2);
-#endif
         auto fill = [&](int64_t tile, int buf) {
             const int64_t tile0 = tile * 32;
             const int64_t i = tile0 + il;
@@ -500,16 +477,6 @@ __global__ __launch_bounds__(512, 2) void nnconv_dw_gen_kernel(
             }
             constexpr int CPL = AC / 8;
             float acc[K + 1][CPL], root[CPL];
-#ifdef QOT_DIAG
-            if (variant == 1) {
-#pragma unroll
-                for (int kk = 0; kk <= K; ++kk)
-#pragma unroll
-                    for (int c_ = 0; c_ < CPL; ++c_) acc[kk][c_] = 1.f + kk;
-#pragma unroll
-                for (int c_ = 0; c_ < CPL; ++c_) root[c_] = 1.f;
-            } else
-#endif
             gen_gather_xch<D, CPL, false, 8>(x, ldx, a0 + CPL * sub, ea, w1, b1, rowptr, col, eidx, invdeg, i, N, xchg[wave], acc, root);
 #pragma unroll
             for (int kk = 0; kk <= K; ++kk)
@@ -528,9 +495,6 @@ __global__ __launch_bounds__(512, 2) void nnconv_dw_gen_kernel(
         }
         return;
     }
-#ifdef QOT_DIAG
-    if (variant == 5) __builtin_amdgcn_s_setprio(2);
-#endif
     f32x16 dw[TPW];
 #pragma unroll
     for (int t = 0; t < TPW; ++t)
@@ -550,9 +514,6 @@ __global__ __launch_bounds__(512, 2) void nnconv_dw_gen_kernel(
     int buf = 0;
 #pragma unroll 1
     for (int k = 0; k < n_mine; ++k, buf ^= 1) {
-#ifdef QOT_DIAG
-        if (variant != 3)
-#endif
         {
             // dW[(kk,a), o] += sum over the tile's nodes: A operand = the tile read transposed (node = k index)
             const float* At = Atile[buf];
@@ -880,30 +841,20 @@ using namespace qot;
         default: return QOT_ERR_UNSUPPORTED;                     \
     }
 
-#ifdef QOT_DIAG
-static int g_gen_variant = 0;
-extern "C" void qot_debug_gen_variant(int v) { g_gen_variant = v; }
-#endif
-
 // Width-generic form of qot_nnconv_fused (same arguments; w_perm in the per-pass layout documented above).
 int qot_nnconv_gen_launch(const float* x, int ld_x, const float* edge_attr, const float* w1, const float* b1,
                           const int32_t* rowptr, const int32_t* col, const int32_t* edge_ids, const float* invdeg,
                           int transpose, const float* w_perm, const float* bias, float* out, int64_t N, int H, int D,
                           const ActParams& ap, hipStream_t stream) {
-#ifdef QOT_DIAG
-    const int variant = g_gen_variant;
-#else
-    const int variant = 0;
-#endif
     int grid = grid_for(N, 32);
     if (grid > 2 * num_cus()) grid = 2 * num_cus();
     QOT_DISPATCH_GEN_H(H, QOT_DISPATCH_D4(D, {
         if (transpose)
             nnconv_gen_kernel<kH, kD, true><<<grid, 256, 0, stream>>>(x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids,
-                                                                       invdeg, w_perm, bias, out, N, ap, variant);
+                                                                       invdeg, w_perm, bias, out, N, ap);
         else
             nnconv_gen_kernel<kH, kD, false><<<grid, 256, 0, stream>>>(x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids,
-                                                                        invdeg, w_perm, bias, out, N, ap, variant);
+                                                                        invdeg, w_perm, bias, out, N, ap);
     }));
     QOT_LAUNCH_CHECK();
     return QOT_OK;
@@ -949,14 +900,9 @@ extern "C" int qot_nnconv_dw(const float* x, int ld_x, const float* grad_out, in
     const int ns = dw_nslice(H);
     if (!ns) return QOT_ERR_UNSUPPORTED;
     const int nsplit = dw_splits(N, ns);
-#ifdef QOT_DIAG
-    const int variant = g_gen_variant;
-#else
-    const int variant = 0;
-#endif
     QOT_DISPATCH_GEN_H(H, QOT_DISPATCH_D4(D, {
         nnconv_dw_gen_kernel<kH, kD><<<nsplit * ns, 512, 0, stream>>>(x, ld_x, grad_out, ld_g, edge_attr, w1, b1, rowptr,
-                                                                      col, eid, invdeg, workspace, N, nsplit, variant);
+                                                                      col, eid, invdeg, workspace, N, nsplit);
         QOT_LAUNCH_CHECK();
         const int64_t elems = (int64_t)(2 * kD + 2) * kH * kH;
         if (nsplit >= 64)

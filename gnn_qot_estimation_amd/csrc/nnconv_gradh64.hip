@@ -27,8 +27,6 @@ constexpr int kGaLd = 516;    // padded GA row (floats): rows 4 banks apart
 
 constexpr int kGhCap = 256;   // edges of a tile staged in LDS by the grad-h kernel (the rest is read directly)
 
-// VARIANT (diagnostic build only): 0 production; 2 no dot phase; 3 no GA MFMA phase; 5 GA phase with the weight fragments
-// of block 0 reused (no L2 stream)
 // SPLIT: the GA products on the bf16 matrix pipe (split_bf16.hpp): Bs = Wk^T pre-split into three bf16 planes, each
 // [nb][16-deep step][lane], bs_planes u32x4 apart.
 // PRESPLIT (split form only): the g tile goes to LDS as three bf16 planes, each [step][lane] u32x4 -- every value split once
@@ -37,7 +35,7 @@ constexpr int kGhCap = 256;   // edges of a tile staged in LDS by the grad-h ker
 constexpr int kGhPlStep = 66;                // u32x4 per step of a plane: 64 lanes + 32 B, the four steps' stores 8 banks apart
 constexpr int kGhPlLd = 4 * kGhPlStep;       // u32x4 per plane
 
-template <int D, int VARIANT = 0, bool SPLIT = false, bool PRESPLIT = false>
+template <int D, bool SPLIT = false, bool PRESPLIT = false>
 __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
     const float* __restrict__ g, int ldg, const float* __restrict__ x, int ldx, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr,
@@ -220,7 +218,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
                     GAt[row * LDGA + nb * 32 + r31] = c[r];
                 }
             }
-        } else if (VARIANT != 3) {
+        } else {
             float4 af[8];
 #pragma unroll
             for (int gq = 0; gq < 8; ++gq) af[gq] = Gt4[at4_slot(gq, hi, r31)];
@@ -229,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
                 const int nb = wave * NBW + t;
                 if (t + 1 < NBW) {
                     const float4* bp = reinterpret_cast<const float4*>(Bp) +
-                                       (int64_t)((VARIANT == 5) ? wave * NBW : nb + 1) * 8 * 64 + lane;
+                                       (int64_t)(nb + 1) * 8 * 64 + lane;
 #pragma unroll
                     for (int gq = 0; gq < 8; ++gq) bf[(t + 1) & 1][gq] = bp[gq * 64];
                 }
@@ -257,42 +255,40 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
         }
         lds_barrier();
         // 3. per-edge dots: the staged slots of this group ...
-        if (VARIANT != 2) {
 #pragma unroll
-            for (int t = 0; t < EPF; ++t) {
-                if (t < mine) {
-                    const int s = il + 32 * t;
-                    float ee[D];
-#pragma unroll
-                    for (int d = 0; d < D; ++d) ee[d] = sea[s * D + d];
-                    edge(sr[s], xr0[t], xr1[t], ee);
-                }
-            }
-            for (int t = EPF; t < mine; ++t) {
+        for (int t = 0; t < EPF; ++t) {
+            if (t < mine) {
                 const int s = il + 32 * t;
-                const float* xp = x + (int64_t)sj[s] * ldx + c0;
-                const float4 y0 = ld4(xp), y1 = ld4(xp + 4);
                 float ee[D];
 #pragma unroll
                 for (int d = 0; d < D; ++d) ee[d] = sea[s * D + d];
-                edge(sr[s], y0, y1, ee);
+                edge(sr[s], xr0[t], xr1[t], ee);
             }
-            // ... and what the tile has beyond the staged ones (a hub's tile): straight from memory, destination by
-            // bisection of the tile's row pointers
-            for (int s = kGhCap + il; s < nt; s += 32) {
-                const int pp = e_t0 + s;
-                int lo = 0;
+        }
+        for (int t = EPF; t < mine; ++t) {
+            const int s = il + 32 * t;
+            const float* xp = x + (int64_t)sj[s] * ldx + c0;
+            const float4 y0 = ld4(xp), y1 = ld4(xp + 4);
+            float ee[D];
 #pragma unroll
-                for (int st = 16; st > 0; st >>= 1)
-                    if (rp_l[lo + st] <= pp) lo += st;
-                const int64_t e = eidx[pp];
-                const float* xp = x + (int64_t)col[pp] * ldx + c0;
-                const float4 y0 = ld4(xp), y1 = ld4(xp + 4);
-                float ee[D];
+            for (int d = 0; d < D; ++d) ee[d] = sea[s * D + d];
+            edge(sr[s], y0, y1, ee);
+        }
+        // ... and what the tile has beyond the staged ones (a hub's tile): straight from memory, destination by
+        // bisection of the tile's row pointers
+        for (int s = kGhCap + il; s < nt; s += 32) {
+            const int pp = e_t0 + s;
+            int lo = 0;
 #pragma unroll
-                for (int d = 0; d < D; ++d) ee[d] = ea[e * D + d];
-                edge(lo, y0, y1, ee);
-            }
+            for (int st = 16; st > 0; st >>= 1)
+                if (rp_l[lo + st] <= pp) lo += st;
+            const int64_t e = eidx[pp];
+            const float* xp = x + (int64_t)col[pp] * ldx + c0;
+            const float4 y0 = ld4(xp), y1 = ld4(xp + 4);
+            float ee[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) ee[d] = ea[e * D + d];
+            edge(lo, y0, y1, ee);
         }
         lds_barrier();        // GAt / Gt / the staged edges are rewritten by the next tile
     }
@@ -314,28 +310,11 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
 
 using namespace qot;
 
-// launch of nnconv_gradh64_kernel (qot_nnconv_gradh_fused, nnconv_mfma.hip); variant: diagnostic builds only
+// launch of nnconv_gradh64_kernel (qot_nnconv_gradh_fused, nnconv_mfma.hip)
 int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, int ld_x, const float* edge_attr, const float* w1,
                               const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* invdeg,
                               const float* b_perm, const void* b_split, int64_t split_stride, float* workspace, int64_t N, int D,
-                              int grid, int variant, hipStream_t stream) {
-#ifdef QOT_DIAG
-    if (variant >= 1 && variant <= 5 && D == 4) {
-#define QOT_GH_V(V) nnconv_gradh64_kernel<4, V><<<grid, 256, 0, stream>>>(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, \
-                                                                        eid, invdeg, b_perm, workspace, N)
-        switch (variant) {
-            case 1: QOT_GH_V(1); break;
-            case 2: QOT_GH_V(2); break;
-            case 3: QOT_GH_V(3); break;
-            case 4: QOT_GH_V(4); break;
-            default: QOT_GH_V(5); break;
-        }
-#undef QOT_GH_V
-        QOT_LAUNCH_CHECK();
-        return QOT_OK;
-    }
-#endif
-    (void)variant;
+                              int grid, hipStream_t stream) {
     if (b_split) {
         // The g tile is split once per tile on its way to LDS unless QOT_GRADH_SPLIT_AFTER_READ=1 (the earlier loop, same
         // results bit for bit).  Read per call, not cached: callers flip it inside one process.
@@ -344,11 +323,11 @@ int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, i
         QOT_DISPATCH_D(D, {
             if (kD <= 4) {
                 if (presplit)
-                    nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), 0, true, true><<<grid, 256, 0, stream>>>(
+                    nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), true, true><<<grid, 256, 0, stream>>>(
                         grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
                         static_cast<const u32x4*>(b_split), split_stride / 8);
                 else
-                    nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), 0, true><<<grid, 256, 0, stream>>>(
+                    nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), true><<<grid, 256, 0, stream>>>(
                         grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
                         static_cast<const u32x4*>(b_split), split_stride / 8);
             }

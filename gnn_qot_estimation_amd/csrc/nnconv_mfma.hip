@@ -36,9 +36,7 @@ namespace qot {
 // h = relu(W1 ea + b1) once; the per-edge loop then only broadcasts (8-lane shuffles) and
 // streams the 256-B source rows, four edges in flight per group.
 // Returns the destination's own row (root block) in registers; blocks 0..K go to LDS.
-// GV (diagnostic build only): 6 every gathered row read from one of two hot addresses; 7 arithmetic ids instead of the
-// index chain; 8 one of the K weighted sums only
-template <int D, bool TRANSPOSE, int GV = 0>
+template <int D, bool TRANSPOSE>
 __device__ __forceinline__ void nnconv_gather_tile(
     float* __restrict__ At, const float* __restrict__ x, int ldx, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr,
@@ -78,24 +76,21 @@ __device__ __forceinline__ void nnconv_gather_tile(
             sc[0] = group8_bcast<U0 + 0>(mysc); sc[1] = group8_bcast<U0 + 1>(mysc);                     \
             sc[2] = group8_bcast<U0 + 2>(mysc); sc[3] = group8_bcast<U0 + 3>(mysc);                     \
             _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                             \
-                const float* xr = x + (int64_t)(GV == 6 ? (jj[u] & 1) : jj[u]) * ldx + c0;              \
+                const float* xr = x + (int64_t)jj[u] * ldx + c0;                                        \
                 xa[u] = ld4(xr);                                                                        \
                 xb[u] = ld4(xr + 4);                                                                    \
             }                                                                                           \
-            _Pragma("unroll") for (int kk = 0; kk < (GV == 8 ? 1 : K); ++kk) {                          \
+            _Pragma("unroll") for (int kk = 0; kk < K; ++kk) {                                          \
                 const float h0 = group8_bcast<U0 + 0>(myh[kk]), h1 = group8_bcast<U0 + 1>(myh[kk]);     \
                 acc0[kk] = QOT_ACC(FIRST, h0, xa[0], acc0[kk]); acc1[kk] = QOT_ACC(FIRST, h0, xb[0], acc1[kk]); \
                 acc0[kk] = fma4(h1, xa[1], acc0[kk]); acc1[kk] = fma4(h1, xb[1], acc1[kk]);             \
-            }                                                                                           \
-            if (GV == 8 && (FIRST)) {                                                                   \
-                _Pragma("unroll") for (int kk = 1; kk < K; ++kk) { acc0[kk] = f4zero(); acc1[kk] = f4zero(); } \
             }                                                                                           \
             acc0[K] = QOT_ACC(FIRST, sc[0], xa[0], acc0[K]); acc1[K] = QOT_ACC(FIRST, sc[0], xb[0], acc1[K]); \
             acc0[K] = fma4(sc[1], xa[1], acc0[K]); acc1[K] = fma4(sc[1], xb[1], acc1[K]);               \
             /* four rows stay in flight, the vector work is skipped in pairs (a wave runs as many slots */ \
             /* as its highest-degree row needs, and VALU time is MFMA time on this part)                */ \
             if (cnt > U0 + 2) {                                                                         \
-                _Pragma("unroll") for (int kk = 0; kk < (GV == 8 ? 1 : K); ++kk) {                      \
+                _Pragma("unroll") for (int kk = 0; kk < K; ++kk) {                                      \
                     const float h2 = group8_bcast<U0 + 2>(myh[kk]), h3 = group8_bcast<U0 + 3>(myh[kk]); \
                     acc0[kk] = fma4(h2, xa[2], acc0[kk]); acc1[kk] = fma4(h2, xb[2], acc1[kk]);         \
                     acc0[kk] = fma4(h3, xa[3], acc0[kk]); acc1[kk] = fma4(h3, xb[3], acc1[kk]);         \
@@ -113,8 +108,8 @@ __device__ __forceinline__ void nnconv_gather_tile(
         float myh[K], mysc = 0.f;                                                                       \
         _Pragma("unroll") for (int kk = 0; kk < K; ++kk) myh[kk] = 0.f;                                 \
         if (p < end) {                                                                                  \
-            myj = (GV == 7) ? (int)(i ^ (p & 31)) : col[p];                                             \
-            const int64_t e = (GV == 7) ? (int64_t)p : (int64_t)eidx[p];                                \
+            myj = col[p];                                                                               \
+            const int64_t e = (int64_t)eidx[p];                                                         \
             float ee[D];                                                                                \
             _Pragma("unroll") for (int d = 0; d < D; ++d) ee[d] = ea[e * D + d];                        \
             mysc = TRANSPOSE ? invdeg[myj] : srow;                                                      \
@@ -143,31 +138,16 @@ __device__ __forceinline__ void nnconv_gather_tile(
     }
 }
 
-#ifdef QOT_DIAG
-#define QOT_DIAG_SECTION 1
-#include "diag/nnconv_mfma_diag.inc"
-#undef QOT_DIAG_SECTION
-#endif
-
-// in-kernel cycle stamps: diagnostic build only (make DIAG=1); nothing in the release build
-#ifdef QOT_DIAG
-#define QOT_DIAG_SECTION 2
-#include "diag/nnconv_mfma_diag.inc"
-#undef QOT_DIAG_SECTION
-#else
-#define QOT_STAMP(slot)
-#endif
-
 // SPLIT (forward only): the products on the bf16 matrix pipe (split_bf16.hpp).  Ws: Wcat pre-split into three bf16
 // planes ws_planes u32x4 apart (qot_nnconv_fused_split); the A fragments are split after their ds_read_b128, i.e. by both column-half waves.
-template <int D, bool TRANSPOSE, int VARIANT = 0, bool SPLIT = false>
+template <int D, bool TRANSPOSE, bool SPLIT = false>
 __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     const float* __restrict__ x, int ldx, const float* __restrict__ ea, const float* __restrict__ w1,
     const float* __restrict__ b1, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const int32_t* __restrict__ eidx, const float* __restrict__ invdeg, const float* __restrict__ Wp,
     const float* __restrict__ bias, float* __restrict__ out, int64_t N, ActParams act,
     const u32x4* __restrict__ Ws = nullptr, int64_t ws_planes = 0) {
-    static_assert(!SPLIT || (!TRANSPOSE && VARIANT == 0), "split form: production forward only");
+    static_assert(!SPLIT || !TRANSPOSE, "split form: forward only");
     constexpr int K = 2 * D;
     constexpr int KM = (K + 1) * 64;        // inner dimension held in LDS (blocks 0..K)
     constexpr int GM = KM / 16;             // float4 B groups per wave for the main part
@@ -185,20 +165,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     if (tile < 0) break;
     const int64_t tile0 = tile * 32;
     float4 root0, root1;
-    unsigned long long t_prev = 0;
-    if (VARIANT == 3 || VARIANT == 9) t_prev = __builtin_amdgcn_s_memtime();
-
-#ifdef QOT_DIAG
-    if (VARIANT == 11) {
-        nnconv_gather_tile_rank1_shape<D>(At, x, ldx, rowptr, col, tile0, N, root0, root1);
-    } else
-#endif
-    if (VARIANT != 1 && VARIANT != 4 && VARIANT != 5 && VARIANT != 9) {
-        nnconv_gather_tile<D, TRANSPOSE, (VARIANT >= 6 && VARIANT <= 8) ? VARIANT : 0>(At, x, ldx, ea, w1, b1, rowptr, col, eidx, invdeg, tile0, N, root0, root1);
-    } else {
-        for (int t = threadIdx.x; t < KM * 32; t += 256) At[t] = 1.0f + (float)(t & 7);
-        root0 = root1 = make_float4(1.f, 1.f, 1.f, 1.f);
-    }
+    nnconv_gather_tile<D, TRANSPOSE>(At, x, ldx, ea, w1, b1, rowptr, col, eidx, invdeg, tile0, N, root0, root1);
     const float4* At4 = reinterpret_cast<const float4*>(At);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nh = wave & 1, kh = wave >> 1;
@@ -285,15 +252,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     for (int q = 0; q < NB - 1; ++q)
 #pragma unroll
         for (int u = 0; u < CH; ++u) bb[q][u] = wp[(q * CH + u) * 64];
-    QOT_STAMP(0)
     lds_barrier();
-    QOT_STAMP(1)
-    if (VARIANT == 2) {   // ablation: gather only
-        if (threadIdx.x < 32 && tile0 + threadIdx.x < N) out[(tile0 + threadIdx.x) * 64] = At[threadIdx.x * 33] + root0.x + rb[0].x + bb[0][0].x;
-        __syncthreads();
-        continue;
-    }
-
     int ch = 0;
     // (r04, measured: the A fragment of group L + 1 read from LDS before the four MFMAs of group L instead of right in front
     //  of its use -- `ds_read_b128; s_waitcnt lgkmcnt(0)` before every group as it stands -- 96.0 -> 96.9 us: no gain, not kept)
@@ -301,22 +260,12 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     for (; ch + NB <= NCH; ch += NB) {
 #pragma unroll
         for (int q = 0; q < NB; ++q) {
-            if (ch + q + NB - 1 < NCH && VARIANT != 4 && VARIANT != 5 && VARIANT != 9) {       // 4 / 5: weight fragments not streamed
+            if (ch + q + NB - 1 < NCH) {
 #pragma unroll
                 for (int u = 0; u < CH; ++u) bb[(q + NB - 1) % NB][u] = wp[((ch + q + NB - 1) * CH + u) * 64];
             }
 #pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                if (VARIANT == 5 || VARIANT == 9) {                            // 5 / 9: operand tile not read either
-                    const float4 a = rb[u & 3], b = bb[q][u];
-                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, c, 0, 0, 0);
-                } else {
-                    c = mfma_group(At4, kh * GM + (ch + q) * CH + u, hi, r31, bb[q][u], c);
-                }
-            }
+            for (int u = 0; u < CH; ++u) c = mfma_group(At4, kh * GM + (ch + q) * CH + u, hi, r31, bb[q][u], c);
         }
     }
     // tail: chunks ch .. NCH-1 are already in buffers 0 .. (their loads were issued above)
@@ -327,9 +276,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
             for (int u = 0; u < CH; ++u) c = mfma_group(At4, kh * GM + (ch + q) * CH + u, hi, r31, bb[q][u], c);
         }
     }
-    QOT_STAMP(2)
     lds_barrier();                         // everyone is done with blocks 0..K
-    QOT_STAMP(3)
     {   // root block (x_i itself) reuses block 0's slots
         float4* At4 = reinterpret_cast<float4*>(At);
         const int sub = threadIdx.x & 7, il = threadIdx.x >> 3;
@@ -340,7 +287,6 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
 #pragma unroll
     for (int u = 0; u < 4; ++u) c = mfma_group(At4, kh * 4 + u, hi, r31, rb[u], c);
     }
-    QOT_STAMP(4)
     // K halves meet through LDS; every wave finishes 8 of the 16 accumulator registers of its
     // (column half), so the stores are spread over all four waves
     float* red = At + 64 * 32;             // disjoint from block 0, which other waves may still read
@@ -406,9 +352,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
             if (i < N) out[i * 64 + colg] = y;
         }
     }
-    QOT_STAMP(5)
     lds_barrier();                         // `red` is consumed before the next tile's gather overwrites it
-    QOT_STAMP(6)
     }
 }
 
@@ -424,12 +368,10 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
 // 32x32 accumulator tiles of gWcat^T across the persistent loop (80 VGPRs), partials go to one slab
 // per workgroup and are summed in a fixed order afterwards (bitwise reproducible).
 
-// VARIANT (diagnostic build only): 0 production; 1 every gathered row read from ONE hot address (no row-load latency);
-// 2 no grad_x loop; 3 no weight-gradient loop; 4 no gather; 5 neither MFMA loop (gather + exchange only)
-// SPLIT: the weight-gradient product as split-bf16 MFMAs (the production form; VARIANT builds keep the fp32 loop).  The
+// SPLIT: the weight-gradient product as split-bf16 MFMAs (the production form).  The
 // grad_x product is the fp32 loop either way: its B operand would be bf16 planes of WcatT, which this entry point
 // does not receive.
-template <int D, int VARIANT = 0, bool SPLIT = false>
+template <int D, bool SPLIT>
 __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
     const float* __restrict__ g, int ldg, const float* __restrict__ xf, int ldx, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr_t,
@@ -475,11 +417,6 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
     // (r04, measured and not kept, tools/ab_adjoint.py, interleaved rounds in one process: static `s_setprio 1` for waves 4-7
     // -- 172.7 us either way; the half index folded into the tile's XOR swizzle, i ^ ((g + 4 hi) & 7), which makes the
     // transposed reads of the X^T U loop conflict-free -- 171.9 us either way: that loop does not wait for LDS bandwidth)
-#ifdef QOT_ADJ_SETPRIO
-    // static priority for the second-dispatched half of the workgroup (waves 4-7 share their SIMDs with waves 0-3 and lose
-    // the age-based arbitration on every phase): MI355X_MICROARCH.md, "Two waves per SIMD", item 4
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
 
 #pragma unroll 1
     for (int64_t it = 0;; ++it) {
@@ -494,7 +431,7 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
             xown = (j < N) ? ld4(xf + j * ldx + 4 * (threadIdx.x & 15)) : f4zero();
         }
         // ---- gather: 16 lanes per source node j (float4 = 64 channels), out-edges over the CSC
-        if (VARIANT != 4) {
+        {
             const int sub = threadIdx.x & 15, il = threadIdx.x >> 4;
             const int c0 = 4 * sub;
             const int64_t j = tile0 + il;
@@ -509,18 +446,15 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
             // out-edges); its first slot writes the accumulators.
 #define QOT_ADJ_EDGE(U)                                                                                  \
                 {                                                                                        \
-                    const int64_t i = (VARIANT == 1) ? (int64_t)(row16_bcast<U>(myi) & 1) : (int64_t)row16_bcast<U>(myi); \
+                    const int64_t i = (int64_t)row16_bcast<U>(myi);                                      \
                     gr[(U) & 3] = ld4(g + i * ldg + c0);                                                 \
                     sc[(U) & 3] = row16_bcast<U>(mysc);                                                  \
                 }
 #define QOT_ADJ_FMA(U, FIRSTSLOT)                                                                        \
                 {                                                                                        \
-                    _Pragma("unroll") for (int kk = 0; kk < (VARIANT == 6 ? 1 : K); ++kk)                \
+                    _Pragma("unroll") for (int kk = 0; kk < K; ++kk)                                     \
                         acc[kk] = (FIRSTSLOT) ? scale4(row16_bcast<U>(myh[kk]), gr[(U) & 3])             \
                                               : fma4(row16_bcast<U>(myh[kk]), gr[(U) & 3], acc[kk]);     \
-                    if (VARIANT == 6 && (FIRSTSLOT)) {                                                   \
-                        _Pragma("unroll") for (int kk = 1; kk < K; ++kk) acc[kk] = f4zero();             \
-                    }                                                                                    \
                     acc[K] = (FIRSTSLOT) ? scale4(sc[(U) & 3], gr[(U) & 3]) : fma4(sc[(U) & 3], gr[(U) & 3], acc[K]); \
                 }
 #define QOT_ADJ_EDGE4(U0, FIRST)                                                                         \
@@ -540,11 +474,11 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
                 float myh[K], mysc = 0.f;                                                                \
                 _Pragma("unroll") for (int kk = 0; kk < K; ++kk) myh[kk] = 0.f;                          \
                 if (p < end) {                                                                           \
-                    myi = (VARIANT == 7) ? (int)(j ^ (p & 31)) : col_t[p];      /* 7: arithmetic ids */  \
-                    const int64_t e = (VARIANT == 7) ? (int64_t)p : (int64_t)eid_t[p];                   \
+                    myi = col_t[p];                                                                      \
+                    const int64_t e = (int64_t)eid_t[p];                                                 \
                     float ee[D];                                                                         \
                     _Pragma("unroll") for (int d = 0; d < D; ++d) ee[d] = ea[e * D + d];                 \
-                    mysc = (VARIANT == 7) ? 0.25f : invdeg[myi];                                         \
+                    mysc = invdeg[myi];                                                                  \
                     _Pragma("unroll") for (int kk = 0; kk < K; ++kk) {                                   \
                         float h = b1[kk];                                                                \
                         _Pragma("unroll") for (int d = 0; d < D; ++d) h = fmaf(w1[kk * D + d], ee[d], h); \
@@ -594,7 +528,7 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
         f32x16 c;
 #pragma unroll
         for (int r = 0; r < 16; ++r) c[r] = 0.f;
-        if (VARIANT != 2 && VARIANT != 5) {
+        {
             int ch = 0;
 #pragma unroll 1
             for (; ch + 1 < NCH; ch += 2) {
@@ -655,7 +589,7 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-        } else if (VARIANT != 3 && VARIANT != 5) {
+        } else {
             float abuf[2][TPW], xbuf[2];
             const float* xsl = xs + hi * 64 + ah * 32 + r31;          // row 2s + hi -> + 128 s
 #pragma unroll
@@ -777,22 +711,6 @@ int qot_nnconv_gradh_gen_launch(const float* grad_out, int ld_g, const float* x,
                                 const int32_t* eid, const float* invdeg, const float* b_perm, float* gw1, float* gb1,
                                 float* workspace, int64_t N, int H, int D, hipStream_t stream);
 
-#ifdef QOT_DIAG
-extern "C" int qot_nnconv_fused_ws(const float* x, int ld_x, const float* edge_attr, const float* w1,
-                                   const float* b1, const int32_t* rowptr, const int32_t* col,
-                                   const int32_t* edge_ids, const float* invdeg, int transpose,
-                                   const float* w_perm, const float* bias, float* out, int64_t N, int H, int D,
-                                   int act, float act_slope, float act_p, uint64_t act_seed,
-                                   const int64_t* act_step, qot_stream_t stream);
-
-static int g_variant = 0;   // ablation switch for tools/ablate_nnconv.py (0 = production)
-extern "C" void qot_debug_set_variant(int v) { g_variant = v; }
-extern "C" void qot_debug_stamps(unsigned long long* host8, int reset) {
-    if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(qot::g_stamps), z, sizeof(z)); }
-    else (void)hipMemcpyFromSymbol(host8, HIP_SYMBOL(qot::g_stamps), 8 * sizeof(unsigned long long));
-}
-#endif
-
 // Wp layout (built by the caller, see functional.nnconv_perm_index): with GT = (K+2)*64/8 groups
 // of 4 k-steps, for column half nh, group g, lane l, r in 0..3:
 //   Wp[((nh*GT + g)*64 + l)*4 + r] = Wcat[8*g + 2*r + (l>>5)][nh*32 + (l&31)]
@@ -814,75 +732,9 @@ extern "C" int qot_nnconv_fused(const float* x, int ld_x, const float* edge_attr
                                      bias, out, N, H, D, make_act(act, act_slope, act_p, act_seed, act_step),
                                      (hipStream_t)stream);
     }
-#ifdef QOT_DIAG
-    static int use_ws = -1;
-    if (use_ws < 0) { const char* e = getenv("QOT_NNCONV_WS"); use_ws = (e && e[0] == '1') ? 1 : 0; }
-    if (use_ws && D <= 4 && !g_variant)
-        return qot_nnconv_fused_ws(x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, transpose, w_perm, bias,
-                                   out, N, H, D, act, act_slope, act_p, act_seed, act_step, stream);
-#endif
     int grid = grid_for(N, 32);
     if (grid > 2 * num_cus()) grid = 2 * num_cus();
     const ActParams ap = make_act(act, act_slope, act_p, act_seed, act_step);
-#ifdef QOT_DIAG
-    if (g_variant >= 100 && g_variant < 110 && D == 4 && !transpose) {      // 100 + v: variant v with ONE workgroup per CU
-        const int v = g_variant - 100, g1 = grid > num_cus() ? num_cus() : grid;
-        if (v == 0)
-            nnconv_mfma64_kernel<4, false, 0><<<g1, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (v == 1)
-            nnconv_mfma64_kernel<4, false, 1><<<g1, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (v == 4)
-            nnconv_mfma64_kernel<4, false, 4><<<g1, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (v == 5)
-            nnconv_mfma64_kernel<4, false, 5><<<g1, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (v == 9)
-            nnconv_mfma64_kernel<4, false, 9><<<g1, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else
-            nnconv_mfma64_kernel<4, false, 2><<<g1, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        QOT_LAUNCH_CHECK();
-        return QOT_OK;
-    }
-    if (g_variant && g_variant <= 10 && D == 4 && !transpose) {
-        if (g_variant == 3)
-            nnconv_mfma64_kernel<4, false, 3><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (g_variant == 1)
-            nnconv_mfma64_kernel<4, false, 1><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (g_variant == 4)
-            nnconv_mfma64_kernel<4, false, 4><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (g_variant == 5)
-            nnconv_mfma64_kernel<4, false, 5><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (g_variant == 6)
-            nnconv_mfma64_kernel<4, false, 6><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (g_variant == 7)
-            nnconv_mfma64_kernel<4, false, 7><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (g_variant == 8)
-            nnconv_mfma64_kernel<4, false, 8><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (g_variant == 9)
-            nnconv_mfma64_kernel<4, false, 9><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else if (g_variant == 10)
-            nnconv_mfma64_kernel<4, false, 11><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        else
-            nnconv_mfma64_kernel<4, false, 2><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, w_perm, bias, out, N, ap);
-        QOT_LAUNCH_CHECK();
-        return QOT_OK;
-    }
-#endif
     QOT_DISPATCH_D(D, {
         if (transpose)
             nnconv_mfma64_kernel<kD, true><<<grid, 256, 0, (hipStream_t)stream>>>(
@@ -914,7 +766,7 @@ extern "C" int qot_nnconv_fused_split(const float* x, int ld_x, const float* edg
     const ActParams ap = make_act(act, act_slope, act_p, act_seed, act_step);
     QOT_DISPATCH_D(D, {
         if (kD <= 4)
-            nnconv_mfma64_kernel<(kD <= 4 ? kD : 4), false, 0, true><<<grid, 256, 0, (hipStream_t)stream>>>(
+            nnconv_mfma64_kernel<(kD <= 4 ? kD : 4), false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
                 x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, nullptr, bias, out, N, ap,
                 static_cast<const u32x4*>(w_split), split_stride / 8);
     });
@@ -928,7 +780,7 @@ extern "C" int qot_nnconv_fused_split(const float* x, int ld_x, const float* edg
 int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, int ld_x, const float* edge_attr, const float* w1,
                               const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* invdeg,
                               const float* b_perm, const void* b_split, int64_t split_stride, float* workspace, int64_t N, int D,
-                              int grid, int variant, hipStream_t stream);
+                              int grid, hipStream_t stream);
 extern "C" size_t qot_nnconv_gradh_workspace_floats(int D) {
     return (size_t)2 * 256 * 2 * (size_t)(2 * D * (D + 1));
 }
@@ -947,26 +799,15 @@ static int nnconv_gradh_impl(const float* grad_out, int ld_g, const float* x, in
         return QOT_ERR_BADARG;
     if (b_split && H != 64) return QOT_ERR_UNSUPPORTED;
     if (!gw1 && H != 64) return QOT_ERR_UNSUPPORTED;
-#ifdef QOT_DIAG
-    if (H == 64 && g_variant == 9)       // A/B: the generic kernel at H = 64 (b_perm in ITS layout)
-        return qot_nnconv_gradh_gen_launch(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm,
-                                           gw1, gb1, workspace, N, H, D, stream);
-#endif
     if (H != 64)     // other widths: GA built 32 input channels at a time (nnconv_gen.hip)
         return qot_nnconv_gradh_gen_launch(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm,
                                            gw1, gb1, workspace, N, H, D, stream);
     int grid = grid_for(N > 0 ? N : 1, 32);
     if (grid > 2 * num_cus()) grid = 2 * num_cus();
     const int K = 2 * D;
-    int variant = 0;
-#ifdef QOT_DIAG
-    if (g_variant >= 31 && g_variant <= 35 && D == 4) variant = g_variant - 30;
-#endif
-    {
-        const int rc = qot_nnconv_gradh64_launch(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm,
-                                                 b_split, split_stride, workspace, N, D, grid, variant, stream);
-        if (rc != QOT_OK) return rc;
-    }
+    const int rc = qot_nnconv_gradh64_launch(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm,
+                                             b_split, split_stride, workspace, N, D, grid, stream);
+    if (rc != QOT_OK) return rc;
     QOT_LAUNCH_CHECK();
     if (!gw1) return QOT_OK;          // partials left in the workspace for qot_nnconv_bwd_finalize
     const int n = K * (D + 1);
@@ -1030,24 +871,6 @@ extern "C" int qot_nnconv_adjoint_dw(const float* grad_out, int ld_g, const floa
     int grid = grid_for(N, 32);
     const int cap = num_cus() * kAdjBlocksPerCu;
     if (grid > cap) grid = cap;
-#ifdef QOT_DIAG
-    if (g_variant >= 11 && g_variant <= 17 && D == 4) {
-#define QOT_ADJ_V(V) nnconv_adjoint_dw64_kernel<4, V><<<grid, 512, 0, stream>>>(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, \
-            rowptr_t, col_t, eid_t, invdeg, w_perm, grad_x, workspace, N)
-        switch (g_variant) {
-            case 11: QOT_ADJ_V(1); break;
-            case 12: QOT_ADJ_V(2); break;
-            case 13: QOT_ADJ_V(3); break;
-            case 14: QOT_ADJ_V(4); break;
-            case 16: QOT_ADJ_V(6); break;
-            case 17: QOT_ADJ_V(7); break;
-            default: QOT_ADJ_V(5); break;
-        }
-#undef QOT_ADJ_V
-        QOT_LAUNCH_CHECK();
-        return QOT_OK;
-    }
-#endif
     // The weight-gradient product runs as split-bf16 MFMAs unless QOT_NNCONV_F32_MFMA=1 (the switch
     // functional.nnconv_split_bf16 reads).  Read per call, not cached: callers flip it inside one process.
     const char* f32_env = getenv("QOT_NNCONV_F32_MFMA");
@@ -1056,11 +879,11 @@ extern "C" int qot_nnconv_adjoint_dw(const float* grad_out, int ld_g, const floa
         if (kD <= 4) {
             constexpr int kD4 = kD <= 4 ? kD : 4;
             if (f32_mfma)
-                nnconv_adjoint_dw64_kernel<kD4, 0, false><<<grid, 512, 0, stream>>>(
+                nnconv_adjoint_dw64_kernel<kD4, false><<<grid, 512, 0, stream>>>(
                     grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr_t, col_t, eid_t, invdeg, w_perm, grad_x,
                     workspace, N);
             else
-                nnconv_adjoint_dw64_kernel<kD4, 0, true><<<grid, 512, 0, stream>>>(
+                nnconv_adjoint_dw64_kernel<kD4, true><<<grid, 512, 0, stream>>>(
                     grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr_t, col_t, eid_t, invdeg, w_perm, grad_x,
                     workspace, N);
         }

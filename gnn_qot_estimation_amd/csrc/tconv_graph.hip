@@ -22,40 +22,10 @@
 
 namespace qot {
 
-// in-kernel cycle stamps: diagnostic build only (make DIAG=1; tools/bench_tconv_graph.py); nothing in the release build
-#ifdef QOT_DIAG
-__device__ int g_tg_variant;           // ablation bits (tools/bench_tconv_graph.py): 1 no edge dots / ge, 2 no source pass, 4 no 1c,
-#define TG_VAR(bit) (tg_var & (bit))   //   8 no activation backward in the commit
-__device__ unsigned long long g_tg_stamps[16];
-#else
-#define TG_VAR(bit) 0
-#endif
-#if defined(QOT_DIAG) && defined(QOT_TG_STAMPS)      // (the stamps cost a third of the kernels' time: a build of their own)
-// (sums kept in registers of thread 0, one atomic per slot at the end)
-#define TG_STAMP_DECL                                                                        \
-    unsigned long long tg_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};                     \
-    unsigned long long tg_t0 = __builtin_amdgcn_s_memtime();
-#define TG_STAMP(slot)                                                                      \
-    {                                                                                       \
-        const unsigned long long tg_t1 = __builtin_amdgcn_s_memtime();                      \
-        tg_acc[slot] += tg_t1 - tg_t0;                                                      \
-        tg_t0 = tg_t1;                                                                      \
-    }
-#define TG_STAMP_FLUSH                                                                      \
-    if (threadIdx.x == 0) {                                                                 \
-        _Pragma("unroll") for (int q = 0; q < 12; ++q)                                      \
-            if (tg_acc[q]) atomicAdd(&g_tg_stamps[q], tg_acc[q]);                           \
-    }
-#else
-#define TG_STAMP_DECL
-#define TG_STAMP(slot)
-#define TG_STAMP_FLUSH
-#endif
-
 // ------------------------------------------------------------------------------------------------ forward
 // Every phase that touches global memory is ONE batch of independent loads: under the burst of 256 workgroups starting
 // together a dependent global round trip costs 0.7-1 us, so the count of SERIALISED trips -- not bytes -- sets the time
-// (first version: ~10 trips, 19.5 us; measured with the diagnostic build's stamps, tools/bench_tconv_graph.py).
+// (first version: ~10 trips, 19.5 us; measured with in-kernel cycle stamps, since removed).
 struct TgFwdLds {
     int tv, ts, slot0, slot_floats, rp, col, al, ea, aa;   // float offsets (rp .. aa: inside a slot)
     size_t bytes(int ns) const { return (size_t)(slot0 + ns * slot_floats) * 4; }
@@ -100,11 +70,6 @@ __global__ __launch_bounds__(1024) void tconv_fwd_graph_kernel(
     float* sAl = sb + L.al;
     float* sEa = sb + L.ea;
     float* sAa = sb + L.aa;
-#ifdef QOT_DIAG
-    const int tg_var = g_tg_variant;       // forward ablation bits: 16 no stage C, 32 no stage B, 64 no edge staging (A),
-#endif                                     // 128 no output stores, 256 no activation, 512 no table staging
-
-    TG_STAMP_DECL
     const int sub = t % TPR, grp = t / TPR, c0 = CPL * sub;
     // ---- trip 1: the first graph's row pointers, the tables (one batch of loads), the per-thread constants
     const int64_t bfirst = (int64_t)blockIdx.x * NS + slot;
@@ -113,7 +78,7 @@ __global__ __launch_bounds__(1024) void tconv_fwd_graph_kernel(
     {
         const int nT4 = n * H / 4, total = 2 * nT4;
         constexpr int TB = 4;
-        for (int base = threadIdx.x; base < (TG_VAR(512) ? 0 : total); base += TB * (int)blockDim.x) {
+        for (int base = threadIdx.x; base < total; base += TB * (int)blockDim.x) {
             float4 v[TB];
 #pragma unroll
             for (int u = 0; u < TB; ++u) {
@@ -148,7 +113,6 @@ __global__ __launch_bounds__(1024) void tconv_fwd_graph_kernel(
             if (live && t <= n) sRp[t] = rowptr[node0 + t];
         }
         __syncthreads();
-        TG_STAMP(0)
         int e0 = 0, eb = 0;
         if (live) {
             e0 = sRp[0];
@@ -156,7 +120,7 @@ __global__ __launch_bounds__(1024) void tconv_fwd_graph_kernel(
             eb = eb < 0 ? 0 : (eb > max_e ? max_e : eb);       // (the index build has checked the slices; memory safety)
         }
         // ---- A: trip 2 = index slice, trip 3 = edge features; the logits are formed here (one thread per edge)
-        for (int pc = 0; pc < (TG_VAR(64) ? 0 : eb); pc += 256 * EB) {
+        for (int pc = 0; pc < eb; pc += 256 * EB) {
             int cj[EB], rw[EB];
             int64_t ei[EB];
 #pragma unroll
@@ -203,9 +167,8 @@ __global__ __launch_bounds__(1024) void tconv_fwd_graph_kernel(
             }
         }
         __syncthreads();
-        TG_STAMP(1)
         // ---- B: edge softmax, two lanes per destination (a quad per destination -- two rounds of 64 -- measured slower)
-        if (live && !TG_VAR(32)) {
+        if (live) {
             const int l = t & 1;
             for (int r = t >> 1; r < n; r += 128) {
                 int beg = sRp[r] - e0, end = sRp[r + 1] - e0;
@@ -235,9 +198,8 @@ __global__ __launch_bounds__(1024) void tconv_fwd_graph_kernel(
             }
         }
         __syncthreads();
-        TG_STAMP(2)
         // ---- C: aggregate, root term, activation
-        if (live && !TG_VAR(16)) {
+        if (live) {
             for (int r = grp; r < n; r += G) {
                 int beg = sRp[r] - e0, end = sRp[r + 1] - e0;
                 beg = beg < 0 ? 0 : (beg > eb ? eb : beg);
@@ -279,18 +241,15 @@ __global__ __launch_bounds__(1024) void tconv_fwd_graph_kernel(
                     for (int d = 0; d < D; ++d)
 #pragma unroll
                         for (int c = 0; c < 4; ++c) oc[c] = fmaf(wl[4 * v + c][d], ad[d], oc[c]);
-                    const float4 o4 = TG_VAR(256) ? make_float4(oc[0] + sk.x, oc[1] + sk.y, oc[2] + sk.z, oc[3] + sk.w)
-                                                  : act_apply4s(make_float4(oc[0] + sk.x, oc[1] + sk.y, oc[2] + sk.z, oc[3] + sk.w),
-                                                                act, stepv, (uint64_t)(i * H + c0 + 4 * v) >> 2);
-                    if (!TG_VAR(128) || o4.x == 12345.678f) st4(out + i * H + c0 + 4 * v, o4);
+                    const float4 o4 = act_apply4s(make_float4(oc[0] + sk.x, oc[1] + sk.y, oc[2] + sk.z, oc[3] + sk.w),
+                                                  act, stepv, (uint64_t)(i * H + c0 + 4 * v) >> 2);
+                    st4(out + i * H + c0 + 4 * v, o4);
                 }
             }
             for (int p = t; p < eb; p += 256) alpha[e0 + p] = sAl[p];
             for (int k2 = t; k2 < n * D; k2 += 256) aa_out[node0 * D + k2] = sAa[k2];
         }
-        TG_STAMP(3)
     }
-    TG_STAMP_FLUSH
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -369,11 +328,6 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
     const int tid = threadIdx.x;
     const int sub = tid % TPR, grp = tid / TPR, c0 = 4 * sub;
     const int nG4 = n * H / 4;
-#ifdef QOT_DIAG
-    const int tg_var = g_tg_variant;
-#endif
-
-    TG_STAMP_DECL
     // ---- the prefetch registers of ONE graph
     int pf_col = 0, pf_row = 0, pf_colt = 0, pf_post = 0, pf_rp = 0, pf_rpt = 0;
     float pf_al = 0.f, pf_aa = 0.f, pf_ea[D];
@@ -445,7 +399,6 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
         eb = eb < 0 ? 0 : (eb > max_e ? max_e : eb);
         const int64_t node0 = pf_node0;
         __syncthreads();                  // tables / the previous graph's pass 1c is done with the tiles
-        TG_STAMP(4)
         // ---- commit the prefetched graph to LDS
         if (tid < eb) {
             const int j = pf_col, it = pf_colt - (int)node0, rr = pf_row - (int)node0, ps = pf_post - e0;
@@ -484,7 +437,7 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
             const int f = tid + NT * k;
             if (f < nG4) {
                 float4 gi = pf_g[k];
-                if (y_act && !TG_VAR(8)) {
+                if (y_act) {
                     const int64_t flat = node0 * H + 4 * (int64_t)f;
                     const float4 yy = pf_y[k];
                     uint64_t z = 0;
@@ -504,7 +457,6 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
             }
         }
         __syncthreads();
-        TG_STAMP(5)
         // ---- request the next graph (and the range of the one after it): in flight under this graph's passes
         {
             const int64_t bn = b + gridDim.x;
@@ -516,7 +468,7 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
             }
         }
         // ---- 1a: da_e = <g_i, T_v[j]>, one thread per edge
-        for (int p = tid; p < (TG_VAR(1) ? 0 : eb); p += NT) {
+        for (int p = tid; p < eb; p += NT) {
             const float* gr = sG + sRow[p] * HP;
             const float* vr = sTv + sCol[p] * HP;
             float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
@@ -529,7 +481,7 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
             sDa[p] = (d0 + d1) + (d2 + d3);
         }
         // ge[i][d] = <g_i, We[:, d]>, one thread per (node, d)
-        for (int q = tid; q < (TG_VAR(1) ? 0 : n * D); q += NT) {
+        for (int q = tid; q < n * D; q += NT) {
             const int i = q / D, d = q % D;
             const float* gr = sG + i * HP;
             const float* wr = sWeT + d * H;
@@ -542,12 +494,11 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
             }
             sGe[q] = (d0 + d1) + (d2 + d3);
         }
-        TG_STAMP(6)
         // ---- 2: source pass; gWe (value path) += g_j (x) (sum alpha ea)_j for the same rows (registers, four channels per lane)
 #pragma unroll
         for (int k = 0; k < MAXR; ++k) {
             const int j = grp + NG * k;
-            if (j < n && !TG_VAR(2)) {
+            if (j < n) {
                 const int beg = sRpT[j], end = sRpT[j + 1];
                 const float4 gj = *reinterpret_cast<const float4*>(sG + j * HP + c0);
                 float ad[D];
@@ -572,12 +523,11 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
             }
         }
         __syncthreads();
-        TG_STAMP(7)
         // ---- 1c: per destination, a QUAD of lanes (edges dealt over the four lanes, sums met by DPP): delta, ds -> gM, gP.
         // gM[r][j] += ds_e by LDS float atomics: row r belongs to this quad alone, a quad's adds of one instruction
         // to one address (duplicate edges) are applied by the LDS in lane order, its instructions in program order --
         // the sum has a fixed order, nothing waits for a read-modify-write round trip
-        for (int r = tid >> 2; r < (TG_VAR(4) ? 0 : n); r += NT / 4) {
+        for (int r = tid >> 2; r < n; r += NT / 4) {
             const int l = tid & 3;
             const int beg = sRp[r], end = sRp[r + 1];
             float ge[D], p1[D];
@@ -606,7 +556,6 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
                 if (l == 0) sGP[r * D + d] += q - sada * sAa[r * D + d];
             }
         }
-        TG_STAMP(8)
     }
     __syncthreads();
     // ---- the workgroup's partial row
@@ -645,8 +594,6 @@ __global__ __launch_bounds__(NT) void tconv_bwd_graph_kernel(
             prow[R.off_gwe + o] = s2;
         }
     }
-    TG_STAMP(9)
-    TG_STAMP_FLUSH
 }
 
 static size_t kLdsMax = 160 * 1024;
@@ -658,14 +605,6 @@ constexpr int kTgBwdThreads = QOT_TG_BWD_THREADS;    // 512: two waves per SIMD 
 }  // namespace qot
 
 using namespace qot;
-
-#ifdef QOT_DIAG
-extern "C" void qot_debug_tg_variant(int v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(qot::g_tg_variant), &v, sizeof(int)); }
-extern "C" void qot_debug_tg_stamps(unsigned long long* host16, int reset) {
-    if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(qot::g_tg_stamps), z, sizeof(z)); }
-    else (void)hipMemcpyFromSymbol(host16, HIP_SYMBOL(qot::g_tg_stamps), 16 * sizeof(unsigned long long));
-}
-#endif
 
 static bool tg_width_ok(int H) { return H == 16 || H == 32 || H == 64 || H == 128 || H == 256; }
 

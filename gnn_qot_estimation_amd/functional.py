@@ -1080,19 +1080,9 @@ class NNConvFn(torch.autograd.Function):
             gx = torch.empty(N, hin, dtype=torch.float32, device=dev)
             ws = torch.empty(_lib.load().qot_nnconv_adjoint_dw_workspace_floats(D), dtype=torch.float32, device=dev)
             deferred = LG.can_defer(*ctx.receivers)
-            # QOT_FORK (experiment, default off): the grad-h kernel on a side stream, "before" = next to the adjoint
-            # kernel, "after" = next to the TransformerConv backward that follows on the main stream
-            fork_mode = os.environ.get("QOT_FORK", "off") if deferred else "off"
-            launch_gradh = lambda: _lib.call(gradh_fn, *gradh_args, None, None, P(wsh), N, hin, D)
-            keep = (g, x, edge_attr, w1, b1, graph.rowptr, graph.col, graph.eid, graph.invdeg, bp, split, wsh)
-            if fork_mode == "before":
-                LG.fork(launch_gradh, keep=keep)
             _lib.call("qot_nnconv_adjoint_dw", P(g), hout, P(x), hin, P(edge_attr), P(w1), P(b1), P(graph.rowptr_t),
                       P(graph.col_t), P(graph.eid_t), P(graph.invdeg), P(wp_adj), P(gx), P(gpar), 2, P(ws), N, hin, D)
-            if fork_mode == "after":
-                LG.fork(launch_gradh, keep=keep)
-            elif fork_mode != "before":
-                launch_gradh()
+            _lib.call(gradh_fn, *gradh_args, None, None, P(wsh), N, hin, D)
             if deferred:             # both second-stage sums join the backward epilogue's multi-role launch
                 LG.defer(_lib.ROLE_NNCONV_FINALIZE64, (ws, wsh, gpar, gw1f, gb1f), (N, D), stage=1)
             else:

@@ -91,14 +91,12 @@ class _BackwardQueue:
         self.clear()
 
     def pending(self) -> bool:
-        return bool(self.stages[0] or self.stages[1] or self.forked)
+        return bool(self.stages[0] or self.stages[1])
 
     def clear(self):
         self.stages = ([], [])
         self.keep = []
         self.stream = None           # raw handle of the stream the backward nodes run on
-        self.stream_obj = None
-        self.forked = []             # side streams with work the epilogue has to wait for
         self.armed = False
 
 
@@ -110,35 +108,9 @@ def _arm():
     if not q.armed:
         q.clear()                        # anything left over belongs to a backward pass that died: its buffers are gone
         q.stream = _lib.stream()         # node execution runs on the forward's stream; the callback may not
-        q.stream_obj = torch.cuda.current_stream()
         torch.autograd.Variable._execution_engine.queue_callback(flush)
         q.armed = True
     return q
-
-
-_SIDE = {}
-
-
-def fork(fn, keep=()):
-    """Run ``fn()`` (kernel launches through ``_lib.call``) on a side stream, ordered behind everything enqueued so far on
-    the current stream, and let the current stream go on; the backward epilogue waits for it.  For a kernel whose result
-    only the epilogue consumes and that uses other hardware than what follows it on the main stream (NNConv's grad-h
-    kernel -- matrix cores, LDS -- next to the latency-bound TransformerConv backward kernels): the two then share the
-    CUs instead of running back to back.  ``keep``: every tensor the forked work touches -- the caching allocator must
-    not hand their blocks to main-stream allocations before the join.  Inside a backward pass only; capture-safe (the
-    side stream joins the capture at the fork and leaves it at the flush)."""
-    q = _arm()
-    cur = torch.cuda.current_stream()
-    key = (cur.device.index, cur.cuda_stream)
-    side = _SIDE.get(key)
-    if side is None:
-        side = _SIDE[key] = torch.cuda.Stream(device=cur.device)
-    side.wait_stream(cur)
-    with torch.cuda.stream(side):
-        fn()
-    if side not in q.forked:
-        q.forked.append(side)
-    q.keep.extend(keep)
 
 
 def defer(kind: int, ptrs, ints, stage: int = 1, keep=()):
@@ -157,17 +129,15 @@ def flush():
         q.armed = False
         return
     s1, s2 = q.stages
-    stream, forked = q.stream, q.forked
-    q.stages, q.forked = ([], []), []
+    stream = q.stream
+    q.stages = ([], [])
     try:
-        for side in forked:              # join: the jobs below read what the forked kernels wrote
-            q.stream_obj.wait_stream(side)
         _lib.run_roles(s1, stream)
         _lib.run_roles(s2, stream)
     finally:
         q.keep = []
         q.armed = False
-        q.stream = q.stream_obj = None
+        q.stream = None
 
 
 def drop_stale():

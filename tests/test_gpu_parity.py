@@ -728,19 +728,12 @@ def _nnconv_fp64(x, ea, w1, b1, wcat, bias, rowptr, col, eids, invdeg, transpose
 
 
 @pytest.mark.parametrize("case", ["random", "hub", "edge_dim2", "no_edges"])
-def test_weight_stationary_nnconv_matches_tile_kernel_and_fp64(cuda_device, case):
-    """The production tile kernel (``qot_nnconv_fused``) against an fp64 restatement of its contract, both index
-    directions, a 700-in-edge hub, edge_dim 2, an edge-less batch; in a diagnostic build (``make DIAG=1``) also the
-    experimental weight-stationary kernel csrc/nnconv_ws.hip (weights in registers, rows by LDS-DMA, operands formed
-    on the fly), which is not part of the release library or its ABI."""
+def test_nnconv_fused_matches_fp64(cuda_device, case):
+    """The tile kernel (``qot_nnconv_fused``, H = 64) against an fp64 restatement of its contract, both index directions,
+    a 700-in-edge hub, edge_dim 2, an edge-less batch; then its activation + dropout epilogue against the fp64 result
+    under the restated mask (``oracle.dropout``): dropped positions exactly zero, kept ones scaled."""
     from gnn_qot_estimation_amd import _lib
-    import ctypes
-    names = ["qot_nnconv_fused"]
-    lib = _lib.load()
-    if hasattr(lib, "qot_nnconv_fused_ws"):
-        fn = lib.qot_nnconv_fused_ws
-        fn.restype, fn.argtypes = lib.qot_nnconv_fused.restype, lib.qot_nnconv_fused.argtypes
-        names.append("qot_nnconv_fused_ws")
+    from oracle import dropout as OD
     from gnn_qot_estimation_amd.functional import nnconv_perm_index
     from gnn_qot_estimation_amd.graph import build_graph_index
     P = _lib.ptr
@@ -767,28 +760,27 @@ def test_weight_stationary_nnconv_matches_tile_kernel_and_fp64(cuda_device, case
     wcat = (torch.randn((K + 2) * H, H, generator=g) / 8).to(dev)
     bias = torch.randn(H, generator=g).to(dev)
     wp = wcat.reshape(-1)[nnconv_perm_index((K + 2) * H, dev)].contiguous()
+    refs = []
     for transpose, (rp, col, eids) in ((0, (gi.rowptr, gi.col, gi.eid)), (1, (gi.rowptr_t, gi.col_t, gi.eid_t))):
         ref = _nnconv_fp64(x, ea, w1, b1, wcat, bias, rp, col, eids, gi.invdeg, transpose)
-        outs = []
-        for name in names:
-            out = torch.full((N, H), float("nan"), device=dev)
-            _lib.call(name, P(x), H, P(ea), P(w1), P(b1), P(rp), P(col), P(eids), P(gi.invdeg), transpose, P(wp),
-                      P(bias), P(out), N, H, D, 0, 0.0, 0.0, 0, None)
-            torch.cuda.synchronize()
-            assert rel_err(out.double().cpu(), ref) <= TOL, (case, transpose, name)
-            outs.append(out)
-        assert rel_err(outs[-1], outs[0]) <= TOL
-    # identical dropout masks and activation epilogue (counter-based draws keyed by element index)
+        refs.append(ref)
+        out = torch.full((N, H), float("nan"), device=dev)
+        _lib.call("qot_nnconv_fused", P(x), H, P(ea), P(w1), P(b1), P(rp), P(col), P(eids), P(gi.invdeg), transpose, P(wp),
+                  P(bias), P(out), N, H, D, 0, 0.0, 0.0, 0, None)
+        torch.cuda.synchronize()
+        assert rel_err(out.double().cpu(), ref) <= TOL, (case, transpose)
+    # activation epilogue and dropout mask (counter-based draws keyed by element index) against the restated mask
+    ref = refs[0]
     step = torch.tensor([3], dtype=torch.int64, device=dev)
-    outs = []
-    for name in names:
-        out = torch.empty(N, H, device=dev)
-        _lib.call(name, P(x), H, P(ea), P(w1), P(b1), P(gi.rowptr), P(gi.col), P(gi.eid), P(gi.invdeg), 0, P(wp),
-                  P(bias), P(out), N, H, D, 1, 0.01, 0.25, 1234, P(step))
-        outs.append(out)
+    out = torch.full((N, H), float("nan"), device=dev)
+    _lib.call("qot_nnconv_fused", P(x), H, P(ea), P(w1), P(b1), P(gi.rowptr), P(gi.col), P(gi.eid), P(gi.invdeg), 0, P(wp),
+              P(bias), P(out), N, H, D, 1, 0.01, 0.25, 1234, P(step))
     torch.cuda.synchronize()
-    assert bool(((outs[0] == 0) == (outs[-1] == 0)).all())
-    assert rel_err(outs[-1], outs[0]) <= TOL
+    out = out.double().cpu()
+    keep = OD.keep_mask(1234, 3, (N, H), 0.25)
+    expected = torch.where(keep, torch.nn.functional.leaky_relu(ref, 0.01) * float(OD.keep_scale(0.25)), torch.zeros_like(ref))
+    assert bool((out[~keep] == 0).all()), case
+    assert rel_err(out, expected) <= TOL, case
 
 
 @pytest.mark.parametrize("B,C", [(3, 64), (16, 260), (64, 25600), (100, 1028), (1024, 512), (1500, 128)])

@@ -30,31 +30,3 @@ for K in (128, 256, 512, 1024, 2048, 4096):
     print(json.dumps({"K": K, "M": M, "lib_tf": round(fl / lib / 1e9, 1), "nt_tf": round(fl / ours / 1e9, 1),
                       "nt_affine_tf": round(fl / aff / 1e9, 1)}))
     del x, z
-
-lib = _lib.load()
-if hasattr(lib, "qot_debug_gemm_variant"):
-    import ctypes
-    lib.qot_debug_gemm_variant.argtypes = [ctypes.c_int]
-    for K in (512, 4096):
-        M = 707008 * 512 // K // 128 * 128
-        x, w = torch.randn(M, K, device=dev), torch.randn(N, K, device=dev)
-        z = torch.empty(M, N, device=dev)
-        s, t = torch.rand(K, device=dev) + 0.5, torch.randn(K, device=dev)
-        fl = 2.0 * M * N * K
-        abl = {}
-        for name, v in (("full", 0), ("no global loads", 1), ("no LDS stores", 2), ("no loads, no stores", 3), ("no barrier", 4),
-                        ("no loads/stores/barrier", 7), ("no C stores", 8), ("no fragment reads", 16), ("MFMAs only", 31),
-                        ("A from one row (L2)", -1), ("C to one row", -2)):
-            lib.qot_debug_gemm_variant(max(v, 0))
-            if hasattr(lib, "qot_debug_gemm256_variant"):
-                lib.qot_debug_gemm256_variant(max(v, 0))
-            lda = 0 if v == -1 else K
-            ldc = 0 if v == -2 else N
-            ms = timeit(lambda: _lib.call("qot_gemm_nt", x, lda, w, K, z, ldc, M, N, K, None, None, None))
-            ms2 = timeit(lambda: _lib.call("qot_gemm_nt", x, lda, w, K, z, ldc, M, N, K, s, t, None))
-            abl[name] = [round(fl / ms / 1e9, 1), round(fl / ms2 / 1e9, 1)]
-        lib.qot_debug_gemm_variant(0)
-        if hasattr(lib, "qot_debug_gemm256_variant"):
-            lib.qot_debug_gemm256_variant(0)
-        print(json.dumps({"K": K, "tile": 256 if lib.qot_gemm256_takes(M, N) else 128, "ablation TF [plain, affine]": abl}))
-        del x, z

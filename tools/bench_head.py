@@ -1,6 +1,5 @@
-"""qot_head_train (read-out forward + criterion + backward in one kernel) alone at cfg2's shape; with the diagnostic build
-(QOT_LIB_PATH=tools/diag/libqot_gnn_diag.so) also its phase ablation."""
-import ctypes, json, os, sys
+"""qot_head_train (read-out forward + criterion + backward in one kernel) alone at cfg2's shape."""
+import json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gnn_qot_estimation_amd import _lib
@@ -28,9 +27,4 @@ def timeit(it=50):
         best = min(best, st.elapsed_time(en) / it * 1e3)
     return round(best, 2)
 res = {"B": B, "head_train_us": timeit()}
-if hasattr(lib, "qot_debug_head_variant"):
-    lib.qot_debug_head_variant.argtypes = [ctypes.c_int]
-    for name, v in (("no pool backward", 1), ("no dense phases", 2), ("no row loads", 4), ("no loads, no pool backward", 5), ("nothing", 7)):
-        lib.qot_debug_head_variant(v); res[name] = timeit()
-    lib.qot_debug_head_variant(0)
 print(json.dumps(res))

@@ -1,8 +1,6 @@
 """TransformerConv graph form (csrc/tconv_graph.hip) piece by piece through the C ABI at cfg2's shape: score matrix job,
-forward, backward, the row sum of the partials and the projection backward, next to the kernels they replace.  With the
-diagnostic build (QOT_LIB_PATH=tools/diag/libqot_gnn_diag.so, `make -C gnn_qot_estimation_amd/csrc DIAG=1`) also the
-in-kernel phase stamps (cycles of thread 0, summed over workgroups)."""
-import ctypes, json, os, sys
+forward, backward, the row sum of the partials and the projection backward, next to the kernels they replace."""
+import json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gnn_qot_estimation_amd import _lib, synthetic as S
@@ -67,36 +65,3 @@ stats = torch.empty(N, 2, device=dev)
 res["fwd_tile_us"] = timeit(lambda: _lib.call("qot_tconv_fwd_tile", off(t4, 0), off(t4, H), off(t4, 2 * H), off(t4, 3 * H), 4 * H,
                                                b.edge_attr, we, g.rowptr, g.colf, g.eid, g.ids32, out, stats, N, H, D, n, B, *act))
 print(json.dumps(res))
-if hasattr(lib, "qot_debug_tg_variant") and not os.environ.get("TG_STAMPS"):
-    lib.qot_debug_tg_variant.argtypes = [ctypes.c_int]
-    abl = {}
-    for name, v in (("full", 0), ("no edge dots / ge", 1), ("no source pass / gWe", 2), ("no 1c", 4), ("no act backward", 8),
-                    ("none of the passes", 7), ("none + no act", 15)):
-        lib.qot_debug_tg_variant(v)
-        abl[name] = timeit(jobs["bwd_graph"])
-    lib.qot_debug_tg_variant(0)
-    print(json.dumps({"bwd_graph ablation (us)": abl}))
-    abl = {}
-    for name, v in (("full", 0), ("no stage C", 16), ("no stage B", 32), ("no edge staging", 64), ("no B, C", 48), ("nothing but the tables", 112),
-                    ("C without its output stores", 128), ("C without the activation (hash)", 256),
-                    ("nothing at all (launch, barriers, per-thread constants)", 624)):
-        lib.qot_debug_tg_variant(v)
-        abl[name] = timeit(jobs["fwd_graph"])
-    lib.qot_debug_tg_variant(0)
-    print(json.dumps({"fwd_graph ablation (us)": abl}))
-if hasattr(lib, "qot_debug_tg_stamps") and os.environ.get("TG_STAMPS"):
-    lib.qot_debug_tg_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    names = ["fwd trip 1 (tables, row pointers) + barrier", "fwd A stage graph, logits", "fwd B softmax",
-             "fwd C aggregate + store", "bwd wait at the top barrier", "bwd commit prefetched graph + barrier",
-             "bwd 1a edge dots, ge (+ prefetch issue)", "bwd 2 source pass, gWe + barrier", "bwd 1c per-destination scalars",
-             "bwd partial row"]
-    for which in ("fwd_graph", "bwd_graph"):
-        lib.qot_debug_tg_stamps(None, 1)
-        jobs[which]()
-        torch.cuda.synchronize()
-        buf = (ctypes.c_ulonglong * 16)()
-        lib.qot_debug_tg_stamps(ctypes.cast(buf, ctypes.c_void_p), 0)
-        wgs = blocks if which == "bwd_graph" else min(256, (B + 3) // 4)
-        for i, nm in enumerate(names):
-            if buf[i]:
-                print(f"  {nm:32s} {buf[i] / wgs:10.0f} cycles per workgroup (s_memtime ticks of thread 0)")
