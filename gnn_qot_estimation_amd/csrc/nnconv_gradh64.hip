@@ -202,16 +202,23 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
 #pragma unroll 1
             for (int t = 0; t < NBW; ++t) {
                 const int nb = wave * NBW + t;
-                f32x16 c;
+                // two accumulators (split_bf16.hpp: mfma_split6_two): GA feeds sums over every edge of a graph, where an
+                // error shared by a graph's rows does not average out
+                f32x16 c, cs;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) c[r] = 0.f;
+                for (int r = 0; r < 16; ++r) { c[r] = 0.f; cs[r] = 0.f; }
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     const int q = 4 * t + s;                  // step of the wave's sequence (blocks are contiguous in Bs)
                     if (q + SL < 4 * NBW) bsp[(s + SL) % (SL + 1)] = load_split_b(bsw + (q + SL) * 64, bs_planes);
-                    if constexpr (PRESPLIT) c = mfma_split6(load_split_b(pla + s * kGhPlStep, kGhPlLd), bsp[s], c);
-                    else c = mfma_split_step(Gt4, 2 * s, hi, r31, bsp[s], c);
+                    if constexpr (PRESPLIT) {
+                        mfma_split6_two(load_split_b(pla + s * kGhPlStep, kGhPlLd), bsp[s], c, cs);
+                    } else {
+                        const float4 a0 = Gt4[at4_slot(2 * s, hi, r31)], a1 = Gt4[at4_slot(2 * s + 1, hi, r31)];
+                        mfma_split6_two(split8(a0, a1), bsp[s], c, cs);
+                    }
                 }
+                c += cs;                                      // (one vector expression: packed adds)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;

@@ -11,7 +11,8 @@
 // fp32's: |x| below ~3.4e38 and parts above the denormal range -- for |x| >= ~2^-110 every part is normal.)
 // A product a*b is then a sum of 9 bf16 cross products, each exact in the MFMA's fp32 accumulation path.  The six
 // largest are kept (hh, hm, mh, hl, lh, mm); |mid| <= 2^-8 |x| and |lo| <= 2^-16 |x|, so the three dropped ones (ml, lm,
-// ll) sum to at most ~2^-23 |a b|, about one rounding of the fp32 MFMA (2^-24 per product).  The six are issued smallest first into ONE fp32 accumulator.
+// ll) sum to at most ~2^-23 |a b|, about one rounding of the fp32 MFMA (2^-24 per product).  The six are issued smallest first into ONE fp32 accumulator
+// (mfma_split6), or the five small ones into an accumulator of their own (mfma_split6_two: the grad-h kernel).
 // Cost per 32 x 32 output block and 16-deep K step: 6 x 32 cycles against 8 x 64 for the fp32 MFMA.
 #pragma once
 #include "mfma_tile.hpp"
@@ -79,6 +80,18 @@ __device__ __forceinline__ f32x16 mfma_split6(const Bf3& a, const Bf3& b, f32x16
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.h, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, c, 0, 0, 0);
     return c;
+}
+
+// The same six products with the five small ones (at most 2^-8 of hh) in an accumulator of their own: summed over the K steps
+// into ONE accumulator every product rounds at the full sum's magnitude (6 roundings per step); kept apart, the small
+// ones round at their own magnitude and the full-size accumulator sees one rounding per step plus the final c + s.
+__device__ __forceinline__ void mfma_split6_two(const Bf3& a, const Bf3& b, f32x16& c, f32x16& s) {
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.m, s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.h, s, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, c, 0, 0, 0);
 }
 
 // Pre-split B fragment of 16-deep step s: three planes of `ps` u32x4 each, 64 lanes per step (16 B per lane and plane).

@@ -10,15 +10,32 @@
 // H-wide weighted key sums per destination; source pass: query AND gradient row per out-edge; per-workgroup partial
 // table rows [B / 8, n, 4H] summed afterwards) become:
 //   destination pass: a workgroup owns table row r for a slice of the graphs -- row r of M staged in LDS once, the value row
-//     the only row gathered per edge, ds_e added into ONE LDS image of row r of grad M as 64-bit fixed point (2^-36: the
-//     lane groups of a workgroup work on different graphs and meet on the same entries in no fixed order; integer sums do
-//     not depend on it, so the result stays bit-reproducible, and the image costs 8 KB instead of a private fp32 row per
-//     lane group -- 36 KB at H = 128, which left two workgroups per CU and made the pass slower than tconv.hip's) -- and
-//     leaves ONE partial row [grad T_skip (H) | grad M (n) | grad P (D)] per (slice, r);
+//     the only row gathered per edge, ds_e left in escr, and ONE partial row [grad T_skip (H) | grad M (n) | grad P (D)]
+//     per (slice, r), whose grad M part the image pass fills;
+//   image pass (tconv_rows_image_kernel, same grid): the ds_e of the slice's in-edges of row r added into ONE LDS image of
+//     row r of grad M as 64-bit fixed point (threads meet on the same entries in no fixed order; integer sums do not depend
+//     on it, so the result stays bit-reproducible, and the image costs 8 KB instead of a private fp32 row per lane group --
+//     36 KB at H = 128, which left two workgroups per CU and made the pass slower than tconv.hip's);
 //   source pass: same ownership by source row: grad T_v[r] accumulated in registers over the slice.
 // P slices of the graphs per row (load balance; hubs of power-law graphs sit at the same rows of every graph: rows are
 // dealt slowest so that the heavy rows start first); the P partial rows are summed in order (QOT_ROLE_SUM_ROWS / the
 // caller).  No atomics on global memory, fixed summation order.
+//
+// The fixed point's scale is a power of two that every workgroup of the image pass takes from its own data, so the image has
+// RELATIVE precision at any gradient scale (training feeds 2^-10 .. 2^-12 of a unit gradient, loss scaling the opposite; a
+// constant 2^-36 lost |ds_e| < 7e-12 and overflowed above 2^27).  The pass reads its ds_e twice: first for the largest |ds_e|
+// (biased exponent eb: max |ds| < 2^(eb - 126)) and the number A of addends (bit length cb: A < 2^cb; every in-edge of the
+// slice is one addend, whichever entry it lands in), then it adds rn(ds_e 2^k) with k = 62 - cb - (eb - 126).  Bound:
+//   every addend is below 2^(62 - cb) in magnitude and rounds by at most 1/2, so any sum of at most A of them stays below
+//   2^62 + A / 2 < 2^63: one bit of headroom under the sign, for the workgroup's OWN addend count (no assumed limit);
+//   the quantum 2^-k is at most 2^-(61 - cb) of the workgroup's largest |ds_e|: below 2^-41 of it for A < 2^20 addends
+//   (cfg5's heaviest row: ~2^11), i.e. 2^17 times finer than the last bit of an fp32 addend of that size, and an entry's
+//   error is at most (its addends) / 2 quanta, where an fp32 sum in any order carries 2^-24 of its running value per addend.
+// A maximum and a count do not depend on the order either, so the pass stays bit-reproducible; k moves by exactly -j when
+// the incoming gradient is scaled by 2^j, so the integers -- and the fp32 read-out scaled back by 2^-k -- are the same:
+// the pass is homogeneous bit for bit (short of fp32 underflow / overflow of ds_e itself).  A ds_e that is NaN or Inf has
+// no integer image: the workgroup's whole row of grad M reads back NaN (so grad T_q[r] and, through grad M^T T_q, grad T_k
+// are non-finite as the other gradients of a diverged step are).
 #include "common.hpp"
 
 namespace qot {
@@ -39,7 +56,7 @@ __host__ __device__ inline int trows_npad(int n) { return (n + 31) / 32 * 32; }
 __host__ __device__ inline int trows_ldrow(int n, int H, int D) { return (H + trows_npad(n) + D + 3) / 4 * 4; }
 
 // grid = n * parts workgroups of 256 threads; workgroup vb: r = vb / parts, part = vb % parts (heavy rows first).
-// LDS (dynamic): sGM[npad] (64-bit) | sM[npad]
+// LDS (dynamic): sM[npad].  escr [slots, 2] leaves as (a_e, ds_e): the image pass reads ds_e, the source pass a_e.
 template <int H, int D>
 __global__ __launch_bounds__(256, (D <= 4 && H <= 128) ? 4 : 3) void tconv_bwd_dst_rows_kernel(
     const float* __restrict__ g, const float* __restrict__ q, const float* __restrict__ v_, int ld,
@@ -58,9 +75,7 @@ __global__ __launch_bounds__(256, (D <= 4 && H <= 128) ? 4 : 3) void tconv_bwd_d
     __shared__ float wred[RPB * H * DCH];
     const int npad = trows_npad(tile_n);
     const int ldrow = trows_ldrow(tile_n, H, D);
-    unsigned long long* sGM = reinterpret_cast<unsigned long long*>(sh);
-    float* sM = sh + 2 * npad;
-    constexpr float kFix = 68719476736.0f;            // 2^36
+    float* sM = sh;
     const int sub = threadIdx.x % TPR, rloc = threadIdx.x / TPR;
     const int vb = blockIdx.x;
     const int r = vb / parts, part = vb % parts;
@@ -70,7 +85,6 @@ __global__ __launch_bounds__(256, (D <= 4 && H <= 128) ? 4 : 3) void tconv_bwd_d
     const float rs = rsqrtf((float)H);
     const int c0 = CPL * sub;
     for (int t = threadIdx.x; t < npad; t += 256) sM[t] = t < tile_n ? rs * Mtab[(int64_t)r * ldm + t] : 0.f;
-    for (int t = threadIdx.x; t < npad; t += 256) sGM[t] = 0ull;
     float4 qi[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) qi[v] = scale4(rs, ld4(q + (int64_t)r * ld + c0 + 4 * v));
@@ -222,14 +236,12 @@ __global__ __launch_bounds__(256, (D <= 4 && H <= 128) ? 4 : 3) void tconv_bwd_d
             pdacc[d] += pd[d];
         }
         if (sub == 0) delta[i] = sada;
-        // pass 2: ds_e into this lane group's image of row r of grad M (its own escr entries: same lane wrote them)
+        // pass 2: ds_e of every in-edge, for the image pass (its own escr entries: same lane wrote them)
         for (int base = beg; base < end; base += BT) {
             const int pme = base + sub;
             if (sub < BT && pme < end) {
-                const int j = colf[pme];
                 const float a = escr[2 * (int64_t)pme], da = escr[2 * (int64_t)pme + 1];
-                const long long fx = __float2ll_rn(a * (da - sada) * kFix);
-                atomicAdd(&sGM[j], (unsigned long long)fx);   // LDS, integer: order-independent
+                escr[2 * (int64_t)pme + 1] = a * (da - sada);
             }
         }
         // grad of lin_edge.weight, the part that is not a function of the table row: g_i[c] * p2_i[d]
@@ -255,7 +267,6 @@ __global__ __launch_bounds__(256, (D <= 4 && H <= 128) ? 4 : 3) void tconv_bwd_d
             st4(out + c0 + 4 * v, a);
         }
     }
-    for (int t = threadIdx.x; t < npad; t += 256) out[H + t] = (float)(long long)sGM[t] * (1.0f / kFix);
     if (threadIdx.x < D) {
         float s = pred[0][threadIdx.x];
         for (int r2 = 1; r2 < RPB; ++r2) s += pred[r2][threadIdx.x];
@@ -280,6 +291,84 @@ __global__ __launch_bounds__(256, (D <= 4 && H <= 128) ? 4 : 3) void tconv_bwd_d
             wedge_partials[(int64_t)blockIdx.x * H * D + ch * D + d0 + dd] = sacc;
         }
     }
+}
+
+// Image pass: row r of grad M for one slice of the graphs, [npad] floats at part_rows[(part * n + r) * ldrow + H], from the
+// ds_e the destination pass left in escr (see the top of this file for the fixed point's scale).  Same grid; the slice's
+// destinations are taken 256 at a time: their in-edge counts are scanned in LDS and the threads share the edges evenly (a
+// hub row of cfg5 holds 64 in-edges per graph, most rows two), each edge read twice (largest |ds_e|, then the sum).
+// LDS (dynamic): sGM[npad] (64-bit)
+__global__ __launch_bounds__(256) void tconv_rows_image_kernel(const float* __restrict__ escr, const int32_t* __restrict__ rowptr,
+                                                               const int32_t* __restrict__ colf, int tile_n, int64_t tile_B,
+                                                               int parts, int ldrow, int H, float* __restrict__ part_rows) {
+    extern __shared__ float sh[];
+    unsigned long long* sGM = reinterpret_cast<unsigned long long*>(sh);
+    __shared__ int sPre[257], sBeg[256];
+    __shared__ unsigned sMaxBits;
+    const int npad = trows_npad(tile_n);
+    const int tid = threadIdx.x;
+    const int vb = blockIdx.x;
+    const int r = vb / parts, part = vb % parts;
+    const int64_t per = (tile_B + parts - 1) / parts;
+    const int64_t b0 = (int64_t)part * per;
+    const int64_t b1 = (b0 + per < tile_B) ? b0 + per : tile_B;
+    for (int t = tid; t < npad; t += 256) sGM[t] = 0ull;
+    if (tid == 0) sMaxBits = 0u;
+    // f(slot) for every in-edge slot of the slice's destinations; returns their number (the same in every thread)
+    auto for_each_edge = [&](auto&& f) {
+        unsigned long long count = 0ull;
+        for (int64_t cb = b0; cb < b1; cb += 256) {
+            int beg = 0, deg = 0;
+            if (cb + tid < b1) {
+                const int64_t i = (cb + tid) * tile_n + r;
+                beg = rowptr[i];
+                deg = rowptr[i + 1] - beg;
+            }
+            __syncthreads();                                   // (the previous chunk's readers are done)
+            sBeg[tid] = beg;
+            sPre[tid + 1] = deg;
+            if (tid == 0) sPre[0] = 0;
+            __syncthreads();
+            for (int off = 1; off < 256; off <<= 1) {          // inclusive scan of the 256 counts
+                const int add = (tid + 1 > off) ? sPre[tid + 1 - off] : 0;
+                __syncthreads();
+                sPre[tid + 1] += add;
+                __syncthreads();
+            }
+            const int total = sPre[256];
+            for (int e = tid; e < total; e += 256) {
+                int lo = 0, hi = 255;                          // the destination d with sPre[d] <= e < sPre[d + 1]
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (sPre[mid] <= e) lo = mid; else hi = mid - 1;
+                }
+                f(sBeg[lo] + (e - sPre[lo]));
+            }
+            count += (unsigned long long)total;
+        }
+        return count;
+    };
+    unsigned mxbits = 0u;                                      // the bits of |x| order as integers, Inf and NaN on top
+    const unsigned long long addends = for_each_edge([&](int slot) {
+        const unsigned bits = __float_as_uint(fabsf(escr[2 * (int64_t)slot + 1]));
+        mxbits = bits > mxbits ? bits : mxbits;
+    });
+    atomicMax(&sMaxBits, mxbits);                              // LDS, integer: order-independent
+    __syncthreads();
+    const bool poisoned = sMaxBits >= 0x7f800000u;             // an Inf or NaN ds_e: no integer image
+    const int eb = (int)(sMaxBits >> 23);                      // max |ds_e| < 2^(eb - 126)
+    const int cb_ = 64 - __clzll((long long)(addends | 1ull)); // addends < 2^cb
+    int kexp = 62 - cb_ - (eb - 126);
+    kexp = kexp > 126 ? 126 : (kexp < -126 ? -126 : kexp);     // (the lower end would need 2^60 addends)
+    const float kUp = __uint_as_float((unsigned)(127 + kexp) << 23), kDown = __uint_as_float((unsigned)(127 - kexp) << 23);
+    if (!poisoned)
+        for_each_edge([&](int slot) {
+            const long long fx = __float2ll_rn(escr[2 * (int64_t)slot + 1] * kUp);
+            atomicAdd(&sGM[colf[slot]], (unsigned long long)fx);            // LDS, integer: order-independent
+        });
+    __syncthreads();
+    float* out = part_rows + ((int64_t)part * tile_n + r) * ldrow + H;
+    for (int t = tid; t < npad; t += 256) out[t] = poisoned ? __uint_as_float(0x7fc00000u) : (float)(long long)sGM[t] * kDown;
 }
 
 // Source pass: grad T_v[r] = sum over the graphs of the slice, over the out-edges of node r, of a_e g_i  ->
@@ -505,7 +594,7 @@ extern "C" int qot_tconv_rows_ld(int n, int H, int D) { return n > 0 ? trows_ldr
 
 static size_t trows_lds_bytes(int n, int H) {
     (void)H;
-    return (size_t)3 * trows_npad(n) * sizeof(float);        // 64-bit grad M image + the row of M
+    return (size_t)3 * trows_npad(n) * sizeof(float);        // 64-bit grad M image (image pass) + the row of M
 }
 
 extern "C" int qot_tconv_rows_supported(int n, int H, int D) {
@@ -531,8 +620,8 @@ extern "C" int qot_tconv_bwd_dst_rows(const float* grad_out, const float* q, con
         return QOT_ERR_BADARG;
     if (!qot_tconv_rows_supported(n, H, D) || (int64_t)n * parts > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
     const ActParams ap = make_act(y_act ? 1 : 0, act_slope, act_p, act_seed, act_step);
-    const size_t lds = trows_lds_bytes(n, H);
-    static size_t allowed[3][8][kMaxDevices];
+    const size_t lds = (size_t)trows_npad(n) * sizeof(float), lds_image = (size_t)2 * trows_npad(n) * sizeof(float);
+    static size_t allowed[3][8][kMaxDevices], allowed_image[kMaxDevices];
     int rc = QOT_ERR_UNSUPPORTED;
 #define QOT_TROWS(HH, HI)                                                                                           \
     if (H == HH) {                                                                                                   \
@@ -547,6 +636,11 @@ extern "C" int qot_tconv_bwd_dst_rows(const float* grad_out, const float* q, con
     QOT_TROWS(64, 0) QOT_TROWS(128, 1) QOT_TROWS(256, 2)
 #undef QOT_TROWS
     if (rc != QOT_OK) return rc;
+    QOT_LAUNCH_CHECK();
+    rc = ensure_dyn_lds(reinterpret_cast<const void*>(tconv_rows_image_kernel), lds_image, allowed_image);
+    if (rc != QOT_OK) return rc;
+    tconv_rows_image_kernel<<<n * parts, 256, lds_image, stream>>>(escr, rowptr, colf, n, B, parts, trows_ldrow(n, H, D), H,
+                                                                   part_rows);
     QOT_LAUNCH_CHECK();
     return QOT_OK;
 }

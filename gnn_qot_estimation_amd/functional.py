@@ -539,9 +539,11 @@ def tconv_rows_ok(qkvs: torch.Tensor, maps, H: int, D: int) -> bool:
 
 
 def _tconv_backward_rows(ctx, g, qkvs, edge_attr, w_edge, stats, y, act_step):
-    """``TConvFn.backward`` in the row form: destination pass (one workgroup per table row and slice of the graphs: grad M
-    row, grad P, grad T_skip), source pass (grad T_v), the slices summed in order, then grad T_q / grad T_k from two small
-    products on the matrix cores.  Returns what ``backward`` returns."""
+    """``TConvFn.backward`` in the row form: destination pass (one workgroup per table row and slice of the graphs: grad P,
+    grad T_skip, ``ds_e`` per edge; then the grad M row as a fixed-point sum whose power-of-two scale each workgroup takes
+    from its own ``ds_e``, so that the result is relative to the incoming gradient's scale -- both launched by
+    ``qot_tconv_bwd_dst_rows``, nothing is read back), source pass (grad T_v), the slices summed in order, then grad T_q /
+    grad T_k from two small products on the matrix cores.  Returns what ``backward`` returns."""
     graph, maps = ctx.graph, ctx.maps
     lib = _lib.load()
     dev = qkvs.device
@@ -552,7 +554,8 @@ def _tconv_backward_rows(ctx, g, qkvs, edge_attr, w_edge, stats, y, act_step):
     B, n = maps[3]
     colf = maps[1]
     scores = ctx.scores
-    parts = int(max(1, min(B, 8)))
+    # (QOT_TCONV_ROWS_PARTS: fewer slices, for tests that need more graphs per workgroup than a small batch gives)
+    parts = int(max(1, min(B, int(os.environ.get("QOT_TCONV_ROWS_PARTS", "8")))))
     npad, ldrow = lib.qot_tconv_rows_npad(n), lib.qot_tconv_rows_ld(n, H, D)
     f32 = dict(dtype=torch.float32, device=dev)
     escr = torch.empty(max(graph.cap, 1), 2, **f32)

@@ -150,7 +150,10 @@ int qot_tconv_fwd_scores(const float* q, const float* v, const float* skip, int 
  * rows (row part * n + r) of qot_tconv_rows_ld(n, H, D) floats, [grad T_skip (H) | grad M (qot_tconv_rows_npad(n): n
  * rounded up to 32, the tail zero) | grad P (D)], parts * n rows of H * D lin_edge partials (sum of g_i[c] p2_i[d]; the
  * T_q part of that gradient is rs * T_q^T grad P), grad_skip [N, H] (gradient wrt the conv output behind the fused
- * activation) and escr / delta for the source pass.  qot_tconv_bwd_src_rows: parts * n partial rows of grad T_v (H).
+ * activation), escr [slots, 2] = (a_e, ds_e) for the source pass, and delta.  qot_tconv_bwd_src_rows: parts * n partial
+ * rows of grad T_v (H).  The grad M rows are summed as 64-bit fixed point whose power-of-two scale every workgroup takes
+ * from its own largest |ds_e| and addend count (relative precision at any gradient scale, bit-reproducible, homogeneous
+ * in grad_out); a workgroup that meets a NaN / Inf ds_e leaves its whole grad M row NaN.
  * The caller sums the `parts` row blocks in order.  H in {64, 128, 256}; qot_tconv_rows_supported(n, H, D). */
 int qot_tconv_rows_supported(int n, int H, int D);
 int qot_tconv_rows_npad(int n);
