@@ -31,7 +31,7 @@ ABI_VERSION = 13         # include/qot_gnn.h: QOT_ABI_VERSION
 # what qot_topological_infer, _mc, _grad and _whatif take alike, up to the status word; each adds its own arguments and the stream
 _INFER_COMMON = ([_p] * 5 + [_i64] * 3 + [_int, _int, _p, _int, _p, _int, _p, _int] + [_p] * 9
                  + [_f, _f, _p, _int, _int, _int, _p])
-# ... and qot_lightpath_infer and _grad, likewise
+# ... and qot_lightpath_infer, _grad and _whatif, likewise
 _LP_COMMON = ([_p] * 6 + [_i64] * 4 + [_p] * 4 + [_f] + [_p] * 4 + [_f] + [_p] * 4 + [_f, _p, _p] + [_int] * 5 + [_p])
 
 SIGNATURES = {
@@ -181,6 +181,7 @@ SIGNATURES = {
     "qot_topological_infer_whatif": (_int, _INFER_COMMON + [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _int, _p]),
     "qot_lightpath_infer": (_int, _LP_COMMON + [_p]),
     "qot_lightpath_infer_grad": (_int, _LP_COMMON + [_p, _int, _p, _p, _p, _p, _p]),
+    "qot_lightpath_infer_whatif": (_int, _LP_COMMON + [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p]),
     "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "qot_status_graph_count": (_int, [_p, _p, _p, _i64, _i64, _int, _i64, _i64, _int, _int, _int, C.c_double, _int, _p, _sz, _p,
                                       _p]),

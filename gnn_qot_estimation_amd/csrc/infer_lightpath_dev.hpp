@@ -25,6 +25,12 @@
 // Every sum has one fixed order that depends on the edge's offset inside its graph's slice and on nothing else: a row is
 // bitwise reproducible, and independent of the other graphs of the launch and of the mode that asked for it.  Widths are run
 // time values (loops stride them by lane); the parameters are read in place, nothing is tabulated or cached.
+//
+// lp_row takes a compile-time EDIT POLICY.  LpNoEdit, the default, is empty: the two kernels above
+// instantiate the row as it stands.  LpWhatIf (infer_lightpath_whatif.hip) is one candidate of LightpathPredictor.what_if:
+// another x_i, some slice positions skipped, further sources behind the slice.  The scans then run the slice's chunks and
+// after them the added list as further chunks of 64; the sums stay "one after the other by rising position, the self loop
+// last", which is the order of the explicitly built graph (its surviving edges in their order, the additions behind them).
 #pragma once
 #include "common.hpp"
 
@@ -115,11 +121,62 @@ __device__ __forceinline__ void lp_dense(const float* __restrict__ w, const floa
     }
 }
 
+// the edit policy of a plain row: nothing is edited, every hook folds away
+struct LpNoEdit {
+    static constexpr bool kEdits = false;
+};
+
+constexpr int kLpMaxDrop = 32;          // removals of one candidate (their offsets are staged in LDS: 256 B)
+
+// the edit policy of one what-if candidate.  The kernel fills xi, add, na, drop, nd (each list bounds-checked against its
+// array) and dl; lp_row calls stage() once the graph's edge slice is known to lie inside the edge array.
+struct LpWhatIf {
+    static constexpr bool kEdits = true;
+    const float* xi;                    // the candidate's feature row [F]; null: the node's own
+    const int64_t* add;                 // its added sources [na], batch node numbering
+    int64_t na;
+    const int64_t* drop;                // its drop positions [nd] in the batch's edge_index
+    int nd;                             // 0 ... kLpMaxDrop
+    int64_t* dl;                        // LDS [kLpMaxDrop]: the drop positions as offsets into the slice
+    int64_t mp;                         // the slice's length rounded up to whole chunks: the added list starts there
+
+    // stages the drop offsets (visible behind the next barrier); false: a position outside the slice [e0, e0 + m)
+    __device__ __forceinline__ bool stage(int64_t e0, int64_t m, int lane) {
+        bool out = false;
+        if (lane < nd) {
+            const int64_t k = drop[lane] - e0;
+            out = k < 0 || k >= m;
+            dl[lane] = k;
+        }
+        mp = (m + kWave - 1) / kWave * kWave;
+        return !__any(out);
+    }
+    __device__ __forceinline__ bool dropped(int64_t k) const {
+        bool hit = false;
+        for (int t = 0; t < nd; ++t) hit = hit || dl[t] == k;      // (every lane reads the same word: a broadcast)
+        return hit;
+    }
+};
+
 // the messages of a chunk: lane `lane` looks at the edge at offset base + lane of the slice.  Returns 0 (no message),
-// 1 (a message from `src`) or 2 (an edge that leaves the graph's node range: nothing is read through it)
+// 1 (a message from `src`) or 2 (an edge that leaves the graph's node range: nothing is read through it).  With an edit:
+// a dropped offset is no message and its ends are not read; offset ed.mp + t is added source t, with destination i.
+template <class Edit = LpNoEdit>
 __device__ __forceinline__ int lp_edge(const LpArgs& a, int64_t e0, int64_t m, int64_t k, int64_t n0, int64_t n1, int64_t i,
-                                       int64_t& src) {
+                                       int64_t& src, const Edit& ed = Edit{}) {
+    if constexpr (Edit::kEdits) {
+        if (k >= ed.mp) {
+            if (k - ed.mp >= ed.na) return 0;
+            const int64_t s = ed.add[k - ed.mp];
+            if (s < n0 || s >= n1) return 2;
+            src = s;
+            return s != i ? 1 : 0;
+        }
+    }
     if (k >= m) return 0;
+    if constexpr (Edit::kEdits) {
+        if (ed.dropped(k)) return 0;
+    }
     const int64_t s = a.ei[e0 + k], d = a.ei[a.E + e0 + k];
     if (s < n0 || s >= n1 || d < n0 || d >= n1) return 2;
     src = s;
@@ -128,10 +185,11 @@ __device__ __forceinline__ int lp_edge(const LpArgs& a, int64_t e0, int64_t m, i
 
 // the output row of node i of graph g (0 <= i < N and 0 <= g < B are the caller's).  Returns 0: the row is written;
 // 1 / 2: refused (NaN row, status bit set) -- 2 when the graph's edge slice R.e0, R.m itself lies inside the edge array.
-// kKeep: K (LDS) and R are filled for the adjoint; the sums are the same either way.
-template <bool kKeep>
+// kKeep: K (LDS) and R are filled for the adjoint; the sums are the same either way.  Edit: the edit policy (above); an
+// edited row is also refused (status bit 2) when its feature row does not carry exactly 1.0f in the LUT column.
+template <bool kKeep, class Edit = LpNoEdit>
 __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int64_t i, int64_t g, float* orow, int lane,
-                                      LpRowRegs& R) {
+                                      LpRowRegs& R, Edit ed = Edit{}) {
     const int F = a.F, C = a.C;
     const int64_t n0 = a.node_ptr[g], n1 = a.node_ptr[g + 1], e0 = a.edge_ptr[g], e1 = a.edge_ptr[g + 1];
     const bool slice_ok = e0 >= 0 && e1 >= e0 && e1 <= a.E;
@@ -141,6 +199,14 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
         return slice_ok ? 2 : 1;
     }
     const int64_t m = e1 - e0;
+    int64_t span = m;                                          // the offsets the scans run over
+    if constexpr (Edit::kEdits) {
+        if (!ed.stage(e0, m, lane)) {                          // (wave-uniform)
+            lp_refuse(a, orow, lane, 2);
+            return 2;
+        }
+        span = ed.mp + ed.na;
+    }
 
     // ---- step 0: s_h, d_h, the destination's row ----
     const int h = lane / F, f = lane - h * F;                  // lanes below 4F own the pair (h, f)
@@ -157,8 +223,18 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
         L.s[h * kLpMaxF + f] = s;
         L.d[h * kLpMaxF + f] = d;
     }
-    if (lane < F) L.xi[lane] = a.x[i * F + lane];
+    if constexpr (Edit::kEdits) {
+        if (lane < F) L.xi[lane] = ed.xi ? ed.xi[lane] : a.x[i * F + lane];
+    } else {
+        if (lane < F) L.xi[lane] = a.x[i * F + lane];
+    }
     __syncthreads();
+    if constexpr (Edit::kEdits) {
+        if (L.xi[a.lut_col] != 1.0f) {                         // (wave-uniform: one LDS word)
+            lp_refuse(a, orow, lane, 4);
+            return 2;
+        }
+    }
     float adst[kLpHeads] = {}, lself[kLpHeads] = {};
     for (int t = 0; t < F; ++t) {                              // (two lp_dot4 in one pass over x_i: one LDS wait per t)
         const float xv = L.xi[t];
@@ -180,9 +256,9 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
 #pragma unroll
     for (int hh = 0; hh < kLpHeads; ++hh) mx[hh] = lself[hh];
     bool bad = false;
-    for (int64_t base = 0; base < m; base += kWave) {
+    for (int64_t base = 0; base < span; base += kWave) {
         int64_t src = 0;
-        const int kind = lp_edge(a, e0, m, base + lane, n0, n1, i, src);
+        const int kind = lp_edge(a, e0, m, base + lane, n0, n1, i, src, ed);
         bad = bad || kind == 2;
         if (kind == 1) {
             float l[kLpHeads] = {};
@@ -208,9 +284,9 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
 
     // ---- step 2: weights and source rows of a chunk -> LDS, then the sums in slice order ----
     float den = 0.f, u = 0.f;
-    for (int64_t base = 0; base < m; base += kWave) {
+    for (int64_t base = 0; base < span; base += kWave) {
         int64_t src = 0;
-        const bool msg = lp_edge(a, e0, m, base + lane, n0, n1, i, src) == 1;
+        const bool msg = lp_edge(a, e0, m, base + lane, n0, n1, i, src, ed) == 1;
         if (msg) {
             float l[kLpHeads] = {};
             lp_dot4(L.s, a.x + src * F, F, l, L.xs + lane * kLpXs);

@@ -1,7 +1,8 @@
 """Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``; its Monte-Carlo dropout
 ``sample``: ``csrc/infer_mc.hip``; its per-link ``sensitivity``: ``csrc/infer_grad.hip``, DESIGN.md
 4.16; its ``what_if`` over edited graphs: ``csrc/infer_whatif.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
-``csrc/infer_lightpath_grad.hip``).
+``csrc/infer_lightpath_grad.hip``; its ``what_if`` over candidate lightpaths:
+``csrc/infer_lightpath_whatif.hip``).
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
 TransformerConv, the NNConv forward and the read-out kernel (``LightpathGNN``: the self-looped graph index, the GAT walk
@@ -182,7 +183,7 @@ def graph_slices(data, ei, N, dev, who):
     return ptr, eptr, B, n_max, max_e, exact
 
 
-WHAT_IF_MAX_DROP = 32           # csrc/infer_whatif.hip: kWhatIfMaxDrop
+WHAT_IF_MAX_DROP = 32           # csrc/infer_whatif.hip: kWhatIfMaxDrop; csrc/infer_lightpath_dev.hpp: kLpMaxDrop
 
 
 def _host_ptr(p, name, total, who):
@@ -671,7 +672,7 @@ class TopologicalPredictor(_DeviceState):
 
 
 # ====================================================================== LightpathGNN
-LP_MAX_FEATURES = 16            # csrc/infer_lightpath_dev.hpp: kLpMaxF (both kernels)
+LP_MAX_FEATURES = 16            # csrc/infer_lightpath_dev.hpp: kLpMaxF (all three kernels)
 LP_MAX_HIDDEN = 256             # kLpMaxC
 LP_MAX_OUTPUTS = 8              # kLpMaxO; also the most outputs one sensitivity call differentiates (Q <= O)
 LP_HEADS = 4                    # kLpHeads: the columns of alpha_self / alpha_edge
@@ -680,6 +681,157 @@ LP_HEADS = 4                    # kLpHeads: the columns of alpha_self / alpha_ed
 class EnvelopeError(ValueError):
     """A model or a batch outside what ``LightpathPredictor`` runs; there is no other path behind it.  (A LUT-less batch is
     NOT one: that is the model's own ``ValueError``.)"""
+
+
+_LpWhatIf = namedtuple("_LpWhatIf", "K A R add_ptr drop_ptr")
+
+
+def lightpath_what_if_args(num_features, x_lut=None, add_src=None, add_ptr=None, drop=None, drop_ptr=None, node=None,
+                           who="LightpathPredictor.what_if"):
+    """The argument checks of ``LightpathPredictor.what_if`` (and of ``materialise_lightpath_what_if``) that need no
+    device: returns ``(K, A, R, add_ptr, drop_ptr)`` with the pointer arrays as int64 host tensors (``None`` where the
+    list is not given), or raises the named ``ValueError``.  ``K`` is the candidate count the arguments agree on, ``None``
+    when none of them states one (the caller takes the number of LUT rows)."""
+    F = int(num_features)
+
+    def shape_of(t):
+        return tuple(t.shape) if isinstance(t, torch.Tensor) else t
+
+    def index_list(t, name, what):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype.is_floating_point or t.dtype.is_complex \
+                or t.dtype == torch.bool:
+            raise ValueError(f"{who}: {name} must be a 1-d integer tensor of {what}, got {shape_of(t)!r}"
+                             f"{' of ' + str(t.dtype) if isinstance(t, torch.Tensor) else ''}")
+
+    counts = []                                            # (the argument that states a candidate count, the count)
+    if x_lut is not None:
+        if not isinstance(x_lut, torch.Tensor) or x_lut.dim() != 2 or x_lut.shape[1] != F or x_lut.dtype != torch.float32:
+            raise ValueError(f"{who}: x_lut must be a float32 tensor [K, {F}] (one feature row per candidate), got "
+                             f"{shape_of(x_lut)!r}{' of ' + str(x_lut.dtype) if isinstance(x_lut, torch.Tensor) else ''}")
+        counts.append(("x_lut", x_lut.shape[0]))
+    if node is not None:
+        index_list(node, "node", "node numbers of the batch, one per candidate")
+        counts.append(("node", node.shape[0]))
+    if (add_src is None) != (add_ptr is None):
+        raise ValueError(f"{who}: add_src and add_ptr must be given together (got only "
+                         f"{'add_ptr' if add_src is None else 'add_src'})")
+    if (drop is None) != (drop_ptr is None):
+        raise ValueError(f"{who}: drop and drop_ptr must be given together (got only "
+                         f"{'drop_ptr' if drop is None else 'drop'})")
+    A, ap, R, dp = 0, None, 0, None
+    if add_src is not None:
+        index_list(add_src, "add_src", "source node numbers of the batch")
+        A = add_src.shape[0]
+        ap = _host_ptr(add_ptr, "add_ptr", A, who)
+        counts.append(("add_ptr", ap.numel() - 1))
+    if drop is not None:
+        index_list(drop, "drop", "positions into data.edge_index")
+        R = drop.shape[0]
+        dp = _host_ptr(drop_ptr, "drop_ptr", R, who)
+        counts.append(("drop_ptr", dp.numel() - 1))
+    K = counts[0][1] if counts else None
+    for name, k in counts[1:]:
+        if k != K:
+            raise ValueError(f"{who}: {counts[0][0]} names {K} candidates, {name} {k}")
+    if dp is not None and dp.numel() > 1:
+        worst = int(dp.diff().max())
+        if worst > WHAT_IF_MAX_DROP:
+            raise ValueError(f"{who}: a candidate removes {worst} edges; at most WHAT_IF_MAX_DROP = {WHAT_IF_MAX_DROP}")
+    return _LpWhatIf(K, A, R, ap, dp)
+
+
+def materialise_lightpath_what_if(data, lut_col, x_lut=None, add_src=None, add_ptr=None, drop=None, drop_ptr=None, node=None):
+    """The explicit batch of the K candidate graphs that ``LightpathPredictor.what_if`` scores: the DEFINITION of that call
+    and what it saves.  Returns ``(batch, node_new)``; ``predict.what_if(...)[0][k]`` is, bit for bit, the row of
+    ``predict(batch)`` that belongs to node ``node_new[k]`` (``torch.searchsorted(model._lut_rows(batch), node_new)`` finds
+    it).  Pure torch, no kernel of ours; works on CPU tensors as well.
+
+    ``data``: the base batch (``x [N, F]``); ``lut_col``: the model's ``is_lut_index``.  Candidate ``k`` is about node
+    ``node[k]`` of the batch (``None``: the LUT rows ``x[:, lut_col] == 1.0`` in node order, candidate ``k`` is row ``k``) and
+    its graph ``batch[node[k]]``.  Graph ``k`` of the result is a copy of that graph's nodes with the node's feature row
+    replaced by ``x_lut[k]`` (``None``: kept), its edges less those at the positions ``drop[drop_ptr[k]:drop_ptr[k + 1]]`` of
+    ``data.edge_index`` (any order, a repeat counts once; they must lie in that graph's edge slice) in their order, and
+    behind them the edges ``(add_src[j], node[k])`` for ``j`` in ``add_ptr[k] ... add_ptr[k + 1]`` in the order given (sources
+    in the batch's node numbering, inside that graph), all renumbered to the candidate's own block.  ``node_new[k]`` is the
+    candidate's node in the new numbering.  The result carries ``x``, ``batch``, ``ptr`` and ``edge_ptr``.  Bad arguments,
+    a node outside ``0 ... N - 1``, a drop position outside its graph's slice, an added source outside its graph or an
+    effective feature row without ``1.0`` in column ``lut_col`` raise ``ValueError``."""
+    from .batch import Batch
+    who = "materialise_lightpath_what_if"
+    x = getattr(data, "x", None)
+    if x is None or x.dim() != 2:
+        raise ValueError(f"{who}: data.x must be [N, F]")
+    N, F = x.shape
+    lut_col = int(lut_col)
+    if not 0 <= lut_col < F:
+        raise ValueError(f"{who}: lut_col {lut_col} is not a column of {F} features")
+    w = lightpath_what_if_args(F, x_lut, add_src, add_ptr, drop, drop_ptr, node, who)
+    dev = x.device
+    ei = _i64(data.edge_index, dev)
+    E = ei.shape[1]
+    ptr, eptr, B, _, _, _ = graph_slices(data, ei, N, dev, who)
+    i64 = dict(dtype=torch.int64, device=dev)
+    if node is None:
+        nd = (x[:, lut_col] == 1.0).nonzero().squeeze(1)
+        if w.K is not None and w.K != nd.shape[0]:
+            raise ValueError(f"{who}: the arguments name {w.K} candidates, the batch has {nd.shape[0]} LUT rows "
+                             f"(node=None: candidate k is LUT row k)")
+    else:
+        nd = _i64(node, dev)
+        if nd.numel() and (int(nd.min()) < 0 or int(nd.max()) >= N):
+            raise ValueError(f"{who}: node must lie in 0 ... {N - 1}")
+    K = nd.shape[0]
+    g = torch.bucketize(nd, ptr[1:], right=True)           # the graph of every candidate's node
+    ar = torch.arange(K, **i64)
+    n_k, m_k = (ptr[1:] - ptr[:-1])[g], (eptr[1:] - eptr[:-1])[g]
+    nptr = torch.zeros(K + 1, **i64)
+    nptr[1:] = torch.cumsum(n_k, 0)
+    bptr = torch.zeros(K + 1, **i64)                       # the base edges of every candidate, dropped ones included
+    bptr[1:] = torch.cumsum(m_k, 0)
+    # nodes: candidate c's block is its base graph's rows, its own row replaced
+    cn = torch.repeat_interleave(ar, n_k)
+    rows = ptr[g][cn] + (torch.arange(cn.shape[0], **i64) - nptr[cn])
+    shift = nptr[:-1] - ptr[g]                             # batch node number -> the candidate's block
+    node_new = nd + shift
+    new_x = x[rows].clone()
+    if x_lut is not None:
+        new_x[node_new] = x_lut.to(device=dev, dtype=x.dtype)
+    if K and not bool((new_x[node_new, lut_col] == 1.0).all()):
+        raise ValueError(f"{who}: a candidate's feature row does not hold 1.0 in the LUT column {lut_col}")
+    # base edges: every position of the base graph's slice, less the dropped ones
+    ce = torch.repeat_interleave(ar, m_k)
+    pos = eptr[g][ce] + (torch.arange(ce.shape[0], **i64) - bptr[ce])
+    if w.R:
+        dpos = _i64(drop, dev)
+        cd = torch.repeat_interleave(ar, w.drop_ptr.to(dev).diff())
+        if bool(((dpos < eptr[g][cd]) | (dpos >= eptr[g + 1][cd])).any()):
+            raise ValueError(f"{who}: a drop position lies outside its candidate's base graph")
+        keep = ~torch.isin(ce * max(E, 1) + pos, cd * max(E, 1) + dpos)
+        ce, pos = ce[keep], pos[keep]
+    # added edges: (source, the candidate's node)
+    ca = torch.zeros(0, **i64)
+    aei = torch.zeros(2, 0, **i64)
+    if w.A:
+        ca = torch.repeat_interleave(ar, w.add_ptr.to(dev).diff())
+        src = _i64(add_src, dev)
+        if bool(((src < ptr[g][ca]) | (src >= ptr[g + 1][ca])).any()):
+            raise ValueError(f"{who}: an added source lies outside its candidate's base graph")
+        aei = torch.stack([src + shift[ca], node_new[ca]])
+    cand = torch.cat([ce, ca])
+    order = torch.argsort(cand, stable=True)               # per candidate: survivors in their order, then the additions
+    out = Batch()
+    out.num_graphs = K
+    out._num_nodes = int(rows.shape[0])
+    out.ptr, out.batch = nptr, cn
+    out.x = new_x
+    out.uniform_node_ids = None
+    out.edge_index = torch.cat([ei[:, pos] + shift[ce], aei], 1)[:, order]
+    counts = torch.bincount(cand, minlength=K)
+    out.edge_ptr = torch.zeros(K + 1, **i64)
+    out.edge_ptr[1:] = torch.cumsum(counts, 0)
+    out.graph_sizes = (int(n_k.max()), int(counts.max())) if K else (0, 0)
+    out.has_self_loops = None
+    return out, node_new
 
 
 # what LightpathPredictor._prepare hands to _launch: the model's shape, the batch on dev, which rows (rows mode: batch,
@@ -709,6 +861,8 @@ class LightpathPredictor(_DeviceState):
 
     ``predict.sensitivity(data)``: the rows together with their Jacobian wrt the node features of each row's one-hop
     in-neighbourhood, in one launch (see there).
+    ``predict.what_if(data, ...)``: K candidate lightpaths -- another feature row for a LUT node, interferers removed and
+    added -- scored in one launch (see there).
 
     Envelope -- ``EnvelopeError`` naming the condition otherwise: a model on the GPU with ``num_layers == 1``, 1 ... 16 input
     features, hidden width 1 ... 256, 1 ... 8 outputs; ``data.x`` of shape ``[N, F]``.  No cap on in-degree, graph size or
@@ -717,7 +871,9 @@ class LightpathPredictor(_DeviceState):
     """
 
     _FLAGS = ("qot_lightpath_infer", "bit 0 an edge leaves its graph's node range, bit 1 a LUT index, graph number or slice "
-                                     "outside the arrays")
+                                     "outside the arrays (what_if: bit 0 also an added source, bit 1 also a candidate's "
+                                     "node or a drop position out of range, bit 2 a candidate's feature row without 1.0 "
+                                     "in the LUT column)")
 
     def __init__(self, model):
         super().__init__()
@@ -769,9 +925,10 @@ class LightpathPredictor(_DeviceState):
             c["infer_lp"] = (tag, res)
         return (x,) + res
 
-    def _prepare(self, data, per_graph, shape=None):
+    def _prepare(self, data, per_graph, shape=None, nodes=None):
         """Everything a launch needs, checked, as an ``_LpPrepared``.  ``per_graph``: one row per graph, found on the device,
-        instead of the model's LUT rows.  ``shape``: ``_check_model()``'s answer, when the caller has asked already."""
+        instead of the model's LUT rows.  ``shape``: ``_check_model()``'s answer, when the caller has asked already.
+        ``nodes``: the nodes whose rows are computed, in the place of the model's LUT rows (``what_if``)."""
         F, C, O = shape or self._check_model()
         dev = self._device()
         x, ei, ptr, eptr, B = self._batch(data, F, dev)
@@ -779,16 +936,18 @@ class LightpathPredictor(_DeviceState):
             idx = batch = None
             rows, count = B, torch.empty(B, dtype=torch.int32, device=dev)
         else:
-            idx = self.model._lut_rows(data)        # the model's ValueError for a LUT-less batch
+            idx = self.model._lut_rows(data) if nodes is None else nodes    # the model's ValueError for a LUT-less batch
             batch, idx = _i64(data.batch, dev), _i64(idx, dev)
             rows, count = idx.shape[0], None
         self._status_on(dev)
         return _LpPrepared(F, C, O, dev, x, ei, batch, ptr, eptr, idx, B, rows, count)
 
-    def _launch(self, name, p, out, *extra):
-        """One launch of entry point ``name``: the arguments the two kernels share (``out`` among them), then ``extra``;
-        none for 0 rows (only with ``allow_empty_lut``, or an empty batch).  Returns what the call hands back beside its
-        rows: ``count``, or ``lut_batch`` -- gathered behind the launch, so that the kernel is not queued after it."""
+    def _launch(self, name, p, out, *extra, inside=True):
+        """One launch of entry point ``name``: the arguments the three kernels share (``out`` among them), then ``extra``;
+        none for 0 rows (only with ``allow_empty_lut``, an empty batch or no candidate).  Returns what the call hands back
+        beside its rows: ``count``, or ``lut_batch`` -- gathered behind the launch, so that the kernel is not queued after
+        it.  ``inside=False``: the rows' nodes are the caller's and unchecked (``what_if``); one outside ``0 ... N - 1`` has
+        -1 in ``lut_batch``."""
         F, C, O, _, x, ei, batch, ptr, eptr, idx, B, rows, count = p
         if rows:
             m = self.model
@@ -800,7 +959,15 @@ class LightpathPredictor(_DeviceState):
                       F, C, O, int(conv.heads), int(m.is_lut_index), self._status, *extra)
         if idx is None:
             return count
-        return batch.index_select(0, idx) if rows else batch[:0]
+        if not rows:
+            return batch[:0]
+        if inside:
+            return batch.index_select(0, idx)
+        N = x.shape[0]
+        if N == 0:
+            return torch.full_like(idx, -1)
+        inside = idx.clamp(0, N - 1)
+        return batch.index_select(0, inside).masked_fill_(inside != idx, -1)
 
     @torch.no_grad()
     def __call__(self, data):
@@ -863,3 +1030,65 @@ class LightpathPredictor(_DeviceState):
         second = self._launch("qot_lightpath_infer_grad", p, out, self._outputs(sel, dev), Q, jac_self, jac_edge, *alpha)
         res = (out, second, jac_self, jac_edge)
         return res + (alpha,) if return_attention_weights else res
+
+    @torch.no_grad()
+    def what_if(self, data, x_lut=None, add_src=None, add_ptr=None, drop=None, drop_ptr=None, node=None):
+        """"What if": scores K candidate lightpaths in ONE kernel launch, ``(out [K, O], lut_batch [K])``, without building
+        the candidates' graphs.  Setting up a lightpath means choosing among K (route, spectrum slot) assignments; each
+        changes the LUT node's own features and the set of established lightpaths it interferes with (its in-neighbours).
+
+        Candidate ``k`` is about node ``node[k]`` (int64 ``[K]``, the batch's node numbering; several candidates may name
+        the same node) and that node's graph.  ``node=None``: the model's LUT rows, ``K == L`` and candidate ``k`` is row
+        ``k`` (with the model's LUT-less ``ValueError`` / ``allow_empty_lut``).  It replaces the node's feature row by
+        ``x_lut[k]`` (``[K, F]`` float32; ``None`` keeps it; the effective row must hold ``1.0`` in column ``is_lut_index``),
+        removes the edges at positions ``drop[drop_ptr[k]:drop_ptr[k + 1]]`` of ``data.edge_index`` (any order, a repeat
+        counts once, at most ``WHAT_IF_MAX_DROP`` = 32 per candidate; inside the graph's edge slice; an edge that is no
+        message into the node changes nothing) and appends the messages ``add_src[add_ptr[k]:add_ptr[k + 1]] -> node[k]``
+        behind the surviving edges in the order given (int64 node numbers of the batch, inside the graph; the node itself
+        is an input self loop and no message; a source that sends already sends once more; no cap on their number).
+
+        ``materialise_lightpath_what_if`` is the definition: ``out[k]`` is, bit for bit, the row of ``self(batch)`` that
+        belongs to node ``node_new[k]`` of the batch it builds; ``lut_batch`` is ``data.batch[node]``.  A candidate's row
+        does not depend on the other candidates, and one without an edit is ``self(data)``'s row of that node.  Every
+        candidate rescans its graph's edge slice: O(m) per candidate, candidates of one node do not share the scan.
+
+        ``add_src`` with ``add_ptr``, ``drop`` with ``drop_ptr``: both or neither.  Hand the pointer arrays over as lists or
+        host tensors: they are checked on the host, a device tensor costs one read each.  With neither list, K comes
+        from ``x_lut``, ``node`` or L.
+
+        Plain tensor without ``grad_fn``; pure (no model state is touched); parameters and running statistics are read at
+        call time.  ``K == 0`` gives ``[0, O]`` without a launch.  Capture inside ``torch.cuda.graph`` is not claimed.
+        Refusals, before any launch: ``EnvelopeError`` for everything ``__call__`` refuses; ``ValueError`` naming the
+        condition for a bad shape or dtype of ``x_lut``, ``add_src``, ``drop`` or ``node``, pointer arrays not non-decreasing
+        from 0 to A (R), candidate counts that disagree between the arguments, more than 32 removals in one candidate.
+        On the device: an added source outside the candidate's graph (status bit 0), a ``node[k]`` outside ``0 ... N - 1``
+        (``lut_batch[k]`` is -1 then) or a drop position outside the graph's slice (bit 1), an effective feature row whose
+        LUT column is not exactly ``1.0`` (bit 2) give NaN in that candidate's row only, and ``check_status()`` raises."""
+        who = "LightpathPredictor.what_if"
+        # the model's shape, then the arguments, are named before the model's device and the batch are looked at
+        shape = self._check_model()
+        w = lightpath_what_if_args(shape[0], x_lut, add_src, add_ptr, drop, drop_ptr, node, who)
+        p = self._prepare(data, False, shape, node)
+        dev, K = p.dev, p.rows
+        if w.K is not None and w.K != K:
+            raise ValueError(f"{who}: the arguments name {w.K} candidates, the batch has {K} LUT rows (node=None: "
+                             f"candidate k is LUT row k)")
+        out = torch.empty(K, p.O, dtype=torch.float32, device=dev)
+
+        def on_dev(given):
+            return _i64(given, dev) if isinstance(given, torch.Tensor) and given.device == dev else None
+        xl = None if x_lut is None else _f32c(x_lut if x_lut.device == dev else x_lut.to(dev))
+        src = aptr = dpos = dptr = None
+        if w.A:
+            src, aptr = _i64(add_src, dev), on_dev(add_ptr)
+        if w.R:
+            dpos, dptr = _i64(drop, dev), on_dev(drop_ptr)
+        if w.A and w.R and aptr is None and dptr is None:   # both pointer arrays are on the host: one upload for the two
+            both = torch.cat([w.add_ptr, w.drop_ptr]).to(dev)
+            aptr, dptr = both[:K + 1], both[K + 1:]
+        elif w.A and aptr is None:
+            aptr = w.add_ptr.to(dev)
+        elif w.R and dptr is None:
+            dptr = w.drop_ptr.to(dev)
+        return out, self._launch("qot_lightpath_infer_whatif", p, out, xl, src, aptr, w.A, dpos, dptr, w.R, K,
+                                 inside=node is None)

@@ -962,6 +962,39 @@ int qot_lightpath_infer_grad(const float* x, const int64_t* edge_index, const in
                              int lut_col, int32_t* status, const int32_t* outputs, int Q, float* jac_self, float* jac_edge,
                              float* alpha_self, float* alpha_edge, qot_stream_t stream);
 
+/* ---- "what if" for the LUT rows: K candidate lightpaths in one launch (LightpathPredictor.what_if) ---
+ * Rows mode only: lut_idx [K] names the candidates' nodes (repeats are the normal case), L == K, count must be NULL.
+ * Candidate k
+ *   - replaces its node's feature row by x_lut[k, 0..F) (x_lut [K, F]; NULL: every candidate keeps its node's row);
+ *   - removes the edges at positions drop[drop_ptr[k] .. drop_ptr[k+1]) of edge_index (at most 32 per candidate; any
+ *     order, a repeat counts once; they must lie in the edge slice of the node's graph; a removed edge is not looked at
+ *     further, an edge that is no message into the node changes nothing; drop_ptr NULL: no removals);
+ *   - appends the messages add_src[add_ptr[k] .. add_ptr[k+1]) -> its node behind the surviving edges, in the order given
+ *     (int64 node numbers of the batch inside the node's graph; a source equal to the node is an input self loop and no
+ *     message; a source that sends already sends once more; no cap on their number; add_ptr NULL: no additions).
+ * out[k, 0..O) ([K, O]) is, bit for bit, the row qot_lightpath_infer writes for that node in the explicitly built graph
+ * (the base graph's nodes with that one row replaced, its surviving edges in their order, the added edges behind them):
+ * the same code runs the same sums in the same order -- the messages one after the other by rising position, the
+ * additions behind the slice, the self loop last.  A candidate's row does not depend on the other candidates, and a
+ * candidate without an edit has qot_lightpath_infer's row.  One wavefront per candidate, each rescans its graph's edge
+ * slice; the batch is only read.  Everything else as qot_lightpath_infer.
+ * Return codes, before any launch, in that entry's order: QOT_ERR_BADARG for a negative size or L != K, then the
+ * envelope (QOT_ERR_UNSUPPORTED), then -- when K > 0 -- QOT_ERR_BADARG for a NULL required pointer, a NULL lut_idx, a
+ * non-NULL count, A > 0 without add_src / add_ptr or R > 0 without drop / drop_ptr.  K == 0: QOT_OK, no launch.
+ * status: bit 0 = an edge of the slice that is not removed, or an added source, leaves the graph's node range; bit 1 =
+ * lut_idx[k] outside 0 .. N-1, a drop position outside the graph's edge slice, more than 32 removals, list slices or graph
+ * slices outside the arrays; bit 2 = the candidate's effective feature row does not hold exactly 1.0f in column lut_col.
+ * Only the flagged candidate's row is NaN; nothing is read through an offending index. */
+int qot_lightpath_infer_whatif(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                               const int64_t* edge_ptr, const int64_t* lut_idx, int64_t L, int64_t N, int64_t E, int64_t B,
+                               const float* w, const float* att_src, const float* att_dst, const float* conv_bias,
+                               float slope_att, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                               const float* bn_var, float bn_eps, const float* w0, const float* b0, const float* w3,
+                               const float* b3, float slope_head, float* out, int32_t* count, int F, int C, int O, int heads,
+                               int lut_col, int32_t* status, const float* x_lut, const int64_t* add_src,
+                               const int64_t* add_ptr, int64_t A, const int64_t* drop, const int64_t* drop_ptr, int64_t R,
+                               int64_t K, qot_stream_t stream);
+
 /* ---- graph construction from network-status samples (csrc/status_graph.hip) ----------------
  * data [S, P, L, Q] fp64 (sample, lp_feat, link, freq), target [S, M] fp64, freq [Q] fp64, all on the device.  samples
  * [G] int64 picks the samples of the call, in order, repeats allowed (NULL: samples 0 .. G-1).  One workgroup per

@@ -61,6 +61,17 @@ are compared first (equal bits); then they alternate in one process, each call b
 and interquartile range as above.
 
     python tools/bench_infer.py --what-if 1 64 1024 [--out profiles/bench_infer_whatif.jsonl]
+
+``--kind lightpath --what-if K [K ...]``: K candidate lightpaths scored in one launch (csrc/infer_lightpath_whatif.hip,
+DESIGN.md 4.19) -- milliseconds per call of ``predict.what_if(data, ...)`` against (a)
+``infer.materialise_lightpath_what_if(...)`` followed by ``predict(batch)`` per call and (b) ``predict`` alone on a batch
+materialised beforehand, as above.  One ``synthetic.lightpath_batch`` graph (a chain of 20 lightpaths, node 0 the LUT) at
+C = 32, F = 5; every candidate is about the LUT node and has a fresh feature row, 2 removals (seeded positions of the
+graph's 38 edges) and 2 additions (seeded sources).  The rows of the three ways are compared first (equal bits; the
+graph has one LUT node, so the LUT rows of the materialised batch are the candidates in order and (a) and (b) pick
+nothing); output and the interquartile rule as for the topological table.
+
+    python tools/bench_infer.py --kind lightpath --what-if 1 8 64 1024 [--out profiles/bench_infer_lightpath_whatif.jsonl]
 """
 import argparse
 import json
@@ -361,6 +372,73 @@ def main_what_if(args, device, commit):
               f"{cell('prebuilt')} | {versus(r, 'materialise')} | {versus(r, 'prebuilt')} |")
 
 
+def measure_lightpath_what_if(K, device, rounds, warmup):
+    from gnn_qot_estimation_amd import infer
+    torch.manual_seed(0)
+    model = q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval()
+    data = S.lightpath_batch(1, min_nodes=20, max_nodes=20).to(device)     # one graph: the lightpath under test and 19 others
+    n, e = int(data.x.shape[0]), int(data.edge_index.shape[1])
+    predict = q.LightpathPredictor(model)
+    gen = torch.Generator().manual_seed(K)
+    x_lut = torch.rand(K, 5, generator=gen)
+    x_lut[:, 1] = 1.0
+    x_lut = x_lut.to(device)
+    node = torch.zeros(K, dtype=torch.long, device=device)                  # every candidate is about the LUT node
+    add = (1 + torch.randint(0, n - 1, (2 * K,), generator=gen)).to(device)
+    first = torch.randint(0, e, (K,), generator=gen)
+    drop = torch.stack([first, (first + 1 + torch.randint(0, e - 1, (K,), generator=gen)) % e], 1).reshape(-1).to(device)
+    ptr = torch.arange(0, 2 * K + 1, 2)                    # a host tensor: checked on the host, uploaded per call
+    kw = dict(x_lut=x_lut, add_src=add, add_ptr=ptr, drop=drop, drop_ptr=ptr, node=node)
+    mat, node_new = infer.materialise_lightpath_what_if(data, 1, **kw)
+    # the graph has one LUT node, so the LUT rows of the materialised batch are the candidates, in order: nothing to pick
+    assert torch.equal(model._lut_rows(mat), node_new)
+
+    ways = {"what_if": lambda: predict.what_if(data, **kw)[0],
+            "materialise": lambda: predict(infer.materialise_lightpath_what_if(data, 1, **kw)[0])[0],
+            "prebuilt": lambda: predict(mat)[0]}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    assert torch.equal(got["what_if"], got["prebuilt"]) and torch.equal(got["materialise"], got["prebuilt"]), K
+    assert tuple(got["what_if"].shape) == (K, 3) and bool(torch.isfinite(got["what_if"]).all())
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed_event(fn))
+    res = dict(shape="lightpath B=1", kind="lightpath_what_if", K=K, added_per_candidate=2, dropped_per_candidate=2, B=1,
+               C=32, F=5, N=n, E=e, rounds=rounds, equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_lightpath_what_if(args, device, commit):
+    rows = []
+    for K in args.what_if:
+        res = measure_lightpath_what_if(K, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| shape | K | what_if ms (IQR) | (a) materialise + predict ms (IQR) | (b) predict, prebuilt ms (IQR) | (a) / what_if "
+          "| (b) / what_if |")
+    print("|---|---|---|---|---|---|---|")
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['shape']} (N={r['N']}, E={r['E']}, C={r['C']}, F={r['F']}) | {r['K']} | {cell('what_if')} | "
+              f"{cell('materialise')} | {cell('prebuilt')} | {versus(r, 'materialise')} | {versus(r, 'prebuilt')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -521,11 +599,11 @@ def main():
                          "(with --kind lightpath: LightpathPredictor's)")
     ap.add_argument("--what-if", type=int, nargs="+", default=None, metavar="K", dest="what_if",
                     help="what-if: predict.what_if on K one-lightpath candidates against materialise_what_if + predict and "
-                         "predict on a prebuilt batch")
+                         "predict on a prebuilt batch (with --kind lightpath: LightpathPredictor's, K candidates of the "
+                         "LUT node)")
     args = ap.parse_args()
-    if args.what_if is not None and (args.kind != "topological" or args.mc is not None or args.grad
-                                     or any(k < 1 for k in args.what_if)):
-        raise SystemExit("--what-if K [K ...] (K >= 1) is a run of its own, for the topological model")
+    if args.what_if is not None and (args.mc is not None or args.grad or any(k < 1 for k in args.what_if)):
+        raise SystemExit("--what-if K [K ...] (K >= 1) is a run of its own")
     if args.mc is not None and args.kind != "topological":
         raise SystemExit("--mc is for the topological model")
     if args.mc is not None and args.grad:
@@ -536,6 +614,8 @@ def main():
         raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    if args.kind == "lightpath" and args.what_if is not None:
+        return main_lightpath_what_if(args, device, commit)
     if args.kind == "lightpath":
         return (main_lightpath_grad if args.grad else main_lightpath)(args, device, commit)
     if args.what_if is not None:
