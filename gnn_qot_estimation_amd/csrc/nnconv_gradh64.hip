@@ -32,8 +32,7 @@ constexpr int kGhCap = 256;   // edges of a tile staged in LDS by the grad-h ker
 // PRESPLIT (split form only): the g tile goes to LDS as three bf16 planes, each [step][lane] u32x4 -- every value split once
 // per tile, an A fragment = three ds_read_b128.  false: the fp32 tile of the fp32 form, every fragment split after its
 // read, by every wave for each of its blocks (16 times per value; kept for comparison, QOT_GRADH_SPLIT_AFTER_READ=1).
-constexpr int kGhPlStep = 66;                // u32x4 per step of a plane: 64 lanes + 32 B, the four steps' stores 8 banks apart
-constexpr int kGhPlLd = 4 * kGhPlStep;       // u32x4 per plane
+// The plane layout (kGhPlStep, kGhPlLd) and its store are split_bf16.hpp's: the forward kernel shares them.
 
 template <int D, bool SPLIT = false, bool PRESPLIT = false>
 __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
@@ -164,16 +163,9 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
                 for (int p = beg + sub; p < end && p < lim; p += 8) sr[p - e_t0] = il;
             }
             if constexpr (PRESPLIT) {
-                // This thread's 8 channels are group sub = 2 s + q of row il: elements 4 q + r of step s, components r of half
-                // hi = 0 (even channels) in words 0-1 of each split plane and of hi = 1 in words 2-3 -- what mfma_split_step
-                // forms from groups 2 s and 2 s + 1.  Six 8-byte stores; rows of absent nodes are zero planes.
-                const Bf3 gs = split8(make_float4(g0.x, g0.z, g1.x, g1.z), make_float4(g0.y, g0.w, g1.y, g1.w));
-                uint2* pl = reinterpret_cast<uint2*>(Gt) + 2 * ((sub >> 1) * kGhPlStep + il) + (sub & 1);
-                const u32x4 ph = __builtin_bit_cast(u32x4, gs.h), pm = __builtin_bit_cast(u32x4, gs.m),
-                            plo = __builtin_bit_cast(u32x4, gs.l);
-                pl[0] = make_uint2(ph[0], ph[1]);                      pl[64] = make_uint2(ph[2], ph[3]);
-                pl[2 * kGhPlLd] = make_uint2(pm[0], pm[1]);            pl[2 * kGhPlLd + 64] = make_uint2(pm[2], pm[3]);
-                pl[4 * kGhPlLd] = make_uint2(plo[0], plo[1]);          pl[4 * kGhPlLd + 64] = make_uint2(plo[2], plo[3]);
+                // This thread's 8 channels are group sub = 2 s + q of row il, split once (split_bf16.hpp: store_split_planes);
+                // rows of absent nodes are zero planes.
+                store_split_planes(Gt, sub, il, g0, g1);
             } else {
                 Gt4[at4_slot(sub, 0, il)] = make_float4(g0.x, g0.z, g1.x, g1.z);
                 Gt4[at4_slot(sub, 1, il)] = make_float4(g0.y, g0.w, g1.y, g1.w);

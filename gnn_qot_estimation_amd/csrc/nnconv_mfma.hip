@@ -21,6 +21,7 @@
 //            lets TWO workgroups share a CU (2 x 80 KB needs every byte of the 160 KiB and
 //            was measured to run one workgroup per CU: gather and MFMA phases serialised).
 //   phase 3  K halves summed through LDS, bias added, 128-B row segments stored.
+// (The split-bf16 forward, the production form, publishes the tile as bf16 planes in two equal K phases instead: PRESPLIT below.)
 // One workgroup gathers while its CU-mate owns the MFMA pipes.  TRANSPOSE runs the adjoint (grad_x) over the CSC with the mean scale taken at
 // the gathered end.
 #include "common.hpp"
@@ -36,12 +37,14 @@ namespace qot {
 // h = relu(W1 ea + b1) once; the per-edge loop then only broadcasts (8-lane shuffles) and
 // streams the 256-B source rows, four edges in flight per group.
 // Returns the destination's own row (root block) in registers; blocks 0..K go to LDS.
-template <int D, bool TRANSPOSE>
+// PRESPLIT: At holds bf16 planes of (K + 2) / 2 blocks (split_bf16.hpp: store_split_planes); the first half of the blocks is
+// split and stored, the others are returned in park0 / park1 (fp32, as accumulated) for the kernel's second phase.
+template <int D, bool TRANSPOSE, bool PRESPLIT = false>
 __device__ __forceinline__ void nnconv_gather_tile(
     float* __restrict__ At, const float* __restrict__ x, int ldx, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const int32_t* __restrict__ eidx, const float* __restrict__ invdeg,
-    int64_t tile0, int64_t N, float4& root0, float4& root1) {
+    int64_t tile0, int64_t N, float4& root0, float4& root1, float4* park0 = nullptr, float4* park1 = nullptr) {
     constexpr int K = 2 * D;
     const int sub = threadIdx.x & 7, il = threadIdx.x >> 3;
     const int c0 = 8 * sub;
@@ -129,6 +132,14 @@ __device__ __forceinline__ void nnconv_gather_tile(
 #undef QOT_FWD_BATCH
 #undef QOT_EDGE4
 #undef QOT_ACC
+    if constexpr (PRESPLIT) {
+        constexpr int HB = (K + 2) / 2;
+#pragma unroll
+        for (int kk = 0; kk < HB; ++kk)
+            store_split_planes(reinterpret_cast<u32x4*>(At) + kk * 3 * kGhPlLd, sub, il, acc0[kk], acc1[kk]);
+#pragma unroll
+        for (int kk = HB; kk <= K; ++kk) { park0[kk - HB] = acc0[kk]; park1[kk - HB] = acc1[kk]; }
+    } else {
     float4* At4 = reinterpret_cast<float4*>(At);
 #pragma unroll
     for (int kk = 0; kk <= K; ++kk) {       // channels c0+{0,2,4,6} -> hi 0 ; c0+{1,3,5,7} -> hi 1
@@ -136,11 +147,22 @@ __device__ __forceinline__ void nnconv_gather_tile(
         At4[at4_slot(g, 0, il)] = make_float4(acc0[kk].x, acc0[kk].z, acc1[kk].x, acc1[kk].z);
         At4[at4_slot(g, 1, il)] = make_float4(acc0[kk].y, acc0[kk].w, acc1[kk].y, acc1[kk].w);
     }
+    }
 }
 
 // SPLIT (forward only): the products on the bf16 matrix pipe (split_bf16.hpp).  Ws: Wcat pre-split into three bf16
 // planes ws_planes u32x4 apart (qot_nnconv_fused_split); the A fragments are split after their ds_read_b128, i.e. by both column-half waves.
-template <int D, bool TRANSPOSE, bool SPLIT = false>
+// PRESPLIT (split form only): every value of the operand tile is split ONCE, by the gather thread that holds it, and LDS
+// holds bf16 planes (split_bf16.hpp: store_split_planes) -- an A fragment is three ds_read_b128, no split8 in the MFMA loops.
+// The K + 2 blocks of the inner dimension as planes are 6 B per value (120 KB at D = 4), so the tile is published in two
+// equal halves: phase A = blocks 0 .. (K+2)/2 - 1, phase B = the others (root block last), which wait in registers as fp32
+// and are split and stored into the same storage behind the barrier that ends phase A's reads.  Wave (nh, kh) takes steps
+// kh (K+2) .. kh (K+2) + K + 1 of each phase; the B ring runs across the phase boundary.  63,360 B of planes + 8 KB for the
+// K-half exchange (which can no longer alias the image) = 71,552 B at D = 4.  false: the split-after-read loop
+// (QOT_NNCONV_FWD_SPLIT_AFTER_READ=1), every value split by both column-half waves.
+__host__ __device__ constexpr int fwd_plane_off(int p) { return (p / 4) * 3 * kGhPlLd + (p % 4) * kGhPlStep; }   // u32x4, phase-local step p
+
+template <int D, bool TRANSPOSE, bool SPLIT = false, bool PRESPLIT = false>
 __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     const float* __restrict__ x, int ldx, const float* __restrict__ ea, const float* __restrict__ w1,
     const float* __restrict__ b1, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -148,11 +170,14 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     const float* __restrict__ bias, float* __restrict__ out, int64_t N, ActParams act,
     const u32x4* __restrict__ Ws = nullptr, int64_t ws_planes = 0) {
     static_assert(!SPLIT || !TRANSPOSE, "split form: forward only");
+    static_assert(!PRESPLIT || SPLIT, "the planes are the split form's");
     constexpr int K = 2 * D;
     constexpr int KM = (K + 1) * 64;        // inner dimension held in LDS (blocks 0..K)
     constexpr int GM = KM / 16;             // float4 B groups per wave for the main part
     constexpr int CH = 4;                       // prefetch chunk (GM = 8D+4 is divisible by 4); 6 spilled inside the MFMA loop
-    __shared__ __attribute__((aligned(16))) float At[KM * 32];
+    constexpr int HB = (K + 2) / 2;             // PRESPLIT: blocks per phase
+    constexpr int PLF = HB * 3 * kGhPlLd * 4;   // PRESPLIT: floats of the plane image; the K-half exchange follows it
+    __shared__ __attribute__((aligned(16))) float At[PRESPLIT ? PLF + 4 * 8 * 64 : KM * 32];
     const int64_t ntiles = (N + 31) / 32;
     // read once per kernel: inside the tile loop each was a load consumed on the spot (an L2 round trip per tile)
     const float bz = bias ? bias[((threadIdx.x >> 6) & 1) * 32 + (threadIdx.x & 31)] : 0.f;
@@ -165,7 +190,13 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     if (tile < 0) break;
     const int64_t tile0 = tile * 32;
     float4 root0, root1;
-    nnconv_gather_tile<D, TRANSPOSE>(At, x, ldx, ea, w1, b1, rowptr, col, eidx, invdeg, tile0, N, root0, root1);
+    float4 park0[PRESPLIT ? HB : 1], park1[PRESPLIT ? HB : 1];      // PRESPLIT: phase B's blocks, root block last
+    if constexpr (PRESPLIT) {
+        nnconv_gather_tile<D, false, true>(At, x, ldx, ea, w1, b1, rowptr, col, eidx, invdeg, tile0, N, park0[HB - 1],
+                                           park1[HB - 1], park0, park1);
+    } else {
+        nnconv_gather_tile<D, TRANSPOSE>(At, x, ldx, ea, w1, b1, rowptr, col, eidx, invdeg, tile0, N, root0, root1);
+    }
     const float4* At4 = reinterpret_cast<const float4*>(At);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nh = wave & 1, kh = wave >> 1;
@@ -173,7 +204,67 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     f32x16 c;
 #pragma unroll
     for (int r = 0; r < 16; ++r) c[r] = 0.f;
-    if constexpr (SPLIT) {
+    if constexpr (PRESPLIT) {
+        // Ws as below.  The wave's steps of both phases are one sequence of 2 NCS chunks of SC steps; B fragments are requested
+        // NBS - 1 chunks ahead into a ring with compile-time slots (fully unrolled), also across the phase boundary.
+        constexpr int SP = K + 2;                  // steps per wave and phase (a phase has 2 SP = 4 HB steps)
+        constexpr int ST = 4 * SP;                 // steps per column half
+        constexpr int SC = 2;                      // steps per chunk
+        constexpr int NCS = SP / SC;               // chunks per phase
+        constexpr int NBS = 3;                     // buffers: 2 chunks (24 MFMAs) of lookahead
+        // chunk j, step u: phase j / NCS, step (j % NCS) SC + u.  The wave's part of the address is kept scalar (the wave index
+        // through readfirstlane), so a request is `global_load_dwordx4 v, lane * 16, s[base]` with SALU address arithmetic:
+        // as per-lane 64-bit pointers the 6 NCS SC addresses were computed in front of the tile loop and spilled.
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        const u32x4* wsp = Ws + ((int64_t)(wv & 1) * ST + (wv >> 1) * SP) * 64;
+        const unsigned lane_u = lane;
+        // A fragments: phase-local step kh SP + t at fwd_plane_off(kh SP + t).  SP is 0 or 2 mod 4, so the offset is a
+        // compile-time one on top of two per-wave bases: one for the chunks with t = 0, 1 mod 4, one for t = 2, 3 mod 4.
+        const u32x4* plane = reinterpret_cast<const u32x4*>(At) + lane;
+        const u32x4* pl_e = plane + kh * (fwd_plane_off(SP) - fwd_plane_off(0));
+        const u32x4* pl_o = plane + kh * (fwd_plane_off(SP + 2) - fwd_plane_off(2));
+        Bf3 sb[NBS][SC];
+#define QOT_FWD_BLOAD(J)                                                                                \
+        _Pragma("unroll") for (int u = 0; u < SC; ++u)                                                  \
+            sb[(J) % NBS][u] = load_split_b(wsp + (((J) / NCS) * 2 * SP + ((J) % NCS) * SC + u) * 64, lane_u, ws_planes);
+#define QOT_FWD_ALOAD(J)                                                                                \
+        _Pragma("unroll") for (int u = 0; u < SC; ++u) {                                                \
+            const int t = ((J) % NCS) * SC + u;                                                         \
+            af[(J) & 1][u] = load_split_b(((t & 2) ? pl_o : pl_e) + fwd_plane_off(t), kGhPlLd);         \
+        }
+        // One chunk: the ring's request NBS - 1 chunks ahead and the next chunk's A fragments (same phase) are issued in front
+        // of this chunk's 6 SC MFMAs; the scheduling barriers keep them there (left to itself the scheduler sank the requests
+        // next to their uses: `s_waitcnt vmcnt(0)` inside the chain)
+#define QOT_FWD_CHUNK(J)                                                                                \
+        {                                                                                               \
+            if ((J) + NBS - 1 < 2 * NCS) { QOT_FWD_BLOAD((J) + NBS - 1) }                               \
+            if (((J) + 1) % NCS != 0) { QOT_FWD_ALOAD((J) + 1) }                                        \
+            __builtin_amdgcn_sched_barrier(0);                                                          \
+            _Pragma("unroll") for (int u = 0; u < SC; ++u) c = mfma_split6(af[(J) & 1][u], sb[(J) % NBS][u], c); \
+            __builtin_amdgcn_sched_barrier(0);                                                          \
+        }
+        Bf3 af[2][SC];
+#pragma unroll
+        for (int j = 0; j < NBS - 1; ++j) QOT_FWD_BLOAD(j)
+        lds_barrier();                         // phase A's planes are published
+        QOT_FWD_ALOAD(0)
+#pragma unroll
+        for (int j = 0; j < NCS; ++j) QOT_FWD_CHUNK(j)
+        lds_barrier();                         // everyone is done with phase A's planes
+        {
+            const int sub = threadIdx.x & 7, il = threadIdx.x >> 3;
+#pragma unroll
+            for (int kk = 0; kk < HB; ++kk)
+                store_split_planes(reinterpret_cast<u32x4*>(At) + kk * 3 * kGhPlLd, sub, il, park0[kk], park1[kk]);
+        }
+        lds_barrier();                         // phase B's planes are published (LDS only: the ring's requests stay in flight)
+        QOT_FWD_ALOAD(NCS)
+#pragma unroll
+        for (int j = NCS; j < 2 * NCS; ++j) QOT_FWD_CHUNK(j)
+#undef QOT_FWD_ALOAD
+#undef QOT_FWD_CHUNK
+#undef QOT_FWD_BLOAD
+    } else if constexpr (SPLIT) {
         // Ws: 3 planes of ws_planes u32x4, each [nh][16-deep step s][lane]; step s = fp32 groups 2s, 2s + 1 (split_bf16.hpp).  The
         // native loop's structure: root fragments and NB - 1 chunks requested before the barrier, compile-time buffers.
         constexpr int ST = (K + 2) * 64 / 16;      // steps per column half
@@ -289,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
     }
     // K halves meet through LDS; every wave finishes 8 of the 16 accumulator registers of its
     // (column half), so the stores are spread over all four waves
-    float* red = At + 64 * 32;             // disjoint from block 0, which other waves may still read
+    float* red = At + (PRESPLIT ? PLF : 64 * 32);      // disjoint from block 0, which other waves may still read; PRESPLIT: behind the planes
     // (compile-time register indices in both branches: a runtime index into the accumulator
     //  vector would be lowered through scratch)
     if (kh) {
@@ -352,7 +443,10 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
             if (i < N) out[i * 64 + colg] = y;
         }
     }
-    lds_barrier();                         // `red` is consumed before the next tile's gather overwrites it
+    // `red` is consumed before the next tile's gather overwrites it.  PRESPLIT: `red` is storage of its own; the next tile's
+    // plane stores follow the barrier above (every wave is through with phase B's reads when it writes `red`), its `red`
+    // stores follow three more barriers
+    if constexpr (!PRESPLIT) lds_barrier();
     }
 }
 
@@ -764,11 +858,22 @@ extern "C" int qot_nnconv_fused_split(const float* x, int ld_x, const float* edg
     int grid = grid_for(N, 32);
     if (grid > 2 * num_cus()) grid = 2 * num_cus();
     const ActParams ap = make_act(act, act_slope, act_p, act_seed, act_step);
+    // The operand tile is split once per tile on its way to LDS, in two K phases, unless QOT_NNCONV_FWD_SPLIT_AFTER_READ=1 (the
+    // earlier loop: another per-wave summation order, so the last bits differ).  Read per call, not cached: callers flip it
+    // inside one process.
+    const char* sar_env = getenv("QOT_NNCONV_FWD_SPLIT_AFTER_READ");
+    const bool presplit = !(sar_env && sar_env[0] == '1' && sar_env[1] == '\0');
     QOT_DISPATCH_D(D, {
-        if (kD <= 4)
-            nnconv_mfma64_kernel<(kD <= 4 ? kD : 4), false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
-                x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, nullptr, bias, out, N, ap,
-                static_cast<const u32x4*>(w_split), split_stride / 8);
+        if (kD <= 4) {
+            if (presplit)
+                nnconv_mfma64_kernel<(kD <= 4 ? kD : 4), false, true, true><<<grid, 256, 0, (hipStream_t)stream>>>(
+                    x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, nullptr, bias, out, N, ap,
+                    static_cast<const u32x4*>(w_split), split_stride / 8);
+            else
+                nnconv_mfma64_kernel<(kD <= 4 ? kD : 4), false, true><<<grid, 256, 0, (hipStream_t)stream>>>(
+                    x, ld_x, edge_attr, w1, b1, rowptr, col, edge_ids, invdeg, nullptr, bias, out, N, ap,
+                    static_cast<const u32x4*>(w_split), split_stride / 8);
+        }
     });
     QOT_LAUNCH_CHECK();
     return QOT_OK;

@@ -106,6 +106,37 @@ __device__ __forceinline__ Bf3 load_split_b(const u32x4* __restrict__ p, int64_t
     return b;
 }
 
+// The same with the step's address wave-uniform (scalar registers) and the lane as a 32-bit offset of its own
+__device__ __forceinline__ Bf3 load_split_b(const u32x4* __restrict__ p, unsigned lane, int64_t ps) {
+    Bf3 b;
+    b.h = __builtin_bit_cast(bf16x8, p[lane]);
+    b.m = __builtin_bit_cast(bf16x8, (p + ps)[lane]);
+    b.l = __builtin_bit_cast(bf16x8, (p + 2 * ps)[lane]);
+    return b;
+}
+
+// A 32-row x 64-channel operand block pre-split in LDS (grad-h's g tile, the forward's operand blocks): three bf16 planes
+// kGhPlLd u32x4 apart, each [16-deep step s of 4][lane = 32 hi + row] u32x4 in the bf16 MFMA's A-fragment order, so that an
+// A fragment is load_split_b(planes + s * kGhPlStep + lane, kGhPlLd).  The steps are 66 u32x4 apart (64 lanes + 32 B): a
+// 16-lane group of the stores below holds two rows x four steps x two q, and with the steps exactly 1 KB apart all four
+// steps would land on the same 8 banks; 32 B more shift step s by 8 banks -- conflict-free.
+constexpr int kGhPlStep = 66;                // u32x4 per step of a plane
+constexpr int kGhPlLd = 4 * kGhPlStep;       // u32x4 per plane
+
+// The store: thread (il, sub) holds channels 8 sub .. 8 sub + 7 of row il in (c0, c1), i.e. fp32 fragment group sub =
+// 2 s + q: elements 4 q + r of step s, components r of half hi = 0 (even channels) in words 2q, 2q + 1 of each plane and
+// of hi = 1 (odd channels) likewise -- what mfma_split_step forms from groups 2 s and 2 s + 1.  Every value is split once;
+// six 8-byte stores; a zero row gives zero planes.
+__device__ __forceinline__ void store_split_planes(void* planes, int sub, int il, float4 c0, float4 c1) {
+    const Bf3 gs = split8(make_float4(c0.x, c0.z, c1.x, c1.z), make_float4(c0.y, c0.w, c1.y, c1.w));
+    uint2* pl = reinterpret_cast<uint2*>(planes) + 2 * ((sub >> 1) * kGhPlStep + il) + (sub & 1);
+    const u32x4 ph = __builtin_bit_cast(u32x4, gs.h), pm = __builtin_bit_cast(u32x4, gs.m),
+                plo = __builtin_bit_cast(u32x4, gs.l);
+    pl[0] = make_uint2(ph[0], ph[1]);                      pl[64] = make_uint2(ph[2], ph[3]);
+    pl[2 * kGhPlLd] = make_uint2(pm[0], pm[1]);            pl[2 * kGhPlLd + 64] = make_uint2(pm[2], pm[3]);
+    pl[4 * kGhPlLd] = make_uint2(plo[0], plo[1]);          pl[4 * kGhPlLd + 64] = make_uint2(plo[2], plo[3]);
+}
+
 // One 16-deep step from a fragment-grouped fp32 LDS tile: the A fragments of groups g and g + 1 (two ds_read_b128), split
 // after the read, times a pre-split B fragment.
 __device__ __forceinline__ f32x16 mfma_split_step(const float4* __restrict__ At4, int g, int hi, int r31, const Bf3& b,

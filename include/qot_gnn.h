@@ -294,7 +294,10 @@ int qot_nnconv_fused(const float* x, int ld_x, const float* edge_attr, const flo
                      qot_stream_t stream);
 /* H == 64, transpose = 0 only: as qot_nnconv_fused with the products on the bf16 matrix pipe, each fp32 product as six
  * bf16 cross products of three-way splits (csrc/split_bf16.hpp).  w_split: Wcat split into three bf16 planes
- * split_stride elements apart (functional.nnconv_split_index, the QOT_ROLE_GATHER3 split part), 16-byte aligned. */
+ * split_stride elements apart (functional.nnconv_split_index, the QOT_ROLE_GATHER3 split part), 16-byte aligned.
+ * The operand tile is split once per tile on its way to LDS (bf16 planes, two K phases) unless
+ * QOT_NNCONV_FWD_SPLIT_AFTER_READ=1 is set in the environment, read on every call: the earlier loop, which splits every
+ * fragment after its read (another per-wave summation order: results differ in the last bits). */
 int qot_nnconv_fused_split(const float* x, int ld_x, const float* edge_attr, const float* w1,
                            const float* b1, const int32_t* rowptr, const int32_t* col,
                            const int32_t* edge_ids, const float* invdeg, const void* w_split,
