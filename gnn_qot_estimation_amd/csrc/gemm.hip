@@ -41,6 +41,8 @@ __device__ __forceinline__ void gemm_read_frag(GemmFrag& f, const float4* __rest
 
 // 16 MFMAs of one k group; the four accumulators take turns: consecutive MFMAs never wait for each other's result
 __device__ __forceinline__ void gemm_group_mfma(const GemmFrag& f, f32x16 (&c)[2][2]) {
+    // (a macro on the component: written as mfma4 per accumulator, i.e. in accumulator-major order, the kernels came out
+    //  with other address arithmetic and up to 27 more VGPRs)
 #define QOT_STEP(COMP)                                                                                       \
     c[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[0].COMP, f.b[0].COMP, c[0][0], 0, 0, 0);             \
     c[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[0].COMP, f.b[1].COMP, c[0][1], 0, 0, 0);             \
@@ -91,6 +93,7 @@ __device__ __forceinline__ void gemm_tile_to_lds(float* __restrict__ tile, const
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
+                // (acc_row(r, hi) spelled out: with the helper's grouping the tile's address arithmetic came out differently)
                 const int pm = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 const int pn = wn * 64 + j * 32 + r31;
                 tile[pm * 128 + (pn ^ ((pm & 7) << 2))] = c[i][j][r];      // XOR on float4 granularity: conflict-free both ways

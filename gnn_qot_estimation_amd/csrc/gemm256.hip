@@ -41,6 +41,8 @@ __device__ __forceinline__ void g2_read_b(float4 (&b)[4], const float4* __restri
 
 // 16 MFMAs of band i of one k group: four accumulators take turns
 __device__ __forceinline__ void g2_band_mfma(const float4& a, const float4 (&b)[4], f32x16 (&c)[4]) {
+    // (a macro on the component: written as mfma4 per accumulator, i.e. in accumulator-major order, the kernels came out
+    //  with other register counts and two or three more s_waitcnt)
 #define QOT_STEP(COMP)                                                                                       \
     _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                            \
         c[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.COMP, b[j].COMP, c[j], 0, 0, 0);
@@ -72,29 +74,6 @@ __device__ __forceinline__ void g2_zero(f32x16 (&c)[4][4]) {
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) c[i][j][r] = 0.f;
-}
-
-// One 32-row band of a wave's quarter (MFMA row i) through the wave's OWN 16 KB of LDS -- no workgroup barrier: a wave's
-// LDS operations complete in order -- so that the global stores are 16 B per lane, 512 contiguous bytes per row.
-// emit(pm, q4, v): row pm of the band, float4 q4 of the wave's 128 columns.
-template <class Emit>
-__device__ __forceinline__ void g2_band_out(float* __restrict__ reg, const f32x16 (&c)[4][4], int i, int hi, int r31, int lane,
-                                            Emit emit) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int pm = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const int pn = j * 32 + r31;
-            reg[pm * 128 + (pn ^ ((pm & 7) << 2))] = c[i][j][r];
-        }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-        const int idx = it * 64 + lane;
-        const int pm = idx >> 5, q4 = idx & 31;
-        emit(pm, q4, ld4(reg + pm * 128 + ((4 * q4) ^ ((pm & 7) << 2))));
-    }
 }
 
 // ---- NT: C[M, N] = A'[M, K] . B[N, K]^T (+ bias), persistent over the output tiles ------------------------------

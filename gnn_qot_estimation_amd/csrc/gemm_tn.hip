@@ -10,10 +10,9 @@
 // to a slab per workgroup (plain stores) and a second pass sums the slabs in a fixed order:
 // bitwise reproducible, no float atomics.
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace qot {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTnBlocks = 256;     // one 512-thread workgroup per CU
 
@@ -74,10 +73,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_kernel(const float* __restrict
 #pragma unroll
     for (int t = 0; t < TPW; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            slab[((kb0 + 4 * t) * 32 + row) * 64 + nh * 32 + r31] = c[t][r];
-        }
+        for (int r = 0; r < 16; ++r)
+            slab[((kb0 + 4 * t) * 32 + acc_row(r, hi)) * 64 + nh * 32 + r31] = c[t][r];
 }
 
 // Sums the slabs of group blockIdx.y (per_group consecutive slabs, slab_stride floats apart)

@@ -1,5 +1,7 @@
-// Helpers shared by the fused NNConv kernels (nnconv_mfma.hip: H = 64 tuned; nnconv_gen.hip: other widths):
-// the fragment-grouped LDS operand tile, the 4-MFMA group, the LDS-only barrier, the XCD-aware persistent tile walk.
+// Helpers shared by the MFMA kernels (nnconv_mfma.hip, nnconv_gradh64.hip: H = 64 tuned; nnconv_gen.hip: other widths;
+// gemm*.hip): the fragment-grouped LDS operand tile and its store, the accumulator row map, the 4-MFMA group, the edge MLP's
+// hidden vector, the quad-shared dropout draws, the LDS-only barrier, the XCD-aware persistent tile walk.
+// A kernel that spells one of these out instead says next to the spot what the helper did to its code.
 #pragma once
 #include "common.hpp"
 
@@ -15,15 +17,68 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // conflict-free.
 __device__ __forceinline__ int at4_slot(int g, int hi, int i) { return (2 * g + hi) * 32 + (i ^ (g & 7)); }
 
-// One 4-MFMA group g: A fragments = one float4 from the LDS tile, B fragments = one float4 of Wp.
-__device__ __forceinline__ f32x16 mfma_group(const float4* __restrict__ At4, int g, int hi, int r31, float4 b,
-                                             f32x16 c) {
-    const float4 a = At4[at4_slot(g, hi, r31)];
+// The gather's side of the tile: the 8 channels (v0 = channels 0..3, v1 = 4..7) that a lane holds of row i are group g.
+__device__ __forceinline__ void store_fragment_grouped(float4* At4, int g, int i, float4 v0, float4 v1) {
+    const float4 even = make_float4(v0.x, v0.z, v1.x, v1.z), odd = make_float4(v0.y, v0.w, v1.y, v1.w);
+    At4[at4_slot(g, 0, i)] = even;
+    At4[at4_slot(g, 1, i)] = odd;
+}
+
+// Tile row held by accumulator register r (0..15) of v_mfma_f32_32x32x2_f32 in lane half hi (= lane >> 5); the column is
+// lane & 31.
+__host__ __device__ constexpr int acc_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
+// Four k-steps of two lanes' fragments: v_mfma_f32_32x32x2_f32 on the components of a and b, in order.
+__device__ __forceinline__ f32x16 mfma4(float4 a, float4 b, f32x16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, c, 0, 0, 0);
     return c;
+}
+
+// One 4-MFMA group g: A fragments = one float4 from the LDS tile, B fragments = one float4 of Wp.
+__device__ __forceinline__ f32x16 mfma_group(const float4* __restrict__ At4, int g, int hi, int r31, float4 b,
+                                             f32x16 c) {
+    return mfma4(At4[at4_slot(g, hi, r31)], b, c);
+}
+
+// Hidden vector of the edge MLP for edge e, times `scale`: h[kk] = relu(b1[kk] + sum_d w1[kk, d] ea[e, d]) * scale, kk < 2 D
+// (the mean scale 1/deg rides on it wherever the caller has it per edge).
+template <int D>
+__device__ __forceinline__ void edge_hidden(const float* __restrict__ w1, const float* __restrict__ b1,
+                                            const float* __restrict__ ea, int64_t e, float scale, float* __restrict__ hid) {
+    float ee[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) ee[d] = ea[e * D + d];
+#pragma unroll
+    for (int kk = 0; kk < 2 * D; ++kk) {
+        float h = b1[kk];
+#pragma unroll
+        for (int d = 0; d < D; ++d) h = fmaf(w1[kk * D + d], ee[d], h);
+        hid[kk] = fmaxf(h, 0.f) * scale;
+    }
+}
+
+// Dropout draws shared inside a quad (the fused NNConv epilogues): one 64-bit hash serves the four columns of a float4
+// group, i.e. the four lanes of a quad for the same row, so every lane hashes NH of the rows and receives the others through
+// quad_perm broadcasts.  Draw t of quad lane S arrives at index S * SS + t * ST.
+template <int S, int NH, int SS, int ST>
+__device__ __forceinline__ void quad_share_from(const uint32_t (&mylo)[NH], const uint32_t (&myhi)[NH], uint32_t (&zlo)[4 * NH],
+                                                uint32_t (&zhi)[4 * NH]) {
+#pragma unroll
+    for (int t = 0; t < NH; ++t) {
+        zlo[S * SS + t * ST] = __builtin_amdgcn_update_dpp(0, mylo[t], S * 0x55, 0xF, 0xF, true);
+        zhi[S * SS + t * ST] = __builtin_amdgcn_update_dpp(0, myhi[t], S * 0x55, 0xF, 0xF, true);
+    }
+}
+template <int NH, int SS, int ST>
+__device__ __forceinline__ void quad_share_draws(const uint32_t (&mylo)[NH], const uint32_t (&myhi)[NH], uint32_t (&zlo)[4 * NH],
+                                                 uint32_t (&zhi)[4 * NH]) {
+    quad_share_from<0, NH, SS, ST>(mylo, myhi, zlo, zhi);
+    quad_share_from<1, NH, SS, ST>(mylo, myhi, zlo, zhi);
+    quad_share_from<2, NH, SS, ST>(mylo, myhi, zlo, zhi);
+    quad_share_from<3, NH, SS, ST>(mylo, myhi, zlo, zhi);
 }
 
 // Accumulators in AGPRs.  At <= 256 registers per lane and no other AGPR use the compiler selects the MFMAs' VGPR form

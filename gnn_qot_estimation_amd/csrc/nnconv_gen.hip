@@ -98,6 +98,8 @@ __device__ __forceinline__ void gen_gather_xch(const float* __restrict__ x, int 
             const float mysc = TRANSPOSE ? invdeg[myj] : 1.0f;
             w[0] = __builtin_bit_cast(float, myj);
             w[1] = mysc;
+            // (edge_hidden of mfma_tile.hpp spelled out: through the helper, which takes the scale as an argument, the scale's
+            //  load moves in front of the feature loads -- one s_waitcnt fewer in nnconv_gen_kernel<256, 3, true>)
 #pragma unroll
             for (int kk = 0; kk < K; ++kk) {
                 float h = b1[kk];
@@ -251,6 +253,8 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
 #pragma unroll
                 for (int u = 0; u < CH; ++u) bc[q][u] = wp[((int64_t)q * GALL + u) * 64];
             lds_barrier();
+            // (the 4-MFMA groups below are mfma4 of mfma_tile.hpp spelled out: with the helper every H = 256 instantiation came
+            //  out with two s_waitcnt fewer, i.e. another placement of the waits in the MFMA loop)
             int ch = 0;
 #pragma unroll 1
             for (; ch + 1 < NCH; ch += 2) {
@@ -342,22 +346,16 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const int rr = jq + 4 * t;
-                        const int row = (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+                        const int row = acc_row(rr, hi);
                         const uint64_t flat = (uint64_t)((tile0 + row) * H + colg);
                         const uint64_t z = act_hash64(act.seed, dstep, flat >> 2);
                         mylo[t] = (uint32_t)z; myhi[t] = (uint32_t)(z >> 32);
                     }
                     uint32_t zlo[16], zhi[16];
-#define QOT_GEN_ZSHARE(S)                                                                                \
-                    _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                      \
-                        zlo[(S) + 4 * t] = __builtin_amdgcn_update_dpp(0, mylo[t], (S) * 0x55, 0xF, 0xF, true); \
-                        zhi[(S) + 4 * t] = __builtin_amdgcn_update_dpp(0, myhi[t], (S) * 0x55, 0xF, 0xF, true); \
-                    }
-                    QOT_GEN_ZSHARE(0) QOT_GEN_ZSHARE(1) QOT_GEN_ZSHARE(2) QOT_GEN_ZSHARE(3)
-#undef QOT_GEN_ZSHARE
+                    quad_share_draws<4, 1, 4>(mylo, myhi, zlo, zhi);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                        const int row = acc_row(r, hi);
                         const int64_t io = tile0 + row;
                         const float v = c[q][r] + bz;
                         float y = v > 0.f ? v : act.slope * v;
@@ -369,7 +367,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                        const int row = acc_row(r, hi);
                         const int64_t io = tile0 + row;
                         if (io < N) out[io * H + colg] = act_apply1(c[q][r] + bz, act, (uint64_t)(io * H + colg));
                     }
@@ -389,7 +387,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gen_kernel(
                 float v = bz;
 #pragma unroll
                 for (int k2 = 0; k2 < KS; ++k2) v += red[((cb0 + NCB * k2) * 16 + r) * 64 + lane];
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int row = acc_row(r, hi);
                 const int64_t io = tile0 + row;
                 if (io < N && colg < H) out[io * H + colg] = act_apply1(v, act, (uint64_t)(io * H + colg));
             }
@@ -540,7 +538,7 @@ __global__ __launch_bounds__(512, 2) void nnconv_dw_gen_kernel(
             const int rb = tt / OCB, cb = tt % OCB;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int row = acc_row(r, hi);
                 slab[(rb * 32 + row) * OC + cb * 32 + r31] = dw[t][r];
             }
         }
@@ -756,7 +754,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh_gen_kernel(
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    const int row = acc_row(r, hi);
                     GAt[row * LDGA + nb * 32 + r31] = c[r];
                 }
             }

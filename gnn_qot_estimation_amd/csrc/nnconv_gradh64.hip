@@ -167,6 +167,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
                 // rows of absent nodes are zero planes.
                 store_split_planes(Gt, sub, il, g0, g1);
             } else {
+                // (store_fragment_grouped spelled out: through the helper the slot's v_or3_b32 takes its operands in the other order)
                 Gt4[at4_slot(sub, 0, il)] = make_float4(g0.x, g0.z, g1.x, g1.z);
                 Gt4[at4_slot(sub, 1, il)] = make_float4(g0.y, g0.w, g1.y, g1.w);
             }
@@ -212,10 +213,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
                 }
                 c += cs;                                      // (one vector expression: packed adds)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    GAt[row * LDGA + nb * 32 + r31] = c[r];
-                }
+                for (int r = 0; r < 16; ++r) GAt[acc_row(r, hi) * LDGA + nb * 32 + r31] = c[r];
             }
         } else {
             float4 af[8];
@@ -234,17 +232,9 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) c[r] = 0.f;
 #pragma unroll
-                for (int gq = 0; gq < 8; ++gq) {
-                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(af[gq].x, bf[t & 1][gq].x, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(af[gq].y, bf[t & 1][gq].y, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(af[gq].z, bf[t & 1][gq].z, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(af[gq].w, bf[t & 1][gq].w, c, 0, 0, 0);
-                }
+                for (int gq = 0; gq < 8; ++gq) c = mfma4(af[gq], bf[t & 1][gq], c);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    GAt[row * LDGA + nb * 32 + r31] = c[r];
-                }
+                for (int r = 0; r < 16; ++r) GAt[acc_row(r, hi) * LDGA + nb * 32 + r31] = c[r];
             }
         }
         if constexpr (PRESPLIT) lds_barrier();       // every wave is through with the planes: sea overwrites them

@@ -112,15 +112,8 @@ __device__ __forceinline__ void nnconv_gather_tile(
         _Pragma("unroll") for (int kk = 0; kk < K; ++kk) myh[kk] = 0.f;                                 \
         if (p < end) {                                                                                  \
             myj = col[p];                                                                               \
-            const int64_t e = (int64_t)eidx[p];                                                         \
-            float ee[D];                                                                                \
-            _Pragma("unroll") for (int d = 0; d < D; ++d) ee[d] = ea[e * D + d];                        \
             mysc = TRANSPOSE ? invdeg[myj] : srow;                                                      \
-            _Pragma("unroll") for (int kk = 0; kk < K; ++kk) {                                          \
-                float h = b1[kk];                                                                       \
-                _Pragma("unroll") for (int d = 0; d < D; ++d) h = fmaf(w1[kk * D + d], ee[d], h);       \
-                myh[kk] = fmaxf(h, 0.f) * mysc;                                                         \
-            }                                                                                           \
+            edge_hidden<D>(w1, b1, ea, (int64_t)eidx[p], mysc, myh);                                    \
         }                                                                                               \
         const int cnt = (end - base < 8) ? end - base : 8;                                              \
         QOT_EDGE4(0, FIRST)                                                                             \
@@ -140,14 +133,18 @@ __device__ __forceinline__ void nnconv_gather_tile(
 #pragma unroll
         for (int kk = HB; kk <= K; ++kk) { park0[kk - HB] = acc0[kk]; park1[kk - HB] = acc1[kk]; }
     } else {
-    float4* At4 = reinterpret_cast<float4*>(At);
 #pragma unroll
-    for (int kk = 0; kk <= K; ++kk) {       // channels c0+{0,2,4,6} -> hi 0 ; c0+{1,3,5,7} -> hi 1
-        const int g = kk * 8 + sub;
-        At4[at4_slot(g, 0, il)] = make_float4(acc0[kk].x, acc0[kk].z, acc1[kk].x, acc1[kk].z);
-        At4[at4_slot(g, 1, il)] = make_float4(acc0[kk].y, acc0[kk].w, acc1[kk].y, acc1[kk].w);
+        for (int kk = 0; kk <= K; ++kk)         // channels c0+{0,2,4,6} -> hi 0 ; c0+{1,3,5,7} -> hi 1
+            store_fragment_grouped(reinterpret_cast<float4*>(At), kk * 8 + sub, il, acc0[kk], acc1[kk]);
     }
-    }
+}
+
+// Root block (x_i itself, kept in registers during the main part) takes block 0's slots once everyone is done with blocks
+// 0..K, and is published: the fp32 image is 72 KB instead of 80 KB.
+__device__ __forceinline__ void root_restage(float* At, float4 root0, float4 root1) {
+    lds_barrier();                         // everyone is done with blocks 0..K
+    store_fragment_grouped(reinterpret_cast<float4*>(At), threadIdx.x & 7, threadIdx.x >> 3, root0, root1);
+    __syncthreads();
 }
 
 // SPLIT (forward only): the products on the bf16 matrix pipe (split_bf16.hpp).  Ws: Wcat pre-split into three bf16
@@ -160,6 +157,11 @@ __device__ __forceinline__ void nnconv_gather_tile(
 // kh (K+2) .. kh (K+2) + K + 1 of each phase; the B ring runs across the phase boundary.  63,360 B of planes + 8 KB for the
 // K-half exchange (which can no longer alias the image) = 71,552 B at D = 4.  false: the split-after-read loop
 // (QOT_NNCONV_FWD_SPLIT_AFTER_READ=1), every value split by both column-half waves.
+// The three product loops (fp32, split-after-read, pre-split) and the epilogue stay inside the kernel body, and the gather's
+// batches stay macros.  As __device__ __forceinline__ functions returning the accumulator the loops compiled to other code:
+// 16 zero moves more per split form, another packing of the epilogue's adds, 1-3 VGPRs more (203 -> 204 at D = 1, 216 ->
+// 218 at D = 2, 240 -> 243 for the fp32 form at D = 4); the epilogue as a function had its two `if (kh)` branches merged
+// into one with runtime accumulator indices (a compare-select chain per register).  tools/regs.py --against shows it.
 __host__ __device__ constexpr int fwd_plane_off(int p) { return (p / 4) * 3 * kGhPlLd + (p % 4) * kGhPlStep; }   // u32x4, phase-local step p
 
 template <int D, bool TRANSPOSE, bool SPLIT = false, bool PRESPLIT = false>
@@ -307,14 +309,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
                 for (int u = 0; u < SC; ++u) c = mfma_split_step(At4, kh * GM + 2 * ((ch + q) * SC + u), hi, r31, sb[q][u], c);
             }
         }
-        lds_barrier();                         // everyone is done with blocks 0..K
-        {   // root block (x_i itself) reuses block 0's slots
-            float4* At4w = reinterpret_cast<float4*>(At);
-            const int sub = threadIdx.x & 7, il = threadIdx.x >> 3;
-            At4w[at4_slot(sub, 0, il)] = make_float4(root0.x, root0.z, root1.x, root1.z);
-            At4w[at4_slot(sub, 1, il)] = make_float4(root0.y, root0.w, root1.y, root1.w);
-        }
-        __syncthreads();
+        root_restage(At, root0, root1);
 #pragma unroll
         for (int u = 0; u < 2; ++u) c = mfma_split_step(At4, kh * 4 + 2 * u, hi, r31, rbs[u], c);
     } else {
@@ -367,14 +362,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
             for (int u = 0; u < CH; ++u) c = mfma_group(At4, kh * GM + (ch + q) * CH + u, hi, r31, bb[q][u], c);
         }
     }
-    lds_barrier();                         // everyone is done with blocks 0..K
-    {   // root block (x_i itself) reuses block 0's slots
-        float4* At4 = reinterpret_cast<float4*>(At);
-        const int sub = threadIdx.x & 7, il = threadIdx.x >> 3;
-        At4[at4_slot(sub, 0, il)] = make_float4(root0.x, root0.z, root1.x, root1.z);
-        At4[at4_slot(sub, 1, il)] = make_float4(root0.y, root0.w, root1.y, root1.w);
-    }
-    __syncthreads();
+    root_restage(At, root0, root1);
 #pragma unroll
     for (int u = 0; u < 4; ++u) c = mfma_group(At4, kh * 4 + u, hi, r31, rb[u], c);
     }
@@ -413,23 +401,17 @@ __global__ __launch_bounds__(256, 2) void nnconv_mfma64_kernel(
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int rr = kh * 8 + 2 * jq + t;
-                const int row = (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+                const int row = acc_row(rr, hi);
                 const uint64_t flat = (uint64_t)((tile0 + row) * 64 + colg);
                 const uint64_t z = act_hash64(act.seed, drop_step, flat >> 2);
                 mylo[t] = (uint32_t)z; myhi[t] = (uint32_t)(z >> 32);
             }
-#define QOT_ZSHARE(S)                                                                                   \
-            zlo[2 * (S)] = __builtin_amdgcn_update_dpp(0, mylo[0], (S) * 0x55, 0xF, 0xF, true);         \
-            zhi[2 * (S)] = __builtin_amdgcn_update_dpp(0, myhi[0], (S) * 0x55, 0xF, 0xF, true);         \
-            zlo[2 * (S) + 1] = __builtin_amdgcn_update_dpp(0, mylo[1], (S) * 0x55, 0xF, 0xF, true);     \
-            zhi[2 * (S) + 1] = __builtin_amdgcn_update_dpp(0, myhi[1], (S) * 0x55, 0xF, 0xF, true);
-            QOT_ZSHARE(0) QOT_ZSHARE(1) QOT_ZSHARE(2) QOT_ZSHARE(3)
-#undef QOT_ZSHARE
+            quad_share_draws<2, 2, 1>(mylo, myhi, zlo, zhi);
         }
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int rr = kh * 8 + r;
-            const int row = (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+            const int row = acc_row(rr, hi);
             const int64_t i = tile0 + row;
             float y = v[r];
             if (act.enabled) {
@@ -569,15 +551,8 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
                 _Pragma("unroll") for (int kk = 0; kk < K; ++kk) myh[kk] = 0.f;                          \
                 if (p < end) {                                                                           \
                     myi = col_t[p];                                                                      \
-                    const int64_t e = (int64_t)eid_t[p];                                                 \
-                    float ee[D];                                                                         \
-                    _Pragma("unroll") for (int d = 0; d < D; ++d) ee[d] = ea[e * D + d];                 \
                     mysc = invdeg[myi];                                                                  \
-                    _Pragma("unroll") for (int kk = 0; kk < K; ++kk) {                                   \
-                        float h = b1[kk];                                                                \
-                        _Pragma("unroll") for (int d = 0; d < D; ++d) h = fmaf(w1[kk * D + d], ee[d], h); \
-                        myh[kk] = fmaxf(h, 0.f) * mysc;                                                  \
-                    }                                                                                    \
+                    edge_hidden<D>(w1, b1, ea, (int64_t)eid_t[p], mysc, myh);                            \
                 }                                                                                        \
                 const int cnt = (end - base < 16) ? end - base : 16;                                     \
                 QOT_ADJ_EDGE4(0, FIRST)                                                                  \
@@ -718,7 +693,7 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
 #pragma unroll
                 for (int slot = 0; slot < 3; ++slot) v[rr] += red[(((kq * 2 + nh) * 3 + slot) * 4 + rr) * 64 + lane];
                 const int reg = 4 * kq + rr;
-                const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hi;
+                const int row = acc_row(reg, hi);
                 const int64_t j = tile0 + row;
                 if (j < N) gx[j * 64 + colg] = v[rr];
             }
@@ -731,12 +706,14 @@ __global__ __launch_bounds__(512, 2) void nnconv_adjoint_dw64_kernel(
     for (int t = 0; t < TPW; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int row = acc_row(r, hi);
             slab[((mb0 + 4 * t) * 32 + row) * 64 + ah * 32 + r31] = dw[t][r];
         }
 }
 
-// level-1/level-2 slab sums (same scheme as gemm_tn.hip; duplicated signature, internal linkage)
+// level-1/level-2 slab sums (same scheme as gemm_tn.hip; duplicated signature, internal linkage).  (Both as wrappers of one
+// __forceinline__ body: other address arithmetic in the loop -- two s_add_u32 / s_addc_u32 pairs for two v_lshl_add_u64 --
+// so the copy stays.)
 __global__ void adj_slab_reduce_kernel(const float* __restrict__ slabs, int nslabs, int per_group, int64_t elems,
                                        int64_t slab_stride, float* __restrict__ dst, int64_t dst_stride) {
     int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
