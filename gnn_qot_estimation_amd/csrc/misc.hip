@@ -146,8 +146,10 @@ __global__ void pool_bwd_kernel(const float* __restrict__ go, const int32_t* __r
 
 // ----------------------------------------------------------------------------- batch norm
 // Column statistics in two stages: each block reduces a contiguous row chunk into
-// partials[blk, 2, C]; a one-block finalize combines the partials in fp64.  Sums are taken
-// on x - x[0,:] (shifted-data form) so E[x^2]-E[x]^2 cancellation stays benign in fp32.
+// partials[blk, 2, C]; the finalize combines the partials in fp64.  A block sums d = x - (the first
+// row of its OWN chunk) and d^2 (shifted-data form), and the finalize turns each block's pair into
+// (mean_b, M2_b) and merges them with Chan's formula: a row far from the others (x[0,:] was the
+// shift of every block once) costs the variance no more than that row adds to it.
 constexpr int kBnMaxBlocks = 2048;
 inline int bn_blocks(int64_t N) {
     int64_t b = (N + 63) / 64;
@@ -155,7 +157,7 @@ inline int bn_blocks(int64_t N) {
     return (int)(b > kBnMaxBlocks ? kBnMaxBlocks : b);
 }
 
-// MODE 0: s1 = sum(x - shift), s2 = sum((x-shift)^2)
+// MODE 0: s1 = sum(x - shift), s2 = sum((x-shift)^2), shift = row r0 of x (the block's first)
 // MODE 1: s1 = sum(dy'), s2 = sum(dy' * xhat)   (dy' = dy * [y > 0] when relu)
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_partial_kernel(
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(
     if (slot < RPB) {
         const int c = 4 * sub;
         float4 sh, mu, rs, wv = f4zero(), bv = f4zero();
-        if (MODE == 0) sh = ld4(x + c);
+        if (MODE == 0) sh = ld4(x + (r0 < N ? r0 : 0) * C + c);      // (a trailing block without rows sums nothing)
         else { mu = ld4(mean + c); rs = ld4(rstd + c); if (relu && !y) { wv = ld4(wgt + c); bv = ld4(bia + c); } }
         for (int64_t r = r0 + slot; r < r1e; r += RPB) {
             float4 xv = ld4(x + ((MODE == 1 && rows) ? (int64_t)rows[r] : r) * C + c);
@@ -219,6 +221,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+// Block b holds rows [b * chunk, min((b + 1) * chunk, N)) and the sums s1, s2 of d = x - x[b * chunk,:] over them:
+// mean = sum_b (n_b shift_b + s1_b) / N; M2 = sum_b (s2_b - s1_b^2 / n_b) + n_b (shift_b + s1_b / n_b - mean)^2 (Chan's
+// formula for many groups at once), all in fp64 with a fixed lane-strided order.
 __global__ void bn_finalize_stats_kernel(const float* __restrict__ x, const float* __restrict__ partials,
                                          int nblk, int64_t N, int C, float eps, float momentum,
                                          float* __restrict__ mean, float* __restrict__ rstd,
@@ -226,19 +231,33 @@ __global__ void bn_finalize_stats_kernel(const float* __restrict__ x, const floa
     const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (c >= C) return;
     const int lane = threadIdx.x & 63;
-    double s1 = 0.0, s2 = 0.0;
+    const int64_t chunk = (N + nblk - 1) / nblk;           // as bn_partial_kernel takes it
+    auto rows_of = [&](int b) -> double {
+        const int64_t r0 = (int64_t)b * chunk;
+        const int64_t r1 = (r0 + chunk < N) ? r0 + chunk : N;
+        return r1 > r0 ? (double)(r1 - r0) : 0.0;
+    };
+    double s = 0.0;
     for (int b = lane; b < nblk; b += 64) {
-        s1 += (double)partials[((int64_t)b * 2) * C + c];
-        s2 += (double)partials[((int64_t)b * 2 + 1) * C + c];
+        const double nb = rows_of(b);
+        if (nb > 0.0) s += nb * (double)x[(int64_t)b * chunk * C + c] + (double)partials[((int64_t)b * 2) * C + c];
     }
-    s1 = wave_sum_f64(s1);
-    s2 = wave_sum_f64(s2);
+    const double dn = (double)N;
+    const double mu = wave_sum_f64(s) / dn;
+    double q = 0.0;
+    for (int b = lane; b < nblk; b += 64) {
+        const double nb = rows_of(b);
+        if (nb > 0.0) {
+            const double s1 = (double)partials[((int64_t)b * 2) * C + c], s2 = (double)partials[((int64_t)b * 2 + 1) * C + c];
+            const double m1 = s1 / nb;
+            const double m2 = s2 - s1 * m1;
+            const double d = (double)x[(int64_t)b * chunk * C + c] + m1 - mu;
+            q += (m2 > 0.0 ? m2 : 0.0) + nb * d * d;       // (a NaN or Inf in the column reaches q through d)
+        }
+    }
+    q = wave_sum_f64(q);
     if (lane) return;
-    double dn = (double)N;
-    double m1 = s1 / dn;
-    double var = s2 / dn - m1 * m1;
-    if (var < 0.0) var = 0.0;
-    double mu = (double)x[c] + m1;
+    const double var = q / dn;
     mean[c] = (float)mu;
     rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (rmean) {
