@@ -3,7 +3,8 @@
 quantities, and against the per-destination kernels it replaces (``QOT_NO_TCONV_GRAPH=1``).
 
 Tolerance: <= 1e-4 relative (BASELINE.json's bar) against the oracle; the two HIP forms agree to rounding (the logits'
-H-term dot is summed in another order)."""
+H-term dot is summed in another order).  What pins the forward kernel itself -- out, alpha, ea_csr and aa from given
+``(t4, M, P)``, and those three from the parameters, element by element against fp64 -- is test_gpu_tconv_fwd.py."""
 import pytest
 import torch
 

@@ -3,7 +3,8 @@ forward (qot_tconv_fwd_scores) and the row form of the backward (csrc/tconv_rows
 two small products) against the per-destination kernels of csrc/tconv.hip on the same batch.  The oracle tests
 (test_gpu_configs.py, test_gpu_parity.py) pin those per-destination kernels, not the row form: their cfg4-shaped batches
 stay below N >= 4 V or use a gradient of order 1.  fp32 sums in another order: 2e-4 of the tensor's scale.
-The row form itself is pinned against fp64, at gradient scales 2^-30 .. 2^30, in test_gpu_grad_scale.py."""
+The row form itself is pinned against fp64, at gradient scales 2^-30 .. 2^30, in test_gpu_grad_scale.py; the FORWARD of the
+scores and rows forms (out, stats, the score matrix) element by element against fp64 in test_gpu_tconv_fwd.py."""
 import pytest
 import torch
 
