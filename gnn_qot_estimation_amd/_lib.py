@@ -171,6 +171,7 @@ SIGNATURES = {
     "qot_skinny_linear_dw_blocks": (_int, [_i64]),
     "qot_skinny_linear_dw": (_int, [_p, _p, _p, _i64, _int, _int, _p]),
     "qot_run_roles": (_int, [_p, _int, _p]),
+    "qot_nnconv_gradh_host_roles": (_int, [_p, _int]),
     "qot_rows_gather": (_int, [_p, _p, _p, _i64, _int, _p]),
     "qot_rows_scatter": (_int, [_p, _p, _p, _i64, _int, _p]),
     **{f"qot_topological_infer{k}_supported": (_int, [_int] * 5) for k in ("", "_mc", "_grad", "_whatif")},
@@ -191,7 +192,8 @@ SIGNATURES = {
 
 MAX_ROLES = 12           # include/qot_gnn.h: QOT_MAX_ROLES
 (ROLE_CSR_BY_GRAPH, ROLE_TABLE_PROJECT_FWD, ROLE_GATHER3, ROLE_SUM_ROWS, ROLE_NNCONV_FINALIZE64, ROLE_TABLE_PROJECT_BWD,
- ROLE_TABLE_SCORES, ROLE_TABLE_PROJECT_BWD_SCORES) = range(1, 9)
+ ROLE_TABLE_SCORES, ROLE_TABLE_PROJECT_BWD_SCORES, ROLE_NNCONV_SLAB_SUM64, ROLE_NNCONV_GRADH_SUM64) = range(1, 11)
+HOSTABLE_ROLES = (ROLE_SUM_ROWS, ROLE_NNCONV_SLAB_SUM64)     # what qot_nnconv_gradh_host_roles accepts
 
 
 class Role(C.Structure):
@@ -222,6 +224,15 @@ def run_roles(roles, stream_handle=None):
     code = (_lib or load()).qot_run_roles(C.addressof(arr), len(roles), stream() if stream_handle is None else stream_handle)
     if code != 0:
         check(code, "qot_run_roles")
+
+
+def host_roles(roles):
+    """Hand ``roles`` (at most ``MAX_ROLES``, kinds of ``HOSTABLE_ROLES``) to the next grad-h call of this thread, which runs them
+    as tail workgroups of its own launch (include/qot_gnn.h: ``qot_nnconv_gradh_host_roles``)."""
+    arr = (Role * max(len(roles), 1))(*roles)
+    code = (_lib or load()).qot_nnconv_gradh_host_roles(C.addressof(arr), len(roles))
+    if code != 0:
+        check(code, "qot_nnconv_gradh_host_roles")
 
 
 _lib = None
@@ -277,9 +288,30 @@ def stream():
     """Raw handle of the current stream.  ``torch.cuda.current_stream()`` builds a Python Stream object
     (~10 us per call, a fifth of an eager step at the reference's own batch size: tools/profile_host.py);
     the raw accessor is the same lookup without the object."""
+    if _pinned_stream is not None:
+        return _pinned_stream
     if _raw_stream is not None and _raw_device is not None:
         return _raw_stream(_raw_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+_pinned_stream = None
+
+
+class on_stream:
+    """``with on_stream(handle):`` -- ``stream()``, hence ``call``, answers ``handle`` (a raw stream handle) inside: the
+    backward epilogue launches from an engine callback, where the current stream need not be the one its nodes ran on."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def __enter__(self):
+        global _pinned_stream
+        self.prev, _pinned_stream = _pinned_stream, self.handle
+
+    def __exit__(self, *exc):
+        global _pinned_stream
+        _pinned_stream = self.prev
 
 
 def check(code: int, what: str):

@@ -116,6 +116,20 @@ __device__ __forceinline__ void lds_barrier() {
 // rows are gathered by the 3-4 consecutive tiles that hold its destinations, so every XCD group
 // walks its own contiguous eighth of the tiles: the rows a tile gathers are then already in that
 // XCD's L2 from the neighbouring tile.  Returns the tile of iteration `it` (or -1 when done).
+// `grid`: the workgroups that walk (blockIdx.x < grid); a launch may carry more behind them (nnconv_gradh64_kernel's tail).
+// (Stated next to the walk over the whole grid, not in place of it: that one's code stays what it was.)
+__device__ __forceinline__ int64_t xcd_tile(int64_t it, int64_t ntiles, unsigned grid) {
+    const int nx = 8;
+    if ((int)grid % nx != 0) {                             // small grids: plain strided walk
+        const int64_t t = (int64_t)blockIdx.x + it * grid;
+        return t < ntiles ? t : -1;
+    }
+    const int xcd = blockIdx.x % nx, slot = blockIdx.x / nx, per_x = grid / nx;
+    const int64_t chunk = (ntiles + nx - 1) / nx;
+    const int64_t local = slot + it * per_x;
+    const int64_t t = xcd * chunk + local;
+    return (local < chunk && t < ntiles) ? t : -1;
+}
 __device__ __forceinline__ int64_t xcd_tile(int64_t it, int64_t ntiles) {
     const int nx = 8;
     if ((int)gridDim.x % nx != 0) {                        // small grids: plain strided walk

@@ -3,6 +3,8 @@
 // the adjoint kernel 2.6 us and spills the forward one (r03; tools/experiments/r03_sched_bench.sh).
 #include "common.hpp"
 #include "mfma_tile.hpp"
+#include "nnconv_finalize_dev.hpp"
+#include "reduce_dev.hpp"
 #include "split_bf16.hpp"
 
 namespace qot {
@@ -33,9 +35,25 @@ constexpr int kGhCap = 256;   // edges of a tile staged in LDS by the grad-h ker
 // per tile, an A fragment = three ds_read_b128.  false: the fp32 tile of the fp32 form, every fragment split after its
 // read, by every wave for each of its blocks (16 times per value; kept for comparison, QOT_GRADH_SPLIT_AFTER_READ=1).
 // The plane layout (kGhPlStep, kGhPlLd) and its store are split_bf16.hpp's: the forward kernel shares them.
+//
+// Hosted sums: the launch is n_main + (tail) workgroups.  The first n_main are the persistent workgroups of the tile walk; the
+// walk's last round is ragged (3200 tiles over 512 workgroups at cfg2: a quarter of the slots runs a 7th tile), and workgroups
+// are handed out in index order, so the tail workgroups start in the slots the others free, while that round finishes.  A tail
+// workgroup runs one virtual block of a hosted job (nnconv_finalize_dev.hpp: HostedTable) and returns: streaming fixed-order
+// sums of partials that EARLIER launches wrote, so neither when nor where it runs changes a bit of any result.  No workgroup
+// waits for another.  Its 4 KB of scratch is the GA tile's storage: the kernel's static LDS is what it was.
+__device__ __forceinline__ void gradh_hosted_tail(const HostedTable& t, int vt, float* __restrict__ scratch) {
+    int r = 0;
+    while (r + 1 < t.n && vt >= t.first[r + 1]) ++r;                    // uniform; <= QOT_MAX_ROLES scalar steps
+    const HostedJob& jb = t.job[r];
+    const int vb = vt - t.first[r];
+    if (jb.kind == kHostedSumRows) sum_rows_body(jb.src, jb.dst, jb.a, jb.b, jb.c, jb.flag, vb, scratch);
+    else if (jb.kind == kHostedSlabSum64) nnconv_slab_sum64_body(jb.src, (int)jb.a, jb.b, jb.dst, jb.flag, vb);
+}
 
 template <int D, bool SPLIT = false, bool PRESPLIT = false>
 __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
+    const HostedTable hosted_by_value, int n_main,      // first, so that the table lies at offset 0 of the argument segment
     const float* __restrict__ g, int ldg, const float* __restrict__ x, int ldx, const float* __restrict__ ea,
     const float* __restrict__ w1, const float* __restrict__ b1, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ col, const int32_t* __restrict__ eidx, const float* __restrict__ invdeg,
@@ -61,6 +79,17 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
     __shared__ int rp_l[36];
     constexpr int LDGA = K * 64 + 4;
     float4* Gt4 = reinterpret_cast<float4*>(Gt);
+    if ((int)blockIdx.x >= n_main) {
+        // a tail workgroup: the table is read where it lies, in the kernel-argument segment (first argument: offset 0),
+        // through a pointer, as roles_kernel reads its own
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef const HostedTable __attribute__((address_space(4))) * KernargTable;
+        gradh_hosted_tail(*(const HostedTable*)(KernargTable)__builtin_amdgcn_kernarg_segment_ptr(), (int)blockIdx.x - n_main, GAt);
+#else
+        gradh_hosted_tail(hosted_by_value, (int)blockIdx.x - n_main, GAt);
+#endif
+        return;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r31 = lane & 31, hi = lane >> 5;
     const int sub = threadIdx.x & 7, il = threadIdx.x >> 3;
@@ -119,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_gradh64_kernel(
 
 #pragma unroll 1
     for (int64_t it = 0;; ++it) {
-        const int64_t tile = xcd_tile(it, ntiles);
+        const int64_t tile = xcd_tile(it, ntiles, (unsigned)n_main);
         if (tile < 0) break;
         const int64_t tile0 = tile * 32;
         const int64_t i = tile0 + il;
@@ -303,7 +332,10 @@ using namespace qot;
 int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, int ld_x, const float* edge_attr, const float* w1,
                               const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* invdeg,
                               const float* b_perm, const void* b_split, int64_t split_stride, float* workspace, int64_t N, int D,
-                              int grid, hipStream_t stream) {
+                              int grid, const qot::HostedTable& hosted, hipStream_t stream) {
+    // `grid` persistent workgroups, then the hosted jobs' (first[n] of them; none: an empty table)
+    const int n_main = grid;
+    grid += hosted.n > 0 ? hosted.first[hosted.n] : 0;
     if (b_split) {
         // The g tile is split once per tile on its way to LDS unless QOT_GRADH_SPLIT_AFTER_READ=1 (the earlier loop, same
         // results bit for bit).  Read per call, not cached: callers flip it inside one process.
@@ -313,11 +345,11 @@ int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, i
             if (kD <= 4) {
                 if (presplit)
                     nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), true, true><<<grid, 256, 0, stream>>>(
-                        grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
+                        hosted, n_main, grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
                         static_cast<const u32x4*>(b_split), split_stride / 8);
                 else
                     nnconv_gradh64_kernel<(kD <= 4 ? kD : 4), true><<<grid, 256, 0, stream>>>(
-                        grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
+                        hosted, n_main, grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, nullptr, workspace, N,
                         static_cast<const u32x4*>(b_split), split_stride / 8);
             }
         });
@@ -327,7 +359,7 @@ int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, i
     QOT_DISPATCH_D(D, {
         if (kD <= 4)
             nnconv_gradh64_kernel<(kD <= 4 ? kD : 4)><<<grid, 256, 0, stream>>>(
-                grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm, workspace, N);
+                hosted, n_main, grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm, workspace, N);
     });
     QOT_LAUNCH_CHECK();
     return QOT_OK;

@@ -862,7 +862,8 @@ extern "C" int qot_nnconv_fused_split(const float* x, int ld_x, const float* edg
 int qot_nnconv_gradh64_launch(const float* grad_out, int ld_g, const float* x, int ld_x, const float* edge_attr, const float* w1,
                               const float* b1, const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* invdeg,
                               const float* b_perm, const void* b_split, int64_t split_stride, float* workspace, int64_t N, int D,
-                              int grid, hipStream_t stream);
+                              int grid, const qot::HostedTable& hosted, hipStream_t stream);
+int qot_hosted_take(qot::HostedTable* t, qot_role_t* planned);      // roles.hip (qot_nnconv_gradh_host_roles)
 extern "C" size_t qot_nnconv_gradh_workspace_floats(int D) {
     return (size_t)2 * 256 * 2 * (size_t)(2 * D * (D + 1));
 }
@@ -874,6 +875,10 @@ static int nnconv_gradh_impl(const float* grad_out, int ld_g, const float* x, in
                              float* gw1, float* gb1,
                              float* workspace, int64_t N, int H, int D, qot_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    // The jobs qot_nnconv_gradh_host_roles left for this call are taken whatever becomes of it (an error drops them).
+    HostedTable hosted;
+    qot_role_t hosted_roles[QOT_MAX_ROLES];
+    const int n_hosted = qot_hosted_take(&hosted, hosted_roles);
     if (N < 0 || !rowptr) return QOT_ERR_BADARG;
     if ((H != 16 && H != 32 && H != 64 && H != 128 && H != 256) || D > 4) return QOT_ERR_UNSUPPORTED;
     if (!grad_out || !x || !w1 || !b1 || !invdeg || !(b_perm || b_split) || (!gw1 != !gb1) || !workspace || (ld_g & 3) ||
@@ -881,14 +886,22 @@ static int nnconv_gradh_impl(const float* grad_out, int ld_g, const float* x, in
         return QOT_ERR_BADARG;
     if (b_split && H != 64) return QOT_ERR_UNSUPPORTED;
     if (!gw1 && H != 64) return QOT_ERR_UNSUPPORTED;
-    if (H != 64)     // other widths: GA built 32 input channels at a time (nnconv_gen.hip)
-        return qot_nnconv_gradh_gen_launch(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm,
-                                           gw1, gb1, workspace, N, H, D, stream);
+    // a hosted job may not read what this call writes: its partials must lie outside the workspace
+    for (int r = 0; r < n_hosted; ++r) {
+        const uintptr_t src = (uintptr_t)hosted.job[r].src, w0 = (uintptr_t)workspace;
+        if (src >= w0 && src < w0 + qot_nnconv_gradh_workspace_floats(D) * sizeof(float)) return QOT_ERR_BADARG;
+    }
+    if (H != 64) {   // other widths: GA built 32 input channels at a time (nnconv_gen.hip); hosted jobs in a launch behind it
+        const int rc = qot_nnconv_gradh_gen_launch(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm,
+                                                   gw1, gb1, workspace, N, H, D, stream);
+        if (rc != QOT_OK || n_hosted == 0) return rc;
+        return qot_run_roles(hosted_roles, n_hosted, stream_);
+    }
     int grid = grid_for(N > 0 ? N : 1, 32);
     if (grid > 2 * num_cus()) grid = 2 * num_cus();
     const int K = 2 * D;
     const int rc = qot_nnconv_gradh64_launch(grad_out, ld_g, x, ld_x, edge_attr, w1, b1, rowptr, col, eid, invdeg, b_perm,
-                                             b_split, split_stride, workspace, N, D, grid, stream);
+                                             b_split, split_stride, workspace, N, D, grid, hosted, stream);
     if (rc != QOT_OK) return rc;
     QOT_LAUNCH_CHECK();
     if (!gw1) return QOT_OK;          // partials left in the workspace for qot_nnconv_bwd_finalize

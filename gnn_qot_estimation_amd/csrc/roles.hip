@@ -15,6 +15,9 @@
 //   backward epilogue  stage 1 {read-out partial sums | NNConv slab + grad-h sums | lin_edge level-1 sums | table
 //                       gradient row sum}, stage 2 {table projection backward | lin_edge level-2 sum}
 //                                                                      -- seven launches before (functional.py)
+//   hosted sums        stage 1's sums, where an H = 64 NNConv backward runs, ride as tail workgroups of its grad-h launch
+//                      instead (qot_nnconv_gradh_host_roles below, nnconv_gradh64.hip); the sum of grad-h's own partials joins
+//                      stage 2                                          -- the stage-1 launch is gone (launch_group.py)
 // Jobs inside one launch MUST be independent (no job may read what another job of the same launch writes).
 #include <cstdlib>
 #include "common.hpp"
@@ -92,6 +95,13 @@ __global__ __launch_bounds__(256) void roles_kernel(const RoleTable t_by_value) 
         nnconv_bwd_finalize64_body(rp<const float>(ro, 0), (int)ro.i[2], ro.i[3], rp<float>(ro, 2), (int)ro.i[4], (int)ro.i[5],
                                    rp<const float>(ro, 1), (int)ro.i[6], (int)ro.i[7], (int)ro.i[4] * (int)ro.i[1],
                                    rp<float>(ro, 3), rp<float>(ro, 4), vb);
+        break;
+    case QOT_ROLE_NNCONV_SLAB_SUM64:          // the two halves of QOT_ROLE_NNCONV_FINALIZE64, same fields
+        nnconv_slab_sum64_body(rp<const float>(ro, 0), (int)ro.i[2], ro.i[3], rp<float>(ro, 2), (int)ro.i[4], vb);
+        break;
+    case QOT_ROLE_NNCONV_GRADH_SUM64:
+        nnconv_gradh_sum64_body(rp<const float>(ro, 1), (int)ro.i[6], (int)ro.i[7], (int)ro.i[4] * (int)ro.i[1], rp<float>(ro, 3),
+                                rp<float>(ro, 4), vb);
         break;
     case QOT_ROLE_TABLE_PROJECT_BWD: {
         const Proj4 p{{rp<const float>(ro, 2), rp<const float>(ro, 3), rp<const float>(ro, 4), rp<const float>(ro, 5)},
@@ -198,11 +208,15 @@ static int plan_role(qot_role_t& r, int64_t* blocks, size_t* lds) {
         if (*blocks > 0x7fffffff) return QOT_ERR_UNSUPPORTED;
         return QOT_OK;
     }
-    case QOT_ROLE_NNCONV_FINALIZE64: {
+    case QOT_ROLE_NNCONV_FINALIZE64:
+    case QOT_ROLE_NNCONV_SLAB_SUM64:
+    case QOT_ROLE_NNCONV_GRADH_SUM64: {
         const int64_t N = i[0], D = i[1];
+        const bool slab = r.kind != QOT_ROLE_NNCONV_GRADH_SUM64, gh = r.kind != QOT_ROLE_NNCONV_SLAB_SUM64;
         if (N <= 0 || D < 1) return QOT_ERR_BADARG;
         if (D > 4) return QOT_ERR_UNSUPPORTED;
-        for (int k = 0; k < 5; ++k) if (!p[k]) return QOT_ERR_BADARG;
+        if (slab && (!p[0] || !p[2])) return QOT_ERR_BADARG;
+        if (gh && (!p[1] || !p[3] || !p[4])) return QOT_ERR_BADARG;
         int64_t agrid = (N + 31) / 32;
         if (agrid > (int64_t)num_cus() * kAdjBlocksPerCu) agrid = (int64_t)num_cus() * kAdjBlocksPerCu;
         int64_t hgrid = (N + 31) / 32;
@@ -212,7 +226,7 @@ static int plan_role(qot_role_t& r, int64_t* blocks, size_t* lds) {
         const int64_t nb1 = (elems / 4 * 16 + 255) / 256;
         const int64_t hn = K * (D + 1);
         i[2] = agrid; i[3] = elems; i[4] = K; i[5] = nb1; i[6] = hgrid; i[7] = hn;      // derived
-        *blocks = nb1 + (hn + 3) / 4;
+        *blocks = (slab ? nb1 : 0) + (gh ? (hn + 3) / 4 : 0);
         return QOT_OK;
     }
     case QOT_ROLE_TABLE_PROJECT_BWD: {
@@ -341,4 +355,63 @@ extern "C" int qot_run_roles(const qot_role_t* roles, int n_roles, qot_stream_t 
     roles_kernel<<<(int)total, 256, lds, stream>>>(t);
     QOT_LAUNCH_CHECK();
     return QOT_OK;
+}
+
+// ---- sums hosted by the next grad-h launch (nnconv_gradh64_kernel's tail workgroups; nnconv_mfma.hip launches) ----------
+// Host state only, per thread: nothing here touches the device, so the call is safe under stream capture.
+namespace {
+struct HostedState {
+    int n = 0;
+    qot_role_t role[QOT_MAX_ROLES];      // planned (derived fields filled)
+    int64_t blocks[QOT_MAX_ROLES];
+};
+thread_local HostedState g_hosted;
+}  // namespace
+
+extern "C" int qot_nnconv_gradh_host_roles(const qot_role_t* roles, int n_roles) {
+    if (n_roles < 0 || n_roles > QOT_MAX_ROLES || (n_roles > 0 && !roles)) return QOT_ERR_BADARG;
+    HostedState st;
+    int64_t total = 0;
+    for (int r = 0; r < n_roles; ++r) {
+        st.role[r] = roles[r];
+        // light kinds only: streaming sums with at most sum_rows_body's 4 KB of scratch, reading nothing of grad-h's own
+        if (st.role[r].kind != QOT_ROLE_SUM_ROWS && st.role[r].kind != QOT_ROLE_NNCONV_SLAB_SUM64)
+            return st.role[r].kind >= QOT_ROLE_CSR_BY_GRAPH && st.role[r].kind <= QOT_ROLE_NNCONV_GRADH_SUM64 ? QOT_ERR_UNSUPPORTED
+                                                                                                               : QOT_ERR_BADARG;
+        size_t need;
+        const int rc = plan_role(st.role[r], &st.blocks[r], &need);
+        if (rc != QOT_OK) return rc;
+        total += st.blocks[r];
+        if (total > 0x3fffffff) return QOT_ERR_UNSUPPORTED;
+    }
+    st.n = n_roles;
+    g_hosted = st;           // (a call with n_roles = 0 withdraws what an earlier call left)
+    return QOT_OK;
+}
+
+// Takes the calling thread's hosted jobs (and clears them): the table for the kernel, and the planned roles for a launch of
+// their own where the grad-h kernel at hand cannot carry them.  Returns their number.
+int qot_hosted_take(qot::HostedTable* t, qot_role_t* planned) {
+    HostedState& st = g_hosted;
+    const int n = st.n;
+    t->n = n;
+    int total = 0;
+    for (int r = 0; r < n; ++r) {
+        const qot_role_t& ro = st.role[r];
+        planned[r] = ro;
+        HostedJob& jb = t->job[r];
+        t->first[r] = total;
+        total += (int)st.blocks[r];
+        if (ro.kind == QOT_ROLE_SUM_ROWS) {
+            jb = HostedJob{kHostedSumRows, (int32_t)ro.i[3], (const float*)ro.p[0], (float*)const_cast<void*>(ro.p[1]), ro.i[0],
+                           ro.i[1], ro.i[2]};
+        } else {
+            jb = HostedJob{kHostedSlabSum64, (int32_t)ro.i[4], (const float*)ro.p[0], (float*)const_cast<void*>(ro.p[2]), ro.i[2],
+                           ro.i[3], 0};
+        }
+    }
+    for (int r = n; r <= QOT_MAX_ROLES; ++r) t->first[r] = total;
+    for (int r = n; r < QOT_MAX_ROLES; ++r) t->job[r] = HostedJob{0, 0, nullptr, nullptr, 0, 0, 0};
+    st.n = 0;
+    return n;
 }

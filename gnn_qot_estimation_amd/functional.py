@@ -1085,11 +1085,20 @@ class NNConvFn(torch.autograd.Function):
             deferred = LG.can_defer(*ctx.receivers)
             _lib.call("qot_nnconv_adjoint_dw", P(g), hout, P(x), hin, P(edge_attr), P(w1), P(b1), P(graph.rowptr_t),
                       P(graph.col_t), P(graph.eid_t), P(graph.invdeg), P(wp_adj), P(gx), P(gpar), 2, P(ws), N, hin, D)
-            _lib.call(gradh_fn, *gradh_args, None, None, P(wsh), N, hin, D)
-            if deferred:             # both second-stage sums join the backward epilogue's multi-role launch
-                LG.defer(_lib.ROLE_NNCONV_FINALIZE64, (ws, wsh, gpar, gw1f, gb1f), (N, D), stage=1)
+            if deferred and LG.hosted_sums():
+                # The grad-h LAUNCH is queued too (nothing of the pass reads its output; the next backward kernel depends on
+                # gx alone): the epilogue launches it carrying the stage-1 sums, the slab sum among them, as tail workgroups
+                # in the slots its ragged last round leaves empty; the sum of its own partials rides with stage 2.
+                LG.defer(_lib.ROLE_NNCONV_SLAB_SUM64, (ws, None, gpar), (N, D), stage=1)
+                LG.defer_gradh(gradh_fn, gradh_args + (None, None, P(wsh), N, hin, D),
+                               (_lib.ROLE_NNCONV_GRADH_SUM64, (None, wsh, None, gw1f, gb1f), (N, D)),
+                               keep=(g, x, edge_attr, w1, b1, graph, split, bp))
             else:
-                _lib.call("qot_nnconv_bwd_finalize", P(ws), P(wsh), P(gpar), P(gw1f), P(gb1f), N, hin, D)
+                _lib.call(gradh_fn, *gradh_args, None, None, P(wsh), N, hin, D)
+                if deferred:             # both second-stage sums join the backward epilogue's multi-role launch
+                    LG.defer(_lib.ROLE_NNCONV_FINALIZE64, (ws, wsh, gpar, gw1f, gb1f), (N, D), stage=1)
+                else:
+                    _lib.call("qot_nnconv_bwd_finalize", P(ws), P(wsh), P(gpar), P(gw1f), P(gb1f), N, hin, D)
         else:
             # grad_x: the forward kernel over the transposed graph with the per-block transposed weights;
             # weight gradient: A^T g by slices of the result, the operand gathered 32 channels at a time

@@ -15,6 +15,14 @@ Two users:
   before the flush; what is returned to autograd are VIEWS of buffers the queue keeps alive, so ``AccumulateGrad``
   still takes them without a copy.
 
+Hosted sums (``defer_gradh``): the H = 64 NNConv backward also queues its grad-h LAUNCH.  The grad-h kernel's persistent tile
+walk ends in a ragged round that leaves three quarters of its workgroup slots idle for a tile time, and nothing of the pass
+reads its output before the epilogue anyway; so the flush launches it behind the last backward kernel with the stage-1 sums
+as tail workgroups of its own launch (``qot_nnconv_gradh_host_roles``), and the sum of its own partials -- the one stage-1
+job it cannot carry -- rides with stage 2: the epilogue is {grad-h + stage-1 sums, stage 2} instead of {grad-h, stage 1,
+stage 2}.  ``QOT_NO_HOSTED_SUMS=1`` (read on every call) restores that schedule exactly; ``QOT_HOSTED_SUMS_EARLY=1`` launches
+grad-h where it always was, carrying only the sums already queued by then (measurements).
+
 ``QOT_NO_LAUNCH_GROUPS=1`` restores one launch per job (A/B measurements, bisecting).
 
 Threading: the backward queue is ONE module-level object armed through an autograd-engine callback -- right for the
@@ -35,6 +43,10 @@ from . import _lib
 
 def enabled() -> bool:
     return os.environ.get("QOT_NO_LAUNCH_GROUPS", "0") != "1"
+
+
+def hosted_sums() -> bool:
+    return os.environ.get("QOT_NO_HOSTED_SUMS", "0") != "1"
 
 
 def can_defer(*receivers) -> bool:
@@ -91,10 +103,11 @@ class _BackwardQueue:
         self.clear()
 
     def pending(self) -> bool:
-        return bool(self.stages[0] or self.stages[1])
+        return bool(self.stages[0] or self.stages[1] or self.gradh)
 
     def clear(self):
         self.stages = ([], [])
+        self.gradh = []              # queued grad-h launches: (entry point, arguments, role of its partial sum)
         self.keep = []
         self.stream = None           # raw handle of the stream the backward nodes run on
         self.armed = False
@@ -122,18 +135,69 @@ def defer(kind: int, ptrs, ints, stage: int = 1, keep=()):
     q.keep.extend(keep)
 
 
+def _take_hostable(s1):
+    """Splits stage 1 into what a grad-h launch can carry (light sums, at most ``MAX_ROLES``) and the rest, order kept."""
+    hosted, rest = [], []
+    for r in s1:
+        (hosted if r.kind in _lib.HOSTABLE_ROLES and len(hosted) < _lib.MAX_ROLES else rest).append(r)
+    return hosted, rest
+
+
+def defer_gradh(fn: str, args, partial_sum, keep=()):
+    """Queue the H = 64 grad-h launch ``fn(*args, stream)`` of an NNConv backward whose second-stage sums are deferred.
+    ``partial_sum``: ``(kind, ptrs, ints)`` of the sum of the launch's own partials.  ``args`` are raw values: ``keep`` holds
+    the tensors behind them.  Only valid inside an autograd backward pass, like ``defer``."""
+    q = _arm()
+    q.keep.extend(keep)
+    q.keep.extend(t for t in partial_sum[1] if isinstance(t, torch.Tensor))
+    role = _lib.make_role(*partial_sum)
+    if os.environ.get("QOT_HOSTED_SUMS_EARLY", "0") == "1":
+        hosted, q.stages[0][:] = _take_hostable(q.stages[0])
+        _lib.host_roles(hosted)
+        with _lib.on_stream(q.stream):
+            _lib.call(fn, *args)
+        q.stages[0].append(role)
+    else:
+        q.gradh.append((fn, args, role))
+
+
+def plan(s1, s2, gradh):
+    """The launches of a flush, in order: ``("gradh", fn, args, hosted roles)`` and ``("roles", roles)`` entries.
+    Without a queued grad-h launch: stage 1, stage 2.  With one: grad-h carrying every stage-1 job it can host (NEVER the
+    sum of its own partials: that one reads what the launch writes), then one launch of stage 2 plus the partial sums, which
+    no stage-2 job reads or writes.  Stage-1 jobs it cannot carry (another kind, more than ``MAX_ROLES``) keep a launch of
+    their own, with the partial sums, in front of stage 2.  Further queued grad-h launches (a second NNConv layer) carry nothing."""
+    if not gradh:
+        return [("roles", r) for r in (s1, s2) if r]
+    hosted, rest = _take_hostable(s1)
+    out = [("gradh", fn, args, hosted if k == 0 else []) for k, (fn, args, _) in enumerate(gradh)]
+    sums = [role for _, _, role in gradh]
+    if rest:
+        out += [("roles", rest + sums)] + ([("roles", s2)] if s2 else [])
+    else:
+        out.append(("roles", s2 + sums))
+    return out
+
+
 def flush():
-    """Launch the pending jobs: one launch for stage 1, one for stage 2 (if any)."""
+    """Launch the pending jobs: one launch for stage 1, one for stage 2 (if any); with a queued grad-h launch, see ``plan``."""
     q = _Q
     if not q.pending():
         q.armed = False
         return
     s1, s2 = q.stages
-    stream = q.stream
-    q.stages = ([], [])
+    gradh, stream = q.gradh, q.stream
+    q.stages, q.gradh = ([], []), []
     try:
-        _lib.run_roles(s1, stream)
-        _lib.run_roles(s2, stream)
+        for step in plan(s1, s2, gradh):
+            if step[0] == "gradh":
+                _, fn, args, hosted = step
+                if hosted:
+                    _lib.host_roles(hosted)
+                with _lib.on_stream(stream):
+                    _lib.call(fn, *args)
+            else:
+                _lib.run_roles(step[1], stream)
     finally:
         q.keep = []
         q.armed = False

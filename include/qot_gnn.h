@@ -756,6 +756,9 @@ int qot_skinny_linear_dw(const float* g, const float* x, float* partials, int64_
  *                             (as qot_table_scores)
  * QOT_ROLE_TABLE_PROJECT_BWD_SCORES  0 S, 1 t4, 2 w_edge, 3 table, 4 wq, 5 wk, 6 wv, 7 ws,  0 V, 1 n, 2 H, 3 D
  *                             8 grad_table, 9 grad_w, 10 grad_b, 11 grad_w_edge (as qot_table_project_bwd_scores)
+ * QOT_ROLE_NNCONV_SLAB_SUM64   the slab half of QOT_ROLE_NNCONV_FINALIZE64 alone: 0 adj_workspace, 2 grad_params (same
+ *                             slots; 1, 3, 4 unused); it depends on qot_nnconv_adjoint_dw only       0 N, 1 D; 2..7 derived
+ * QOT_ROLE_NNCONV_GRADH_SUM64  the grad-h half alone: 1 gradh_workspace, 3 gw1, 4 gb1 (0, 2 unused)   0 N, 1 D; 2..7 derived
  * "derived" fields are filled by the library in its own copy; callers leave them 0. */
 #define QOT_MAX_ROLES 12
 enum {
@@ -766,7 +769,9 @@ enum {
     QOT_ROLE_NNCONV_FINALIZE64 = 5,
     QOT_ROLE_TABLE_PROJECT_BWD = 6,
     QOT_ROLE_TABLE_SCORES = 7,
-    QOT_ROLE_TABLE_PROJECT_BWD_SCORES = 8
+    QOT_ROLE_TABLE_PROJECT_BWD_SCORES = 8,
+    QOT_ROLE_NNCONV_SLAB_SUM64 = 9,
+    QOT_ROLE_NNCONV_GRADH_SUM64 = 10
 };
 typedef struct qot_role {
     int32_t kind;
@@ -775,6 +780,25 @@ typedef struct qot_role {
     int64_t i[8];
 } qot_role_t;
 int qot_run_roles(const qot_role_t* roles, int n_roles, qot_stream_t stream);
+
+/* Sums hosted by the next grad-h launch.  The persistent tile walk of the H = 64 grad-h kernel ends in a ragged round (at
+ * 12.5 tiles per CU three quarters of its workgroup slots idle for the last tile time); workgroups appended to that launch
+ * start in the freed slots.  This call hands the NEXT qot_nnconv_gradh_split / qot_nnconv_gradh_fused call of the calling
+ * thread up to QOT_MAX_ROLES jobs to run there.
+ *   - Kinds: QOT_ROLE_SUM_ROWS and QOT_ROLE_NNCONV_SLAB_SUM64 (streaming sums, at most 4 KB of scratch); any other known
+ *     kind: QOT_ERR_UNSUPPORTED.  Each role is validated as qot_run_roles validates it; on any error NOTHING is stored
+ *     (what an earlier call left stays).  n_roles = 0 withdraws what an earlier call left.
+ *   - A hosted job may read only what launches enqueued BEFORE the grad-h call wrote; it must not read what the grad-h call
+ *     writes (a QOT_ROLE_SUM_ROWS whose partials lie in the grad-h call's workspace makes that call return QOT_ERR_BADARG
+ *     before it launches anything), and hosted jobs are independent of each other.  No workgroup waits for another: the
+ *     results are the same bits whenever and wherever the jobs run.
+ *   - Contract: when the work of the next grad-h call is done, the hosted jobs are done.  At H = 64 (every form: fp32 or
+ *     split, 1 <= D <= 4) they are tail workgroups of the grad-h kernel itself; at any other width the grad-h call launches
+ *     them through qot_run_roles on its own stream right behind its kernel.  A grad-h call that returns an error before
+ *     its launch drops them.  The state is taken (cleared) by that one call: a later grad-h call hosts nothing.
+ *   - Host state only (thread-local, no device access): safe under stream capture.  Nothing is read from `roles` after
+ *     the call returns. */
+int qot_nnconv_gradh_host_roles(const qot_role_t* roles, int n_roles);
 
 /* ---- row gather / scatter (LUT read-out and its adjoint) ---------------------------- */
 int qot_rows_gather(const float* x, const int32_t* idx, float* out, int64_t n_idx, int C,

@@ -44,13 +44,15 @@ if not other:
               f" mfma {sum(n for o, n in ops.items() if o.startswith('v_mfma'))}")
 else:
     old = kernels(other, f"/tmp/{name}.against.s")
-    for sym in sorted(set(new) | set(old), key=demangled):
+    # namesakes by demangled name without the argument list: a kernel that gained an argument is still compared with itself
+    new, old = ({demangled(sym): v for sym, v in d.items()} for d in (new, old))
+    for sym in sorted(set(new) | set(old)):
         if sym not in new or sym not in old:
-            print(f"{demangled(sym):70s} only in the {'first' if sym in new else 'second'} build")
+            print(f"{sym:70s} only in the {'first' if sym in new else 'second'} build")
             continue
         (fn, on, ln), (fo, oo, lo) = new[sym], old[sym]
         diff = {o: on[o] - oo[o] for o in set(on) | set(oo) if on[o] != oo[o]}
-        print(f"{demangled(sym):70s} " + " ".join(f"{k} {fn[k]}/{fo[k]}" for k, _ in KEYS) +
+        print(f"{sym:70s} " + " ".join(f"{k} {fn[k]}/{fo[k]}" for k, _ in KEYS) +
               f" | figures {'equal' if fn == fo else 'DIFFER'} | opcodes {'equal' if not diff else 'DIFFER ' + str(diff)}"
               f" | listing {'identical' if ln == lo else 'differs'}")
 print("asm:", f"/tmp/{name}.s")
