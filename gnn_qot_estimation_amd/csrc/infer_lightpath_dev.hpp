@@ -31,6 +31,8 @@
 // another x_i, some slice positions skipped, further sources behind the slice.  The scans then run the slice's chunks and
 // after them the added list as further chunks of 64; the sums stay "one after the other by rising position, the self loop
 // last", which is the order of the explicitly built graph (its surviving edges in their order, the additions behind them).
+// LpStaged (infer_lightpath_status.hip) is the row without a graph: x_i and the sources' rows are staged in
+// LDS by the caller, the slice is empty, and message t is staged row t -- the same scans over the staged list alone.
 #pragma once
 #include "common.hpp"
 
@@ -124,6 +126,7 @@ __device__ __forceinline__ void lp_dense(const float* __restrict__ w, const floa
 // the edit policy of a plain row: nothing is edited, every hook folds away
 struct LpNoEdit {
     static constexpr bool kEdits = false;
+    static constexpr bool kStaged = false;
 };
 
 constexpr int kLpMaxDrop = 32;          // removals of one candidate (their offsets are staged in LDS: 256 B)
@@ -132,6 +135,7 @@ constexpr int kLpMaxDrop = 32;          // removals of one candidate (their offs
 // array) and dl; lp_row calls stage() once the graph's edge slice is known to lie inside the edge array.
 struct LpWhatIf {
     static constexpr bool kEdits = true;
+    static constexpr bool kStaged = false;
     const float* xi;                    // the candidate's feature row [F]; null: the node's own
     const int64_t* add;                 // its added sources [na], batch node numbering
     int64_t na;
@@ -158,12 +162,39 @@ struct LpWhatIf {
     }
 };
 
+// the edit policy of a row whose neighbourhood the caller has staged (infer_lightpath_status.hip): there is
+// no graph -- node_ptr, edge_ptr, edge_index and x are not read, i and g are not looked at.  The edge slice is empty, x_i is
+// the staged row `xi`, and the "added sources" are the `na` staged rows themselves, in the order the messages are summed:
+// message t is row t.  All of them are messages (the caller leaves the destination out).
+struct LpStaged {
+    static constexpr bool kEdits = false;                      // no slice: nothing to drop, nothing to stage
+    static constexpr bool kStaged = true;
+    const float* xi;                    // the destination's feature row [F] (LDS)
+    const float* rows;                  // the sources' feature rows [na][kLpXs] (LDS)
+    int64_t na;
+};
+
+// where the feature row of message source `src` is read from: row src of x, or staged row src
+template <class Edit>
+__device__ __forceinline__ const float* lp_src_row(const LpArgs& a, const Edit& ed, int64_t src, int F) {
+    if constexpr (Edit::kStaged) {
+        return ed.rows + src * kLpXs;
+    } else {
+        return a.x + src * F;
+    }
+}
+
 // the messages of a chunk: lane `lane` looks at the edge at offset base + lane of the slice.  Returns 0 (no message),
 // 1 (a message from `src`) or 2 (an edge that leaves the graph's node range: nothing is read through it).  With an edit:
 // a dropped offset is no message and its ends are not read; offset ed.mp + t is added source t, with destination i.
+// Staged: offset t < na is the message from staged row t.
 template <class Edit = LpNoEdit>
 __device__ __forceinline__ int lp_edge(const LpArgs& a, int64_t e0, int64_t m, int64_t k, int64_t n0, int64_t n1, int64_t i,
                                        int64_t& src, const Edit& ed = Edit{}) {
+    if constexpr (Edit::kStaged) {
+        src = k;
+        return k < ed.na ? 1 : 0;                              // (nothing below is reached)
+    }
     if constexpr (Edit::kEdits) {
         if (k >= ed.mp) {
             if (k - ed.mp >= ed.na) return 0;
@@ -191,15 +222,21 @@ template <bool kKeep, class Edit = LpNoEdit>
 __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int64_t i, int64_t g, float* orow, int lane,
                                       LpRowRegs& R, Edit ed = Edit{}) {
     const int F = a.F, C = a.C;
-    const int64_t n0 = a.node_ptr[g], n1 = a.node_ptr[g + 1], e0 = a.edge_ptr[g], e1 = a.edge_ptr[g + 1];
+    int64_t n0 = 0, n1 = 0, e0 = 0, e1 = 0;                    // (staged: no graph, an empty slice)
+    if constexpr (!Edit::kStaged) {
+        n0 = a.node_ptr[g]; n1 = a.node_ptr[g + 1]; e0 = a.edge_ptr[g]; e1 = a.edge_ptr[g + 1];
+    }
     const bool slice_ok = e0 >= 0 && e1 >= e0 && e1 <= a.E;
     R.n0 = n0; R.n1 = n1; R.e0 = e0; R.m = e1 - e0;
-    if (n0 < 0 || n1 > a.N || i < n0 || i >= n1 || !slice_ok) {
-        lp_refuse(a, orow, lane, 2);
-        return slice_ok ? 2 : 1;
+    if constexpr (!Edit::kStaged) {
+        if (n0 < 0 || n1 > a.N || i < n0 || i >= n1 || !slice_ok) {
+            lp_refuse(a, orow, lane, 2);
+            return slice_ok ? 2 : 1;
+        }
     }
     const int64_t m = e1 - e0;
     int64_t span = m;                                          // the offsets the scans run over
+    if constexpr (Edit::kStaged) span = ed.na;
     if constexpr (Edit::kEdits) {
         if (!ed.stage(e0, m, lane)) {                          // (wave-uniform)
             lp_refuse(a, orow, lane, 2);
@@ -223,7 +260,9 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
         L.s[h * kLpMaxF + f] = s;
         L.d[h * kLpMaxF + f] = d;
     }
-    if constexpr (Edit::kEdits) {
+    if constexpr (Edit::kStaged) {
+        if (lane < F) L.xi[lane] = ed.xi[lane];
+    } else if constexpr (Edit::kEdits) {
         if (lane < F) L.xi[lane] = ed.xi ? ed.xi[lane] : a.x[i * F + lane];
     } else {
         if (lane < F) L.xi[lane] = a.x[i * F + lane];
@@ -262,7 +301,7 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
         bad = bad || kind == 2;
         if (kind == 1) {
             float l[kLpHeads] = {};
-            lp_dot4(L.s, a.x + src * F, F, l);
+            lp_dot4(L.s, lp_src_row(a, ed, src, F), F, l);
 #pragma unroll
             for (int hh = 0; hh < kLpHeads; ++hh) mx[hh] = fmaxf(mx[hh], lp_leaky(l[hh] + adst[hh], a.slope_att));
         }
@@ -289,7 +328,7 @@ __device__ __forceinline__ int lp_row(const LpArgs& a, LpLds& L, LpKeep* K, int6
         const bool msg = lp_edge(a, e0, m, base + lane, n0, n1, i, src, ed) == 1;
         if (msg) {
             float l[kLpHeads] = {};
-            lp_dot4(L.s, a.x + src * F, F, l, L.xs + lane * kLpXs);
+            lp_dot4(L.s, lp_src_row(a, ed, src, F), F, l, L.xs + lane * kLpXs);
 #pragma unroll
             for (int hh = 0; hh < kLpHeads; ++hh)
                 L.pw[hh * kWave + lane] = expf(lp_leaky(l[hh] + adst[hh], a.slope_att) - mx[hh]);

@@ -17,28 +17,21 @@
 // Everything a sample produces depends on that sample alone, so a graph is bit-identical in any chunk.
 //
 // Scaling is (v - min) / (max - min) in fp64 (IEEE division), one rounding to fp32; the file is compiled with
-// -ffp-contract=off.
-#include "common.hpp"
+// -ffp-contract=off.  The scan, the table and the scaling are status_scan_dev.hpp's, shared with
+// infer_lightpath_status.hip.
+#include "status_scan_dev.hpp"
 
 namespace qot {
 namespace sg {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kCap = QOT_SG_MAX_LIGHTPATHS;      // 256
-constexpr int kQCap = QOT_SG_MAX_FREQS;          // 1024
+// (the workgroup's geometry, kCap / kQCap, the first-seen table, discover(), sample_of() and scaled(): status_scan_dev.hpp)
 constexpr int kTopo = QOT_SG_NODES;              // 75
 constexpr int kCells = kTopo * kTopo;            // 5625
 constexpr int kAdjWords = kCap * kCap / 32;      // 2048
-static_assert(kCap == kThreads, "one thread per lightpath / adjacency row");
 
 // scratch slot of one sample: first[kCap] int32, then the matrix (adjacency bits or int16 winners)
 constexpr size_t kMatBytes = kCells * 2 > kAdjWords * 4 ? (size_t)((kCells * 2 + 15) / 16 * 16) : (size_t)kAdjWords * 4;
 constexpr size_t kSlotBytes = (size_t)kCap * 4 + kMatBytes;
-
-__device__ __forceinline__ int wave_prefix(uint64_t mask) {      // set bits of mask below this lane
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-}
 
 // exclusive prefix of v over the block's threads (thread order) and the block total; `part` holds kWaves + 1 ints
 __device__ __forceinline__ int block_exscan(int v, int* part, int& total) {
@@ -63,93 +56,6 @@ __device__ __forceinline__ int block_exscan(int v, int* part, int& total) {
     return base + inc - v;
 }
 
-struct Table {
-    int64_t conn[kCap];
-    int32_t first[kCap];
-    int64_t chunk_conn[kThreads];
-    unsigned long long new_mask[kWaves];
-    int wave_new[kWaves];
-    int n;
-};
-
-// The lightpaths of one sample in first-seen order.  chan (optional): lightpath number of every channel, -1 when the
-// channel is empty.  Returns status bits.
-__device__ int discover(const double* __restrict__ d, int P, int LQ, int conn_row, Table& T, int16_t* __restrict__ chan) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int bad = 0;
-    if (tid == 0) T.n = 0;
-    __syncthreads();
-    for (int base = 0; base < LQ; base += kThreads) {
-        const int c = base + tid;
-        bool occ = false;
-        int64_t conn = 0;
-        if (c < LQ) {
-            for (int p = 0; p < P; ++p) occ |= (d[(int64_t)p * LQ + c] != 0.0);
-            if (occ) {
-                const double cv = d[(int64_t)conn_row * LQ + c];
-                if (!(fabs(cv) <= 9007199254740992.0)) {          // NaN, inf or beyond +-2^53
-                    bad |= QOT_SG_BAD_CONN;
-                    occ = false;
-                } else {
-                    conn = (int64_t)cv;                            // truncation, as int(...) does
-                }
-            }
-        }
-        const int n0 = T.n;
-        int idx = -1;
-        if (occ)
-            for (int i = 0; i < n0; ++i)
-                if (T.conn[i] == conn) { idx = i; break; }
-        const bool isnew = occ && idx < 0;
-        T.chunk_conn[tid] = conn;
-        const unsigned long long m = __ballot(isnew);
-        if (lane == 0) T.new_mask[w] = m;
-        __syncthreads();
-        // the first channel of the chunk with this conn appends it
-        bool first = isnew;
-        if (isnew) {
-            for (int ww = 0; ww <= w && first; ++ww) {
-                unsigned long long mm = T.new_mask[ww];
-                if (ww == w) mm &= (1ull << lane) - 1ull;
-                while (mm) {
-                    const int j = ww * 64 + __builtin_ctzll(mm);
-                    mm &= mm - 1;
-                    if (T.chunk_conn[j] == conn) { first = false; break; }
-                }
-            }
-        }
-        const unsigned long long fm = __ballot(first);
-        if (lane == 0) T.wave_new[w] = __popcll(fm);
-        __syncthreads();
-        int rank = wave_prefix(fm), total = 0;
-#pragma unroll
-        for (int k = 0; k < kWaves; ++k) {
-            const int p = T.wave_new[k];
-            if (k < w) rank += p;
-            total += p;
-        }
-        if (first) {
-            const int slot = n0 + rank;
-            if (slot < kCap) {
-                T.conn[slot] = conn;
-                T.first[slot] = c;
-                idx = slot;
-            } else {
-                bad |= QOT_SG_TOO_MANY;
-            }
-        }
-        __syncthreads();                                           // table complete; everybody has read T.n
-        const int n1 = n0 + total < kCap ? n0 + total : kCap;
-        if (tid == 0) T.n = n1;
-        if (isnew && !first)
-            for (int i = n0; i < n1; ++i)
-                if (T.conn[i] == conn) { idx = i; break; }
-        if (chan && c < LQ) chan[c] = (int16_t)idx;
-        __syncthreads();
-    }
-    return bad;
-}
-
 struct CountArgs {
     const double* data;
     const double* freq;
@@ -162,12 +68,6 @@ struct CountArgs {
     int16_t* chan;
     int32_t* info;
 };
-
-__device__ __forceinline__ int64_t sample_of(const int64_t* samples, int64_t g, int64_t S, bool& ok) {
-    const int64_t s = samples ? samples[g] : g;
-    ok = s >= 0 && s < S;
-    return s;
-}
 
 __global__ __launch_bounds__(kThreads) void count_lightpath(CountArgs a) {
     __shared__ Table T;
@@ -346,11 +246,6 @@ struct FillArgs {
     float* y;                 // [G, 3]
 };
 
-__device__ __forceinline__ float scaled(double v, const double* col) {
-    if (col[3] != 0.0) v = (v - col[1]) / col[2];
-    return (float)v;
-}
-
 __device__ __forceinline__ void fill_y(const FillArgs& a, int64_t g, int64_t s) {
     if (threadIdx.x < 3) {
         const double* col = a.tcols + 4 * threadIdx.x;
@@ -383,17 +278,8 @@ __global__ __launch_bounds__(kThreads) void fill_lightpath(FillArgs a) {
     if (tid < n) {
         const int c = first[tid];
         if (c >= 0 && c < LQ) {
-            for (int k = 0; k < a.ncol; ++k) {
-                const double* col = a.cols + 4 * k;
-                const int r = (int)col[0];
-                float out;
-                if (r < 0)
-                    out = (d[(int64_t)a.osnr_row * LQ + c] == -1.0 && d[(int64_t)a.snr_row * LQ + c] == -1.0 &&
-                           d[(int64_t)a.ber_row * LQ + c] == -1.0) ? 1.0f : 0.0f;
-                else
-                    out = r < a.P ? scaled(d[(int64_t)r * LQ + c], col) : 0.0f;
-                a.feat[(nb + tid) * a.ncol + k] = out;
-            }
+            for (int k = 0; k < a.ncol; ++k)
+                a.feat[(nb + tid) * a.ncol + k] = sg_feature(d, a.P, LQ, a.osnr_row, a.snr_row, a.ber_row, a.cols, k, c);
         }
     }
     __syncthreads();

@@ -1,0 +1,151 @@
+// The scan of one network-status sample data[P, L, Q] (fp64) by one 256-thread workgroup, shared by the graph builder
+// (status_graph.hip) and the status-to-row kernel (infer_lightpath_status.hip): both run
+// discover(), so the lightpaths of a sample, their numbering and their first channels are the same table in both.  Stated
+// once here for both: the workgroup's geometry and caps, the first-seen table and its insert, the sample pick, the
+// occupancy / conn rule of one channel (sg_conn) and the fp64 column scaling (scaled).
+//
+// Channels are scanned in the order c = l * Q + q, 256 at a time: occupied = any of the P values != 0; the distinct
+// trunc(conn_id) values are appended, in first-seen order, to an LDS table (conn, first channel).
+//
+// Scaling is (v - min) / (max - min) in fp64 (IEEE division), one rounding to fp32.  The expression holds a subtraction
+// and a division, nothing a contraction could fuse; `scaled` is compiled under `fp contract(off)` all the same, so it is
+// the same code in a translation unit built with -ffp-contract=off (status_graph.hip) and in one that is not.
+#pragma once
+#include "common.hpp"
+
+namespace qot {
+namespace sg {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kCap = QOT_SG_MAX_LIGHTPATHS;      // 256
+constexpr int kQCap = QOT_SG_MAX_FREQS;          // 1024
+static_assert(kCap == kThreads, "one thread per lightpath / adjacency row");
+
+__device__ __forceinline__ int wave_prefix(uint64_t mask) {      // set bits of mask below this lane
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+}
+
+struct Table {
+    int64_t conn[kCap];
+    int32_t first[kCap];
+    int64_t chunk_conn[kThreads];
+    unsigned long long new_mask[kWaves];
+    int wave_new[kWaves];
+    int n;
+};
+
+// The conn of a channel whose conn_id value is cv: false when the value is NaN, inf or beyond +-2^53 (the channel then
+// counts as empty and the caller flags QOT_SG_BAD_CONN); truncation, as int(...) does.
+__device__ __forceinline__ bool sg_conn(double cv, int64_t& conn) {
+    if (!(fabs(cv) <= 9007199254740992.0)) return false;
+    conn = (int64_t)cv;
+    return true;
+}
+
+// The lightpaths of one sample in first-seen order.  chan (optional): lightpath number of every channel, -1 when the
+// channel is empty.  Returns status bits.
+__device__ int discover(const double* __restrict__ d, int P, int LQ, int conn_row, Table& T, int16_t* __restrict__ chan) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int bad = 0;
+    if (tid == 0) T.n = 0;
+    __syncthreads();
+    for (int base = 0; base < LQ; base += kThreads) {
+        const int c = base + tid;
+        bool occ = false;
+        int64_t conn = 0;
+        if (c < LQ) {
+            for (int p = 0; p < P; ++p) occ |= (d[(int64_t)p * LQ + c] != 0.0);
+            if (occ) {
+                const double cv = d[(int64_t)conn_row * LQ + c];
+                if (!sg_conn(cv, conn)) {                          // NaN, inf or beyond +-2^53
+                    bad |= QOT_SG_BAD_CONN;
+                    occ = false;
+                }
+            }
+        }
+        const int n0 = T.n;
+        int idx = -1;
+        if (occ)
+            for (int i = 0; i < n0; ++i)
+                if (T.conn[i] == conn) { idx = i; break; }
+        const bool isnew = occ && idx < 0;
+        T.chunk_conn[tid] = conn;
+        const unsigned long long m = __ballot(isnew);
+        if (lane == 0) T.new_mask[w] = m;
+        __syncthreads();
+        // the first channel of the chunk with this conn appends it
+        bool first = isnew;
+        if (isnew) {
+            for (int ww = 0; ww <= w && first; ++ww) {
+                unsigned long long mm = T.new_mask[ww];
+                if (ww == w) mm &= (1ull << lane) - 1ull;
+                while (mm) {
+                    const int j = ww * 64 + __builtin_ctzll(mm);
+                    mm &= mm - 1;
+                    if (T.chunk_conn[j] == conn) { first = false; break; }
+                }
+            }
+        }
+        const unsigned long long fm = __ballot(first);
+        if (lane == 0) T.wave_new[w] = __popcll(fm);
+        __syncthreads();
+        int rank = wave_prefix(fm), total = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; ++k) {
+            const int p = T.wave_new[k];
+            if (k < w) rank += p;
+            total += p;
+        }
+        if (first) {
+            const int slot = n0 + rank;
+            if (slot < kCap) {
+                T.conn[slot] = conn;
+                T.first[slot] = c;
+                idx = slot;
+            } else {
+                bad |= QOT_SG_TOO_MANY;
+            }
+        }
+        __syncthreads();                                           // table complete; everybody has read T.n
+        const int n1 = n0 + total < kCap ? n0 + total : kCap;
+        if (tid == 0) T.n = n1;
+        if (isnew && !first)
+            for (int i = n0; i < n1; ++i)
+                if (T.conn[i] == conn) { idx = i; break; }
+        if (chan && c < LQ) chan[c] = (int16_t)idx;
+        __syncthreads();
+    }
+    return bad;
+}
+
+__device__ __forceinline__ int64_t sample_of(const int64_t* samples, int64_t g, int64_t S, bool& ok) {
+    const int64_t s = samples ? samples[g] : g;
+    ok = s >= 0 && s < S;
+    return s;
+}
+
+// the is_lut flag of a lightpath: osnr == snr == ber == -1 on its first channel c
+__device__ __forceinline__ bool sg_is_lut(const double* __restrict__ d, int LQ, int osnr_row, int snr_row, int ber_row, int c) {
+    return d[(int64_t)osnr_row * LQ + c] == -1.0 && d[(int64_t)snr_row * LQ + c] == -1.0 && d[(int64_t)ber_row * LQ + c] == -1.0;
+}
+
+// one output column: col = (lp_feat row, min, max - min, has_range)
+__device__ __forceinline__ float scaled(double v, const double* col) {
+#pragma clang fp contract(off)
+    if (col[3] != 0.0) v = (v - col[1]) / col[2];
+    return (float)v;
+}
+
+// column k of the feature row of the lightpath whose first channel is c (cols [ncol, 4]; lp_feat row -1: is_lut; a row
+// outside the P rows of data reads as 0)
+__device__ __forceinline__ float sg_feature(const double* __restrict__ d, int P, int LQ, int osnr_row, int snr_row, int ber_row,
+                                            const double* __restrict__ cols, int k, int c) {
+    const double* col = cols + 4 * k;
+    const int r = (int)col[0];
+    if (r < 0) return sg_is_lut(d, LQ, osnr_row, snr_row, ber_row, c) ? 1.0f : 0.0f;
+    return r < P ? scaled(d[(int64_t)r * LQ + c], col) : 0.0f;
+}
+
+}  // namespace sg
+}  // namespace qot

@@ -2,7 +2,8 @@
 ``sample``: ``csrc/infer_mc.hip``; its per-link ``sensitivity``: ``csrc/infer_grad.hip``, DESIGN.md
 4.16; its ``what_if`` over edited graphs: ``csrc/infer_whatif.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
 ``csrc/infer_lightpath_grad.hip``; its ``what_if`` over candidate lightpaths:
-``csrc/infer_lightpath_whatif.hip``).
+``csrc/infer_lightpath_whatif.hip``; its ``from_status`` over network-status samples:
+``csrc/infer_lightpath_status.hip``).
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
 TransformerConv, the NNConv forward and the read-out kernel (``LightpathGNN``: the self-looped graph index, the GAT walk
@@ -16,7 +17,7 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib
+from . import _lib, to_graph
 from .functional import _f32c
 from .graph import _cache
 
@@ -357,7 +358,9 @@ class _DeviceState:
         code = int(self._status.item())
         self._status.zero_()
         if code:
-            raise _lib.QotError("%s flagged the batch (status %d): %s" % (self._FLAGS[0], code, self._FLAGS[1]))
+            named = "; ".join(text for bit, text in getattr(self, "_CAUSES", ()) if code & bit)
+            raise _lib.QotError("%s flagged the batch (status %d): %s%s" % (self._FLAGS[0], code, self._FLAGS[1],
+                                                                           named and " -- here: " + named))
 
 
 # what TopologicalPredictor._prepare hands to _launch: the model's shape, the batch on dev, its size bounds, the tables
@@ -834,6 +837,49 @@ def materialise_lightpath_what_if(data, lut_col, x_lut=None, add_src=None, add_p
     return out, node_new
 
 
+LP_STATUS_MAX_FREQS = 1024      # include/qot_gnn.h: QOT_SG_MAX_FREQS
+# include/qot_gnn.h: QOT_LP_STATUS_*, the status bits of qot_lightpath_infer_status (above the other kernels' 1, 2, 4)
+LP_STATUS_BAD_CONN, LP_STATUS_TOO_MANY, LP_STATUS_BAD_SAMPLE = 8, 16, 32
+
+_LpStatus = namedtuple("_LpStatus", "features S P L Q conn_row osnr_row snr_row ber_row freq_threshold")
+
+
+def lightpath_status_args(status, in_channels, is_lut_index, features_to_consider=to_graph.DEFAULT_FEATURES,
+                          freq_threshold=0.05, who="LightpathPredictor.from_status"):
+    """The argument checks of ``LightpathPredictor.from_status`` that need no device: returns an ``_LpStatus`` (the feature
+    list, the chunk's sizes, the ``lp_feat`` rows the kernel reads, the threshold as a float) or raises -- ``TypeError`` for
+    a ``status`` that is no ``DeviceStatus``, ``ValueError`` for a threshold that is no finite positive number,
+    ``EnvelopeError`` naming the condition for everything else; a chunk on the CPU is named last."""
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    thr = freq_threshold
+    if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not 0.0 < float(thr) < float("inf"):
+        raise ValueError(f"{who}: freq_threshold must be a finite positive number, got {thr!r}")
+    feats = list(features_to_consider)
+    S, P, L, Q = (int(v) for v in status.data.shape)
+    if Q > LP_STATUS_MAX_FREQS:
+        raise EnvelopeError(f"{who}: at most {LP_STATUS_MAX_FREQS} frequency slots per link, got {Q}")
+    if L * Q >= 1 << 31:
+        raise EnvelopeError(f"{who}: links x frequency slots must stay below 2^31, got {L} x {Q}")
+    if len(feats) + 1 != int(in_channels):
+        raise EnvelopeError(f"{who}: {len(feats)} features + is_lut are {len(feats) + 1} columns, the model takes "
+                            f"in_channels = {in_channels}")
+    if "is_lut" in feats:
+        raise EnvelopeError(f"{who}: is_lut is not a feature of the status; the column is added to features_to_consider")
+    col = sorted(feats + ["is_lut"]).index("is_lut")
+    if col != int(is_lut_index):
+        raise EnvelopeError(f"{who}: is_lut is column {col} of the sorted feature names, the model's is_lut_index is "
+                            f"{is_lut_index}")
+    fi = status.feature_indexes
+    missing = [n for n in feats + ["conn_id", "osnr", "snr", "ber"] if n not in fi]
+    if missing:
+        raise EnvelopeError(f"{who}: the status has no lp_feat row named {', '.join(repr(n) for n in missing)}")
+    if not status.data.is_cuda:
+        raise EnvelopeError(f"{who}: the status chunk is on the CPU; there is no CPU form of this call "
+                            f"(NetworkStatus.to_device)")
+    return _LpStatus(feats, S, P, L, Q, fi["conn_id"], fi["osnr"], fi["snr"], fi["ber"], float(thr))
+
+
 # what LightpathPredictor._prepare hands to _launch: the model's shape, the batch on dev, which rows (rows mode: batch,
 # idx; graphs mode: a fresh count) and how many
 _LpPrepared = namedtuple("_LpPrepared", "F C O dev x ei batch ptr eptr idx B rows count")
@@ -863,6 +909,8 @@ class LightpathPredictor(_DeviceState):
     in-neighbourhood, in one launch (see there).
     ``predict.what_if(data, ...)``: K candidate lightpaths -- another feature row for a LUT node, interferers removed and
     added -- scored in one launch (see there).
+    ``predict.from_status(status)``: ``per_graph``'s rows straight from network-status samples, no graph in between, one
+    launch and no host read (see there).
 
     Envelope -- ``EnvelopeError`` naming the condition otherwise: a model on the GPU with ``num_layers == 1``, 1 ... 16 input
     features, hidden width 1 ... 256, 1 ... 8 outputs; ``data.x`` of shape ``[N, F]``.  No cap on in-degree, graph size or
@@ -873,7 +921,12 @@ class LightpathPredictor(_DeviceState):
     _FLAGS = ("qot_lightpath_infer", "bit 0 an edge leaves its graph's node range, bit 1 a LUT index, graph number or slice "
                                      "outside the arrays (what_if: bit 0 also an added source, bit 1 also a candidate's "
                                      "node or a drop position out of range, bit 2 a candidate's feature row without 1.0 "
-                                     "in the LUT column)")
+                                     "in the LUT column; from_status: bit 3 a bad conn_id, bit 4 too many lightpaths, bit 5 "
+                                     "a sample number out of range)")
+    # the bits of qot_lightpath_infer_status, named when check_status() finds them: the device builder's own words
+    _CAUSES = tuple((bit, next(t for b, t in to_graph._SG_CAUSES if b == sg)) for bit, sg in (
+        (LP_STATUS_BAD_CONN, to_graph.SG_BAD_CONN), (LP_STATUS_TOO_MANY, to_graph.SG_TOO_MANY),
+        (LP_STATUS_BAD_SAMPLE, to_graph.SG_BAD_SAMPLE)))
 
     def __init__(self, model):
         super().__init__()
@@ -925,12 +978,19 @@ class LightpathPredictor(_DeviceState):
             c["infer_lp"] = (tag, res)
         return (x,) + res
 
-    def _prepare(self, data, per_graph, shape=None, nodes=None):
+    def _prepare(self, data, per_graph, shape=None, nodes=None, samples=None):
         """Everything a launch needs, checked, as an ``_LpPrepared``.  ``per_graph``: one row per graph, found on the device,
         instead of the model's LUT rows.  ``shape``: ``_check_model()``'s answer, when the caller has asked already.
-        ``nodes``: the nodes whose rows are computed, in the place of the model's LUT rows (``what_if``)."""
+        ``nodes``: the nodes whose rows are computed, in the place of the model's LUT rows (``what_if``).  ``data=None``
+        (``from_status``): there is no batch, one row for each of ``samples`` status samples and an int64 ``count``."""
         F, C, O = shape or self._check_model()
         dev = self._device()
+        if data is None:
+            x = ei = ptr = eptr = idx = batch = None
+            B = rows = samples
+            count = torch.empty(B, dtype=torch.int64, device=dev)
+            self._status_on(dev)
+            return _LpPrepared(F, C, O, dev, x, ei, batch, ptr, eptr, idx, B, rows, count)
         x, ei, ptr, eptr, B = self._batch(data, F, dev)
         if per_graph:
             idx = batch = None
@@ -954,7 +1014,8 @@ class LightpathPredictor(_DeviceState):
             conv, bn, l0, l3 = m.conv1, m.norm1.module, m.mlp[0], m.mlp[3]
             w = [_f32c(t.detach()) for t in (conv.lin.weight, conv.att_src, conv.att_dst, conv.bias, bn.weight, bn.bias,
                                              bn.running_mean, bn.running_var, l0.weight, l0.bias, l3.weight, l3.bias)]
-            _lib.call(name, x, ei, batch, ptr, eptr, idx, 0 if idx is None else rows, x.shape[0], ei.shape[1], B, *w[:4],
+            N, E = (0, 0) if x is None else (x.shape[0], ei.shape[1])       # (no batch: from_status)
+            _lib.call(name, x, ei, batch, ptr, eptr, idx, 0 if idx is None else rows, N, E, B, *w[:4],
                       float(conv.negative_slope), *w[4:8], float(bn.eps), *w[8:], float(m.mlp[1].negative_slope), out, count,
                       F, C, O, int(conv.heads), int(m.is_lut_index), self._status, *extra)
         if idx is None:
@@ -980,6 +1041,59 @@ class LightpathPredictor(_DeviceState):
         p = self._prepare(data, True)
         out = torch.empty(p.rows, p.O, dtype=torch.float32, device=p.dev)
         return out, self._launch("qot_lightpath_infer", p, out)
+
+    @torch.no_grad()
+    def from_status(self, status, samples=None, features_to_consider=to_graph.DEFAULT_FEATURES, freq_threshold=0.05):
+        """The QoT of the lightpath under test of network-status samples, straight from the samples: ``(out [G, O] float32,
+        count [G] int64)`` in ONE kernel launch (``csrc/infer_lightpath_status.hip``), without the graphs in between, with
+        nothing read back, legal inside ``torch.cuda.graph`` capture.
+
+        ``status``: a ``to_graph.DeviceStatus`` on the model's device.  ``samples``: ``None`` (all, in order), a sequence
+        of sample numbers (uploaded) or an int64 device tensor (used in place: the form to capture); a repeated number is
+        allowed and gives equal rows.  ``features_to_consider`` and
+        ``freq_threshold`` as ``to_graph.device_batch``.
+
+        The definition is what the tree computes already: with ``batch = to_graph.device_batch(status, "lightpath",
+        features_to_consider, samples, freq_threshold)``, ``out`` is ``self.per_graph(batch)[0]`` bit for bit (NaN rows as
+        NaN) and ``count`` its count as int64: ``count[g]`` lightpaths of sample ``g`` carry ``osnr == snr == ber == -1``
+        on their first channel, ``out[g]`` is the row of the first-seen one, NaN when there is none.
+        ``to_graph.lut_neighbourhood`` states on the host which lightpaths send a message into that row.  A sample's row
+        depends on that sample alone; parameters and running statistics are read at call time.
+
+        Refusals before any launch: ``TypeError`` for a ``status`` that is no ``DeviceStatus``; ``ValueError`` for a
+        ``freq_threshold`` that is no finite positive number or a ``samples`` tensor that is not 1-d int64;
+        ``EnvelopeError`` for everything ``__call__`` refuses, a chunk on the CPU or on another device than the model, more
+        than 1024 frequency slots, ``len(features_to_consider) + 1 != in_channels``, ``is_lut`` sorting to another column
+        than ``model.is_lut_index``, a feature or ``conn_id`` / ``osnr`` / ``snr`` / ``ber`` missing from ``lp_feat``.
+        ``G == 0`` gives empty tensors without a launch.  On the device, since nothing is read back: a ``conn_id`` that is
+        not finite or beyond +-2^53, more than 256 lightpaths in a sample, a sample number outside the chunk -- that
+        sample's row is NaN and its count 0, the other rows are untouched, and ``check_status()`` raises naming the cause.
+        (The column table of a feature list is uploaded on its first call with a chunk: make that call before capturing.)"""
+        who = "LightpathPredictor.from_status"
+        shape = self._check_model()
+        sa = lightpath_status_args(status, shape[0], self.model.is_lut_index, features_to_consider, freq_threshold, who)
+        dev = self._device()
+        if status.device != dev:
+            raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
+        if samples is None:
+            picks, G = None, sa.S
+        elif isinstance(samples, torch.Tensor):
+            if samples.dim() != 1 or samples.dtype != torch.int64:
+                raise ValueError(f"{who}: samples must be a sequence or a 1-d int64 tensor, got {samples.dtype} "
+                                 f"{tuple(samples.shape)}")
+            picks = _i64(samples, dev)
+            G = int(picks.shape[0])
+        else:
+            picks = torch.tensor([int(v) for v in samples], dtype=torch.int64).to(dev)
+            G = int(picks.shape[0])
+        p = self._prepare(None, True, shape, samples=G)
+        out = torch.empty(G, p.O, dtype=torch.float32, device=dev)
+        if G == 0:
+            return out, p.count
+        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
+        count = self._launch("qot_lightpath_infer_status", p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L, sa.Q,
+                             sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold)
+        return out, count
 
     @torch.no_grad()
     def sensitivity(self, data, outputs=None, *, per_graph=False, return_attention_weights=False):

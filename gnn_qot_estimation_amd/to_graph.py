@@ -30,6 +30,8 @@ Device form: ``NetworkStatus.to_device`` keeps a chunk 
 ``build_shard(..., device=...)`` / ``device_batch`` run ``csrc/status_graph.hip`` over it -- one workgroup per sample, no
 ``networkx`` -- and return a resident ``PackedGraphs`` / ``Batch``.  Its directed links are in the canonical order
 (source, target) inside each graph; ``canonical_link_order`` brings a host-built shard into the same order.
+``infer.LightpathPredictor.from_status`` predicts from a ``DeviceStatus`` without building the
+graphs; ``lut_neighbourhood`` states on the host which lightpaths of a sample its row takes.
 """
 from __future__ import annotations
 
@@ -223,6 +225,33 @@ def create_lightpath_graph(sample_index: int, features_to_consider: Sequence[str
     for a, b in lightpath_pairs(link_idx, freq_val, conn, freq_threshold):
         G.add_edge(f"lightpath_{a}", f"lightpath_{b}")
     return G
+
+
+def lut_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], freq_threshold: float = 0.05):
+    """What ``LightpathPredictor.from_status`` takes of one sample ``[lp_feat, link, freq]``, stated on the host:
+    ``(count, conn, interferers)``.  ``count``: the lightpaths whose first-seen channel carries ``osnr == snr == ber ==
+    -1``; ``conn``: the ``conn_id`` of the first-seen one of them, ``None`` when there is none; ``interferers``: the
+    ``conn_id`` values, in first-seen order, of the OTHER lightpaths that occupy, on some link the lightpath is routed
+    over, a slot with ``0 < |f1 - f2| < freq_threshold`` to one of its own (fp64) -- each once, however many links and
+    slots the pair shares; a pair of the lightpath's own slots names nobody.  These are the neighbours of the LUT node in
+    ``create_lightpath_graph``'s graph without the node itself, and the messages of its row in their order."""
+    fi = feature_indexes
+    sample, freq = np.asarray(sample, dtype=np.float64), np.asarray(freq, dtype=np.float64)
+    link_idx, freq_idx, vec = _occupied(sample)
+    conn = vec[fi["conn_id"], :].astype(np.int64)
+    _, first = np.unique(conn, return_index=True)
+    seen_order = np.sort(first)
+    flagged = [int(i) for i in seen_order
+               if vec[fi["osnr"], i] == -1 and vec[fi["snr"], i] == -1 and vec[fi["ber"], i] == -1]
+    if not flagged:
+        return 0, None, []
+    a = int(conn[flagged[0]])
+    hit = set()
+    for t in np.flatnonzero(conn == a):                       # every channel of the lightpath
+        on_link = np.flatnonzero((link_idx == link_idx[t]) & (conn != a))
+        diff = np.abs(freq[freq_idx[t]] - freq[freq_idx[on_link]])
+        hit.update(conn[on_link[(diff > 0) & (diff < freq_threshold)]].tolist())
+    return len(flagged), a, [int(conn[i]) for i in seen_order if int(conn[i]) in hit]
 
 
 # ------------------------------------------------------------------------------------------ store_graphs.py counterpart

@@ -1070,6 +1070,39 @@ int qot_status_graph_fill(const double* data, const double* target, const int64_
                           const int64_t* node_ptr, const int64_t* edge_ptr, int64_t n_total, int64_t e_total,
                           int64_t* edge_index, float* feat, int64_t* node_ids, float* y, qot_stream_t stream);
 
+/* ---- the LUT row of every network-status sample in one launch (LightpathPredictor.from_status) -------
+ * From data [S, P, L, Q] fp64 to out [G, O] fp32 and count [G] int64 without a graph in between: for sample samples[g]
+ * (NULL: sample g), count[g] is the number of lightpaths with osnr == snr == ber == -1 on their first channel and out[g]
+ * the row of the first-seen one (NaN when there is none).  Both are, bit for bit, what qot_lightpath_infer's graphs mode
+ * gives for the QOT_SG_LIGHTPATH graph that qot_status_graph_count / _fill build of that sample with the same cols and
+ * freq_threshold: the lightpaths are the same first-seen table, the feature rows the same fp64 scaling rounded once, the
+ * interferers of the row's lightpath a -- every b != a that shares a link with a on slots with 0 < |freq[q1] - freq[q2]|
+ * < freq_threshold (fp64), once however many links and slots the pair shares -- are summed one after the other by rising
+ * lightpath number, the self loop last, by the same row routine.  One 256-thread workgroup per sample; no workspace.
+ *
+ * The argument list is qot_lightpath_infer's up to `status`, then the sample's.  There is no batch: x, edge_index, batch,
+ * node_ptr, edge_ptr and lut_idx must be NULL and n_lut, N, E 0 (QOT_ERR_BADARG otherwise); G takes B's place; count is
+ * int64 here.  cols [ncol, 4] fp64 as qot_status_graph_fill's, ncol == F, and the is_lut column (row -1) at lut_col.
+ * Return codes before any launch: QOT_ERR_BADARG for a negative size, P, L or Q < 1; the envelope of qot_lightpath_infer
+ * and Q <= QOT_SG_MAX_FREQS, L * Q < 2^31, G < 2^31 (QOT_ERR_UNSUPPORTED); QOT_ERR_BADARG for ncol != F, a row outside
+ * 0 .. P-1, a freq_threshold that is not a finite positive number and -- when G > 0 -- a NULL required pointer or S == 0.
+ * G == 0: QOT_OK, no launch.
+ * status (optional, device int32, caller-zeroed), on the device since nothing is read back; the bits lie above
+ * qot_lightpath_infer's and _whatif's (1, 2, 4).  The flagged sample's row is NaN and its count 0, the other rows are
+ * untouched; no index is formed from an offending value. */
+#define QOT_LP_STATUS_BAD_CONN 8     /* a conn_id not finite or beyond +-2^53 */
+#define QOT_LP_STATUS_TOO_MANY 16    /* more than QOT_SG_MAX_LIGHTPATHS lightpaths in a sample */
+#define QOT_LP_STATUS_BAD_SAMPLE 32  /* a sample number outside [0, S) */
+int qot_lightpath_infer_status(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                               const int64_t* edge_ptr, const int64_t* lut_idx, int64_t n_lut, int64_t N, int64_t E, int64_t G,
+                               const float* w, const float* att_src, const float* att_dst, const float* conv_bias,
+                               float slope_att, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                               const float* bn_var, float bn_eps, const float* w0, const float* b0, const float* w3,
+                               const float* b3, float slope_head, float* out, int64_t* count, int F, int C, int O, int heads,
+                               int lut_col, int32_t* status, const double* data, const double* freq, const int64_t* samples,
+                               int64_t S, int P, int64_t L, int64_t Q, int conn_row, int osnr_row, int snr_row, int ber_row,
+                               const double* cols, int ncol, double freq_threshold, qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

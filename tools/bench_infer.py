@@ -72,6 +72,16 @@ graph has one LUT node, so the LUT rows of the materialised batch are the candid
 nothing); output and the interquartile rule as for the topological table.
 
     python tools/bench_infer.py --kind lightpath --what-if 1 8 64 1024 [--out profiles/bench_infer_lightpath_whatif.jsonl]
+
+``--kind lightpath --from-status``: the LUT rows straight from network-status samples (csrc/infer_lightpath_status.hip,
+DESIGN.md 4.20) -- milliseconds per call of ``predict.from_status(status)`` against
+``predict.per_graph(to_graph.device_batch(status, "lightpath"))`` (two builder launches, one host read, the row kernel;
+that path is what it was before ``from_status`` existed).  ``synthetic_network_status`` samples on the 60 x 72 grid (64
+distinct ones, tiled) at S = 1, 8, 512, C = 32, F = 5, threshold 0.05.  The rows of the two ways are compared first (equal
+bits); then they alternate in one process, each call between two ``torch.cuda.Event``s, median and interquartile range and
+the "no difference" rule as above.
+
+    python tools/bench_infer.py --kind lightpath --from-status [--out profiles/bench_infer_lightpath_status.jsonl]
 """
 import argparse
 import json
@@ -439,6 +449,61 @@ def main_lightpath_what_if(args, device, commit):
               f"{cell('materialise')} | {cell('prebuilt')} | {versus(r, 'materialise')} | {versus(r, 'prebuilt')} |")
 
 
+STATUS_SIZES = (1, 8, 512)
+
+
+def measure_from_status(Sn, device, rounds, warmup):
+    from gnn_qot_estimation_amd import to_graph as TG
+    torch.manual_seed(0)
+    model = q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval()
+    predict = q.LightpathPredictor(model)
+    distinct = min(Sn, 64)                                  # distinct samples are generated once, then tiled
+    ns = TG.synthetic_network_status(distinct, seed=0)      # the 60 x 72 grid
+    st = ns.to_device(device, [g % distinct for g in range(Sn)])
+    ways = {"from_status": lambda: predict.from_status(st)[0],
+            "graphs": lambda: predict.per_graph(TG.device_batch(st, "lightpath"))[0]}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    assert torch.equal(got["from_status"], got["graphs"]) and bool(torch.isfinite(got["graphs"]).all()), Sn
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed_event(fn))
+    res = dict(shape="status 60 x 72", kind="lightpath_from_status", S=Sn, P=int(st.data.shape[1]), L=60, Q=72, C=32, F=5,
+               rounds=rounds, equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_from_status(args, device, commit):
+    rows = []
+    for Sn in STATUS_SIZES:
+        res = measure_from_status(Sn, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| S | from_status ms (IQR) | device_batch + per_graph ms (IQR) | graphs / from_status |")
+    print("|---|---|---|---|")
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        a, b = r["from_status_ms"], r["graphs_ms"]
+        same = abs(a - b) <= max(r["from_status_iqr_ms"], r["graphs_iqr_ms"])
+        print(f"| {r['S']} | {cell('from_status')} | {cell('graphs')} | {'no difference' if same else f'{b / a:.2f}x'} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -601,7 +666,11 @@ def main():
                     help="what-if: predict.what_if on K one-lightpath candidates against materialise_what_if + predict and "
                          "predict on a prebuilt batch (with --kind lightpath: LightpathPredictor's, K candidates of the "
                          "LUT node)")
+    ap.add_argument("--from-status", action="store_true", dest="from_status",
+                    help="with --kind lightpath: predict.from_status(status) against device_batch + per_graph")
     args = ap.parse_args()
+    if args.from_status and (args.kind != "lightpath" or args.mc is not None or args.grad or args.what_if is not None):
+        raise SystemExit("--from-status goes with --kind lightpath and is a run of its own")
     if args.what_if is not None and (args.mc is not None or args.grad or any(k < 1 for k in args.what_if)):
         raise SystemExit("--what-if K [K ...] (K >= 1) is a run of its own")
     if args.mc is not None and args.kind != "topological":
@@ -614,6 +683,8 @@ def main():
         raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    if args.from_status:
+        return main_from_status(args, device, commit)
     if args.kind == "lightpath" and args.what_if is not None:
         return main_lightpath_what_if(args, device, commit)
     if args.kind == "lightpath":
