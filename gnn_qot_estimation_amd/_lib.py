@@ -180,6 +180,8 @@ SIGNATURES = {
     "qot_topological_infer_mc": (_int, _INFER_COMMON + [_int, _i64, _u64, _f, _f, _int, _p]),
     "qot_topological_infer_grad": (_int, _INFER_COMMON + [_p, _int, _p, _p, _p]),
     "qot_topological_infer_whatif": (_int, _INFER_COMMON + [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _int, _p]),
+    "qot_topological_infer_status": (_int, _INFER_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _p, _int,
+                                                            _p]),
     "qot_lightpath_infer": (_int, _LP_COMMON + [_p]),
     "qot_lightpath_infer_grad": (_int, _LP_COMMON + [_p, _int, _p, _p, _p, _p, _p]),
     "qot_lightpath_infer_whatif": (_int, _LP_COMMON + [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p]),

@@ -17,44 +17,20 @@
 // Everything a sample produces depends on that sample alone, so a graph is bit-identical in any chunk.
 //
 // Scaling is (v - min) / (max - min) in fp64 (IEEE division), one rounding to fp32; the file is compiled with
-// -ffp-contract=off.  The scan, the table and the scaling are status_scan_dev.hpp's, shared with
-// infer_lightpath_status.hip.
+// -ffp-contract=off.  The scan, the table, the scaling, the topological pair contest and the walk's runs are
+// status_scan_dev.hpp's, shared with infer_lightpath_status.hip and infer_topological_status.hip (4.21).
 #include "status_scan_dev.hpp"
 
 namespace qot {
 namespace sg {
 
-// (the workgroup's geometry, kCap / kQCap, the first-seen table, discover(), sample_of() and scaled(): status_scan_dev.hpp)
-constexpr int kTopo = QOT_SG_NODES;              // 75
-constexpr int kCells = kTopo * kTopo;            // 5625
+// (the workgroup's geometry, kCap / kQCap, kTopo / kCells, the first-seen table, discover(), sample_of(), scaled(), the block
+// scan, the pair contest topo_winners() and the walk's run topo_run(): status_scan_dev.hpp)
 constexpr int kAdjWords = kCap * kCap / 32;      // 2048
 
 // scratch slot of one sample: first[kCap] int32, then the matrix (adjacency bits or int16 winners)
 constexpr size_t kMatBytes = kCells * 2 > kAdjWords * 4 ? (size_t)((kCells * 2 + 15) / 16 * 16) : (size_t)kAdjWords * 4;
 constexpr size_t kSlotBytes = (size_t)kCap * 4 + kMatBytes;
-
-// exclusive prefix of v over the block's threads (thread order) and the block total; `part` holds kWaves + 1 ints
-__device__ __forceinline__ int block_exscan(int v, int* part, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();                                  // part may still be read from an earlier call
-    if (lane == 63) part[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) {
-        const int p = part[k];
-        if (k < w) base += p;
-        tot += p;
-    }
-    total = tot;
-    return base + inc - v;
-}
 
 struct CountArgs {
     const double* data;
@@ -178,35 +154,7 @@ __global__ __launch_bounds__(kThreads) void count_topological(CountArgs a) {
     for (int k = tid; k < kCells; k += kThreads) mat[k] = -1;
     int bad = discover(d, a.P, LQ, a.conn_row, T, nullptr);
     const int n = T.n;
-    // end nodes of lightpath tid (255 = not usable)
-    int u = 255, v = 255;
-    if (tid < n) {
-        const int c = T.first[tid];
-        const double sv = d[(int64_t)a.src_row * LQ + c], dv = d[(int64_t)a.dst_row * LQ + c];
-        // written so that a NaN fails the test
-        const bool good = sv >= 1.0 && sv <= (double)kTopo && dv >= 1.0 && dv <= (double)kTopo && sv == trunc(sv) && dv == trunc(dv);
-        if (good) {
-            const int su = (int)sv - 1, dvv = (int)dv - 1;
-            u = su < dvv ? su : dvv;
-            v = su < dvv ? dvv : su;
-        } else {
-            bad |= QOT_SG_BAD_ENDPOINT;
-        }
-    }
-    eu[tid] = (uint8_t)u;
-    ev[tid] = (uint8_t)v;
-    __syncthreads();
-    if (u != 255) {
-        const int64_t mine = T.conn[tid];
-        bool win = true;
-        for (int j = 0; j < n; ++j)
-            if (eu[j] == u && ev[j] == v && T.conn[j] > mine) { win = false; break; }
-        if (win) {                                                  // conn values are distinct: one winner per pair
-            mat[u * kTopo + v] = (int16_t)tid;
-            mat[v * kTopo + u] = (int16_t)tid;
-        }
-    }
-    __syncthreads();
+    bad |= topo_winners(d, LQ, a.src_row, a.dst_row, T, n, mat, eu, ev);
     int cnt = 0, self = 0;
     for (int k = tid; k < kCells; k += kThreads)
         if (mat[k] >= 0) {
@@ -323,10 +271,8 @@ __global__ __launch_bounds__(kThreads) void fill_topological(FillArgs a) {
     if (tid < kTopo) a.node_ids[nb + tid] = tid;
     __syncthreads();
     // thread t owns a contiguous run of cells: row-major order is (source, target) order
-    constexpr int kPer = (kCells + kThreads - 1) / kThreads;
-    const int k0 = tid * kPer, k1 = k0 + kPer < kCells ? k0 + kPer : kCells;
-    int cnt = 0;
-    for (int k = k0; k < k1; ++k) cnt += mat[k] >= 0;
+    int k0, k1;
+    const int cnt = topo_run(mat, k0, k1);
     int total;
     int e = block_exscan(cnt, part, total);
     if (total != m) return;

@@ -1,8 +1,10 @@
 // The scan of one network-status sample data[P, L, Q] (fp64) by one 256-thread workgroup, shared by the graph builder
-// (status_graph.hip) and the status-to-row kernel (infer_lightpath_status.hip): both run
-// discover(), so the lightpaths of a sample, their numbering and their first channels are the same table in both.  Stated
-// once here for both: the workgroup's geometry and caps, the first-seen table and its insert, the sample pick, the
-// occupancy / conn rule of one channel (sg_conn) and the fp64 column scaling (scaled).
+// (status_graph.hip) and the status-to-row kernels (infer_lightpath_status.hip, DESIGN.md 4.20;
+// infer_topological_status.hip): all run discover(), so the lightpaths of a sample, their numbering and
+// their first channels are the same table in all.  Stated once here: the workgroup's geometry and caps, the first-seen
+// table and its insert, the sample pick, the occupancy / conn rule of one channel (sg_conn), the fp64 column scaling
+// (scaled) and, for the topological representation, the block scan, the pair contest that fills the 75 x 75 winner
+// matrix (topo_winners) and the row-major run of cells a thread walks (topo_run).
 //
 // Channels are scanned in the order c = l * Q + q, 256 at a time: occupied = any of the P values != 0; the distinct
 // trunc(conn_id) values are appended, in first-seen order, to an LDS table (conn, first channel).
@@ -20,6 +22,8 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kCap = QOT_SG_MAX_LIGHTPATHS;      // 256
 constexpr int kQCap = QOT_SG_MAX_FREQS;          // 1024
+constexpr int kTopo = QOT_SG_NODES;              // 75
+constexpr int kCells = kTopo * kTopo;            // 5625
 static_assert(kCap == kThreads, "one thread per lightpath / adjacency row");
 
 __device__ __forceinline__ int wave_prefix(uint64_t mask) {      // set bits of mask below this lane
@@ -145,6 +149,81 @@ __device__ __forceinline__ float sg_feature(const double* __restrict__ d, int P,
     const int r = (int)col[0];
     if (r < 0) return sg_is_lut(d, LQ, osnr_row, snr_row, ber_row, c) ? 1.0f : 0.0f;
     return r < P ? scaled(d[(int64_t)r * LQ + c], col) : 0.0f;
+}
+
+// exclusive prefix of v over the block's threads (thread order) and the block total; `part` holds kWaves + 1 ints
+__device__ __forceinline__ int block_exscan(int v, int* part, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();                                  // part may still be read from an earlier call
+    if (lane == 63) part[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) {
+        const int p = part[k];
+        if (k < w) base += p;
+        tot += p;
+    }
+    total = tot;
+    return base + inc - v;
+}
+
+// ---- the topological representation: which lightpath gives the link of every node pair.  Thread t reads the end nodes of
+// lightpath t (t < n = T.n) on its first channel; among the lightpaths of one unordered node pair the one with the largest
+// conn wins, and its number goes to mat[u][v] and mat[v][u] (a self loop: the one cell).  mat [kCells] holds -1 everywhere
+// on entry; eu / ev [kCap] are scratch.  Nothing read from data is used as an index before the 1 .. 75 test.  Returns
+// QOT_SG_BAD_ENDPOINT or 0 (per thread); ends with a barrier, behind which mat is complete.
+__device__ __forceinline__ int topo_winners(const double* __restrict__ d, int LQ, int src_row, int dst_row, const Table& T,
+                                            int n, int16_t* mat, uint8_t* eu, uint8_t* ev) {
+    const int tid = threadIdx.x;
+    int bad = 0;
+    // end nodes of lightpath tid (255 = not usable)
+    int u = 255, v = 255;
+    if (tid < n) {
+        const int c = T.first[tid];
+        const double sv = d[(int64_t)src_row * LQ + c], dv = d[(int64_t)dst_row * LQ + c];
+        // written so that a NaN fails the test
+        const bool good = sv >= 1.0 && sv <= (double)kTopo && dv >= 1.0 && dv <= (double)kTopo && sv == trunc(sv) && dv == trunc(dv);
+        if (good) {
+            const int su = (int)sv - 1, dvv = (int)dv - 1;
+            u = su < dvv ? su : dvv;
+            v = su < dvv ? dvv : su;
+        } else {
+            bad |= QOT_SG_BAD_ENDPOINT;
+        }
+    }
+    eu[tid] = (uint8_t)u;
+    ev[tid] = (uint8_t)v;
+    __syncthreads();
+    if (u != 255) {
+        const int64_t mine = T.conn[tid];
+        bool win = true;
+        for (int j = 0; j < n; ++j)
+            if (eu[j] == u && ev[j] == v && T.conn[j] > mine) { win = false; break; }
+        if (win) {                                                  // conn values are distinct: one winner per pair
+            mat[u * kTopo + v] = (int16_t)tid;
+            mat[v * kTopo + u] = (int16_t)tid;
+        }
+    }
+    __syncthreads();
+    return bad;
+}
+
+// Thread t's contiguous run [k0, k1) of the matrix's cells: row-major order is (source, target) order, so the exclusive
+// scan of the runs' link counts numbers the directed links canonically.  Returns the links in the run.
+constexpr int kTopoPer = (kCells + kThreads - 1) / kThreads;
+__device__ __forceinline__ int topo_run(const int16_t* mat, int& k0, int& k1) {
+    k0 = threadIdx.x * kTopoPer;
+    k1 = k0 + kTopoPer < kCells ? k0 + kTopoPer : kCells;
+    int cnt = 0;
+    for (int k = k0; k < k1; ++k) cnt += mat[k] >= 0;
+    return cnt;
 }
 
 }  // namespace sg

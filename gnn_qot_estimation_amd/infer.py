@@ -1,6 +1,7 @@
 """Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``; its Monte-Carlo dropout
 ``sample``: ``csrc/infer_mc.hip``; its per-link ``sensitivity``: ``csrc/infer_grad.hip``, DESIGN.md
-4.16; its ``what_if`` over edited graphs: ``csrc/infer_whatif.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
+4.16; its ``what_if`` over edited graphs: ``csrc/infer_whatif.hip``; its ``from_status`` over network-status
+samples: ``csrc/infer_topological_status.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
 ``csrc/infer_lightpath_grad.hip``; its ``what_if`` over candidate lightpaths:
 ``csrc/infer_lightpath_whatif.hip``; its ``from_status`` over network-status samples:
 ``csrc/infer_lightpath_status.hip``).
@@ -331,6 +332,48 @@ def materialise_what_if(data, add_edge_index, add_edge_attr, add_ptr, drop=None,
     return out
 
 
+# include/qot_gnn.h: QOT_TOPO_STATUS_*, the status bits of qot_topological_infer_status (above the other kernels' 1, 2, 4)
+TOPO_STATUS_BAD_CONN, TOPO_STATUS_TOO_MANY, TOPO_STATUS_BAD_SAMPLE, TOPO_STATUS_BAD_ENDPOINT = 8, 16, 32, 64
+TOPO_STATUS_MAX_FREQS = 1024    # include/qot_gnn.h: QOT_SG_MAX_FREQS
+TOPO_STATUS_MAX_LINKS = 512     # csrc/infer_topological_status.hip: kTopoStatusLinks, two directed links per lightpath
+
+_TopoStatus = namedtuple("_TopoStatus", "features S P L Q conn_row src_row dst_row")
+
+
+def topological_status_args(status, edge_dim, features_to_consider=to_graph.DEFAULT_FEATURES, samples=None,
+                            num_embeddings=None, model_device=None, who="TopologicalPredictor.from_status"):
+    """The argument checks of ``TopologicalPredictor.from_status`` that need no device: returns a ``_TopoStatus`` (the
+    feature list, the chunk's sizes, the ``lp_feat`` rows the kernel reads) or raises -- ``TypeError`` for a ``status`` that
+    is no ``DeviceStatus``, ``IndexError`` for an embedding table (``num_embeddings`` rows) that does not hold the 75 nodes
+    of the topology, ``ValueError`` naming the condition for everything else; a chunk on the CPU, then one on another
+    device than ``model_device``, are named last."""
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    feats = list(features_to_consider)
+    S, P, L, Q = (int(v) for v in status.data.shape)
+    if Q > TOPO_STATUS_MAX_FREQS:
+        raise ValueError(f"{who}: at most {TOPO_STATUS_MAX_FREQS} frequency slots per link, got {Q}")
+    if L * Q >= 1 << 31:
+        raise ValueError(f"{who}: links x frequency slots must stay below 2^31, got {L} x {Q}")
+    if len(feats) != int(edge_dim):
+        raise ValueError(f"{who}: {len(feats)} features, the model takes edge_dim = {edge_dim}")
+    fi = status.feature_indexes
+    missing = [n for n in feats + ["conn_id", "src_id", "dst_id"] if n not in fi]
+    if missing:
+        raise ValueError(f"{who}: the status has no lp_feat row named {', '.join(repr(n) for n in missing)}")
+    if isinstance(samples, torch.Tensor) and (samples.dim() != 1 or samples.dtype != torch.int64):
+        raise ValueError(f"{who}: samples must be a sequence or a 1-d int64 tensor, got {samples.dtype} "
+                         f"{tuple(samples.shape)}")
+    if num_embeddings is not None and int(num_embeddings) < to_graph.NUM_TOPOLOGY_NODES:
+        raise IndexError("index out of range in self")
+    if not status.data.is_cuda:
+        raise ValueError(f"{who}: the status chunk is on the CPU; there is no CPU form of this call "
+                         f"(NetworkStatus.to_device)")
+    if model_device is not None and status.device != model_device:
+        raise ValueError(f"{who}: the status chunk is on {status.device}, the model on {model_device}")
+    return _TopoStatus(feats, S, P, L, Q, fi["conn_id"], fi["src_id"], fi["dst_id"])
+
+
 class _DeviceState:
     """What both predictors keep on the device beside the model: the status word their kernels flag a batch in and the
     ``outputs`` selections of ``sensitivity``.  ``_FLAGS`` of a predictor: its kernel's name, the meaning of the status bits."""
@@ -387,17 +430,26 @@ class TopologicalPredictor(_DeviceState):
     ``predictor.sample(data, samples)``: Monte-Carlo dropout, ``samples`` stochastic forwards in one launch (see there).
     ``predictor.sensitivity(data)``: the output together with its Jacobian wrt the edge features, in one launch.
     ``predictor.what_if(data, ...)``: K small edits of the batch's graphs (edges added / removed), scored in one launch.
+    ``predictor.from_status(status)``: ``__call__``'s rows straight from network-status samples, no graph in between, one
+    launch and no host read (see there).
     """
 
     _FLAGS = ("qot_topological_infer", "bit 0 an edge leaves its graph's node range, bit 1 slices outside the arrays, "
                                        "bit 2 a node id outside the table (what_if: bit 0 also an added edge, bit 1 also a "
-                                       "graph number or a drop position out of range)")
+                                       "graph number or a drop position out of range; from_status: bit 3 a bad conn_id, "
+                                       "bit 4 too many lightpaths, bit 5 a sample number out of range, bit 6 a bad "
+                                       "src_id / dst_id)")
+    # the bits of qot_topological_infer_status, named when check_status() finds them: the device builder's own words
+    _CAUSES = tuple((bit, next(t for b, t in to_graph._SG_CAUSES if b == sg)) for bit, sg in (
+        (TOPO_STATUS_BAD_CONN, to_graph.SG_BAD_CONN), (TOPO_STATUS_TOO_MANY, to_graph.SG_TOO_MANY),
+        (TOPO_STATUS_BAD_SAMPLE, to_graph.SG_BAD_SAMPLE), (TOPO_STATUS_BAD_ENDPOINT, to_graph.SG_BAD_ENDPOINT)))
 
     def __init__(self, model):
         super().__init__()
         self.model = model
         self._tables = None
         self._tag = None
+        self._topology = None           # from_status: (device, arange(75), an empty edge_index)
         self._check_model()
 
     # ------------------------------------------------------------------ envelope
@@ -672,6 +724,63 @@ class TopologicalPredictor(_DeviceState):
         self._launch("qot_topological_infer_whatif", p._replace(max_e=max_e), out, aei, aea, add_ptr_d, w.A, dpos, dptr, w.R,
                      g, K, w.max_add)
         return out
+
+    @torch.no_grad()
+    def from_status(self, status, samples=None, features_to_consider=to_graph.DEFAULT_FEATURES):
+        """The QoT of network-status samples, straight from the samples: ``(out [G, O] float32, links [G] int64)`` in ONE
+        kernel launch (``csrc/infer_topological_status.hip``), without the graphs in between, with nothing read back, legal
+        inside ``torch.cuda.graph`` capture.
+
+        ``status``: a ``to_graph.DeviceStatus`` on the model's device.  ``samples``: ``None`` (all, in order), a sequence
+        of sample numbers (uploaded) or a 1-d int64 device tensor (used in place: the form to capture); a repeated number
+        is allowed and gives equal rows.  ``features_to_consider`` as ``to_graph.device_batch``.
+
+        The definition is what the tree computes already: with ``batch = to_graph.device_batch(status, "topological",
+        features_to_consider, samples)``, ``out`` is ``self(batch)`` bit for bit and ``links[g]`` is ``batch.edge_ptr[g + 1] -
+        batch.edge_ptr[g]``, the directed links of sample ``g``'s graph: 75 nodes, one link pair per unordered node pair
+        that some lightpath joins (a lightpath from a node to itself: one self loop), with the features of the pair's
+        lightpath of largest ``conn_id``.  ``to_graph.topological_links`` states the selection on the host.  A sample's row
+        depends on that sample alone; ``model.training`` does not matter; parameter updates are followed as ``__call__``
+        follows them.
+
+        Refusals before any launch: ``TypeError`` for a ``status`` that is no ``DeviceStatus``; ``ValueError`` naming the
+        condition for everything ``_check_model`` refuses, ``len(features_to_consider) != edge_dim``, a feature or
+        ``conn_id`` / ``src_id`` / ``dst_id`` missing from ``lp_feat``, more than 1024 frequency slots, ``L * Q >= 2^31``, a
+        ``samples`` tensor that is not 1-d int64, a chunk on the CPU or on another device than the model; ``IndexError``
+        when the embedding table has fewer than 75 rows, as the model raises.  ``G == 0`` gives empty tensors without a
+        launch.  On the device, since nothing is read back: a ``conn_id`` that is not finite or beyond +-2^53, more than
+        256 lightpaths in a sample, a sample number outside the chunk, a ``src_id`` / ``dst_id`` that is no integer in
+        1 ... 75 -- that sample's row is NaN and its ``links`` 0, the other rows are untouched, and ``check_status()``
+        raises naming the cause.  (The column table of a feature list, ``arange(75)`` and the parameter tables are uploaded
+        by the first call with a chunk: make that call before capturing.)"""
+        who = "TopologicalPredictor.from_status"
+        H, D, O = self._check_model()
+        emb = self.model.node_embeddings.weight
+        dev = emb.device
+        sa = topological_status_args(status, D, features_to_consider, samples, emb.shape[0], dev, who)
+        if samples is None:
+            picks, G = None, sa.S
+        elif isinstance(samples, torch.Tensor):
+            picks = _i64(samples, dev)
+            G = int(picks.shape[0])
+        else:
+            picks = torch.tensor([int(v) for v in samples], dtype=torch.int64).to(dev)
+            G = int(picks.shape[0])
+        out = torch.empty(G, O, dtype=torch.float32, device=dev)
+        links = torch.empty(G, dtype=torch.int64, device=dev)
+        if G == 0:
+            return out, links
+        if self._topology is None or self._topology[0] != dev:
+            self._topology = (dev, torch.arange(to_graph.NUM_TOPOLOGY_NODES, dtype=torch.int64, device=dev),
+                              torch.empty(2, 0, dtype=torch.int64, device=dev))
+        _, ids, no_edges = self._topology
+        t = self._refresh(H, D)
+        self._status_on(dev)
+        cols, _, ncol = to_graph._column_tables(status, "topological", sa.features)
+        p = _Prepared(H, D, O, dev, ids, no_edges, None, None, None, to_graph.NUM_TOPOLOGY_NODES, TOPO_STATUS_MAX_LINKS, G, t)
+        self._launch("qot_topological_infer_status", p, out, links, status.data, picks, sa.S, sa.P, sa.L, sa.Q, sa.conn_row,
+                     sa.src_row, sa.dst_row, cols, ncol)
+        return out, links
 
 
 # ====================================================================== LightpathGNN

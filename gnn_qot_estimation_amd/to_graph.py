@@ -32,6 +32,9 @@ Device form: ``NetworkStatus.to_device`` keeps a chunk 
 (source, target) inside each graph; ``canonical_link_order`` brings a host-built shard into the same order.
 ``infer.LightpathPredictor.from_status`` predicts from a ``DeviceStatus`` without building the
 graphs; ``lut_neighbourhood`` states on the host which lightpaths of a sample its row takes.
+``infer.TopologicalPredictor.from_status`` (DESIGN.md section 4.21) does the same for the topological model;
+``topological_links`` states on the host the directed links of a sample's graph, in canonical order, and the lightpath
+that gives each its features.
 """
 from __future__ import annotations
 
@@ -252,6 +255,29 @@ def lut_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dic
         diff = np.abs(freq[freq_idx[t]] - freq[freq_idx[on_link]])
         hit.update(conn[on_link[(diff > 0) & (diff < freq_threshold)]].tolist())
     return len(flagged), a, [int(conn[i]) for i in seen_order if int(conn[i]) in hit]
+
+
+def topological_links(sample: np.ndarray, feature_indexes: Dict[str, int]):
+    """What ``TopologicalPredictor.from_status`` takes of one sample ``[lp_feat, link, freq]``, stated on the host:
+    ``(edge_index [2, m] int64, conn [m] int64)``.  The lightpaths are the distinct ``trunc(conn_id)`` of the occupied
+    channels, each with the ``src_id`` / ``dst_id`` of its first channel in scan order; among the lightpaths of one
+    unordered node pair the one with the largest ``conn_id`` wins the pair; a winner between ``u != v`` gives the directed
+    links ``(u, v)`` and ``(v, u)``, one with ``u == v`` the single self loop.  Nodes are 0-based (``src_id - 1``), the
+    links ascending by ``(source, target)`` -- the canonical order -- and ``conn[e]`` is the winner whose features link ``e``
+    carries.  These are the links of ``create_topological_graph``'s graph after ``canonical_link_order``."""
+    fi = feature_indexes
+    _, _, vec = _occupied(np.asarray(sample, dtype=np.float64))
+    conn = vec[fi["conn_id"], :].astype(np.int64)
+    uniq, first = np.unique(conn, return_index=True)
+    winner: Dict[tuple, int] = {}
+    for c, i in zip(uniq.tolist(), first.tolist()):           # ascending conn: the last one written is the largest
+        u, v = int(vec[fi["src_id"], i]) - 1, int(vec[fi["dst_id"], i]) - 1
+        winner[(min(u, v), max(u, v))] = c
+    links = sorted({(a, b, c) for (u, v), c in winner.items() for a, b in ((u, v), (v, u))})
+    if not links:
+        return np.zeros((2, 0), dtype=np.int64), np.zeros(0, dtype=np.int64)
+    arr = np.asarray(links, dtype=np.int64)
+    return np.ascontiguousarray(arr[:, :2].T), np.ascontiguousarray(arr[:, 2])
 
 
 # ------------------------------------------------------------------------------------------ store_graphs.py counterpart

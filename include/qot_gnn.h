@@ -1103,6 +1103,40 @@ int qot_lightpath_infer_status(const float* x, const int64_t* edge_index, const 
                                int64_t S, int P, int64_t L, int64_t Q, int conn_row, int osnr_row, int snr_row, int ber_row,
                                const double* cols, int ncol, double freq_threshold, qot_stream_t stream);
 
+/* ---- the TopologicalGNN row of every network-status sample in one launch (TopologicalPredictor.from_status, DESIGN.md
+ * 4.21) -- From data [S, P, L, Q] fp64 to out [G, O] fp32 and links [G] int64 without a graph in between: for sample
+ * samples[g] (NULL: sample g), out[g] is, bit for bit, the row qot_topological_infer writes for the QOT_SG_TOPOLOGICAL
+ * graph that qot_status_graph_count / _fill build of that sample with the same cols, and links[g] that graph's directed
+ * link count.  The lightpaths are the same first-seen table; among the lightpaths of one unordered node pair the largest
+ * conn wins; a winner with u != v gives the links (u, v) and (v, u), one with u == v the self loop; the links are numbered
+ * ascending by (source, target); a link's features are the winner's, the same fp64 scaling rounded once (a row outside
+ * 0 .. P-1 reads 0); the forward is the eval kernel's code behind another edge source.  One 256-thread workgroup per
+ * sample; no workspace.
+ *
+ * The argument list is qot_topological_infer's up to `status`, then the sample's.  There is no batch: node_ids is the
+ * caller's arange(QOT_SG_NODES) with N == n_max == QOT_SG_NODES, max_e must be 512 (2 x QOT_SG_MAX_LIGHTPATHS, the
+ * kernel's own edge cap), edge_index, edge_attr, node_ptr and edge_ptr must be NULL and E 0 (QOT_ERR_BADARG otherwise); G
+ * takes B's place.  cols [ncol, 4] fp64 as qot_status_graph_fill's, ncol == D.
+ * Return codes before any launch: QOT_ERR_BADARG for a negative size, P, L or Q < 1; the envelope of
+ * qot_topological_infer at (75, 512) with this kernel's static LDS added to the image, Q <= QOT_SG_MAX_FREQS, L * Q <
+ * 2^31, G < 2^31 (QOT_ERR_UNSUPPORTED); QOT_ERR_BADARG for ncol != D, a row outside 0 .. P-1 and -- when G > 0 -- a NULL
+ * required pointer, a bad ld4 / ldm or S == 0.  G == 0: QOT_OK, no launch.
+ * status (optional, device int32, caller-zeroed), on the device since nothing is read back; the bits lie above
+ * qot_topological_infer's (1, 2, 4).  The flagged sample's row is NaN and its links 0, the other rows are untouched; no
+ * index is formed from an offending value. */
+#define QOT_TOPO_STATUS_BAD_CONN 8       /* a conn_id not finite or beyond +-2^53 */
+#define QOT_TOPO_STATUS_TOO_MANY 16      /* more than QOT_SG_MAX_LIGHTPATHS lightpaths in a sample */
+#define QOT_TOPO_STATUS_BAD_SAMPLE 32    /* a sample number outside [0, S) */
+#define QOT_TOPO_STATUS_BAD_ENDPOINT 64  /* a src_id / dst_id that is not an integer in 1 .. QOT_SG_NODES */
+int qot_topological_infer_status(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                                 const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t G, int n_max,
+                                 int max_e, const float* t4, int ld4, const float* M, int ldm, const float* P, int V,
+                                 const float* w_edge, const float* w1, const float* b1, const float* wcat, const float* bias2,
+                                 const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
+                                 float slope_head, float* out, int H, int D, int O, int32_t* status, int64_t* links,
+                                 const double* data, const int64_t* samples, int64_t S, int rows, int64_t L, int64_t Q,
+                                 int conn_row, int src_row, int dst_row, const double* cols, int ncol, qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

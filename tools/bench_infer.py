@@ -82,6 +82,12 @@ bits); then they alternate in one process, each call between two ``torch.cuda.Ev
 the "no difference" rule as above.
 
     python tools/bench_infer.py --kind lightpath --from-status [--out profiles/bench_infer_lightpath_status.jsonl]
+
+``--kind topological --from-status``: the same for ``TopologicalPredictor`` (csrc/infer_topological_status.hip, DESIGN.md
+4.21) -- ``predict.from_status(status)`` against ``predict(to_graph.device_batch(status, "topological"))``, at S = 1, 8, 512
+and hidden widths 64 and 16 (V = 75, edge_dim 4, 3 outputs); same samples, same protocol.
+
+    python tools/bench_infer.py --kind topological --from-status [--out profiles/bench_infer_topological_status.jsonl]
 """
 import argparse
 import json
@@ -452,16 +458,28 @@ def main_lightpath_what_if(args, device, commit):
 STATUS_SIZES = (1, 8, 512)
 
 
-def measure_from_status(Sn, device, rounds, warmup):
+STATUS_WIDTHS = (64, 16)                                    # --kind topological: the headline's width, the reference's
+
+
+def measure_from_status(Sn, device, rounds, warmup, H=None):
+    """``H``: ``None`` measures ``LightpathPredictor``, a hidden width ``TopologicalPredictor`` at that width."""
     from gnn_qot_estimation_amd import to_graph as TG
     torch.manual_seed(0)
-    model = q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval()
-    predict = q.LightpathPredictor(model)
     distinct = min(Sn, 64)                                  # distinct samples are generated once, then tiled
     ns = TG.synthetic_network_status(distinct, seed=0)      # the 60 x 72 grid
     st = ns.to_device(device, [g % distinct for g in range(Sn)])
-    ways = {"from_status": lambda: predict.from_status(st)[0],
-            "graphs": lambda: predict.per_graph(TG.device_batch(st, "lightpath"))[0]}
+    if H is None:
+        model = q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval()
+        predict = q.LightpathPredictor(model)
+        ways = {"from_status": lambda: predict.from_status(st)[0],
+                "graphs": lambda: predict.per_graph(TG.device_batch(st, "lightpath"))[0]}
+        what = dict(kind="lightpath_from_status", C=32, F=5)
+    else:
+        model = q.TopologicalGNN(75, H, 3, 4, dropout_p=0.0).to(device).eval()
+        predict = q.TopologicalPredictor(model)
+        ways = {"from_status": lambda: predict.from_status(st)[0],
+                "graphs": lambda: predict(TG.device_batch(st, "topological"))}
+        what = dict(kind="topological_from_status", H=H, D=4, V=75)
     got = {k: fn() for k, fn in ways.items()}
     torch.cuda.synchronize()
     predict.check_status()
@@ -473,8 +491,7 @@ def measure_from_status(Sn, device, rounds, warmup):
     for _ in range(rounds):
         for k, fn in ways.items():
             times[k].append(timed_event(fn))
-    res = dict(shape="status 60 x 72", kind="lightpath_from_status", S=Sn, P=int(st.data.shape[1]), L=60, Q=72, C=32, F=5,
-               rounds=rounds, equal_bits=True)
+    res = dict(shape="status 60 x 72", S=Sn, P=int(st.data.shape[1]), L=60, Q=72, rounds=rounds, equal_bits=True, **what)
     for k, ts in times.items():
         q1, _, q3 = statistics.quantiles(ts, n=4)
         res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
@@ -484,24 +501,28 @@ def measure_from_status(Sn, device, rounds, warmup):
 
 def main_from_status(args, device, commit):
     rows = []
-    for Sn in STATUS_SIZES:
-        res = measure_from_status(Sn, device, args.rounds, args.warmup)
-        res["commit"] = commit or None
-        res["device"] = torch.cuda.get_device_name(0)
-        rows.append(res)
-        print(json.dumps(res), flush=True)
+    topological = args.kind == "topological"
+    for H in (STATUS_WIDTHS if topological else (None,)):
+        for Sn in STATUS_SIZES:
+            res = measure_from_status(Sn, device, args.rounds, args.warmup, H)
+            res["commit"] = commit or None
+            res["device"] = torch.cuda.get_device_name(0)
+            rows.append(res)
+            print(json.dumps(res), flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             for r in rows:
                 f.write(json.dumps(r) + "\n")
-    print("\n| S | from_status ms (IQR) | device_batch + per_graph ms (IQR) | graphs / from_status |")
-    print("|---|---|---|---|")
+    other = "device_batch + predict" if topological else "device_batch + per_graph"
+    print(f"\n| {'H | ' if topological else ''}S | from_status ms (IQR) | {other} ms (IQR) | graphs / from_status |")
+    print("|---|---|---|---|" + ("---|" if topological else ""))
     for r in rows:
         cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
         a, b = r["from_status_ms"], r["graphs_ms"]
         same = abs(a - b) <= max(r["from_status_iqr_ms"], r["graphs_iqr_ms"])
-        print(f"| {r['S']} | {cell('from_status')} | {cell('graphs')} | {'no difference' if same else f'{b / a:.2f}x'} |")
+        head = f"| {r['H']} " if topological else ""
+        print(f"{head}| {r['S']} | {cell('from_status')} | {cell('graphs')} | {'no difference' if same else f'{b / a:.2f}x'} |")
 
 
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
@@ -667,10 +688,11 @@ def main():
                          "predict on a prebuilt batch (with --kind lightpath: LightpathPredictor's, K candidates of the "
                          "LUT node)")
     ap.add_argument("--from-status", action="store_true", dest="from_status",
-                    help="with --kind lightpath: predict.from_status(status) against device_batch + per_graph")
+                    help="predict.from_status(status) against device_batch + per_graph (--kind lightpath) or device_batch + "
+                         "predict (--kind topological)")
     args = ap.parse_args()
-    if args.from_status and (args.kind != "lightpath" or args.mc is not None or args.grad or args.what_if is not None):
-        raise SystemExit("--from-status goes with --kind lightpath and is a run of its own")
+    if args.from_status and (args.mc is not None or args.grad or args.what_if is not None):
+        raise SystemExit("--from-status is a run of its own")
     if args.what_if is not None and (args.mc is not None or args.grad or any(k < 1 for k in args.what_if)):
         raise SystemExit("--what-if K [K ...] (K >= 1) is a run of its own")
     if args.mc is not None and args.kind != "topological":
