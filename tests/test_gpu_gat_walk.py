@@ -38,10 +38,24 @@ def _graph(kind, n, seed):
 # small cases: every width on every kind of graph (one destination per lane group: the index pipeline's clamps and the
 # first-destination path); large cases: more rows than one resident round of workgroups has lane groups (1024 workgroups x
 # 256 / min(64, C) of them), so that every lane group walks a run of several destinations and the cache / prefetch paths run
-_SMALL = [(k, n, C) for C in (4, 16, 64, 128, 256)
+# (asserted per case from ``qot_gat_chunk_rows``; the forward's grid is ``min(occupancy, 8) x CUs`` workgroups, 3 to 7 per CU
+# by width on the MI355X: tests/test_gpu_gat_kernels.py prints them)
+_SMALL = [(k, n, C) for C in (4, 8, 16, 32, 64, 128, 256)
           for k, n in (("chain", 257), ("shuffled_chain", 131), ("hubs", 203), ("band", 96))]
 _LARGE = [("chain", 70001, 4), ("band", 70001, 16), ("hubs", 70001, 4), ("chain", 20001, 64), ("chain", 9001, 128),
           ("hubs", 9001, 128), ("shuffled_chain", 9001, 128), ("band", 9001, 128), ("band", 9001, 256), ("chain", 13001, 256)]
+
+
+def _large_rows(n, C, device):
+    """The listed row count where it gives every lane group of the forward two destinations on this device; where the
+    forward's grid (``min(occupancy, 8) x CUs``, at most 2048 workgroups of RPB lane groups) still holds all of them in
+    one round, the count that does whatever the occupancy: ``3 min(8 CUs, 2048) RPB + RPB + 1``."""
+    from gnn_qot_estimation_amd import _lib
+    rpb = 256 // min(64, C)
+    if _lib.load().qot_gat_chunk_rows(n, 4, C) // rpb >= 2:
+        return n
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return 3 * min(8 * cus, 2048) * rpb + rpb + 1
 
 
 @pytest.mark.parametrize("thin", [False, True])
@@ -58,6 +72,11 @@ def test_gatconv_walk_matches_oracle(cuda_device, monkeypatch, kind, n, C, thin)
         monkeypatch.setenv("QOT_GAT_THIN_MIN_ROWS", "1")
     else:
         monkeypatch.setenv("QOT_NO_GAT_THIN", "1")
+    if (kind, n, C) in _LARGE:
+        listed, n = n, _large_rows(n, C, cuda_device)
+        run = _lib.load().qot_gat_chunk_rows(n, 4, C) // (256 // min(64, C))
+        print(f"{kind} C = {C}: listed {listed} rows, run {n}: {run} destinations per lane group")
+        assert run >= 2, (kind, n, C, run)
     torch.manual_seed(1)
     ref = O.GATConv(5, C, heads=4)
     hip = q.GATConv(5, C, heads=4)
