@@ -23,31 +23,11 @@
 //
 // On the device: a conn_id that is not finite or beyond +-2^53 (QOT_LP_STATUS_BAD_CONN), more than 256 lightpaths
 // (QOT_LP_STATUS_TOO_MANY), a sample number outside [0, S) (QOT_LP_STATUS_BAD_SAMPLE): the sample's row is NaN, its count 0.
-#include "infer_lightpath_dev.hpp"
-#include "status_scan_dev.hpp"
+// channel_conn, the slot walk and the staging are infer_lightpath_status_dev.hpp's, shared with infer_lightpath_place.hip.
+#include "infer_lightpath_status_dev.hpp"
 
 namespace qot {
 namespace {
-
-struct LpStatusArgs {
-    const double* data; const double* freq; const int64_t* samples;
-    int64_t S;
-    int P, L, Q;
-    int conn_row, osnr_row, snr_row, ber_row;
-    const double* cols;                 // [F, 4]: lp_feat row (-1 = is_lut), min, max - min, has_range
-    double thr;
-    int64_t* count;
-};
-
-// whether channel c is occupied, and by which conn (bad conn values: the sample has been refused before this is asked)
-__device__ __forceinline__ bool channel_conn(const double* __restrict__ d, int P, int LQ, int conn_row, int c, int64_t& conn) {
-    const double cv = d[(int64_t)conn_row * LQ + c];
-    if (cv != 0.0) return sg::sg_conn(cv, conn);
-    bool occ = false;
-    for (int p = 0; p < P; ++p) occ |= (d[(int64_t)p * LQ + c] != 0.0);
-    conn = 0;
-    return occ;
-}
 
 __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_status_kernel(const LpArgs a, const LpStatusArgs st) {
     __shared__ sg::Table T;
@@ -119,33 +99,14 @@ __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_status_kernel(co
             const int c1 = base + w * 64 + __builtin_ctzll(mask);
             mask &= mask - 1;
             const int l = c1 / st.Q, q1 = c1 - l * st.Q;
-            const double f1 = freq[q1];
-            for (int q2 = lane; q2 < st.Q; q2 += 64) {
-                const double df = fabs(f1 - freq[q2]);
-                if (!(df > 0.0 && df < st.thr)) continue;
-                int64_t conn;
-                if (!channel_conn(d, st.P, LQ, st.conn_row, l * st.Q + q2, conn) || conn == conn_a) continue;
-                for (int i = 0; i < n; ++i)
-                    if (T.conn[i] == conn) { nb[i] = 1; break; }
-            }
+            lp_mark_slots(d, st, LQ, l, q1, freq, T, n, conn_a, nb, lane);
         }
     }
     __syncthreads();
     if (w != 0) return;
 
     // ---- phase 3: the rows of the neighbourhood by rising lightpath number, then the row ----
-    int na = 0;
-    for (int base = 0; base < n; base += kWave) {
-        const int j = base + lane;
-        const bool is = j < n && nb[j] != 0;
-        const unsigned long long m = __ballot(is);
-        if (is) {
-            float* r = rows + (na + sg::wave_prefix(m)) * kLpXs;
-            const int c = T.first[j];
-            for (int k = 0; k < a.F; ++k) r[k] = sg::sg_feature(d, st.P, LQ, st.osnr_row, st.snr_row, st.ber_row, st.cols, k, c);
-        }
-        na += __popcll(m);
-    }
+    const int na = lp_stage_marked(d, st, LQ, a.F, T, n, nb, rows, lane);
     if (lane < a.F) xi[lane] = sg::sg_feature(d, st.P, LQ, st.osnr_row, st.snr_row, st.ber_row, st.cols, lane, T.first[lut]);
     __syncthreads();
     LpStaged ed;
@@ -173,20 +134,9 @@ extern "C" int qot_lightpath_infer_status(const float* x, const int64_t* edge_in
                                           int osnr_row, int snr_row, int ber_row, const double* cols, int ncol,
                                           double freq_threshold, qot_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    // there is no graph: the batch arguments of the common prefix must be empty
-    if (x || edge_index || batch || node_ptr || edge_ptr || lut_idx || n_lut != 0 || N != 0 || E != 0) return QOT_ERR_BADARG;
-    if (G < 0 || S < 0 || P < 1 || L < 1 || Q < 1) return QOT_ERR_BADARG;
-    if (F < 1 || F > kLpMaxF) return QOT_ERR_UNSUPPORTED;
-    if (C < 1 || C > kLpMaxC) return QOT_ERR_UNSUPPORTED;
-    if (O < 1 || O > kLpMaxO) return QOT_ERR_UNSUPPORTED;
-    if (heads != kLpHeads) return QOT_ERR_UNSUPPORTED;
-    if (lut_col < 0 || lut_col >= F) return QOT_ERR_UNSUPPORTED;
-    if (Q > QOT_SG_MAX_FREQS || L * Q >= (int64_t)1 << 31 || G >= (int64_t)1 << 31) return QOT_ERR_UNSUPPORTED;
-    if (ncol != F) return QOT_ERR_BADARG;
-    if (conn_row < 0 || conn_row >= P || osnr_row < 0 || osnr_row >= P || snr_row < 0 || snr_row >= P || ber_row < 0 ||
-        ber_row >= P)
-        return QOT_ERR_BADARG;
-    if (!(freq_threshold > 0.0) || !(freq_threshold <= 1.7976931348623157e308)) return QOT_ERR_BADARG;
+    const int rc = lp_status_envelope(x, edge_index, batch, node_ptr, edge_ptr, lut_idx, n_lut, N, E, G, F, C, O, heads, lut_col,
+                                      S, P, L, Q, conn_row, osnr_row, snr_row, ber_row, ncol, freq_threshold);
+    if (rc != QOT_OK) return rc;
     if (G == 0) return QOT_OK;
     if (!w || !att_src || !att_dst || !conv_bias || !bn_weight || !bn_bias || !bn_mean || !bn_var || !w0 || !b0 || !w3 || !b3 ||
         !out || !count || !data || !freq || !cols || S == 0)

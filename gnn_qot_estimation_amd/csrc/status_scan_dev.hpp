@@ -1,6 +1,6 @@
 // The scan of one network-status sample data[P, L, Q] (fp64) by one 256-thread workgroup, shared by the graph builder
 // (status_graph.hip) and the status-to-row kernels (infer_lightpath_status.hip, DESIGN.md 4.20;
-// infer_topological_status.hip): all run discover(), so the lightpaths of a sample, their numbering and
+// infer_topological_status.hip; infer_lightpath_place.hip): all run discover(), so the lightpaths of a sample, their numbering and
 // their first channels are the same table in all.  Stated once here: the workgroup's geometry and caps, the first-seen
 // table and its insert, the sample pick, the occupancy / conn rule of one channel (sg_conn), the fp64 column scaling
 // (scaled) and, for the topological representation, the block scan, the pair contest that fills the 75 x 75 winner
@@ -149,6 +149,20 @@ __device__ __forceinline__ float sg_feature(const double* __restrict__ d, int P,
     const int r = (int)col[0];
     if (r < 0) return sg_is_lut(d, LQ, osnr_row, snr_row, ber_row, c) ? 1.0f : 0.0f;
     return r < P ? scaled(d[(int64_t)r * LQ + c], col) : 0.0f;
+}
+
+// The same two for a lightpath that is not in the sample: v is its raw lp_feat vector [P] (LightpathPredictor.place's
+// candidate, infer_lightpath_place.hip).  The doubles that reach `scaled` are those a channel holding v would give.
+__device__ __forceinline__ bool sg_is_lut_vec(const double* __restrict__ v, int osnr_row, int snr_row, int ber_row) {
+    return v[osnr_row] == -1.0 && v[snr_row] == -1.0 && v[ber_row] == -1.0;
+}
+
+__device__ __forceinline__ float sg_feature_vec(const double* __restrict__ v, int P, int osnr_row, int snr_row, int ber_row,
+                                                const double* __restrict__ cols, int k) {
+    const double* col = cols + 4 * k;
+    const int r = (int)col[0];
+    if (r < 0) return sg_is_lut_vec(v, osnr_row, snr_row, ber_row) ? 1.0f : 0.0f;
+    return r < P ? scaled(v[r], col) : 0.0f;
 }
 
 // exclusive prefix of v over the block's threads (thread order) and the block total; `part` holds kWaves + 1 ints

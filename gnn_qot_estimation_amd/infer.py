@@ -4,7 +4,8 @@
 samples: ``csrc/infer_topological_status.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
 ``csrc/infer_lightpath_grad.hip``; its ``what_if`` over candidate lightpaths:
 ``csrc/infer_lightpath_whatif.hip``; its ``from_status`` over network-status samples:
-``csrc/infer_lightpath_status.hip``).
+``csrc/infer_lightpath_status.hip``; its ``place`` of candidate lightpaths into such samples:
+``csrc/infer_lightpath_place.hip``).
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
 TransformerConv, the NNConv forward and the read-out kernel (``LightpathGNN``: the self-looped graph index, the GAT walk
@@ -401,7 +402,8 @@ class _DeviceState:
         code = int(self._status.item())
         self._status.zero_()
         if code:
-            named = "; ".join(text for bit, text in getattr(self, "_CAUSES", ()) if code & bit)
+            causes = tuple(getattr(self, "_CAUSES", ())) + tuple(getattr(self, "_PLACE_CAUSES", ()))
+            named = "; ".join(text for bit, text in causes if code & bit)
             raise _lib.QotError("%s flagged the batch (status %d): %s%s" % (self._FLAGS[0], code, self._FLAGS[1],
                                                                            named and " -- here: " + named))
 
@@ -989,6 +991,104 @@ def lightpath_status_args(status, in_channels, is_lut_index, features_to_conside
     return _LpStatus(feats, S, P, L, Q, fi["conn_id"], fi["osnr"], fi["snr"], fi["ber"], float(thr))
 
 
+# include/qot_gnn.h: QOT_LP_PLACE_*, the status bits qot_lightpath_infer_place adds beside QOT_LP_STATUS_*
+LP_PLACE_BAD_CELL, LP_PLACE_OCCUPIED, LP_PLACE_CONN_TAKEN, LP_PLACE_NOT_LUT = 64, 128, 256, 512
+_LP_PLACE_CAUSES = (
+    (LP_PLACE_BAD_CELL, "place: a link or frequency index outside the sample, or a cell_ptr slice that is empty, descending "
+                        "or beyond the cells"),
+    (LP_PLACE_OCCUPIED, "place: a cell whose channel is occupied in the sample"),
+    (LP_PLACE_CONN_TAKEN, "place: a candidate's conn_id is a lightpath of the sample already"),
+    (LP_PLACE_NOT_LUT, "place: a candidate's values without osnr == snr == ber == -1"),
+)
+
+# samples / cell_ptr: int64 tensors, on the host checked (cell_ptr) and to be uploaded, or on the device and used in place
+_LpPlace = namedtuple("_LpPlace", "status K M samples cell_ptr")
+
+
+def _place_lists(status, samples, values, cells, cell_ptr, who):
+    """The checks of the candidate lists that ``lightpath_place_args`` and ``materialise_placement`` share: returns ``(K,
+    M, samples, cell_ptr)`` with the last two as 1-d int64 tensors -- the caller's own tensor where one was given -- or
+    raises the named ``ValueError``."""
+    def got(t):
+        return f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+
+    P = int(status.data.shape[1])
+    if not isinstance(values, torch.Tensor) or values.dim() != 2 or values.dtype != torch.float64 or values.shape[1] != P:
+        raise ValueError(f"{who}: values must be a float64 tensor [K, {P}] (one raw lp_feat vector per candidate), got "
+                         f"{got(values)}")
+    K = int(values.shape[0])
+    if not isinstance(cells, torch.Tensor) or cells.dim() != 2 or cells.dtype != torch.int64 or cells.shape[0] != 2:
+        raise ValueError(f"{who}: cells must be an int64 tensor [2, M] (link index, frequency index), got {got(cells)}")
+    M = int(cells.shape[1])
+    for name, t in (("values", values), ("cells", cells)):
+        if t.device != status.data.device:
+            raise ValueError(f"{who}: {name} is on {t.device}, the status chunk on {status.data.device}")
+    if isinstance(samples, torch.Tensor):
+        if samples.dim() != 1 or samples.dtype != torch.int64 or samples.shape[0] != K:
+            raise ValueError(f"{who}: samples must be an int, a sequence or a 1-d int64 tensor of {K} sample numbers (one "
+                             f"per row of values), got {got(samples)}")
+    elif isinstance(samples, bool) or samples is None:
+        raise ValueError(f"{who}: samples must be an int, a sequence or a 1-d int64 tensor, got {got(samples)}")
+    elif isinstance(samples, int):
+        samples = torch.full((K,), samples, dtype=torch.int64)
+    else:
+        samples = torch.tensor([int(v) for v in samples], dtype=torch.int64).reshape(-1)
+        if samples.shape[0] != K:
+            raise ValueError(f"{who}: samples names {samples.shape[0]} candidates, values has {K} rows")
+    if isinstance(cell_ptr, torch.Tensor):
+        if cell_ptr.dim() != 1 or cell_ptr.dtype != torch.int64 or cell_ptr.shape[0] != K + 1:
+            raise ValueError(f"{who}: cell_ptr must be a sequence or a 1-d int64 tensor of K + 1 = {K + 1} offsets into "
+                             f"cells, got {got(cell_ptr)}")
+    else:
+        cell_ptr = torch.tensor([int(v) for v in cell_ptr], dtype=torch.int64).reshape(-1)
+        if cell_ptr.shape[0] != K + 1:
+            raise ValueError(f"{who}: cell_ptr must hold K + 1 = {K + 1} offsets into cells, got {cell_ptr.shape[0]}")
+    if not cell_ptr.is_cuda:                               # on the host: checked here; on the device: by the kernel
+        if int(cell_ptr[0]) != 0 or int(cell_ptr[-1]) != M or (K and int(cell_ptr.diff().min()) < 0):
+            raise ValueError(f"{who}: cell_ptr must be non-decreasing from 0 to M = {M}, got {cell_ptr.tolist()}")
+        if K and int(cell_ptr.diff().min()) == 0:
+            raise ValueError(f"{who}: candidate {int(cell_ptr.diff().argmin())} has an empty slice of cells")
+    return K, M, samples, cell_ptr
+
+
+def lightpath_place_args(status, in_channels, is_lut_index, samples, values, cells, cell_ptr,
+                         features_to_consider=to_graph.DEFAULT_FEATURES, freq_threshold=0.05,
+                         who="LightpathPredictor.place"):
+    """The argument checks of ``LightpathPredictor.place`` that need no device: returns an ``_LpPlace`` (``status``: the
+    ``_LpStatus`` of ``lightpath_status_args``; ``K``, ``M``; ``samples`` and ``cell_ptr`` as 1-d int64 tensors) or raises
+    -- ``TypeError`` for a ``status`` that is no ``DeviceStatus``; ``ValueError`` naming the argument for ``values`` not
+    float64 ``[K, P]``, ``cells`` not int64 ``[2, M]``, either on another device than the chunk, ``samples`` or ``cell_ptr``
+    of the wrong length or dtype, a host ``cell_ptr`` that is not non-decreasing from 0 to ``M`` or has an empty slice
+    (one on the device is checked by the kernel), a bad ``freq_threshold``; then ``EnvelopeError`` for everything
+    ``lightpath_status_args`` refuses, a chunk on the CPU last."""
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    K, M, samples, cell_ptr = _place_lists(status, samples, values, cells, cell_ptr, who)
+    sa = lightpath_status_args(status, in_channels, is_lut_index, features_to_consider, freq_threshold, who)
+    return _LpPlace(sa, K, M, samples, cell_ptr)
+
+
+def materialise_placement(status, samples, values, cells, cell_ptr):
+    """The K edited samples that ``LightpathPredictor.place`` scores without building them: the DEFINITION of that call
+    and what it saves.  Returns a ``DeviceStatus`` of K samples; sample ``k`` is ``status.data[samples[k]]`` with
+    ``values[k]`` written into each of the channels ``cells[:, cell_ptr[k]:cell_ptr[k + 1]]`` (``target`` rows follow their
+    samples).  ``predict.place(...)[0][k]`` is, bit for bit, the row ``predict(to_graph.device_batch(edited, "lightpath",
+    ...))`` gives the candidate's node of graph ``k``, and -- the candidate being the first-seen flagged lightpath of its
+    edited sample -- ``predict.from_status(edited)[0][k]``.  Pure torch on the status' device (CPU tensors as well), no
+    kernel of ours; ``status`` is not modified.  Arguments as ``place``; occupied cells are overwritten, not refused."""
+    who = "materialise_placement"
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    K, M, samples, cell_ptr = _place_lists(status, samples, values, cells, cell_ptr, who)
+    dev = status.data.device
+    samples, cell_ptr = samples.to(dev), cell_ptr.to(dev)
+    edited = status.data.index_select(0, samples)
+    cand = torch.repeat_interleave(torch.arange(K, device=dev), cell_ptr.diff(), output_size=M)
+    edited[cand, :, cells[0], cells[1]] = values.index_select(0, cand)
+    return to_graph.DeviceStatus(edited, status.target.index_select(0, samples), status.freq, status.lp_feat, status.metric,
+                                 status.link)
+
+
 # what LightpathPredictor._prepare hands to _launch: the model's shape, the batch on dev, which rows (rows mode: batch,
 # idx; graphs mode: a fresh count) and how many
 _LpPrepared = namedtuple("_LpPrepared", "F C O dev x ei batch ptr eptr idx B rows count")
@@ -1020,6 +1120,9 @@ class LightpathPredictor(_DeviceState):
     added -- scored in one launch (see there).
     ``predict.from_status(status)``: ``per_graph``'s rows straight from network-status samples, no graph in between, one
     launch and no host read (see there).
+    ``predict.place(status, samples, values, cells, cell_ptr)``: K candidate (route, slot) assignments of a NEW lightpath,
+    each placed into a status sample that does not hold it yet -- the interferers are found by the kernel -- one launch and
+    no host read (see there).
 
     Envelope -- ``EnvelopeError`` naming the condition otherwise: a model on the GPU with ``num_layers == 1``, 1 ... 16 input
     features, hidden width 1 ... 256, 1 ... 8 outputs; ``data.x`` of shape ``[N, F]``.  No cap on in-degree, graph size or
@@ -1031,11 +1134,14 @@ class LightpathPredictor(_DeviceState):
                                      "outside the arrays (what_if: bit 0 also an added source, bit 1 also a candidate's "
                                      "node or a drop position out of range, bit 2 a candidate's feature row without 1.0 "
                                      "in the LUT column; from_status: bit 3 a bad conn_id, bit 4 too many lightpaths, bit 5 "
-                                     "a sample number out of range)")
+                                     "a sample number out of range; place: those, bit 6 a bad cell, bit 7 an occupied "
+                                     "cell, bit 8 a conn_id taken, bit 9 values not under test)")
     # the bits of qot_lightpath_infer_status, named when check_status() finds them: the device builder's own words
     _CAUSES = tuple((bit, next(t for b, t in to_graph._SG_CAUSES if b == sg)) for bit, sg in (
         (LP_STATUS_BAD_CONN, to_graph.SG_BAD_CONN), (LP_STATUS_TOO_MANY, to_graph.SG_TOO_MANY),
         (LP_STATUS_BAD_SAMPLE, to_graph.SG_BAD_SAMPLE)))
+    # ... and the bits qot_lightpath_infer_place adds, named by check_status() behind them
+    _PLACE_CAUSES = _LP_PLACE_CAUSES
 
     def __init__(self, model):
         super().__init__()
@@ -1202,6 +1308,64 @@ class LightpathPredictor(_DeviceState):
         cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
         count = self._launch("qot_lightpath_infer_status", p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L, sa.Q,
                              sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold)
+        return out, count
+
+    @torch.no_grad()
+    def place(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES,
+              freq_threshold=0.05):
+        """Routing and spectrum assignment: scores K candidate (route, slot) assignments of a NEW lightpath against the
+        status samples of the established ones, ``(out [K, O] float32, count [K] int64)`` in ONE kernel launch
+        (``csrc/infer_lightpath_place.hip``), without the edited samples or their graphs, with nothing read back, legal
+        inside ``torch.cuda.graph`` capture.  The caller does not name the interferers: the kernel finds them by the rule
+        of the graph builder (same link, ``0 < |f1 - f2| < freq_threshold``).
+
+        ``status``: a ``to_graph.DeviceStatus`` on the model's device; never written.  ``samples``: the sample each
+        candidate is placed into -- an int (all K), a sequence, or a 1-d int64 device tensor (used in place: the form to
+        capture); repeated numbers are the normal case.  ``values [K, P]`` float64 on the device: row ``k`` is the raw
+        ``lp_feat`` vector the candidate writes into each of its channels (``conn_id``, ``src_id``, ``dst_id``, the features,
+        ``osnr = snr = ber = -1``), in status units: the kernel scales it with the column table ``from_status`` uses.
+        ``cells [2, M]`` int64 on the device: (link index, frequency index) pairs; candidate ``k`` occupies
+        ``cells[:, cell_ptr[k]:cell_ptr[k + 1]]`` -- no cap on their number, duplicates allowed.  ``cell_ptr``: K + 1 offsets;
+        a host sequence is checked here and uploaded, an int64 device tensor is used in place and checked by the kernel.
+
+        ``materialise_placement`` is the definition: with ``edited`` its K samples and ``batch =
+        to_graph.device_batch(edited, "lightpath", ...)``, ``out[k]`` is, bit for bit, the row ``self(batch)`` gives the
+        candidate's node of graph ``k`` (``to_graph.place_lightpath`` states its number), and ``count[k]`` the flagged
+        lightpaths of ``edited[k]``: the sample's own plus one.  When the candidate is the only or the first-seen flagged
+        one, that is ``self.from_status(edited)[0][k]``.  ``to_graph.placement_neighbourhood`` states on the host which
+        lightpaths send a message into the row.  A candidate's row depends on its sample and itself alone; every
+        candidate rescans its sample, O(L Q + cells Q): candidates of one sample do not share the scan.
+
+        Refusals before any launch (``lightpath_place_args``): ``TypeError`` for a ``status`` that is no ``DeviceStatus``;
+        ``ValueError`` for a bad ``freq_threshold``, ``values`` not float64 ``[K, P]``, ``cells`` not int64 ``[2, M]``,
+        ``samples`` or ``cell_ptr`` of the wrong length or dtype, a host ``cell_ptr`` that is not non-decreasing from 0 to M
+        or has an empty slice; ``EnvelopeError`` for everything ``from_status`` refuses.  ``K == 0`` gives empty tensors
+        without a launch.  On the device, since nothing is read back: a cell outside the sample or a bad ``cell_ptr``
+        slice, an occupied cell, a ``conn_id`` the sample holds already, ``values[k]`` without ``osnr == snr == ber == -1``,
+        a ``conn_id`` that is not finite or beyond +-2^53, a sample that holds 256 lightpaths already, a sample number
+        outside the chunk -- that candidate's row is NaN and its count 0, the other rows are untouched, and
+        ``check_status()`` raises naming the cause.  (The column table of a feature list is uploaded on its first call
+        with a chunk: make that call before capturing.)"""
+        who = "LightpathPredictor.place"
+        shape = self._check_model()
+        pa = lightpath_place_args(status, shape[0], self.model.is_lut_index, samples, values, cells, cell_ptr,
+                                  features_to_consider, freq_threshold, who)
+        sa = pa.status
+        dev = self._device()
+        if status.device != dev:
+            raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
+        p = self._prepare(None, True, shape, samples=pa.K)
+        out = torch.empty(pa.K, p.O, dtype=torch.float32, device=dev)
+        if pa.K == 0:
+            return out, p.count
+        picks, ptr = pa.samples, pa.cell_ptr
+        if not picks.is_cuda and not ptr.is_cuda:           # both lists are on the host: one upload for the two
+            both = torch.cat([picks, ptr]).to(dev)
+            picks, ptr = both[:pa.K], both[pa.K:]
+        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
+        count = self._launch("qot_lightpath_infer_place", p, out, status.data, status.freq, _i64(picks, dev), sa.S, sa.P, sa.L,
+                             sa.Q, sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
+                             values.contiguous(), cells.contiguous(), _i64(ptr, dev), pa.M)
         return out, count
 
     @torch.no_grad()

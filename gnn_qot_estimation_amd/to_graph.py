@@ -257,6 +257,67 @@ def lut_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dic
     return len(flagged), a, [int(conn[i]) for i in seen_order if int(conn[i]) in hit]
 
 
+def _cells_of(cells, L: int, Q: int):
+    cells = np.asarray(cells, dtype=np.int64)
+    if cells.ndim != 2 or cells.shape[0] != 2 or cells.shape[1] < 1:
+        raise ValueError(f"cells must be [2, m] (link index, frequency index) with m >= 1, got {tuple(cells.shape)}")
+    if ((cells[0] < 0) | (cells[0] >= L) | (cells[1] < 0) | (cells[1] >= Q)).any():
+        raise ValueError(f"a cell lies outside the {L} links x {Q} frequency slots of the sample")
+    return cells
+
+
+def place_lightpath(sample: np.ndarray, values_row: np.ndarray, cells, feature_indexes: Dict[str, int]):
+    """One candidate of ``LightpathPredictor.place``, stated on the host: ``(edited, node)``.  ``edited`` is a copy of
+    ``sample [lp_feat, link, freq]`` with the raw ``lp_feat`` vector ``values_row`` written into every channel of ``cells
+    [2, m]`` (link index, frequency index; a repeated cell is written once more); ``node`` is the candidate's number in
+    the first-seen order of ``edited``: its node in ``create_lightpath_graph``'s graph.  ``ValueError`` for a cell outside
+    the sample, a cell whose channel is occupied (any of its values != 0) and a ``conn_id`` that truncates to one the
+    sample holds already.  The input is not modified."""
+    fi = feature_indexes
+    sample = np.asarray(sample, dtype=np.float64)
+    values_row = np.asarray(values_row, dtype=np.float64)
+    if sample.ndim != 3 or values_row.shape != (sample.shape[0],):
+        raise ValueError("sample must be [lp_feat, link, freq] and values_row [lp_feat]")
+    cells = _cells_of(cells, sample.shape[1], sample.shape[2])
+    occupied = np.any(sample != 0, axis=0)
+    if occupied[cells[0], cells[1]].any():
+        l, q = cells[:, np.flatnonzero(occupied[cells[0], cells[1]])[0]]
+        raise ValueError(f"the channel of cell (link {int(l)}, slot {int(q)}) is occupied in the sample")
+    conn = int(values_row[fi["conn_id"]])
+    if conn in set(sample[fi["conn_id"]][occupied].astype(np.int64).tolist()):
+        raise ValueError(f"conn_id {conn} is a lightpath of the sample already")
+    edited = sample.copy()
+    edited[:, cells[0], cells[1]] = values_row[:, None]
+    _, _, vec = _occupied(edited)
+    seen = vec[fi["conn_id"], :].astype(np.int64)
+    _, first = np.unique(seen, return_index=True)
+    order = [int(seen[i]) for i in np.sort(first)]
+    return edited, order.index(conn)
+
+
+def placement_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], cells,
+                            freq_threshold: float = 0.05):
+    """Who sends a message into the row of a candidate of ``LightpathPredictor.place``, stated on the UNEDITED sample
+    ``[lp_feat, link, freq]`` plus the candidate's ``cells [2, m]``: the ``conn_id`` values, in the sample's first-seen
+    order, of the lightpaths that occupy, on the link of some cell, a slot with ``0 < |f1 - f2| < freq_threshold`` to that
+    cell's (fp64) -- each once, however many links and slots are shared.  The candidate's own cells are free in the
+    sample, so a pair of them names nobody.  For a candidate that is the first-seen flagged lightpath of its edited sample
+    this is ``lut_neighbourhood(place_lightpath(...)[0], ...)[2]``: the candidate fills free channels only, so every other
+    lightpath keeps its place in first-seen order."""
+    fi = feature_indexes
+    sample, freq = np.asarray(sample, dtype=np.float64), np.asarray(freq, dtype=np.float64)
+    cells = _cells_of(cells, sample.shape[1], sample.shape[2])
+    link_idx, freq_idx, vec = _occupied(sample)
+    conn = vec[fi["conn_id"], :].astype(np.int64)
+    _, first = np.unique(conn, return_index=True)
+    hit = set()
+    for l, q in cells.T:
+        on_link = np.flatnonzero(link_idx == l)
+        diff = np.abs(freq[q] - freq[freq_idx[on_link]])
+        hit.update(conn[on_link[(diff > 0) & (diff < freq_threshold)]].tolist())
+    return [int(conn[i]) for i in np.sort(first) if int(conn[i]) in hit]
+
+
 def topological_links(sample: np.ndarray, feature_indexes: Dict[str, int]):
     """What ``TopologicalPredictor.from_status`` takes of one sample ``[lp_feat, link, freq]``, stated on the host:
     ``(edge_index [2, m] int64, conn [m] int64)``.  The lightpaths are the distinct ``trunc(conn_id)`` of the occupied

@@ -1103,6 +1103,43 @@ int qot_lightpath_infer_status(const float* x, const int64_t* edge_index, const 
                                int64_t S, int P, int64_t L, int64_t Q, int conn_row, int osnr_row, int snr_row, int ber_row,
                                const double* cols, int ncol, double freq_threshold, qot_stream_t stream);
 
+/* ---- K candidate lightpaths placed into network-status samples, one launch (LightpathPredictor.place)
+ * Candidate k is the raw lp_feat vector values[k, P] (fp64, status units) written into the channels cells[:, cell_ptr[k] :
+ * cell_ptr[k + 1]] of sample samples[k]; cells [2, M] int64 holds link indices, then frequency indices; cell_ptr [K + 1]
+ * int64; samples [K] int64 (required; repeats are the normal case).  Let edited_k be that sample with values[k] in each of
+ * the candidate's cells.  out[k] is, bit for bit, the row that graphs mode of the eval entry gives the candidate's node in
+ * the QOT_SG_LIGHTPATH graph of edited_k (same cols, same freq_threshold), and count[k] the lightpaths of edited_k with
+ * osnr == snr == ber == -1 on their first channel: the sample's own flagged ones plus one.  When the candidate is the
+ * first-seen flagged lightpath of edited_k this is what the status entry above gives for edited_k.  edited_k is never
+ * built and data is never written: the candidate fills free channels, so the other lightpaths keep their first-seen
+ * numbers; its interferers -- every lightpath of the sample on a slot with 0 < |freq[q1] - freq[q2]| < freq_threshold
+ * (fp64) of the link of one of its cells, once each; a pair of its own cells names nobody -- are summed by rising
+ * first-seen number, the self loop last.  One 256-thread workgroup per candidate: O(L Q) for the scan plus O(cells Q); no
+ * cap on the cells of a candidate, duplicates allowed; no workspace.
+ *
+ * The argument list is the status entry's up to freq_threshold (K takes G's place; the batch arguments of the common
+ * prefix must be empty), then values, cells, cell_ptr, M.  Return codes before any launch: the status entry's, and
+ * QOT_ERR_BADARG for M < 0 or -- when K > 0 -- a NULL samples, values or cell_ptr, or NULL cells with M > 0.  K == 0:
+ * QOT_OK, no launch.
+ * status, on the device since nothing is read back: the refused candidate's row is NaN and its count 0, the other rows
+ * are untouched; nothing read from data or values is used as an index.  The bits lie beside QOT_LP_STATUS_*, which are
+ * reused: BAD_CONN also for a candidate conn_id that is not finite or beyond +-2^53, TOO_MANY for a sample that holds
+ * QOT_SG_MAX_LIGHTPATHS lightpaths already (edited_k would hold one more), BAD_SAMPLE as there. */
+#define QOT_LP_PLACE_BAD_CELL 64     /* a link / frequency index outside [0, L) / [0, Q), or a cell_ptr slice that is empty, descending or beyond M */
+#define QOT_LP_PLACE_OCCUPIED 128    /* a cell whose channel is occupied in the sample */
+#define QOT_LP_PLACE_CONN_TAKEN 256  /* the candidate's conn_id equals a lightpath of the sample */
+#define QOT_LP_PLACE_NOT_LUT 512     /* values[k] without osnr == snr == ber == -1 */
+int qot_lightpath_infer_place(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                              const int64_t* edge_ptr, const int64_t* lut_idx, int64_t n_lut, int64_t N, int64_t E, int64_t K,
+                              const float* w, const float* att_src, const float* att_dst, const float* conv_bias,
+                              float slope_att, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                              const float* bn_var, float bn_eps, const float* w0, const float* b0, const float* w3,
+                              const float* b3, float slope_head, float* out, int64_t* count, int F, int C, int O, int heads,
+                              int lut_col, int32_t* status, const double* data, const double* freq, const int64_t* samples,
+                              int64_t S, int P, int64_t L, int64_t Q, int conn_row, int osnr_row, int snr_row, int ber_row,
+                              const double* cols, int ncol, double freq_threshold, const double* values, const int64_t* cells,
+                              const int64_t* cell_ptr, int64_t M, qot_stream_t stream);
+
 /* ---- the TopologicalGNN row of every network-status sample in one launch (TopologicalPredictor.from_status, DESIGN.md
  * 4.21) -- From data [S, P, L, Q] fp64 to out [G, O] fp32 and links [G] int64 without a graph in between: for sample
  * samples[g] (NULL: sample g), out[g] is, bit for bit, the row qot_topological_infer writes for the QOT_SG_TOPOLOGICAL

@@ -88,6 +88,21 @@ the "no difference" rule as above.
 and hidden widths 64 and 16 (V = 75, edge_dim 4, 3 outputs); same samples, same protocol.
 
     python tools/bench_infer.py --kind topological --from-status [--out profiles/bench_infer_topological_status.jsonl]
+
+``--kind lightpath --place K [K ...]``: K candidate (route, slot) assignments of a new lightpath scored against one status
+sample in one launch (csrc/infer_lightpath_place.hip) -- milliseconds per call of ``predict.place(status,
+...)`` against (a) ``infer.materialise_placement(...)`` (K edited copies of the sample) followed by
+``predict.from_status(edited)`` per call and (b) ``to_graph.device_batch(status)`` (two builder launches, one host read)
+followed by ``predict.what_if`` per call, with each candidate's interferers worked out beforehand on the host
+(``to_graph.placement_neighbourhood``) and its feature row scaled beforehand -- what a caller had to do before ``place``
+existed.  One ``synthetic_network_status`` sample on the 60 x 72 grid without a lightpath under test of its own; every
+candidate takes one free slot on 1 - 6 free links (seeded; ``--cells N``: on N links, ``--links L``: a grid of L links
+instead of 60 -- the pair tells the cost of the sample scan, O(L Q), from that of the walk, O(cells Q)); C = 32, F = 5,
+threshold 0.05.  For (b) the sample also
+holds a placeholder lightpath under test on channel (0, 0), out of reach of every candidate, whose node the candidates
+take over.  The rows of the three ways are compared first (equal bits); output and the interquartile rule as above.
+
+    python tools/bench_infer.py --kind lightpath --place 1 8 64 1024 [--out profiles/bench_infer_lightpath_place.jsonl]
 """
 import argparse
 import json
@@ -525,6 +540,118 @@ def main_from_status(args, device, commit):
         print(f"{head}| {r['S']} | {cell('from_status')} | {cell('graphs')} | {'no difference' if same else f'{b / a:.2f}x'} |")
 
 
+def measure_place(K, device, rounds, warmup, thr=0.05, num_links=60, per_candidate=None):
+    import numpy as np
+    from gnn_qot_estimation_amd import infer, to_graph as TG
+    torch.manual_seed(0)
+    model = q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval()
+    predict = q.LightpathPredictor(model)
+    ns = TG.synthetic_network_status(1, num_links=num_links, seed=0)      # the 60 x 72 grid by default
+    fi, feats = ns.feature_indexes, list(TG.DEFAULT_FEATURES)
+    data = ns.data.copy()
+    under_test = (data[0, fi["osnr"]] == -1) & (data[0, fi["snr"]] == -1) & (data[0, fi["ber"]] == -1)
+    data[0][:, under_test] = 0.0                            # the sample's own lightpath under test goes
+    data[0, :, 0, :4] = 0.0                                 # room for (b)'s placeholder: nobody within 3 slots of (0, 0)
+    L, Q = data.shape[2], data.shape[3]
+    free = ~np.any(data[0] != 0, axis=0)
+    rng = np.random.default_rng(K)
+    values, cells, ptr = np.zeros((K, len(ns.lp_feat))), [], [0]
+    for k in range(K):
+        want = per_candidate or int(rng.integers(1, 7))
+        while True:                                         # one slot (>= 4: clear of the placeholder) on 1 - 6 free links
+            slot = int(rng.integers(4, Q))
+            open_links = np.flatnonzero(free[:, slot])
+            if len(open_links) >= want:
+                links = rng.choice(open_links, size=want, replace=False)
+                break
+        cells.append(np.stack([links, np.full_like(links, slot)]))
+        ptr.append(ptr[-1] + len(links))
+        v = values[k]
+        v[fi["conn_id"]], v[fi["src_id"]], v[fi["dst_id"]] = 10000 + k, 1, 2
+        v[fi["mod_order"]], v[fi["path_len"]] = float(rng.choice([4, 8, 16, 32, 64])), float(rng.integers(24214, 7834746))
+        v[fi["num_spans"]], v[fi["freq"]] = float(rng.integers(1, 107)), ns.freq[slot]
+        v[fi["osnr"]] = v[fi["snr"]] = v[fi["ber"]] = -1.0
+    cells = np.concatenate(cells, axis=1).astype(np.int64)
+    status_of = lambda d: TG.NetworkStatus(d, ns.target, ns.lp_feat, ns.metric, ns.link, ns.freq).to_device(device)  # noqa: E731
+    st = status_of(data)
+    samples = torch.zeros(K, dtype=torch.int64, device=device)
+    values_d, cells_d = torch.from_numpy(values).to(device), torch.from_numpy(cells).to(device)
+    ptr_d = torch.tensor(ptr, dtype=torch.int64, device=device)
+    # (b): the placeholder under test on (0, 0) is the first lightpath seen, node 0; the candidates take its node over
+    held = data.copy()
+    held[0, :, 0, 0] = values[0]
+    held[0, fi["conn_id"], 0, 0] = 9999.0
+    st_b = status_of(held)
+    _, _, vec = TG._occupied(held[0])
+    seen = vec[fi["conn_id"]].astype(np.int64)
+    node_of = {int(seen[i]): n for n, i in enumerate(np.sort(np.unique(seen, return_index=True)[1]))}
+    assert node_of[9999] == 0
+    add, add_ptr = [], [0]
+    for k in range(K):
+        near = TG.placement_neighbourhood(data[0], ns.freq, fi, cells[:, ptr[k]:ptr[k + 1]], thr)
+        add += [node_of[c] for c in near]
+        add_ptr.append(len(add))
+    cols = TG._column_tables(st, "lightpath", feats)[0]    # (lp_feat row, min, max - min, has_range) per sorted column
+    row = cols[:, 0].long()
+    raw = values_d[:, row.clamp(min=0)]
+    x_lut = torch.where(cols[:, 3] != 0, (raw - cols[:, 1]) / cols[:, 2], raw)
+    x_lut = torch.where(row < 0, torch.ones_like(x_lut), x_lut).float()      # the is_lut column
+    what_if = dict(x_lut=x_lut, add_src=torch.tensor(add, dtype=torch.int64, device=device),
+                   add_ptr=torch.tensor(add_ptr, dtype=torch.int64), node=torch.zeros(K, dtype=torch.int64, device=device))
+
+    ways = {"place": lambda: predict.place(st, samples, values_d, cells_d, ptr_d, feats, thr)[0],
+            "materialise": lambda: predict.from_status(infer.materialise_placement(st, samples, values_d, cells_d, ptr_d),
+                                                       None, feats, thr)[0],
+            "what_if": lambda: predict.what_if(TG.device_batch(st_b, "lightpath", feats, None, thr), **what_if)[0]}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    assert torch.equal(got["place"], got["materialise"]) and torch.equal(got["place"], got["what_if"]), K
+    assert tuple(got["place"].shape) == (K, 3) and bool(torch.isfinite(got["place"]).all())
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed_event(fn))
+    res = dict(shape=f"status {L} x {Q}", kind="lightpath_place", K=K, cells=int(cells.shape[1]), interferers=len(add),
+               lightpaths=len(node_of) - 1, S=1, P=int(st.data.shape[1]), L=L, Q=Q, C=32, F=5, freq_threshold=thr, rounds=rounds,
+               equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_place(args, device, commit):
+    rows = []
+    for K in args.place:
+        res = measure_place(K, device, args.rounds, args.warmup, num_links=args.links, per_candidate=args.cells)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| grid | K | cells | interferers | place ms (IQR) | (a) materialise_placement + from_status ms (IQR) | (b) device_batch + "
+          "what_if ms (IQR) | (a) / place | (b) / place |")
+    print("|---|---|---|---|---|---|---|---|---|")
+
+    def against(r, other):
+        a, b = r["place_ms"], r[other + "_ms"]
+        same = abs(a - b) <= max(r["place_iqr_ms"], r[other + "_iqr_ms"])
+        return "no difference" if same else f"{b / a:.2f}x"
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['L']} x {r['Q']} | {r['K']} | {r['cells']} | {r['interferers']} | {cell('place')} | {cell('materialise')} | {cell('what_if')} | "
+              f"{against(r, 'materialise')} | {against(r, 'what_if')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -690,7 +817,22 @@ def main():
     ap.add_argument("--from-status", action="store_true", dest="from_status",
                     help="predict.from_status(status) against device_batch + per_graph (--kind lightpath) or device_batch + "
                          "predict (--kind topological)")
+    ap.add_argument("--place", type=int, nargs="+", default=None, metavar="K",
+                    help="--kind lightpath: predict.place on K candidates of one status sample against materialise_placement + "
+                         "from_status and device_batch + what_if with the interferers precomputed")
+    ap.add_argument("--links", type=int, default=60, metavar="L",
+                    help="with --place: the links of the sample's grid (the scan of a sample is O(L Q): 6 against 60 tells "
+                         "what the scan costs)")
+    ap.add_argument("--cells", type=int, default=None, metavar="N",
+                    help="with --place: N links per candidate instead of 1 - 6 (the walk is O(cells Q))")
     args = ap.parse_args()
+    if args.place is None and (args.links != 60 or args.cells is not None):
+        raise SystemExit("--links and --cells go with --place")
+    if args.links < 6 or (args.cells is not None and not 1 <= args.cells <= args.links):
+        raise SystemExit("--links L (>= 6, what synthetic_network_status routes over) and --cells N (1 ... L)")
+    if args.place is not None and (args.kind != "lightpath" or args.from_status or args.mc is not None or args.grad
+                                   or args.what_if is not None or any(k < 1 for k in args.place)):
+        raise SystemExit("--kind lightpath --place K [K ...] (K >= 1) is a run of its own")
     if args.from_status and (args.mc is not None or args.grad or args.what_if is not None):
         raise SystemExit("--from-status is a run of its own")
     if args.what_if is not None and (args.mc is not None or args.grad or any(k < 1 for k in args.what_if)):
@@ -705,6 +847,8 @@ def main():
         raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    if args.place is not None:
+        return main_place(args, device, commit)
     if args.from_status:
         return main_from_status(args, device, commit)
     if args.kind == "lightpath" and args.what_if is not None:
