@@ -182,6 +182,8 @@ SIGNATURES = {
     "qot_topological_infer_whatif": (_int, _INFER_COMMON + [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _int, _p]),
     "qot_topological_infer_status": (_int, _INFER_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _p, _int,
                                                             _p]),
+    "qot_topological_infer_place": (_int, _INFER_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _p, _int,
+                                                           _p, _p, _p, _i64, _p]),
     "qot_lightpath_infer": (_int, _LP_COMMON + [_p]),
     "qot_lightpath_infer_grad": (_int, _LP_COMMON + [_p, _int, _p, _p, _p, _p, _p]),
     "qot_lightpath_infer_whatif": (_int, _LP_COMMON + [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p]),

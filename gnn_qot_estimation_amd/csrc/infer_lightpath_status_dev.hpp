@@ -21,14 +21,10 @@ struct LpStatusArgs {
     int64_t* count;
 };
 
-// whether channel c is occupied, and by which conn (bad conn values: the sample has been refused before this is asked)
+// who occupies channel c: the rule is status_scan_dev.hpp's, shared with infer_topological_place.hip; the lightpath
+// kernels keep calling it by this name
 __device__ __forceinline__ bool channel_conn(const double* __restrict__ d, int P, int LQ, int conn_row, int c, int64_t& conn) {
-    const double cv = d[(int64_t)conn_row * LQ + c];
-    if (cv != 0.0) return sg::sg_conn(cv, conn);
-    bool occ = false;
-    for (int p = 0; p < P; ++p) occ |= (d[(int64_t)p * LQ + c] != 0.0);
-    conn = 0;
-    return occ;
+    return sg::channel_conn(d, P, LQ, conn_row, c, conn);
 }
 
 // One wave, one channel (l, q1) of lightpath conn_a: its lanes walk the Q slots of link l, test 0 < |freq[q1] - freq[q2]| <

@@ -16,7 +16,8 @@
 //   3  infer_phases12<H, D, InferStatusEdges> over nodes 0 .. 74 (node_ids: the caller's arange(75)) and the m links --
 //      the source reads a link's ends from its word and column k of its features as scaled(d[r_k, first[lightpath]]) --
 //      then infer_phases34 into out[g].
-// The LDS image is infer_lds(75, 512, H, D) as dynamic LDS; the table, the matrix and the link words are static beside it
+// Steps 2 and 3, the edge source and the entry's envelope are infer_topological_status_dev.hpp's, shared with
+// infer_topological_place.hip.  The LDS image is infer_lds(75, 512, H, D) as dynamic LDS; the table, the matrix and the link words are static beside it
 // (kTopoStatusStatic bytes, which the entry point adds when it checks the budget).  No workspace, no global scratch.
 // Nothing read from data is used as an index before it is checked: a conn is only compared, the end nodes pass the
 // 1 .. 75 test first, the channel numbers come from the loop counters.  All global writes are ordinary vector stores
@@ -25,55 +26,9 @@
 // On the device: a conn_id that is not finite or beyond +-2^53 (QOT_TOPO_STATUS_BAD_CONN), more than 256 lightpaths
 // (QOT_TOPO_STATUS_TOO_MANY), a sample number outside [0, S) (QOT_TOPO_STATUS_BAD_SAMPLE), a src_id / dst_id that is no
 // integer in 1 .. 75 (QOT_TOPO_STATUS_BAD_ENDPOINT): the sample's row is NaN, its link count 0.
-#include "infer_dev.hpp"
-#include "status_scan_dev.hpp"
+#include "infer_topological_status_dev.hpp"
 
 namespace qot {
-
-constexpr int kTopoStatusLinks = 2 * sg::kCap;        // 512: the image's edge cap, a constant of this kernel
-// the static LDS beside the image: table, matrix, end nodes, scan parts, link words, the flag word
-constexpr size_t kTopoStatusStatic = sizeof(sg::Table) + (size_t)((sg::kCells * 2 + 15) / 16 * 16) + 2 * sg::kCap +
-                                     (sg::kWaves + 1) * 4 + (size_t)kTopoStatusLinks * 4 + 16;
-
-struct TopoStatusArgs {
-    const double* data; const int64_t* samples;
-    int64_t S;
-    int P, L, Q;
-    int conn_row, src_row, dst_row;
-    const double* cols;                 // [D, 4]: lp_feat row, min, max - min, has_range
-    int64_t* links;
-};
-
-// the links of one sample as an edge source: see InferBaseEdges (infer_dev.hpp) for what a source states
-struct InferStatusEdges {
-    const uint32_t* rec;                // LDS: source << 24 | target << 16 | lightpath, canonical order
-    const int32_t* first;               // LDS: the first channel of every lightpath
-    const double* d;                    // the sample [P, LQ]
-    const double* cols;
-    int P, LQ;
-
-    __device__ __forceinline__ float attr(const InferArgs&, int64_t, int c, int D) const {
-        const int e = c / D;
-        const double* col = cols + 4 * (c - e * D);
-        const int r = (int)col[0];
-        return (r >= 0 && r < P) ? sg::scaled(d[(int64_t)r * LQ + first[rec[e] & 0xFFFFu]], col) : 0.0f;
-    }
-    __device__ __forceinline__ bool skips(int) const { return false; }
-    __device__ __forceinline__ bool ends_of(const InferArgs&, int64_t, int64_t, int, int e, int& j, int& i) const {
-        const uint32_t w = rec[e];
-        j = (int)(w >> 24);
-        i = (int)((w >> 16) & 0xFFu);
-        return true;
-    }
-    __device__ __forceinline__ int slots(int m, const int*, int) const { return m; }
-};
-
-__device__ __forceinline__ int topo_status_bits(int sg_bits) {
-    return ((sg_bits & QOT_SG_BAD_CONN) ? QOT_TOPO_STATUS_BAD_CONN : 0) |
-           ((sg_bits & QOT_SG_TOO_MANY) ? QOT_TOPO_STATUS_TOO_MANY : 0) |
-           ((sg_bits & QOT_SG_BAD_SAMPLE) ? QOT_TOPO_STATUS_BAD_SAMPLE : 0) |
-           ((sg_bits & QOT_SG_BAD_ENDPOINT) ? QOT_TOPO_STATUS_BAD_ENDPOINT : 0);
-}
 
 template <int H, int D>
 __global__ __launch_bounds__(kInferThreads) void topological_infer_status_kernel(const InferArgs a, const TopoStatusArgs st) {
@@ -112,34 +67,8 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_status_kernel
         return;
     }
 
-    // ---- step 2: the directed links in canonical order ----
-    int k0, k1;
-    const int cnt = sg::topo_run(mat, k0, k1);
-    int m;
-    int e = sg::block_exscan(cnt, part, m);
-    if (m > kTopoStatusLinks) {                                    // (256 lightpaths win 256 pairs at most: never; uniform)
-        if (tid == 0) st.links[g] = 0;
-        infer_refuse(a, 2, orow);
-        return;
-    }
-    for (int k = k0; k < k1; ++k) {
-        const int i = mat[k];
-        if (i < 0) continue;
-        rec[e++] = ((uint32_t)(k / sg::kTopo) << 24) | ((uint32_t)(k % sg::kTopo) << 16) | (uint32_t)i;
-    }
-    __syncthreads();
-
-    // ---- step 3: the forward over nodes 0 .. 74 and the m links ----
-    const InferStatusEdges src{rec, T.first, d, st.cols, st.P, LQ};
-    bad = infer_phases12<H, D, InferStatusEdges>(a, lds, infer_lds(a.cap_n, a.cap_m, H, D), 0, 0, sg::kTopo, m, src);
-    if (bad) {
-        if (tid == 0) st.links[g] = 0;
-        infer_refuse(a, bad, orow);
-        return;
-    }
-    if (tid == 0) st.links[g] = m;
-    const InferLds L = infer_lds(a.cap_n, a.cap_m, H, D);           // (restated, as in infer.hip)
-    infer_phases34<H, D, false>(a, lds, L, sg::kTopo, lds + L.x1, orow, InferDrop{});
+    // ---- steps 2 and 3: the directed links in canonical order, the forward over nodes 0 .. 74 and the links ----
+    topo_status_forward<H, D>(a, lds, mat, part, rec, InferStatusEdges{rec, T.first, d, st.cols, st.P, LQ}, orow, st.links + g);
 }
 
 }  // namespace qot
@@ -155,19 +84,10 @@ extern "C" int qot_topological_infer_status(const int64_t* node_ids, const int64
                                             int H, int D, int O, int32_t* status, int64_t* links, const double* data,
                                             const int64_t* samples, int64_t S, int rows_p, int64_t L, int64_t Q, int conn_row,
                                             int src_row, int dst_row, const double* cols, int ncol, qot_stream_t stream_) {
-    if (!infer_sizes_ok(N, E, G, n_max, max_e, V)) return QOT_ERR_BADARG;
-    // there is no graph: the batch arguments of the common prefix must be empty, the nodes the 75 of the topology
-    if (edge_index || edge_attr || node_ptr || edge_ptr || E != 0 || N != sg::kTopo || n_max != sg::kTopo ||
-        max_e != kTopoStatusLinks)
-        return QOT_ERR_BADARG;
-    if (S < 0 || rows_p < 1 || L < 1 || Q < 1) return QOT_ERR_BADARG;
-    const size_t image = infer_lds_bytes(kInferEval, n_max, max_e, H, D);
-    if (!infer_supported(kInferEval, n_max, max_e, H, D, O) || image + kTopoStatusStatic > kInferLdsMax)
-        return QOT_ERR_UNSUPPORTED;
-    if (Q > QOT_SG_MAX_FREQS || L * Q >= (int64_t)1 << 31 || G >= (int64_t)1 << 31) return QOT_ERR_UNSUPPORTED;
-    if (ncol != D) return QOT_ERR_BADARG;
-    if (conn_row < 0 || conn_row >= rows_p || src_row < 0 || src_row >= rows_p || dst_row < 0 || dst_row >= rows_p)
-        return QOT_ERR_BADARG;
+    size_t image;
+    const int rc = topo_status_envelope(edge_index, edge_attr, node_ptr, edge_ptr, N, E, G, n_max, max_e, V, H, D, O, S, rows_p,
+                                        L, Q, conn_row, src_row, dst_row, ncol, image);
+    if (rc != QOT_OK) return rc;
     if (G == 0) return QOT_OK;
     if (ld4 < 4 * H || (ld4 & 3) || ldm < V) return QOT_ERR_BADARG;
     if (!node_ids || !t4 || !M || !P || !w_edge || !w1 || !b1 || !wcat || !bias2 || !w0 || !b0 || !w3 || !b3 || !out || !links ||

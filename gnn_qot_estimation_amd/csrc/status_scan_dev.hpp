@@ -1,8 +1,9 @@
 // The scan of one network-status sample data[P, L, Q] (fp64) by one 256-thread workgroup, shared by the graph builder
 // (status_graph.hip) and the status-to-row kernels (infer_lightpath_status.hip, DESIGN.md 4.20;
-// infer_topological_status.hip; infer_lightpath_place.hip): all run discover(), so the lightpaths of a sample, their numbering and
+// infer_topological_status.hip; infer_lightpath_place.hip; infer_topological_place.hip,
+// DESIGN.md 4.23): all run discover(), so the lightpaths of a sample, their numbering and
 // their first channels are the same table in all.  Stated once here: the workgroup's geometry and caps, the first-seen
-// table and its insert, the sample pick, the occupancy / conn rule of one channel (sg_conn), the fp64 column scaling
+// table and its insert, the sample pick, the occupancy / conn rule of one channel (sg_conn, channel_conn), the fp64 column scaling
 // (scaled) and, for the topological representation, the block scan, the pair contest that fills the 75 x 75 winner
 // matrix (topo_winners) and the row-major run of cells a thread walks (topo_run).
 //
@@ -45,6 +46,16 @@ __device__ __forceinline__ bool sg_conn(double cv, int64_t& conn) {
     if (!(fabs(cv) <= 9007199254740992.0)) return false;
     conn = (int64_t)cv;
     return true;
+}
+
+// whether channel c is occupied, and by which conn (bad conn values: the sample has been refused before this is asked)
+__device__ __forceinline__ bool channel_conn(const double* __restrict__ d, int P, int LQ, int conn_row, int c, int64_t& conn) {
+    const double cv = d[(int64_t)conn_row * LQ + c];
+    if (cv != 0.0) return sg_conn(cv, conn);
+    bool occ = false;
+    for (int p = 0; p < P; ++p) occ |= (d[(int64_t)p * LQ + c] != 0.0);
+    conn = 0;
+    return occ;
 }
 
 // The lightpaths of one sample in first-seen order.  chan (optional): lightpath number of every channel, -1 when the
@@ -193,15 +204,22 @@ __device__ __forceinline__ int block_exscan(int v, int* part, int& total) {
 // conn wins, and its number goes to mat[u][v] and mat[v][u] (a self loop: the one cell).  mat [kCells] holds -1 everywhere
 // on entry; eu / ev [kCap] are scratch.  Nothing read from data is used as an index before the 1 .. 75 test.  Returns
 // QOT_SG_BAD_ENDPOINT or 0 (per thread); ends with a barrier, behind which mat is complete.
+// cand (optional): the raw lp_feat vector of one more lightpath that the sample does not hold (TopologicalPredictor.place's
+// candidate, infer_topological_place.hip).  It joins the contest as lightpath n: the caller has n < kCap and its conn,
+// distinct from the sample's, in T.conn[n]; thread n takes its end nodes from cand under the same test.
 __device__ __forceinline__ int topo_winners(const double* __restrict__ d, int LQ, int src_row, int dst_row, const Table& T,
-                                            int n, int16_t* mat, uint8_t* eu, uint8_t* ev) {
+                                            int n, int16_t* mat, uint8_t* eu, uint8_t* ev,
+                                            const double* __restrict__ cand = nullptr) {
     const int tid = threadIdx.x;
     int bad = 0;
+    const bool is_cand = cand != nullptr && tid == n;
+    if (cand) ++n;
     // end nodes of lightpath tid (255 = not usable)
     int u = 255, v = 255;
     if (tid < n) {
-        const int c = T.first[tid];
-        const double sv = d[(int64_t)src_row * LQ + c], dv = d[(int64_t)dst_row * LQ + c];
+        const int c = is_cand ? 0 : T.first[tid];
+        const double sv = is_cand ? cand[src_row] : d[(int64_t)src_row * LQ + c];
+        const double dv = is_cand ? cand[dst_row] : d[(int64_t)dst_row * LQ + c];
         // written so that a NaN fails the test
         const bool good = sv >= 1.0 && sv <= (double)kTopo && dv >= 1.0 && dv <= (double)kTopo && sv == trunc(sv) && dv == trunc(dv);
         if (good) {

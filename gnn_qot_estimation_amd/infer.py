@@ -1,7 +1,8 @@
 """Single-launch inference: ``TopologicalPredictor`` (``csrc/infer.hip``; its Monte-Carlo dropout
 ``sample``: ``csrc/infer_mc.hip``; its per-link ``sensitivity``: ``csrc/infer_grad.hip``, DESIGN.md
 4.16; its ``what_if`` over edited graphs: ``csrc/infer_whatif.hip``; its ``from_status`` over network-status
-samples: ``csrc/infer_topological_status.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
+samples: ``csrc/infer_topological_status.hip``; its ``place`` of candidate lightpaths into such samples:
+``csrc/infer_topological_place.hip``) and ``LightpathPredictor`` (``csrc/infer_lightpath.hip``; its per-neighbour ``sensitivity``:
 ``csrc/infer_lightpath_grad.hip``; its ``what_if`` over candidate lightpaths:
 ``csrc/infer_lightpath_whatif.hip``; its ``from_status`` over network-status samples:
 ``csrc/infer_lightpath_status.hip``; its ``place`` of candidate lightpaths into such samples:
@@ -375,6 +376,36 @@ def topological_status_args(status, edge_dim, features_to_consider=to_graph.DEFA
     return _TopoStatus(feats, S, P, L, Q, fi["conn_id"], fi["src_id"], fi["dst_id"])
 
 
+# include/qot_gnn.h: QOT_TOPO_PLACE_*, the status bits qot_topological_infer_place adds beside QOT_TOPO_STATUS_*
+TOPO_PLACE_BAD_CELL, TOPO_PLACE_OCCUPIED, TOPO_PLACE_CONN_TAKEN = 128, 256, 512
+_TOPO_PLACE_CAUSES = (
+    (TOPO_PLACE_BAD_CELL, "place: a link or frequency index outside the sample, or a cell_ptr slice that is empty, descending "
+                          "or beyond the cells"),
+    (TOPO_PLACE_OCCUPIED, "place: a cell whose channel is occupied in the sample"),
+    (TOPO_PLACE_CONN_TAKEN, "place: a candidate's conn_id is a lightpath of the sample already"),
+)
+
+# samples / cell_ptr: int64 tensors, on the host checked (cell_ptr) and to be uploaded, or on the device and used in place
+_TopoPlace = namedtuple("_TopoPlace", "status K M samples cell_ptr")
+
+
+def topological_place_args(status, edge_dim, samples, values, cells, cell_ptr,
+                           features_to_consider=to_graph.DEFAULT_FEATURES, num_embeddings=None, model_device=None,
+                           who="TopologicalPredictor.place"):
+    """The argument checks of ``TopologicalPredictor.place`` that need no device: returns a ``_TopoPlace`` (``status``:
+    the ``_TopoStatus`` of ``topological_status_args``; ``K``, ``M``; ``samples`` and ``cell_ptr`` as 1-d int64 tensors) or
+    raises -- ``TypeError`` for a ``status`` that is no ``DeviceStatus``; ``ValueError`` naming the argument for ``values``
+    not float64 ``[K, P]``, ``cells`` not int64 ``[2, M]``, either on another device than the chunk, ``samples`` or
+    ``cell_ptr`` of the wrong length or dtype, a host ``cell_ptr`` that is not non-decreasing from 0 to ``M`` or has an
+    empty slice (one on the device is checked by the kernel); then everything ``topological_status_args`` refuses, a
+    chunk on the CPU last."""
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    K, M, samples, cell_ptr = _place_lists(status, samples, values, cells, cell_ptr, who)
+    sa = topological_status_args(status, edge_dim, features_to_consider, None, num_embeddings, model_device, who)
+    return _TopoPlace(sa, K, M, samples, cell_ptr)
+
+
 class _DeviceState:
     """What both predictors keep on the device beside the model: the status word their kernels flag a batch in and the
     ``outputs`` selections of ``sensitivity``.  ``_FLAGS`` of a predictor: its kernel's name, the meaning of the status bits."""
@@ -434,17 +465,22 @@ class TopologicalPredictor(_DeviceState):
     ``predictor.what_if(data, ...)``: K small edits of the batch's graphs (edges added / removed), scored in one launch.
     ``predictor.from_status(status)``: ``__call__``'s rows straight from network-status samples, no graph in between, one
     launch and no host read (see there).
+    ``predictor.place(status, samples, values, cells, cell_ptr)``: K candidate lightpaths, each placed into a status sample
+    that does not hold it yet, scored in one launch without the edited samples (see there).
     """
 
     _FLAGS = ("qot_topological_infer", "bit 0 an edge leaves its graph's node range, bit 1 slices outside the arrays, "
                                        "bit 2 a node id outside the table (what_if: bit 0 also an added edge, bit 1 also a "
                                        "graph number or a drop position out of range; from_status: bit 3 a bad conn_id, "
                                        "bit 4 too many lightpaths, bit 5 a sample number out of range, bit 6 a bad "
-                                       "src_id / dst_id)")
+                                       "src_id / dst_id; place: those, the candidate's values included, bit 7 a bad cell or "
+                                       "cell_ptr slice, bit 8 an occupied cell, bit 9 a conn_id of the sample)")
     # the bits of qot_topological_infer_status, named when check_status() finds them: the device builder's own words
     _CAUSES = tuple((bit, next(t for b, t in to_graph._SG_CAUSES if b == sg)) for bit, sg in (
         (TOPO_STATUS_BAD_CONN, to_graph.SG_BAD_CONN), (TOPO_STATUS_TOO_MANY, to_graph.SG_TOO_MANY),
         (TOPO_STATUS_BAD_SAMPLE, to_graph.SG_BAD_SAMPLE), (TOPO_STATUS_BAD_ENDPOINT, to_graph.SG_BAD_ENDPOINT)))
+    # ... and the bits qot_topological_infer_place adds, named by check_status() behind them
+    _PLACE_CAUSES = _TOPO_PLACE_CAUSES
 
     def __init__(self, model):
         super().__init__()
@@ -772,6 +808,14 @@ class TopologicalPredictor(_DeviceState):
         links = torch.empty(G, dtype=torch.int64, device=dev)
         if G == 0:
             return out, links
+        self._launch_status("qot_topological_infer_status", status, sa, (H, D, O), out, links, picks)
+        return out, links
+
+    def _launch_status(self, name, status, sa, shape, out, links, picks, *extra):
+        """One launch of a status entry point (``from_status``, ``place``): the 75 nodes of the topology in place of a
+        batch, ``out.shape[0]`` rows, the sample arguments of ``sa``, then ``extra``."""
+        H, D, O = shape
+        dev = out.device
         if self._topology is None or self._topology[0] != dev:
             self._topology = (dev, torch.arange(to_graph.NUM_TOPOLOGY_NODES, dtype=torch.int64, device=dev),
                               torch.empty(2, 0, dtype=torch.int64, device=dev))
@@ -779,9 +823,60 @@ class TopologicalPredictor(_DeviceState):
         t = self._refresh(H, D)
         self._status_on(dev)
         cols, _, ncol = to_graph._column_tables(status, "topological", sa.features)
-        p = _Prepared(H, D, O, dev, ids, no_edges, None, None, None, to_graph.NUM_TOPOLOGY_NODES, TOPO_STATUS_MAX_LINKS, G, t)
-        self._launch("qot_topological_infer_status", p, out, links, status.data, picks, sa.S, sa.P, sa.L, sa.Q, sa.conn_row,
-                     sa.src_row, sa.dst_row, cols, ncol)
+        p = _Prepared(H, D, O, dev, ids, no_edges, None, None, None, to_graph.NUM_TOPOLOGY_NODES, TOPO_STATUS_MAX_LINKS,
+                      int(out.shape[0]), t)
+        self._launch(name, p, out, links, status.data, picks, sa.S, sa.P, sa.L, sa.Q, sa.conn_row, sa.src_row, sa.dst_row,
+                     cols, ncol, *extra)
+
+    @torch.no_grad()
+    def place(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES):
+        """Routing and spectrum assignment with the topological model: scores K candidate assignments of a NEW lightpath
+        against the status samples of the established ones, ``(out [K, O] float32, links [K] int64)`` in ONE kernel
+        launch (``csrc/infer_topological_place.hip``), without the edited samples or their graphs, with nothing read
+        back, legal inside ``torch.cuda.graph`` capture.
+
+        ``status``, ``samples``, ``values [K, P]`` float64, ``cells [2, M]`` int64 and ``cell_ptr`` have the meaning and
+        the accepted forms they have in ``LightpathPredictor.place``: candidate ``k`` is the raw ``lp_feat`` vector
+        ``values[k]`` (``conn_id``, ``src_id``, ``dst_id``, the features, in status units) written into the channels
+        ``cells[:, cell_ptr[k]:cell_ptr[k + 1]]`` of sample ``samples[k]``; ``status.data`` is never written.  There is no
+        ``freq_threshold`` (the topological graph has no interference rule) and ``osnr`` / ``snr`` / ``ber`` are not read.
+
+        ``materialise_placement`` is the definition: with ``edited`` its K samples, ``out`` is
+        ``self.from_status(edited, features_to_consider=...)[0]`` bit for bit and ``links`` that call's ``links`` -- hence
+        both equal ``self(to_graph.device_batch(edited, "topological", ...))`` as well.  The candidate joins the pair
+        contest: when its ``trunc(conn_id)`` is larger than the conn of every lightpath of the sample on the same
+        unordered node pair, or the pair is new (``links`` grows by 2, by 1 for a self loop), the pair's links carry the
+        candidate's scaled features; otherwise the edited graph is the unedited one and the row is
+        ``self.from_status(status, samples)[0][k]``.  The cells do not enter the graph: they decide only whether the
+        placement is legal.  ``to_graph.placement_links`` states the links and the outcome on the host.  A candidate's
+        row depends on its sample and itself alone; every candidate rescans its sample, O(L Q + cells): candidates of
+        one sample do not share the scan.
+
+        Refusals before any launch (``topological_place_args``): ``TypeError`` for a ``status`` that is no
+        ``DeviceStatus``; ``ValueError`` for ``values`` not float64 ``[K, P]``, ``cells`` not int64 ``[2, M]``, ``samples``
+        or ``cell_ptr`` of the wrong length or dtype, a host ``cell_ptr`` that is not non-decreasing from 0 to M or has an
+        empty slice, then everything ``from_status`` refuses.  ``K == 0`` gives empty tensors without a launch.  On the
+        device, since nothing is read back: a cell outside the sample or a bad ``cell_ptr`` slice, an occupied cell, a
+        ``conn_id`` the sample holds already, a ``conn_id`` that is not finite or beyond +-2^53, a ``src_id`` / ``dst_id``
+        that is no integer in 1 ... 75 (an all-zero ``values`` row falls here), a sample that holds 256 lightpaths
+        already, a sample number outside the chunk -- that candidate's row is NaN and its ``links`` 0, the other rows are
+        untouched, and ``check_status()`` raises naming the cause.  (The column table of a feature list, ``arange(75)``
+        and the parameter tables are uploaded by the first call with a chunk: make that call before capturing.)"""
+        who = "TopologicalPredictor.place"
+        H, D, O = self._check_model()
+        emb = self.model.node_embeddings.weight
+        dev = emb.device
+        pa = topological_place_args(status, D, samples, values, cells, cell_ptr, features_to_consider, emb.shape[0], dev, who)
+        out = torch.empty(pa.K, O, dtype=torch.float32, device=dev)
+        links = torch.empty(pa.K, dtype=torch.int64, device=dev)
+        if pa.K == 0:
+            return out, links
+        picks, ptr = pa.samples, pa.cell_ptr
+        if not picks.is_cuda and not ptr.is_cuda:           # both lists are on the host: one upload for the two
+            both = torch.cat([picks, ptr]).to(dev)
+            picks, ptr = both[:pa.K], both[pa.K:]
+        self._launch_status("qot_topological_infer_place", status, pa.status, (H, D, O), out, links, _i64(picks, dev),
+                            values.contiguous(), cells.contiguous(), _i64(ptr, dev), pa.M)
         return out, links
 
 
@@ -1069,13 +1164,16 @@ def lightpath_place_args(status, in_channels, is_lut_index, samples, values, cel
 
 
 def materialise_placement(status, samples, values, cells, cell_ptr):
-    """The K edited samples that ``LightpathPredictor.place`` scores without building them: the DEFINITION of that call
-    and what it saves.  Returns a ``DeviceStatus`` of K samples; sample ``k`` is ``status.data[samples[k]]`` with
-    ``values[k]`` written into each of the channels ``cells[:, cell_ptr[k]:cell_ptr[k + 1]]`` (``target`` rows follow their
-    samples).  ``predict.place(...)[0][k]`` is, bit for bit, the row ``predict(to_graph.device_batch(edited, "lightpath",
-    ...))`` gives the candidate's node of graph ``k``, and -- the candidate being the first-seen flagged lightpath of its
-    edited sample -- ``predict.from_status(edited)[0][k]``.  Pure torch on the status' device (CPU tensors as well), no
-    kernel of ours; ``status`` is not modified.  Arguments as ``place``; occupied cells are overwritten, not refused."""
+    """The K edited samples that ``LightpathPredictor.place`` and ``TopologicalPredictor.place`` score without building
+    them: the DEFINITION of both calls and what they save.  Returns a ``DeviceStatus`` of K samples; sample ``k`` is
+    ``status.data[samples[k]]`` with ``values[k]`` written into each of the channels ``cells[:, cell_ptr[k]:cell_ptr[k +
+    1]]`` (``target`` rows follow their samples).  For a ``LightpathPredictor``, ``predict.place(...)[0][k]`` is, bit for
+    bit, the row ``predict(to_graph.device_batch(edited, "lightpath", ...))`` gives the candidate's node of graph ``k``,
+    and -- the candidate being the first-seen flagged lightpath of its edited sample --
+    ``predict.from_status(edited)[0][k]``.  For a ``TopologicalPredictor``, ``predict.place(...)`` is
+    ``predict.from_status(edited)``, rows and link counts, bit for bit.  Pure torch on the status' device (CPU tensors as
+    well), no kernel of ours; ``status`` is not modified.  Arguments as ``place``; occupied cells are overwritten, not
+    refused."""
     who = "materialise_placement"
     if not isinstance(status, to_graph.DeviceStatus):
         raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")

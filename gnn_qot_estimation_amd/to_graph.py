@@ -341,6 +341,27 @@ def topological_links(sample: np.ndarray, feature_indexes: Dict[str, int]):
     return np.ascontiguousarray(arr[:, :2].T), np.ascontiguousarray(arr[:, 2])
 
 
+def placement_links(sample: np.ndarray, values_row: np.ndarray, cells, feature_indexes: Dict[str, int]):
+    """One candidate of ``TopologicalPredictor.place``, stated on the host: ``(edge_index [2, m] int64, conn [m] int64,
+    outcome)``.  ``edge_index`` and ``conn`` are ``topological_links`` of the edited sample, ``place_lightpath(sample,
+    values_row, cells, feature_indexes)[0]`` (its ``ValueError`` for an illegal placement as there).  ``outcome`` says what
+    the candidate did to the graph of the unedited sample: ``"new pair"`` -- no lightpath of the sample joins its unordered
+    node pair, the graph grows by two links (one for a self loop); ``"takes the pair"`` -- its ``trunc(conn_id)`` is larger
+    than that of every lightpath of the sample on the pair, whose links now carry the candidate's features; ``"loses the
+    pair"`` -- it is not, and the edited graph is the unedited one.  The cells decide only whether the placement is legal."""
+    fi = feature_indexes
+    edited, _ = place_lightpath(sample, values_row, cells, fi)
+    edge_index, conn = topological_links(edited, fi)
+    values_row = np.asarray(values_row, dtype=np.float64)
+    c = int(values_row[fi["conn_id"]])
+    u, v = int(values_row[fi["src_id"]]) - 1, int(values_row[fi["dst_id"]]) - 1
+    before, _ = topological_links(sample, fi)
+    had_pair = bool(((before[0] == u) & (before[1] == v)).any())
+    if not had_pair:
+        return edge_index, conn, "new pair"
+    return edge_index, conn, "takes the pair" if (conn == c).any() else "loses the pair"
+
+
 # ------------------------------------------------------------------------------------------ store_graphs.py counterpart
 def store_graphs(dataset: Source, representation: str = "lightpath", directory: Optional[str] = None,
                  features_to_consider: Sequence[str] = DEFAULT_FEATURES, storage_type: str = "pickle",

@@ -1174,6 +1174,40 @@ int qot_topological_infer_status(const int64_t* node_ids, const int64_t* edge_in
                                  const double* data, const int64_t* samples, int64_t S, int rows, int64_t L, int64_t Q,
                                  int conn_row, int src_row, int dst_row, const double* cols, int ncol, qot_stream_t stream);
 
+/* ---- K candidate lightpaths placed into network-status samples, the TopologicalGNN row of each in one launch
+ * (TopologicalPredictor.place) -- Candidate k is the raw lp_feat vector values[k, rows] (fp64, status
+ * units) written into the channels cells[:, cell_ptr[k] : cell_ptr[k + 1]] of sample samples[k]; cells [2, n_cells] int64
+ * holds link indices, then frequency indices; cell_ptr [K + 1] int64; samples [K] int64 (required; repeats are the normal
+ * case).  Let edited_k be that sample with values[k] in each of the candidate's cells.  out[k] and links[k] are, bit for
+ * bit, what the status entry above gives for edited_k with the same cols.  edited_k is never built and data is never
+ * written: the candidate fills free channels, so the sample's lightpaths keep their first channels, and the candidate
+ * joins the pair contest as one more lightpath whose end nodes and features come from values[k] -- when its trunc(conn_id)
+ * is the largest on its unordered node pair (or the pair is new: 2 more links, 1 for a self loop) the pair's links carry
+ * its features, otherwise the row is the unedited sample's.  The cells decide only whether the placement is legal.  One
+ * 256-thread workgroup per candidate: O(L Q) for the scan plus O(cells); no cap on the cells of a candidate, duplicates
+ * allowed; no workspace.
+ *
+ * The argument list is the status entry's up to ncol (K takes G's place), then values, cells, cell_ptr, n_cells.  Return
+ * codes before any launch: the status entry's, and QOT_ERR_BADARG for n_cells < 0 or -- when K > 0 -- a NULL samples,
+ * values or cell_ptr, or NULL cells with n_cells > 0.  K == 0: QOT_OK, no launch.
+ * status, on the device since nothing is read back: the refused candidate's row is NaN and its links 0, the other rows
+ * are untouched; nothing read from data or values is used as an index before it is checked.  The bits lie beside
+ * QOT_TOPO_STATUS_*, which are reused: BAD_CONN also for a candidate conn_id that is not finite or beyond +-2^53,
+ * BAD_ENDPOINT also for a candidate src_id / dst_id that is no integer in 1 .. QOT_SG_NODES, TOO_MANY for a sample that
+ * holds QOT_SG_MAX_LIGHTPATHS lightpaths already (edited_k would hold one more), BAD_SAMPLE as there. */
+#define QOT_TOPO_PLACE_BAD_CELL 128    /* a link / frequency index outside [0, L) / [0, Q), or a cell_ptr slice that is empty, descending or beyond n_cells */
+#define QOT_TOPO_PLACE_OCCUPIED 256    /* a cell whose channel is occupied in the sample */
+#define QOT_TOPO_PLACE_CONN_TAKEN 512  /* the candidate's conn_id equals a lightpath of the sample */
+int qot_topological_infer_place(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                                const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t K, int n_max,
+                                int max_e, const float* t4, int ld4, const float* M, int ldm, const float* P, int V,
+                                const float* w_edge, const float* w1, const float* b1, const float* wcat, const float* bias2,
+                                const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
+                                float slope_head, float* out, int H, int D, int O, int32_t* status, int64_t* links,
+                                const double* data, const int64_t* samples, int64_t S, int rows, int64_t L, int64_t Q,
+                                int conn_row, int src_row, int dst_row, const double* cols, int ncol, const double* values,
+                                const int64_t* cells, const int64_t* cell_ptr, int64_t n_cells, qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

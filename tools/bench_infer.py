@@ -103,6 +103,16 @@ holds a placeholder lightpath under test on channel (0, 0), out of reach of ever
 take over.  The rows of the three ways are compared first (equal bits); output and the interquartile rule as above.
 
     python tools/bench_infer.py --kind lightpath --place 1 8 64 1024 [--out profiles/bench_infer_lightpath_place.jsonl]
+
+``--kind topological --place K [K ...]``: the same question for ``TopologicalPredictor`` (csrc/infer_topological_place.hip,
+DESIGN.md 4.23) -- ``predict.place(status, ...)`` against ``infer.materialise_placement(...)`` followed by
+``predict.from_status(edited)`` per call, at hidden widths 64 and 16 (V = 75, edge_dim 4, 3 outputs).  The same sample and
+cells as above (``--links``, ``--cells`` as there); a third of the candidates join a random node pair, a third the pair of
+a lightpath of the sample (in the reverse orientation) with a conn above every conn of the sample, a third such a pair
+with a conn below.  Rows and link counts of the two ways are compared first (equal bits); two medians count as different
+when they are further apart than the sum of their interquartile ranges.
+
+    python tools/bench_infer.py --kind topological --place 1 8 64 1024 [--out profiles/bench_infer_topological_place.jsonl]
 """
 import argparse
 import json
@@ -652,6 +662,98 @@ def main_place(args, device, commit):
               f"{against(r, 'materialise')} | {against(r, 'what_if')} |")
 
 
+def measure_topological_place(K, H, device, rounds, warmup, num_links=60, per_candidate=None):
+    import numpy as np
+    from gnn_qot_estimation_amd import infer, to_graph as TG
+    torch.manual_seed(0)
+    model = q.TopologicalGNN(75, H, 3, 4, dropout_p=0.0).to(device).eval()
+    predict = q.TopologicalPredictor(model)
+    ns = TG.synthetic_network_status(1, num_links=num_links, seed=0)      # the 60 x 72 grid by default
+    fi, feats = ns.feature_indexes, list(TG.DEFAULT_FEATURES)
+    data = ns.data
+    L, Q = data.shape[2], data.shape[3]
+    free = ~np.any(data[0] != 0, axis=0)
+    held = data[0][:, ~free]                                # the sample's lightpaths, a column per occupied channel
+    rng = np.random.default_rng(K)
+    values, cells, ptr = np.zeros((K, len(ns.lp_feat))), [], [0]
+    outcomes = {"new or random pair": 0, "takes the pair": 0, "loses the pair": 0}
+    for k in range(K):
+        want = per_candidate or int(rng.integers(1, 7))
+        while True:                                         # one slot on 1 - 6 free links
+            slot = int(rng.integers(0, Q))
+            open_links = np.flatnonzero(free[:, slot])
+            if len(open_links) >= want:
+                links = rng.choice(open_links, size=want, replace=False)
+                break
+        cells.append(np.stack([links, np.full_like(links, slot)]))
+        ptr.append(ptr[-1] + len(links))
+        v = values[k]
+        # a third each: a random node pair; the pair of a lightpath of the sample with a conn above all; with one below all
+        if k % 3 == 0:
+            v[fi["conn_id"]], (v[fi["src_id"]], v[fi["dst_id"]]) = 10000 + k, rng.integers(1, 76, size=2)
+            outcomes["new or random pair"] += 1
+        else:
+            other = held[:, int(rng.integers(0, held.shape[1]))]
+            v[fi["src_id"]], v[fi["dst_id"]] = other[fi["dst_id"]], other[fi["src_id"]]
+            v[fi["conn_id"]] = 10000 + k if k % 3 == 1 else -1 - k
+            outcomes["takes the pair" if k % 3 == 1 else "loses the pair"] += 1
+        v[fi["mod_order"]], v[fi["path_len"]] = float(rng.choice([4, 8, 16, 32, 64])), float(rng.integers(24214, 7834746))
+        v[fi["num_spans"]], v[fi["freq"]] = float(rng.integers(1, 107)), ns.freq[slot]
+        v[fi["osnr"]] = v[fi["snr"]] = v[fi["ber"]] = -1.0
+    cells = np.concatenate(cells, axis=1).astype(np.int64)
+    st = ns.to_device(device)
+    samples = torch.zeros(K, dtype=torch.int64, device=device)
+    values_d, cells_d = torch.from_numpy(values).to(device), torch.from_numpy(cells).to(device)
+    ptr_d = torch.tensor(ptr, dtype=torch.int64, device=device)
+
+    ways = {"place": lambda: predict.place(st, samples, values_d, cells_d, ptr_d, feats),
+            "materialise": lambda: predict.from_status(infer.materialise_placement(st, samples, values_d, cells_d, ptr_d),
+                                                       None, feats)}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    assert torch.equal(got["place"][0], got["materialise"][0]) and torch.equal(got["place"][1], got["materialise"][1]), K
+    assert tuple(got["place"][0].shape) == (K, 3) and bool(torch.isfinite(got["place"][0]).all())
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    times = {k: [] for k in ways}
+    for _ in range(rounds):
+        for k, fn in ways.items():
+            times[k].append(timed_event(fn))
+    res = dict(shape=f"status {L} x {Q}", kind="topological_place", K=K, H=H, D=4, V=75, cells=int(cells.shape[1]),
+               candidates=outcomes, S=1, P=int(st.data.shape[1]), L=L, Q=Q, rounds=rounds, equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_topological_place(args, device, commit):
+    rows = []
+    for H in STATUS_WIDTHS:
+        for K in args.place:
+            res = measure_topological_place(K, H, device, args.rounds, args.warmup, num_links=args.links, per_candidate=args.cells)
+            res["commit"] = commit or None
+            res["device"] = torch.cuda.get_device_name(0)
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| H | grid | K | cells | place ms (IQR) | materialise_placement + from_status ms (IQR) | materialise / place |")
+    print("|---|---|---|---|---|---|---|")
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        a, b = r["place_ms"], r["materialise_ms"]
+        same = abs(a - b) <= r["place_iqr_ms"] + r["materialise_iqr_ms"]    # differ: by more than the sum of the IQRs
+        print(f"| {r['H']} | {r['L']} x {r['Q']} | {r['K']} | {r['cells']} | {cell('place')} | {cell('materialise')} | "
+              f"{'no difference' if same else f'{b / a:.2f}x'} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -818,8 +920,8 @@ def main():
                     help="predict.from_status(status) against device_batch + per_graph (--kind lightpath) or device_batch + "
                          "predict (--kind topological)")
     ap.add_argument("--place", type=int, nargs="+", default=None, metavar="K",
-                    help="--kind lightpath: predict.place on K candidates of one status sample against materialise_placement + "
-                         "from_status and device_batch + what_if with the interferers precomputed")
+                    help="predict.place on K candidates of one status sample against materialise_placement + from_status "
+                         "(--kind lightpath: and against device_batch + what_if with the interferers precomputed)")
     ap.add_argument("--links", type=int, default=60, metavar="L",
                     help="with --place: the links of the sample's grid (the scan of a sample is O(L Q): 6 against 60 tells "
                          "what the scan costs)")
@@ -830,9 +932,9 @@ def main():
         raise SystemExit("--links and --cells go with --place")
     if args.links < 6 or (args.cells is not None and not 1 <= args.cells <= args.links):
         raise SystemExit("--links L (>= 6, what synthetic_network_status routes over) and --cells N (1 ... L)")
-    if args.place is not None and (args.kind != "lightpath" or args.from_status or args.mc is not None or args.grad
-                                   or args.what_if is not None or any(k < 1 for k in args.place)):
-        raise SystemExit("--kind lightpath --place K [K ...] (K >= 1) is a run of its own")
+    if args.place is not None and (args.from_status or args.mc is not None or args.grad or args.what_if is not None
+                                   or any(k < 1 for k in args.place)):
+        raise SystemExit("--place K [K ...] (K >= 1) is a run of its own")
     if args.from_status and (args.mc is not None or args.grad or args.what_if is not None):
         raise SystemExit("--from-status is a run of its own")
     if args.what_if is not None and (args.mc is not None or args.grad or any(k < 1 for k in args.what_if)):
@@ -848,7 +950,7 @@ def main():
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     if args.place is not None:
-        return main_place(args, device, commit)
+        return (main_place if args.kind == "lightpath" else main_topological_place)(args, device, commit)
     if args.from_status:
         return main_from_status(args, device, commit)
     if args.kind == "lightpath" and args.what_if is not None:
