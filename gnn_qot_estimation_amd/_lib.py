@@ -191,6 +191,10 @@ SIGNATURES = {
                                                        C.c_double, _p]),
     "qot_lightpath_infer_place": (_int, _LP_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _int, _p, _int,
                                                       C.c_double, _p, _p, _p, _i64, _p]),
+    "qot_topological_infer_place_release": (_int, _INFER_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _p,
+                                                                   _int, _p, _p, _p, _i64, _p, _p, _i64, _p]),
+    "qot_lightpath_infer_place_release": (_int, _LP_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _int, _p,
+                                                              _int, C.c_double, _p, _p, _p, _i64, _p, _p, _i64, _p]),
     "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "qot_status_graph_count": (_int, [_p, _p, _p, _i64, _i64, _int, _i64, _i64, _int, _int, _int, C.c_double, _int, _p, _sz, _p,
                                       _p]),

@@ -1,8 +1,8 @@
 // The scan of one network-status sample data[P, L, Q] (fp64) by one 256-thread workgroup, shared by the graph builder
 // (status_graph.hip) and the status-to-row kernels (infer_lightpath_status.hip, DESIGN.md 4.20;
 // infer_topological_status.hip; infer_lightpath_place.hip; infer_topological_place.hip,
-// DESIGN.md 4.23): all run discover(), so the lightpaths of a sample, their numbering and
-// their first channels are the same table in all.  Stated once here: the workgroup's geometry and caps, the first-seen
+// DESIGN.md 4.23; the two *_place_release.hip files): all run discover(), so the lightpaths of a sample,
+// their numbering and their first channels are the same table in all.  Stated once here: the workgroup's geometry and caps, the first-seen
 // table and its insert, the sample pick, the occupancy / conn rule of one channel (sg_conn, channel_conn), the fp64 column scaling
 // (scaled) and, for the topological representation, the block scan, the pair contest that fills the 75 x 75 winner
 // matrix (topo_winners) and the row-major run of cells a thread walks (topo_run).
@@ -207,16 +207,21 @@ __device__ __forceinline__ int block_exscan(int v, int* part, int& total) {
 // cand (optional): the raw lp_feat vector of one more lightpath that the sample does not hold (TopologicalPredictor.place's
 // candidate, infer_topological_place.hip).  It joins the contest as lightpath n: the caller has n < kCap and its conn,
 // distinct from the sample's, in T.conn[n]; thread n takes its end nodes from cand under the same test.
+// gone (optional, [kCap] bytes): lightpaths released from the sample before the candidate is placed
+// (infer_topological_place_release.hip).  A gone lightpath is not usable before its end nodes are looked at: it contests no
+// pair and its end nodes flag nothing.  slot (with cand; -1: n, as above): the table slot the candidate takes instead -- a
+// gone lightpath's, so that a full table still has room for it; the caller has its conn in T.conn[slot].
 __device__ __forceinline__ int topo_winners(const double* __restrict__ d, int LQ, int src_row, int dst_row, const Table& T,
                                             int n, int16_t* mat, uint8_t* eu, uint8_t* ev,
-                                            const double* __restrict__ cand = nullptr) {
+                                            const double* __restrict__ cand = nullptr, const uint8_t* gone = nullptr,
+                                            int slot = -1) {
     const int tid = threadIdx.x;
     int bad = 0;
-    const bool is_cand = cand != nullptr && tid == n;
-    if (cand) ++n;
+    const bool is_cand = cand != nullptr && tid == (slot < 0 ? n : slot);
+    if (cand && slot < 0) ++n;
     // end nodes of lightpath tid (255 = not usable)
     int u = 255, v = 255;
-    if (tid < n) {
+    if (tid < n && !(gone != nullptr && !is_cand && gone[tid] != 0)) {
         const int c = is_cand ? 0 : T.first[tid];
         const double sv = is_cand ? cand[src_row] : d[(int64_t)src_row * LQ + c];
         const double dv = is_cand ? cand[dst_row] : d[(int64_t)dst_row * LQ + c];

@@ -6,7 +6,8 @@ samples: ``csrc/infer_topological_status.hip``; its ``place`` of
 ``csrc/infer_lightpath_grad.hip``; its ``what_if`` over candidate lightpaths:
 ``csrc/infer_lightpath_whatif.hip``; its ``from_status`` over network-status samples:
 ``csrc/infer_lightpath_status.hip``; its ``place`` of candidate lightpaths into such samples:
-``csrc/infer_lightpath_place.hip``).
+``csrc/infer_lightpath_place.hip``).  Both ``place`` calls take ``release=`` / ``release_ptr=`` for a reroute:
+``csrc/infer_lightpath_place_release.hip``, ``csrc/infer_topological_place_release.hip``, DESIGN.md 4.24.
 
 ``model(data)`` in eval mode goes through the training machinery: a launch group, the prologue launch, the graph form of
 TransformerConv, the NNConv forward and the read-out kernel (``LightpathGNN``: the self-looped graph index, the GAT walk
@@ -385,6 +386,70 @@ _TOPO_PLACE_CAUSES = (
     (TOPO_PLACE_CONN_TAKEN, "place: a candidate's conn_id is a lightpath of the sample already"),
 )
 
+PLACE_MAX_RELEASE = 32          # include/qot_gnn.h: QOT_PLACE_MAX_RELEASE, released lightpaths per candidate
+# include/qot_gnn.h: the status bits the two *_place_release entries (place with release=) add, the same two in both
+TOPO_PLACE_NO_SUCH_CONN, TOPO_PLACE_BAD_RELEASE = 1024, 2048
+LP_PLACE_NO_SUCH_CONN, LP_PLACE_BAD_RELEASE = 1024, 2048
+_TOPO_RELEASE_CAUSES = (
+    (TOPO_PLACE_NO_SUCH_CONN, "place: a released conn_id is no lightpath of the sample"),
+    (TOPO_PLACE_BAD_RELEASE, f"place: a release_ptr slice that is descending, beyond the released conns or longer than "
+                             f"{PLACE_MAX_RELEASE}"),
+)
+_LP_RELEASE_CAUSES = tuple((lp, text) for lp, (_, text) in zip((LP_PLACE_NO_SUCH_CONN, LP_PLACE_BAD_RELEASE),
+                                                               _TOPO_RELEASE_CAUSES))
+
+# release: the caller's int64 tensor; release_ptr: an int64 tensor, on the host checked and to be uploaded, or on the
+# device and used in place
+_PlaceRelease = namedtuple("_PlaceRelease", "R release release_ptr")
+
+
+def place_release_args(status, K, release, release_ptr, who="place"):
+    """The checks of ``release`` / ``release_ptr`` of both ``place`` methods and of ``materialise_placement`` that need no
+    device, beside ``lightpath_place_args`` / ``topological_place_args`` (which give ``K``): returns ``None`` when both are
+    ``None``, else a ``_PlaceRelease`` (``R``; ``release``; ``release_ptr`` as a 1-d int64 tensor, the caller's own where
+    one was given) or raises ``ValueError`` naming the argument -- only one of the two given; ``release`` not a 1-d int64
+    tensor on the chunk's device; ``release_ptr`` of the wrong length or dtype; a host ``release_ptr`` that is not
+    non-decreasing from 0 to ``R`` or has a slice longer than ``PLACE_MAX_RELEASE`` (one on the device is checked by the
+    kernel)."""
+    def got(t):
+        return f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+
+    if release is None and release_ptr is None:
+        return None
+    if release is None or release_ptr is None:
+        raise ValueError(f"{who}: release and release_ptr go together, got only "
+                         f"{'release_ptr' if release is None else 'release'}")
+    if not isinstance(release, torch.Tensor) or release.dim() != 1 or release.dtype != torch.int64:
+        raise ValueError(f"{who}: release must be a 1-d int64 tensor of conn_id values, got {got(release)}")
+    if release.device != status.data.device:
+        raise ValueError(f"{who}: release is on {release.device}, the status chunk on {status.data.device}")
+    R = int(release.shape[0])
+    if isinstance(release_ptr, torch.Tensor):
+        if release_ptr.dim() != 1 or release_ptr.dtype != torch.int64 or release_ptr.shape[0] != K + 1:
+            raise ValueError(f"{who}: release_ptr must be a sequence or a 1-d int64 tensor of K + 1 = {K + 1} offsets into "
+                             f"release, got {got(release_ptr)}")
+    else:
+        release_ptr = torch.tensor([int(v) for v in release_ptr], dtype=torch.int64).reshape(-1)
+        if release_ptr.shape[0] != K + 1:
+            raise ValueError(f"{who}: release_ptr must hold K + 1 = {K + 1} offsets into release, got {release_ptr.shape[0]}")
+    if not release_ptr.is_cuda:                            # on the host: checked here; on the device: by the kernel
+        if int(release_ptr[0]) != 0 or int(release_ptr[-1]) != R or (K and int(release_ptr.diff().min()) < 0):
+            raise ValueError(f"{who}: release_ptr must be non-decreasing from 0 to R = {R}, got {release_ptr.tolist()}")
+        if K and int(release_ptr.diff().max()) > PLACE_MAX_RELEASE:
+            raise ValueError(f"{who}: candidate {int(release_ptr.diff().argmax())} releases "
+                             f"{int(release_ptr.diff().max())} lightpaths, at most {PLACE_MAX_RELEASE}")
+    return _PlaceRelease(R, release, release_ptr)
+
+
+def _place_index_lists(dev, *lists):
+    """The int64 index lists of a ``place`` call on ``dev``: those on the host go up in ONE copy, those on the device
+    stay the caller's tensors."""
+    host = [t for t in lists if not t.is_cuda]
+    if host:
+        up = iter(torch.cat(host).to(dev).split([int(t.shape[0]) for t in host]))
+    return [_i64(t, dev) if t.is_cuda else next(up) for t in lists]
+
+
 # samples / cell_ptr: int64 tensors, on the host checked (cell_ptr) and to be uploaded, or on the device and used in place
 _TopoPlace = namedtuple("_TopoPlace", "status K M samples cell_ptr")
 
@@ -433,7 +498,8 @@ class _DeviceState:
         code = int(self._status.item())
         self._status.zero_()
         if code:
-            causes = tuple(getattr(self, "_CAUSES", ())) + tuple(getattr(self, "_PLACE_CAUSES", ()))
+            causes = (tuple(getattr(self, "_CAUSES", ())) + tuple(getattr(self, "_PLACE_CAUSES", ()))
+                      + tuple(getattr(self, "_RELEASE_CAUSES", ())))
             named = "; ".join(text for bit, text in causes if code & bit)
             raise _lib.QotError("%s flagged the batch (status %d): %s%s" % (self._FLAGS[0], code, self._FLAGS[1],
                                                                            named and " -- here: " + named))
@@ -481,6 +547,8 @@ class TopologicalPredictor(_DeviceState):
         (TOPO_STATUS_BAD_SAMPLE, to_graph.SG_BAD_SAMPLE), (TOPO_STATUS_BAD_ENDPOINT, to_graph.SG_BAD_ENDPOINT)))
     # ... and the bits qot_topological_infer_place adds, named by check_status() behind them
     _PLACE_CAUSES = _TOPO_PLACE_CAUSES
+    # ... and the two of qot_topological_infer_place_release (place with release=), behind those
+    _RELEASE_CAUSES = _TOPO_RELEASE_CAUSES
 
     def __init__(self, model):
         super().__init__()
@@ -829,7 +897,8 @@ class TopologicalPredictor(_DeviceState):
                      cols, ncol, *extra)
 
     @torch.no_grad()
-    def place(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES):
+    def place(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES, *,
+              release=None, release_ptr=None):
         """Routing and spectrum assignment with the topological model: scores K candidate assignments of a NEW lightpath
         against the status samples of the established ones, ``(out [K, O] float32, links [K] int64)`` in ONE kernel
         launch (``csrc/infer_topological_place.hip``), without the edited samples or their graphs, with nothing read
@@ -861,15 +930,36 @@ class TopologicalPredictor(_DeviceState):
         that is no integer in 1 ... 75 (an all-zero ``values`` row falls here), a sample that holds 256 lightpaths
         already, a sample number outside the chunk -- that candidate's row is NaN and its ``links`` 0, the other rows are
         untouched, and ``check_status()`` raises naming the cause.  (The column table of a feature list, ``arange(75)``
-        and the parameter tables are uploaded by the first call with a chunk: make that call before capturing.)"""
+        and the parameter tables are uploaded by the first call with a chunk: make that call before capturing.)
+
+        ``release [R]`` (int64, on the chunk's device) with ``release_ptr`` (K + 1 offsets, a host sequence or an int64
+        device tensor, as ``cell_ptr``): a REROUTE, or an admission together with a tear-down, in the same launch
+        (``csrc/infer_topological_place_release.hip``).  Candidate ``k`` first releases the lightpaths of
+        its sample whose ``trunc(conn_id)`` is in ``release[release_ptr[k]:release_ptr[k + 1]]`` -- an empty slice and a conn
+        named twice are allowed, at most ``PLACE_MAX_RELEASE = 32`` -- and is then placed;
+        ``materialise_placement(..., release=, release_ptr=)`` is the definition as above.  A released lightpath contests
+        no pair (the pair goes to the largest surviving conn, to the candidate, or disappears), frees its channels for the
+        candidate's cells, may have any ``src_id`` / ``dst_id``, and the candidate may carry its ``conn_id``; a sample of
+        256 lightpaths is accepted when at least one is released.  ``to_graph.placement_links(release=)`` states the
+        links on the host.  More refusals: before any launch (``place_release_args``) only one of the two given,
+        ``release`` not a 1-d int64 tensor on the chunk's device, ``release_ptr`` of the wrong length or dtype, a host
+        ``release_ptr`` not non-decreasing from 0 to R or with a slice longer than 32; on the device a released conn the
+        sample does not hold and a bad slice of a device ``release_ptr``.  Without the two keywords the call is the one
+        above, through the same C entry."""
         who = "TopologicalPredictor.place"
         H, D, O = self._check_model()
         emb = self.model.node_embeddings.weight
         dev = emb.device
         pa = topological_place_args(status, D, samples, values, cells, cell_ptr, features_to_consider, emb.shape[0], dev, who)
+        ra = place_release_args(status, pa.K, release, release_ptr, who)
         out = torch.empty(pa.K, O, dtype=torch.float32, device=dev)
         links = torch.empty(pa.K, dtype=torch.int64, device=dev)
         if pa.K == 0:
+            return out, links
+        if ra is not None:
+            picks, ptr, rptr = _place_index_lists(dev, pa.samples, pa.cell_ptr, ra.release_ptr)
+            self._launch_status("qot_topological_infer_place_release", status, pa.status, (H, D, O), out, links, picks,
+                                values.contiguous(), cells.contiguous(), ptr, pa.M, ra.release.contiguous(), rptr, ra.R)
             return out, links
         picks, ptr = pa.samples, pa.cell_ptr
         if not picks.is_cuda and not ptr.is_cuda:           # both lists are on the host: one upload for the two
@@ -1163,7 +1253,7 @@ def lightpath_place_args(status, in_channels, is_lut_index, samples, values, cel
     return _LpPlace(sa, K, M, samples, cell_ptr)
 
 
-def materialise_placement(status, samples, values, cells, cell_ptr):
+def materialise_placement(status, samples, values, cells, cell_ptr, release=None, release_ptr=None):
     """The K edited samples that ``LightpathPredictor.place`` and ``TopologicalPredictor.place`` score without building
     them: the DEFINITION of both calls and what they save.  Returns a ``DeviceStatus`` of K samples; sample ``k`` is
     ``status.data[samples[k]]`` with ``values[k]`` written into each of the channels ``cells[:, cell_ptr[k]:cell_ptr[k +
@@ -1173,14 +1263,29 @@ def materialise_placement(status, samples, values, cells, cell_ptr):
     ``predict.from_status(edited)[0][k]``.  For a ``TopologicalPredictor``, ``predict.place(...)`` is
     ``predict.from_status(edited)``, rows and link counts, bit for bit.  Pure torch on the status' device (CPU tensors as
     well), no kernel of ours; ``status`` is not modified.  Arguments as ``place``; occupied cells are overwritten, not
-    refused."""
+    refused.
+
+    ``release [R]`` with ``release_ptr`` (as ``place``; ``place_release_args`` checks them): sample ``k`` first has all P
+    rows zeroed in every occupied channel whose ``trunc(conn_id)`` is in ``release[release_ptr[k]:release_ptr[k + 1]]``,
+    then gets ``values[k]`` in its cells.  Occupancy and conn are the kernels' rule: a channel is occupied when any of its
+    values != 0; its conn is ``trunc(conn_id)``, and a ``conn_id`` that is NaN, infinite or beyond +-2^53 matches nothing.
+    A conn that names no lightpath of the sample releases nothing here (``place`` refuses it on the device)."""
     who = "materialise_placement"
     if not isinstance(status, to_graph.DeviceStatus):
         raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
     K, M, samples, cell_ptr = _place_lists(status, samples, values, cells, cell_ptr, who)
+    ra = place_release_args(status, K, release, release_ptr, who)
     dev = status.data.device
     samples, cell_ptr = samples.to(dev), cell_ptr.to(dev)
     edited = status.data.index_select(0, samples)
+    if ra is not None and ra.R:
+        who_k = torch.repeat_interleave(torch.arange(K, device=dev), ra.release_ptr.to(dev).diff(), output_size=ra.R)
+        cv = edited[:, status.feature_indexes["conn_id"]]                         # [K, L, Q]
+        named = (edited != 0).any(1) & (cv.abs() <= 2.0 ** 53)                   # occupied, with a conn to compare
+        conn = torch.where(named, cv, torch.zeros_like(cv)).trunc().to(torch.int64)
+        hit = (conn.index_select(0, who_k) == ra.release[:, None, None]) & named.index_select(0, who_k)   # [R, L, Q]
+        gone = torch.zeros(edited.shape[0], *hit.shape[1:], dtype=torch.int32, device=dev).index_add_(0, who_k, hit.int())
+        edited.masked_fill_((gone > 0)[:, None], 0.0)
     cand = torch.repeat_interleave(torch.arange(K, device=dev), cell_ptr.diff(), output_size=M)
     edited[cand, :, cells[0], cells[1]] = values.index_select(0, cand)
     return to_graph.DeviceStatus(edited, status.target.index_select(0, samples), status.freq, status.lp_feat, status.metric,
@@ -1240,6 +1345,8 @@ class LightpathPredictor(_DeviceState):
         (LP_STATUS_BAD_SAMPLE, to_graph.SG_BAD_SAMPLE)))
     # ... and the bits qot_lightpath_infer_place adds, named by check_status() behind them
     _PLACE_CAUSES = _LP_PLACE_CAUSES
+    # ... and the two of qot_lightpath_infer_place_release (place with release=), behind those
+    _RELEASE_CAUSES = _LP_RELEASE_CAUSES
 
     def __init__(self, model):
         super().__init__()
@@ -1410,7 +1517,7 @@ class LightpathPredictor(_DeviceState):
 
     @torch.no_grad()
     def place(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES,
-              freq_threshold=0.05):
+              freq_threshold=0.05, *, release=None, release_ptr=None):
         """Routing and spectrum assignment: scores K candidate (route, slot) assignments of a NEW lightpath against the
         status samples of the established ones, ``(out [K, O] float32, count [K] int64)`` in ONE kernel launch
         (``csrc/infer_lightpath_place.hip``), without the edited samples or their graphs, with nothing read back, legal
@@ -1443,11 +1550,26 @@ class LightpathPredictor(_DeviceState):
         a ``conn_id`` that is not finite or beyond +-2^53, a sample that holds 256 lightpaths already, a sample number
         outside the chunk -- that candidate's row is NaN and its count 0, the other rows are untouched, and
         ``check_status()`` raises naming the cause.  (The column table of a feature list is uploaded on its first call
-        with a chunk: make that call before capturing.)"""
+        with a chunk: make that call before capturing.)
+
+        ``release [R]`` (int64, on the chunk's device) with ``release_ptr`` (K + 1 offsets, a host sequence or an int64
+        device tensor, as ``cell_ptr``): a REROUTE, or an admission together with a tear-down, in the same launch
+        (``csrc/infer_lightpath_place_release.hip``).  Candidate ``k`` first releases the lightpaths of
+        its sample whose ``trunc(conn_id)`` is in ``release[release_ptr[k]:release_ptr[k + 1]]`` -- an empty slice and a conn
+        named twice are allowed, at most ``PLACE_MAX_RELEASE = 32`` -- and is then placed;
+        ``materialise_placement(..., release=, release_ptr=)`` is the definition as above, and ``count[k]`` the flagged
+        survivors plus one.  A released lightpath sends no message, frees its channels for the candidate's cells, and
+        the candidate may carry its ``conn_id``; a sample of 256 lightpaths is accepted when at least one is released.
+        ``to_graph.placement_neighbourhood(release=)`` states the messages on the host.  More refusals: before any launch
+        (``place_release_args``) only one of the two given, ``release`` not a 1-d int64 tensor on the chunk's device,
+        ``release_ptr`` of the wrong length or dtype, a host ``release_ptr`` not non-decreasing from 0 to R or with a
+        slice longer than 32; on the device a released conn the sample does not hold and a bad slice of a device
+        ``release_ptr``.  Without the two keywords the call is the one above, through the same C entry."""
         who = "LightpathPredictor.place"
         shape = self._check_model()
         pa = lightpath_place_args(status, shape[0], self.model.is_lut_index, samples, values, cells, cell_ptr,
                                   features_to_consider, freq_threshold, who)
+        ra = place_release_args(status, pa.K, release, release_ptr, who)
         sa = pa.status
         dev = self._device()
         if status.device != dev:
@@ -1456,6 +1578,13 @@ class LightpathPredictor(_DeviceState):
         out = torch.empty(pa.K, p.O, dtype=torch.float32, device=dev)
         if pa.K == 0:
             return out, p.count
+        if ra is not None:
+            picks, ptr, rptr = _place_index_lists(dev, pa.samples, pa.cell_ptr, ra.release_ptr)
+            cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
+            count = self._launch("qot_lightpath_infer_place_release", p, out, status.data, status.freq, picks, sa.S, sa.P,
+                                 sa.L, sa.Q, sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
+                                 values.contiguous(), cells.contiguous(), ptr, pa.M, ra.release.contiguous(), rptr, ra.R)
+            return out, count
         picks, ptr = pa.samples, pa.cell_ptr
         if not picks.is_cuda and not ptr.is_cuda:           # both lists are on the host: one upload for the two
             both = torch.cat([picks, ptr]).to(dev)

@@ -266,19 +266,38 @@ def _cells_of(cells, L: int, Q: int):
     return cells
 
 
-def place_lightpath(sample: np.ndarray, values_row: np.ndarray, cells, feature_indexes: Dict[str, int]):
+def _released(sample: np.ndarray, release, feature_indexes: Dict[str, int]):
+    """``(copy of sample with every occupied channel of the lightpaths ``release`` zeroed, the released conns)``: what a
+    candidate of ``place(..., release=)`` is placed into.  A channel is occupied when any of its values != 0, its conn is
+    ``trunc(conn_id)``; a conn named twice is released once; ``ValueError`` for a conn the sample does not hold."""
+    release = sorted({int(c) for c in np.asarray(release, dtype=np.int64).reshape(-1).tolist()})
+    occupied = np.any(sample != 0, axis=0)
+    conn = np.where(occupied, sample[feature_indexes["conn_id"]], 0.0).astype(np.int64)
+    unknown = [c for c in release if not (occupied & (conn == c)).any()]
+    if unknown:
+        raise ValueError(f"released conn_id {unknown[0]} is no lightpath of the sample")
+    out = sample.copy()
+    out[:, occupied & np.isin(conn, release)] = 0.0
+    return out, release
+
+
+def place_lightpath(sample: np.ndarray, values_row: np.ndarray, cells, feature_indexes: Dict[str, int], release=()):
     """One candidate of ``LightpathPredictor.place``, stated on the host: ``(edited, node)``.  ``edited`` is a copy of
     ``sample [lp_feat, link, freq]`` with the raw ``lp_feat`` vector ``values_row`` written into every channel of ``cells
     [2, m]`` (link index, frequency index; a repeated cell is written once more); ``node`` is the candidate's number in
     the first-seen order of ``edited``: its node in ``create_lightpath_graph``'s graph.  ``ValueError`` for a cell outside
     the sample, a cell whose channel is occupied (any of its values != 0) and a ``conn_id`` that truncates to one the
-    sample holds already.  The input is not modified."""
+    sample holds already.  The input is not modified.
+    ``release``: conn ids of lightpaths that are released first (``place(..., release=)``): their channels are zeroed
+    before anything else is looked at, so they are free for the cells and their conn ids for the candidate; a conn the
+    sample does not hold is a ``ValueError``.  The survivors keep their channels, hence their relative first-seen order."""
     fi = feature_indexes
     sample = np.asarray(sample, dtype=np.float64)
     values_row = np.asarray(values_row, dtype=np.float64)
     if sample.ndim != 3 or values_row.shape != (sample.shape[0],):
         raise ValueError("sample must be [lp_feat, link, freq] and values_row [lp_feat]")
     cells = _cells_of(cells, sample.shape[1], sample.shape[2])
+    sample, _ = _released(sample, release, fi)
     occupied = np.any(sample != 0, axis=0)
     if occupied[cells[0], cells[1]].any():
         l, q = cells[:, np.flatnonzero(occupied[cells[0], cells[1]])[0]]
@@ -296,17 +315,24 @@ def place_lightpath(sample: np.ndarray, values_row: np.ndarray, cells, feature_i
 
 
 def placement_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], cells,
-                            freq_threshold: float = 0.05):
+                            freq_threshold: float = 0.05, release=()):
     """Who sends a message into the row of a candidate of ``LightpathPredictor.place``, stated on the UNEDITED sample
     ``[lp_feat, link, freq]`` plus the candidate's ``cells [2, m]``: the ``conn_id`` values, in the sample's first-seen
     order, of the lightpaths that occupy, on the link of some cell, a slot with ``0 < |f1 - f2| < freq_threshold`` to that
     cell's (fp64) -- each once, however many links and slots are shared.  The candidate's own cells are free in the
     sample, so a pair of them names nobody.  For a candidate that is the first-seen flagged lightpath of its edited sample
     this is ``lut_neighbourhood(place_lightpath(...)[0], ...)[2]``: the candidate fills free channels only, so every other
-    lightpath keeps its place in first-seen order."""
+    lightpath keeps its place in first-seen order.
+    ``release``: conn ids of lightpaths released first (``place(..., release=)``; a conn the sample does not hold is a
+    ``ValueError``).  Still stated on the UNEDITED sample: the walk and the first-seen order are the unedited sample's, and
+    the released lightpaths are struck from the result.  That is the edited sample's neighbourhood in its message order,
+    because releasing zeroes whole channels and the candidate fills channels that are free afterwards: a survivor keeps
+    every channel it had, so who is near a cell, each survivor's first channel and the survivors' relative first-seen
+    order are what they were."""
     fi = feature_indexes
     sample, freq = np.asarray(sample, dtype=np.float64), np.asarray(freq, dtype=np.float64)
     cells = _cells_of(cells, sample.shape[1], sample.shape[2])
+    _, gone = _released(sample, release, fi)
     link_idx, freq_idx, vec = _occupied(sample)
     conn = vec[fi["conn_id"], :].astype(np.int64)
     _, first = np.unique(conn, return_index=True)
@@ -315,6 +341,7 @@ def placement_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexe
         on_link = np.flatnonzero(link_idx == l)
         diff = np.abs(freq[q] - freq[freq_idx[on_link]])
         hit.update(conn[on_link[(diff > 0) & (diff < freq_threshold)]].tolist())
+    hit -= set(gone)
     return [int(conn[i]) for i in np.sort(first) if int(conn[i]) in hit]
 
 
@@ -341,16 +368,20 @@ def topological_links(sample: np.ndarray, feature_indexes: Dict[str, int]):
     return np.ascontiguousarray(arr[:, :2].T), np.ascontiguousarray(arr[:, 2])
 
 
-def placement_links(sample: np.ndarray, values_row: np.ndarray, cells, feature_indexes: Dict[str, int]):
+def placement_links(sample: np.ndarray, values_row: np.ndarray, cells, feature_indexes: Dict[str, int], release=()):
     """One candidate of ``TopologicalPredictor.place``, stated on the host: ``(edge_index [2, m] int64, conn [m] int64,
     outcome)``.  ``edge_index`` and ``conn`` are ``topological_links`` of the edited sample, ``place_lightpath(sample,
     values_row, cells, feature_indexes)[0]`` (its ``ValueError`` for an illegal placement as there).  ``outcome`` says what
     the candidate did to the graph of the unedited sample: ``"new pair"`` -- no lightpath of the sample joins its unordered
     node pair, the graph grows by two links (one for a self loop); ``"takes the pair"`` -- its ``trunc(conn_id)`` is larger
     than that of every lightpath of the sample on the pair, whose links now carry the candidate's features; ``"loses the
-    pair"`` -- it is not, and the edited graph is the unedited one.  The cells decide only whether the placement is legal."""
+    pair"`` -- it is not, and the edited graph is the unedited one.  The cells decide only whether the placement is legal.
+    ``release``: conn ids of lightpaths released first (``place(..., release=)``; a conn the sample does not hold is a
+    ``ValueError``).  They take no part in the pair contest, and ``outcome`` is then stated against the graph of the
+    survivors: a pair whose only lightpaths were released is new to the candidate."""
     fi = feature_indexes
-    edited, _ = place_lightpath(sample, values_row, cells, fi)
+    edited, _ = place_lightpath(sample, values_row, cells, fi, release)
+    sample, _ = _released(np.asarray(sample, dtype=np.float64), release, fi)
     edge_index, conn = topological_links(edited, fi)
     values_row = np.asarray(values_row, dtype=np.float64)
     c = int(values_row[fi["conn_id"]])

@@ -1208,6 +1208,58 @@ int qot_topological_infer_place(const int64_t* node_ids, const int64_t* edge_ind
                                 int conn_row, int src_row, int dst_row, const double* cols, int ncol, const double* values,
                                 const int64_t* cells, const int64_t* cell_ptr, int64_t n_cells, qot_stream_t stream);
 
+/* ---- the two place entries with established lightpaths RELEASED in the same launch: a reroute, or an admission together
+ * with a tear-down (LightpathPredictor.place / TopologicalPredictor.place with release=) -- Candidate k
+ * names, beside the place entry's arguments, the conns release[release_ptr[k] : release_ptr[k + 1]] (release [R] int64,
+ * release_ptr [K + 1] int64; an empty slice and a conn named twice are allowed, at most QOT_PLACE_MAX_RELEASE per
+ * candidate).  Let edited_k be sample samples[k] with all rows zeroed in every occupied channel whose trunc(conn_id) is one
+ * of them (occupancy and conn as everywhere: any value != 0; a conn_id of 0 in an occupied channel is conn 0), then
+ * values[k] written into the candidate's cells.  out[k] and count[k] / links[k] are, bit for bit, what the place entry's
+ * definition says of this edited_k: the lightpath entry gives the row of the candidate's node and the flagged survivors
+ * plus one, the topological entry what its status entry gives for edited_k.  edited_k is never built and data is never
+ * written.  Releasing zeroes whole channels and the candidate fills channels that are free afterwards, so a survivor keeps
+ * its first channel and the survivors their relative first-seen order: the messages of the lightpath row are the
+ * surviving interferers' by rising first-seen number of the unedited sample, the self loop last; in the pair contest a
+ * released lightpath takes no part, so its pair goes to the largest surviving conn, to the candidate, or disappears.
+ *
+ * Each argument list is its place entry's up to M / n_cells, then release, release_ptr, R.  Return codes before any
+ * launch: the place entry's, and QOT_ERR_BADARG for R < 0 or -- when K > 0 -- a NULL release_ptr, or NULL release with
+ * R > 0.  K == 0: QOT_OK, no launch.
+ * status: the place entry's bits with these differences -- OCCUPIED only for a cell whose owner survives; CONN_TAKEN and
+ * (topological) BAD_ENDPOINT are tested against the survivors and the candidate, so the candidate may carry a released
+ * conn_id; TOO_MANY for survivors + 1 > QOT_SG_MAX_LIGHTPATHS, and still for more than QOT_SG_MAX_LIGHTPATHS lightpaths in
+ * the unedited sample, which the table cannot hold -- and the two below.  The release_ptr slice is checked against [0, R]
+ * and the cap before release is read; nothing read from data, values or release is used as an index: conns are only
+ * compared. */
+#define QOT_PLACE_MAX_RELEASE 32            /* released lightpaths per candidate */
+#define QOT_LP_PLACE_NO_SUCH_CONN 1024      /* a released conn that is no lightpath of the sample */
+#define QOT_LP_PLACE_BAD_RELEASE 2048       /* a release_ptr slice that is descending, beyond R or longer than QOT_PLACE_MAX_RELEASE */
+#define QOT_TOPO_PLACE_NO_SUCH_CONN 1024    /* a released conn that is no lightpath of the sample */
+#define QOT_TOPO_PLACE_BAD_RELEASE 2048     /* a release_ptr slice that is descending, beyond R or longer than QOT_PLACE_MAX_RELEASE */
+int qot_lightpath_infer_place_release(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                                      const int64_t* edge_ptr, const int64_t* lut_idx, int64_t n_lut, int64_t N, int64_t E,
+                                      int64_t K, const float* w, const float* att_src, const float* att_dst,
+                                      const float* conv_bias, float slope_att, const float* bn_weight, const float* bn_bias,
+                                      const float* bn_mean, const float* bn_var, float bn_eps, const float* w0, const float* b0,
+                                      const float* w3, const float* b3, float slope_head, float* out, int64_t* count, int F,
+                                      int C, int O, int heads, int lut_col, int32_t* status, const double* data,
+                                      const double* freq, const int64_t* samples, int64_t S, int P, int64_t L, int64_t Q,
+                                      int conn_row, int osnr_row, int snr_row, int ber_row, const double* cols, int ncol,
+                                      double freq_threshold, const double* values, const int64_t* cells,
+                                      const int64_t* cell_ptr, int64_t M, const int64_t* release, const int64_t* release_ptr,
+                                      int64_t R, qot_stream_t stream);
+int qot_topological_infer_place_release(const int64_t* node_ids, const int64_t* edge_index, const float* edge_attr,
+                                        const int64_t* node_ptr, const int64_t* edge_ptr, int64_t N, int64_t E, int64_t K,
+                                        int n_max, int max_e, const float* t4, int ld4, const float* M, int ldm, const float* P,
+                                        int V, const float* w_edge, const float* w1, const float* b1, const float* wcat,
+                                        const float* bias2, const float* w0, const float* b0, const float* w3, const float* b3,
+                                        float slope_conv, float slope_head, float* out, int H, int D, int O, int32_t* status,
+                                        int64_t* links, const double* data, const int64_t* samples, int64_t S, int rows,
+                                        int64_t L, int64_t Q, int conn_row, int src_row, int dst_row, const double* cols,
+                                        int ncol, const double* values, const int64_t* cells, const int64_t* cell_ptr,
+                                        int64_t n_cells, const int64_t* release, const int64_t* release_ptr, int64_t R,
+                                        qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

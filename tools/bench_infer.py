@@ -113,6 +113,20 @@ with a conn below.  Rows and link counts of the two ways are compared first (equ
 when they are further apart than the sum of their interquartile ranges.
 
     python tools/bench_infer.py --kind topological --place 1 8 64 1024 [--out profiles/bench_infer_topological_place.jsonl]
+
+``--place K [K ...] --release R`` (either kind): a reroute -- every candidate releases R lightpaths of the sample in the same
+launch (csrc/infer_*_place_release.hip).  ``predict.place(..., release=, release_ptr=)`` against (a)
+``infer.materialise_placement(..., release, release_ptr)`` followed by ``predict.from_status(edited)`` -- the only way
+before -- and (b) plain ``predict.place`` of the same candidates with nothing released: the cost of the edit itself, timed
+in an alternation of its own (``release_pair_ms`` beside ``place_ms``), away from (a)'s K copies of the sample.  Each
+candidate sits one slot beside a channel of a lightpath of the sample, on that link and on 0 - 5 more free links; that
+lightpath is released (an interferer of the unreleased placement; in the topological model the winner of its node pair),
+and R - 1 more; one channel of the last released lightpath is one of the candidate's cells -- in (b) a free cell of the
+candidate's slot takes its place, so both walk as many cells.  ``--kind lightpath`` runs at threshold 0.12: at 0.05 the
+neighbour slot, 0.05 away, does not interfere.  The rows of ``place(release=)`` and (a) are compared first (equal bits).
+
+    python tools/bench_infer.py --kind lightpath --place 1 8 64 1024 --release 2 [--out profiles/bench_infer_lightpath_place_release.jsonl]
+    python tools/bench_infer.py --kind topological --place 1 8 64 1024 --release 2 [--out profiles/bench_infer_topological_place_release.jsonl]
 """
 import argparse
 import json
@@ -754,6 +768,137 @@ def main_topological_place(args, device, commit):
               f"{'no difference' if same else f'{b / a:.2f}x'} |")
 
 
+def measure_place_release(kind, K, R, H, device, rounds, warmup, thr=0.12, num_links=60, per_candidate=None):
+    """``place(..., release=)`` of K candidates, R released lightpaths each, against (a) ``materialise_placement(release=)`` +
+    ``from_status`` and (b) plain ``place`` of the same candidates with nothing released (the reused cell swapped for a free
+    one on the same slot, so that both walk as many cells)."""
+    import numpy as np
+    from gnn_qot_estimation_amd import infer, to_graph as TG
+    torch.manual_seed(0)
+    if kind == "lightpath":
+        predict = q.LightpathPredictor(q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval())
+    else:
+        predict = q.TopologicalPredictor(q.TopologicalGNN(75, H, 3, 4, dropout_p=0.0).to(device).eval())
+    ns = TG.synthetic_network_status(1, num_links=num_links, seed=0)      # the 60 x 72 grid by default
+    fi, feats = ns.feature_indexes, list(TG.DEFAULT_FEATURES)
+    data = ns.data.copy()
+    if kind == "lightpath":                                 # the sample's own lightpath under test goes, as in --place
+        under_test = (data[0, fi["osnr"]] == -1) & (data[0, fi["snr"]] == -1) & (data[0, fi["ber"]] == -1)
+        data[0][:, under_test] = 0.0
+    L, Q = data.shape[2], data.shape[3]
+    free = ~np.any(data[0] != 0, axis=0)
+    occ = np.argwhere(~free)
+    conn_of = data[0, fi["conn_id"]].astype(np.int64)
+    conns = sorted({int(conn_of[l, f]) for l, f in occ})
+    if R > min(len(conns), infer.PLACE_MAX_RELEASE):
+        raise SystemExit(f"--release {R}: the sample holds {len(conns)} lightpaths, the cap is {infer.PLACE_MAX_RELEASE}")
+    # channels with a free neighbour slot on their link: where a candidate meets an interferer at 0.05 < thr
+    beside = [(int(l), int(f), int(g)) for l, f in occ for g in (f - 1, f + 1) if 0 <= g < Q and free[l, g]]
+    rng = np.random.default_rng(K)
+    values, cells, plain_cells, ptr, release = np.zeros((K, len(ns.lp_feat))), [], [], [0], []
+    met, winners = 0, 0
+    for k in range(K):
+        want = per_candidate or int(rng.integers(1, 7))
+        while True:                                         # next to a lightpath's channel, on 1 - 6 free links of that slot
+            l0, f0, slot = beside[int(rng.integers(len(beside)))]
+            open_links = np.setdiff1d(np.flatnonzero(free[:, slot]), [l0])
+            if len(open_links) >= want:                     # (want - 1 more for the candidate, one for plain place's swap)
+                links = np.concatenate([[l0], rng.choice(open_links, size=want, replace=False)])
+                break
+        first = int(conn_of[l0, f0])                        # released: an interferer of the unreleased placement
+        others = [c for c in conns if c != first]
+        rel = [first] + [int(c) for c in rng.choice(others, size=R - 1, replace=False)]
+        reuse = occ[[int(conn_of[l, f]) == rel[-1] for l, f in occ]][0]         # a channel of a released lightpath
+        mine = np.stack([links[:want], np.full(want, slot)])
+        cells.append(np.concatenate([mine, reuse.reshape(2, 1)], axis=1))
+        plain_cells.append(np.concatenate([mine, np.array([[links[want]], [slot]])], axis=1))
+        ptr.append(ptr[-1] + want + 1)
+        release += rel
+        met += first in TG.placement_neighbourhood(data[0], ns.freq, fi, mine, thr)
+        v = values[k]
+        if kind == "lightpath" or k % 3 == 0:
+            v[fi["conn_id"]], (v[fi["src_id"]], v[fi["dst_id"]]) = 10000 + k, rng.integers(1, 76, size=2)
+        else:                                               # the pair of the released neighbour, above or below every conn
+            v[fi["src_id"]], v[fi["dst_id"]] = data[0, fi["dst_id"], l0, f0], data[0, fi["src_id"], l0, f0]
+            v[fi["conn_id"]] = 10000 + k if k % 3 == 1 else -1 - k
+        v[fi["mod_order"]], v[fi["path_len"]] = float(rng.choice([4, 8, 16, 32, 64])), float(rng.integers(24214, 7834746))
+        v[fi["num_spans"]], v[fi["freq"]] = float(rng.integers(1, 107)), ns.freq[slot]
+        v[fi["osnr"]] = v[fi["snr"]] = v[fi["ber"]] = -1.0
+    if kind == "topological":                               # how many candidates release the winner of some node pair
+        won = set(TG.topological_links(data[0], fi)[1].tolist())
+        winners = sum(bool(won & set(release[k * R:(k + 1) * R])) for k in range(K))
+        assert winners == K
+    else:
+        assert met == K
+    st = TG.NetworkStatus(data, ns.target, ns.lp_feat, ns.metric, ns.link, ns.freq).to_device(device)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device)       # noqa: E731
+    samples, values_d = torch.zeros(K, dtype=torch.int64, device=device), torch.from_numpy(values).to(device)
+    cells_d, plain_d, ptr_d = dev(np.concatenate(cells, axis=1)), dev(np.concatenate(plain_cells, axis=1)), dev(ptr)
+    rel_d, rptr_d = dev(release), dev(np.arange(K + 1) * R)
+    tail = (feats, thr) if kind == "lightpath" else (feats,)
+    ways = {"release": lambda: predict.place(st, samples, values_d, cells_d, ptr_d, *tail, release=rel_d, release_ptr=rptr_d),
+            "materialise": lambda: predict.from_status(infer.materialise_placement(st, samples, values_d, cells_d, ptr_d,
+                                                                                   rel_d, rptr_d), None, *tail),
+            "place": lambda: predict.place(st, samples, values_d, plain_d, ptr_d, *tail)}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    assert torch.equal(got["release"][0], got["materialise"][0]) and torch.equal(got["release"][1], got["materialise"][1]), K
+    assert tuple(got["release"][0].shape) == (K, 3) and all(bool(torch.isfinite(g[0]).all()) for g in got.values())
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    # two alternations, so that plain place is not timed right behind materialise_placement's K copies of the sample: the
+    # call that follows them is up to a third slower at K >= 64 (measured: DESIGN.md 4.24), whichever of the two it is
+    times = {k: [] for k in ("release", "materialise", "release_pair", "place")}
+    for _ in range(rounds):
+        times["release"].append(timed_event(ways["release"]))
+        times["materialise"].append(timed_event(ways["materialise"]))
+    for _ in range(warmup):
+        ways["release"](), ways["place"]()
+    for _ in range(rounds):
+        times["release_pair"].append(timed_event(ways["release"]))
+        times["place"].append(timed_event(ways["place"]))
+    res = dict(shape=f"status {L} x {Q}", kind=f"{kind}_place_release", K=K, R=R, cells=int(ptr[-1]), lightpaths=len(conns), S=1,
+               P=int(st.data.shape[1]), L=L, Q=Q, rounds=rounds, equal_bits=True, released_interferers=met,
+               released_winners=winners)
+    res.update(dict(C=32, F=5, freq_threshold=thr) if kind == "lightpath" else dict(H=H, D=4, V=75))
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_place_release(args, device, commit):
+    rows = []
+    for H in ((None,) if args.kind == "lightpath" else STATUS_WIDTHS):
+        for K in args.place:
+            res = measure_place_release(args.kind, K, args.release, H, device, args.rounds, args.warmup, num_links=args.links,
+                                        per_candidate=args.cells)
+            res["commit"] = commit or None
+            res["device"] = torch.cuda.get_device_name(0)
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| H | grid | K | R | cells | place(release=) ms (IQR) | (a) materialise_placement(release=) + from_status ms (IQR) | "
+          "(a) / release | place(release=) beside (b) ms (IQR) | (b) plain place ms (IQR) | release / (b) |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+
+    def ratio(r, num, den):                                 # differ: by more than the sum of the IQRs
+        same = abs(r[num + "_ms"] - r[den + "_ms"]) <= r[num + "_iqr_ms"] + r[den + "_iqr_ms"]
+        return "no difference" if same else f"{r[num + '_ms'] / r[den + '_ms']:.2f}x"
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r.get('H', '-')} | {r['L']} x {r['Q']} | {r['K']} | {r['R']} | {r['cells']} | {cell('release')} | "
+              f"{cell('materialise')} | {ratio(r, 'materialise', 'release')} | {cell('release_pair')} | {cell('place')} | "
+              f"{ratio(r, 'release_pair', 'place')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -927,9 +1072,14 @@ def main():
                          "what the scan costs)")
     ap.add_argument("--cells", type=int, default=None, metavar="N",
                     help="with --place: N links per candidate instead of 1 - 6 (the walk is O(cells Q))")
+    ap.add_argument("--release", type=int, default=None, metavar="R",
+                    help="with --place: every candidate releases R lightpaths of the sample in the same launch (place(..., "
+                         "release=)), against materialise_placement(release=) + from_status and against plain place")
     args = ap.parse_args()
-    if args.place is None and (args.links != 60 or args.cells is not None):
-        raise SystemExit("--links and --cells go with --place")
+    if args.place is None and (args.links != 60 or args.cells is not None or args.release is not None):
+        raise SystemExit("--links, --cells and --release go with --place")
+    if args.release is not None and args.release < 1:
+        raise SystemExit("--release R (R >= 1)")
     if args.links < 6 or (args.cells is not None and not 1 <= args.cells <= args.links):
         raise SystemExit("--links L (>= 6, what synthetic_network_status routes over) and --cells N (1 ... L)")
     if args.place is not None and (args.from_status or args.mc is not None or args.grad or args.what_if is not None
@@ -949,6 +1099,8 @@ def main():
         raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    if args.place is not None and args.release is not None:
+        return main_place_release(args, device, commit)
     if args.place is not None:
         return (main_place if args.kind == "lightpath" else main_topological_place)(args, device, commit)
     if args.from_status:
