@@ -34,13 +34,6 @@
 namespace qot {
 namespace {
 
-struct LpPlaceArgs {
-    const double* values;               // [K, P] raw lp_feat vectors
-    const int64_t* cells;               // [2, M]: link indices, then frequency indices
-    const int64_t* cell_ptr;            // [K + 1]
-    int64_t M;
-};
-
 __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_place_kernel(const LpArgs a, const LpStatusArgs st,
                                                                              const LpPlaceArgs pl) {
     __shared__ sg::Table T;
@@ -54,73 +47,19 @@ __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_place_kernel(con
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t k = blockIdx.x;
     float* orow = a.out + k * a.O;
-    const double* v = pl.values + k * (int64_t)st.P;
 
-    // ---- what the candidate's own arguments say (every value is uniform over the block) ----
-    bool ok;
-    const int64_t s = sg::sample_of(st.samples, k, st.S, ok);
-    const int64_t lo = pl.cell_ptr[k], hi = pl.cell_ptr[k + 1];
-    int64_t conn_a = 0;
-    int early = ok ? 0 : QOT_LP_STATUS_BAD_SAMPLE;
-    if (lo < 0 || hi <= lo || hi > pl.M) early |= QOT_LP_PLACE_BAD_CELL;
-    if (!sg::sg_conn(v[st.conn_row], conn_a)) early |= QOT_LP_STATUS_BAD_CONN;
-    if (!sg::sg_is_lut_vec(v, st.osnr_row, st.snr_row, st.ber_row)) early |= QOT_LP_PLACE_NOT_LUT;
-    if (early) {                                                   // block-uniform
-        if (w == 0) {
-            if (lane == 0) st.count[k] = 0;
-            lp_refuse(a, orow, lane, early);
-        }
-        return;
-    }
-    const int LQ = st.L * st.Q;
-    const double* d = st.data + s * (int64_t)st.P * LQ;
-    for (int q = tid; q < st.Q; q += sg::kThreads) freq[q] = st.freq[q];
-    nb[tid] = 0;
-    if (tid == 0) bad_all = 0;
-
-    // ---- phase 1: the lightpaths of the unedited sample, their flags, the candidate's conn among them ----
-    const int bad = sg::discover(d, st.P, LQ, st.conn_row, T, nullptr);      // (begins and ends with a barrier)
-    const int n = T.n;
-    int mine = ((bad & QOT_SG_BAD_CONN) ? QOT_LP_STATUS_BAD_CONN : 0) | ((bad & QOT_SG_TOO_MANY) ? QOT_LP_STATUS_TOO_MANY : 0);
-    if (tid < n && T.conn[tid] == conn_a) mine |= QOT_LP_PLACE_CONN_TAKEN;
-    if (tid == 0 && n >= sg::kCap) mine |= QOT_LP_STATUS_TOO_MANY;            // the edited sample would hold n + 1
-    if (mine) atomicOr(&bad_all, mine);
-    const bool flag = tid < n && sg::sg_is_lut(d, LQ, st.osnr_row, st.snr_row, st.ber_row, T.first[tid]);
-    const unsigned long long fm = __ballot(flag);
-    if (lane == 0) lut_mask[w] = fm;
-    __syncthreads();
-    if (bad_all) {                                                 // block-uniform
-        if (w == 0) {
-            if (lane == 0) st.count[k] = 0;
-            lp_refuse(a, orow, lane, bad_all);
-        }
-        return;
-    }
-    int cnt = 1;                                                   // the candidate itself
-#pragma unroll
-    for (int j = 0; j < sg::kWaves; ++j) cnt += __popcll(lut_mask[j]);
-    __syncthreads();                                               // (bad_all is written again below)
-
-    // ---- phase 2: the candidate's cells, a wave each ----
-    for (int64_t c = lo + w; c < hi; c += sg::kWaves) {            // (wave-uniform)
-        const int64_t l = pl.cells[c], q1 = pl.cells[pl.M + c];
-        int cell = 0;
-        int64_t conn;
-        if (l < 0 || l >= st.L || q1 < 0 || q1 >= st.Q) cell = QOT_LP_PLACE_BAD_CELL;
-        else if (channel_conn(d, st.P, LQ, st.conn_row, (int)l * st.Q + (int)q1, conn)) cell = QOT_LP_PLACE_OCCUPIED;
-        if (cell) {
-            if (lane == 0) atomicOr(&bad_all, cell);
-            continue;
-        }
-        lp_mark_slots(d, st, LQ, (int)l, (int)q1, freq, T, n, conn_a, nb, lane);
-    }
-    __syncthreads();
+    // ---- phases 1 and 2 (infer_lightpath_status_dev.hpp, shared with infer_lightpath_place_impact.hip) ----
+    LpPlaceScan r;
+    const int bad = lp_place_scan(st, pl, k, T, freq, nb, lut_mask, &bad_all, r);    // (block-uniform, behind a barrier)
     if (w != 0) return;
-    if (bad_all) {                                                 // (wave-uniform)
+    if (bad) {
         if (lane == 0) st.count[k] = 0;
-        lp_refuse(a, orow, lane, bad_all);
+        lp_refuse(a, orow, lane, bad);
         return;
     }
+    const double* d = r.d;
+    const double* v = r.v;
+    const int LQ = r.LQ, n = r.n, cnt = r.cnt;
     if (lane == 0) st.count[k] = cnt;
 
     // ---- phase 3: the rows of the neighbourhood by rising lightpath number, then the row ----

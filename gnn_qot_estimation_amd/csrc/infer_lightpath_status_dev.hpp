@@ -4,7 +4,9 @@
 // the row of a candidate that the sample does not hold yet).  Stated once here for both: the sample's arguments, who
 // occupies a channel (channel_conn), the walk over the slots of one link that marks the interferers of one channel
 // (lp_mark_slots) and the staging of the marked lightpaths' feature rows by rising lightpath number (lp_stage_marked) --
-// so who interferes, and in which order the messages are summed, is the same code in both.
+// so who interferes, and in which order the messages are summed, is the same code in both.  infer_lightpath_place.hip and
+// infer_lightpath_place_impact.hip (place_impact, DESIGN.md 4.25: the candidate's row and the retest of the lightpaths it
+// disturbs) further share the candidate's arguments (LpPlaceArgs) and phases 1 and 2 of a candidate (lp_place_scan).
 #pragma once
 #include "infer_lightpath_dev.hpp"
 #include "status_scan_dev.hpp"
@@ -62,6 +64,88 @@ __device__ __forceinline__ int lp_stage_marked(const double* __restrict__ d, con
         na += __popcll(m);
     }
     return na;
+}
+
+// One candidate of LightpathPredictor.place: the raw lp_feat vector values[k] in the channels cells[:, cell_ptr[k] :
+// cell_ptr[k + 1]] of sample samples[k]
+struct LpPlaceArgs {
+    const double* values;               // [K, P] raw lp_feat vectors
+    const int64_t* cells;               // [2, M]: link indices, then frequency indices
+    const int64_t* cell_ptr;            // [K + 1]
+    int64_t M;
+};
+
+// what lp_place_scan leaves for the phases behind it (every value is uniform over the block)
+struct LpPlaceScan {
+    const double* d;                    // the candidate's sample
+    const double* v;                    // values[k]
+    int64_t conn_a, lo, hi;             // the candidate's truncated conn, its slice of cells
+    int LQ, n, cnt;                     // L * Q; the sample's lightpaths; its flagged ones + 1
+};
+
+// Phases 1 and 2 of candidate k by its whole workgroup: the candidate's own arguments; discover() on the
+// unedited sample, thread t reads lightpath t's is_lut flag on its first channel and compares its conn with the
+// candidate's; then wave w takes the cells lo + w, lo + w + 4, ...: range check, the channel must be free, and the wave's
+// lanes walk the Q slots of the cell's link and mark nb[] (lp_mark_slots; a duplicate cell marks the same bytes again).
+// T, freq [kQCap], nb [kCap], lut_mask [kWaves] and bad_all are the caller's LDS.  Returns the candidate's refusal bits
+// (QOT_LP_STATUS_* / QOT_LP_PLACE_*), the same in every thread, behind a barrier: 0 -- T, freq, nb and r are complete;
+// otherwise nothing has been written to global memory and the caller refuses the candidate.
+__device__ __forceinline__ int lp_place_scan(const LpStatusArgs& st, const LpPlaceArgs& pl, int64_t k, sg::Table& T,
+                                             double* freq, uint8_t* nb, unsigned long long* lut_mask, int* bad_all,
+                                             LpPlaceScan& r) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const double* v = pl.values + k * (int64_t)st.P;
+
+    // ---- what the candidate's own arguments say ----
+    bool ok;
+    const int64_t s = sg::sample_of(st.samples, k, st.S, ok);
+    const int64_t lo = pl.cell_ptr[k], hi = pl.cell_ptr[k + 1];
+    int64_t conn_a = 0;
+    int early = ok ? 0 : QOT_LP_STATUS_BAD_SAMPLE;
+    if (lo < 0 || hi <= lo || hi > pl.M) early |= QOT_LP_PLACE_BAD_CELL;
+    if (!sg::sg_conn(v[st.conn_row], conn_a)) early |= QOT_LP_STATUS_BAD_CONN;
+    if (!sg::sg_is_lut_vec(v, st.osnr_row, st.snr_row, st.ber_row)) early |= QOT_LP_PLACE_NOT_LUT;
+    if (early) return early;                                       // block-uniform
+    const int LQ = st.L * st.Q;
+    const double* d = st.data + s * (int64_t)st.P * LQ;
+    for (int q = tid; q < st.Q; q += sg::kThreads) freq[q] = st.freq[q];
+    nb[tid] = 0;
+    if (tid == 0) *bad_all = 0;
+
+    // ---- phase 1: the lightpaths of the unedited sample, their flags, the candidate's conn among them ----
+    const int bad = sg::discover(d, st.P, LQ, st.conn_row, T, nullptr);      // (begins and ends with a barrier)
+    const int n = T.n;
+    int mine = ((bad & QOT_SG_BAD_CONN) ? QOT_LP_STATUS_BAD_CONN : 0) | ((bad & QOT_SG_TOO_MANY) ? QOT_LP_STATUS_TOO_MANY : 0);
+    if (tid < n && T.conn[tid] == conn_a) mine |= QOT_LP_PLACE_CONN_TAKEN;
+    if (tid == 0 && n >= sg::kCap) mine |= QOT_LP_STATUS_TOO_MANY;            // the edited sample would hold n + 1
+    if (mine) atomicOr(bad_all, mine);
+    const bool flag = tid < n && sg::sg_is_lut(d, LQ, st.osnr_row, st.snr_row, st.ber_row, T.first[tid]);
+    const unsigned long long fm = __ballot(flag);
+    if (lane == 0) lut_mask[w] = fm;
+    __syncthreads();
+    if (*bad_all) return *bad_all;                                 // block-uniform; nobody writes it again
+    int cnt = 1;                                                   // the candidate itself
+#pragma unroll
+    for (int j = 0; j < sg::kWaves; ++j) cnt += __popcll(lut_mask[j]);
+    __syncthreads();                                               // (bad_all is written again below)
+
+    // ---- phase 2: the candidate's cells, a wave each ----
+    for (int64_t c = lo + w; c < hi; c += sg::kWaves) {            // (wave-uniform)
+        const int64_t l = pl.cells[c], q1 = pl.cells[pl.M + c];
+        int cell = 0;
+        int64_t conn;
+        if (l < 0 || l >= st.L || q1 < 0 || q1 >= st.Q) cell = QOT_LP_PLACE_BAD_CELL;
+        else if (channel_conn(d, st.P, LQ, st.conn_row, (int)l * st.Q + (int)q1, conn)) cell = QOT_LP_PLACE_OCCUPIED;
+        if (cell) {
+            if (lane == 0) atomicOr(bad_all, cell);
+            continue;
+        }
+        lp_mark_slots(d, st, LQ, (int)l, (int)q1, freq, T, n, conn_a, nb, lane);
+    }
+    __syncthreads();
+    r.d = d; r.v = v; r.conn_a = conn_a; r.lo = lo; r.hi = hi;
+    r.LQ = LQ; r.n = n; r.cnt = cnt;
+    return *bad_all;
 }
 
 // What both entry points check of the arguments they share behind `status` (before any launch; G rows are asked for)

@@ -1292,6 +1292,85 @@ def materialise_placement(status, samples, values, cells, cell_ptr, release=None
                                  status.link)
 
 
+PLACE_MAX_AFFECTED = 32         # include/qot_gnn.h: QOT_PLACE_MAX_AFFECTED, retested lightpaths per candidate
+_LABEL_ROWS = ("osnr", "snr", "ber")
+
+# what LightpathPredictor.place_impact returns: place(...)'s out [K, O] and count [K]; affected [K, A] int64 conn ids, -1
+# padded, and n_affected [K] int64, their true number; before / after [K, A, O] float32, NaN padded
+PlaceImpact = namedtuple("PlaceImpact", "out count affected n_affected before after")
+
+
+def lightpath_place_impact_args(status, in_channels, is_lut_index, samples, values, cells, cell_ptr,
+                                features_to_consider=to_graph.DEFAULT_FEATURES, freq_threshold=0.05, max_affected=8,
+                                who="LightpathPredictor.place_impact"):
+    """The argument checks of ``LightpathPredictor.place_impact`` that need no device: ``ValueError`` for a
+    ``max_affected`` that is no int in ``1 ... PLACE_MAX_AFFECTED``; ``EnvelopeError`` for a feature list that holds
+    ``osnr``, ``snr`` or ``ber`` (the retest rewrites those rows, so they must not be features); then everything
+    ``lightpath_place_args`` refuses, whose ``_LpPlace`` is returned."""
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    if isinstance(max_affected, bool) or not isinstance(max_affected, int) or not 1 <= max_affected <= PLACE_MAX_AFFECTED:
+        raise ValueError(f"{who}: max_affected must be an int in 1 ... {PLACE_MAX_AFFECTED}, got {max_affected!r}")
+    labels = [n for n in features_to_consider if n in _LABEL_ROWS]
+    if labels:
+        raise EnvelopeError(f"{who}: {', '.join(repr(n) for n in labels)} cannot be a feature: retesting a lightpath rewrites "
+                            f"its osnr, snr and ber")
+    return lightpath_place_args(status, in_channels, is_lut_index, samples, values, cells, cell_ptr, features_to_consider,
+                                freq_threshold, who)
+
+
+def materialise_retest(status, samples, conns, values=None, cells=None, cell_ptr=None):
+    """The samples in which an ESTABLISHED lightpath is the lightpath under test, without or with a candidate established
+    next to it: the DEFINITION of ``LightpathPredictor.place_impact``'s ``before`` and ``after``.  Returns a
+    ``DeviceStatus`` of T samples; sample ``t`` is ``status.data[samples[t]]`` with two edits, in this order.  (1) Only
+    when ``values`` is given (then ``cells`` and ``cell_ptr`` too, all as ``place`` takes them, T candidates): ``values[t]``
+    is written into each of the channels ``cells[:, cell_ptr[t]:cell_ptr[t + 1]]`` with its ``osnr``, ``snr`` and ``ber``
+    entries replaced by 0.0 -- the candidate as an established neighbour, unflagged, ``is_lut`` 0: how every neighbour of
+    a lightpath under test looks in the training data.  (2) Every occupied channel whose ``trunc(conn_id)`` is
+    ``conns[t]`` gets ``osnr = snr = ber = -1``.  Occupancy and conn follow the rule of ``materialise_placement``.  A
+    flagged lightpath the sample holds already stays flagged.
+
+    ``before[k, i]`` is, bit for bit, the row ``predict(to_graph.device_batch(materialise_retest(status, [samples[k]],
+    [affected[k, i]]), "lightpath", ...))`` gives the node of conn ``affected[k, i]`` (``to_graph.placement_impact`` states
+    its number) -- ``predict.from_status(...)[0][0]`` where that lightpath is the sample's first flagged one -- and
+    ``after[k, i]`` the same with ``values[k:k + 1]``, candidate ``k``'s cells and ``[0, m]`` passed in as well.  Pure
+    torch on the status' device (CPU tensors as well), no kernel of ours; ``status`` is not modified."""
+    who = "materialise_retest"
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    dev = status.data.device
+    fi = status.feature_indexes
+    conns = torch.as_tensor(conns, dtype=torch.int64).reshape(-1).to(dev)
+    T = int(conns.shape[0])
+    if values is None:
+        if cells is not None or cell_ptr is not None:
+            raise ValueError(f"{who}: cells and cell_ptr go with values")
+        if isinstance(samples, int) and not isinstance(samples, bool):
+            samples = [samples] * T
+        samples = torch.as_tensor(samples, dtype=torch.int64).reshape(-1).to(dev)
+        if samples.shape[0] != T:
+            raise ValueError(f"{who}: samples names {samples.shape[0]} samples, conns {T} lightpaths")
+        edited = status.data.index_select(0, samples)
+    else:
+        K, M, samples, cell_ptr = _place_lists(status, samples, values, cells, cell_ptr, who)
+        if K != T:
+            raise ValueError(f"{who}: values has {K} rows, conns names {T} lightpaths")
+        samples, cell_ptr = samples.to(dev), cell_ptr.to(dev)
+        edited = status.data.index_select(0, samples)
+        established = values.clone()
+        established[:, [fi[n] for n in _LABEL_ROWS]] = 0.0
+        cand = torch.repeat_interleave(torch.arange(K, device=dev), cell_ptr.diff(), output_size=M)
+        edited[cand, :, cells[0], cells[1]] = established.index_select(0, cand)
+    cv = edited[:, fi["conn_id"]]                                                 # [T, L, Q]
+    named = (edited != 0).any(1) & (cv.abs() <= 2.0 ** 53)                       # occupied, with a conn to compare
+    conn = torch.where(named, cv, torch.zeros_like(cv)).trunc().to(torch.int64)
+    under_test = named & (conn == conns[:, None, None])
+    for n in _LABEL_ROWS:
+        edited[:, fi[n]].masked_fill_(under_test, -1.0)
+    return to_graph.DeviceStatus(edited, status.target.index_select(0, samples), status.freq, status.lp_feat, status.metric,
+                                 status.link)
+
+
 # what LightpathPredictor._prepare hands to _launch: the model's shape, the batch on dev, which rows (rows mode: batch,
 # idx; graphs mode: a fresh count) and how many
 _LpPrepared = namedtuple("_LpPrepared", "F C O dev x ei batch ptr eptr idx B rows count")
@@ -1326,6 +1405,9 @@ class LightpathPredictor(_DeviceState):
     ``predict.place(status, samples, values, cells, cell_ptr)``: K candidate (route, slot) assignments of a NEW lightpath,
     each placed into a status sample that does not hold it yet -- the interferers are found by the kernel -- one launch and
     no host read (see there).
+    ``predict.place_impact(status, samples, values, cells, cell_ptr)``: ``place``'s rows together with the retest of the
+    established lightpaths each candidate disturbs -- their rows as the lightpath under test before and after the candidate
+    is lit -- one launch and no host read (see there).
 
     Envelope -- ``EnvelopeError`` naming the condition otherwise: a model on the GPU with ``num_layers == 1``, 1 ... 16 input
     features, hidden width 1 ... 256, 1 ... 8 outputs; ``data.x`` of shape ``[N, F]``.  No cap on in-degree, graph size or
@@ -1594,6 +1676,63 @@ class LightpathPredictor(_DeviceState):
                              sa.Q, sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
                              values.contiguous(), cells.contiguous(), _i64(ptr, dev), pa.M)
         return out, count
+
+    @torch.no_grad()
+    def place_impact(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES,
+                     freq_threshold=0.05, max_affected=8):
+        """The admission decision's second half: ``place``'s rows together with a RETEST of the established lightpaths
+        each candidate lands next to -- do they stay above their thresholds once it is lit? -- as ``PlaceImpact(out [K, O]
+        float32, count [K] int64, affected [K, A] int64, n_affected [K] int64, before [K, A, O] float32, after [K, A, O]
+        float32)`` with ``A = max_affected``, in ONE kernel launch (``csrc/infer_lightpath_place_impact.hip``, DESIGN.md
+        4.25), with nothing read back and ``status.data`` never written; legal inside ``torch.cuda.graph`` capture under
+        the conditions of ``place`` (index arguments as device tensors, one call made first).
+
+        ``samples``, ``values``, ``cells``, ``cell_ptr``, ``features_to_consider`` and ``freq_threshold`` are ``place``'s,
+        checked by the same routines.  ``out`` and ``count`` are ``place(...)``'s, bit for bit.  ``affected[k, :n]``, ``n =
+        min(n_affected[k], A)``: the ``conn_id`` values of the lightpaths of sample ``samples[k]`` that interfere with
+        candidate ``k``, in the sample's first-seen order -- ``to_graph.placement_neighbourhood``'s list, the message order
+        of the candidate's row; the interference rule is symmetric, so they are the only lightpaths whose own
+        neighbourhood the candidate changes.  ``n_affected[k]`` is their true number: more than ``A`` is no error, the
+        first ``A`` are written.  ``before[k, i]``: the eval-mode row of lightpath ``affected[k, i]`` retested as the
+        lightpath under test of the unedited sample; ``after[k, i]``: the same row once the candidate is established next
+        to it (unflagged, ``is_lut`` 0).  The slots behind ``n`` hold -1 / NaN.
+
+        ``materialise_retest`` is the definition: ``before[k, i]`` is, bit for bit, the row ``self(to_graph.device_batch(
+        materialise_retest(status, [samples[k]], [affected[k, i]]), "lightpath", ...))`` gives the node of that conn, and
+        ``after[k, i]`` the same with ``values[k:k + 1]``, the candidate's cells and ``[0, m]`` passed in as well;
+        ``to_graph.placement_impact`` states the nodes and the messages on the host.  The sample's own flagged lightpath,
+        if it has one, stays flagged: it may be one of the affected, and it carries ``is_lut = 1`` where it is a message
+        source.
+
+        Refusals before any launch (``lightpath_place_impact_args``): ``place``'s; ``ValueError`` for a ``max_affected``
+        that is no int in ``1 ... PLACE_MAX_AFFECTED = 32``; ``EnvelopeError`` for a feature list that holds ``osnr``,
+        ``snr`` or ``ber`` -- the retest rewrites those rows.  ``K == 0`` gives empty tensors without a launch.  On the
+        device every refusal of ``place`` applies, with the same status bits: the refused candidate has a NaN ``out`` row,
+        ``count`` 0, ``n_affected`` 0, ``affected`` all -1, ``before`` and ``after`` all NaN; the other candidates are
+        untouched, and ``check_status()`` raises naming the cause.  There is no ``release=`` here."""
+        who = "LightpathPredictor.place_impact"
+        shape = self._check_model()
+        pa = lightpath_place_impact_args(status, shape[0], self.model.is_lut_index, samples, values, cells, cell_ptr,
+                                         features_to_consider, freq_threshold, max_affected, who)
+        sa = pa.status
+        dev = self._device()
+        if status.device != dev:
+            raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
+        p = self._prepare(None, True, shape, samples=pa.K)
+        K, A = pa.K, max_affected
+        out = torch.empty(K, p.O, dtype=torch.float32, device=dev)
+        affected = torch.empty(K, A, dtype=torch.int64, device=dev)
+        n_affected = torch.empty(K, dtype=torch.int64, device=dev)
+        before = torch.empty(K, A, p.O, dtype=torch.float32, device=dev)
+        after = torch.empty(K, A, p.O, dtype=torch.float32, device=dev)
+        if K == 0:
+            return PlaceImpact(out, p.count, affected, n_affected, before, after)
+        picks, ptr = _place_index_lists(dev, pa.samples, pa.cell_ptr)
+        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
+        count = self._launch("qot_lightpath_infer_place_impact", p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L,
+                             sa.Q, sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
+                             values.contiguous(), cells.contiguous(), ptr, pa.M, affected, n_affected, before, after, A)
+        return PlaceImpact(out, count, affected, n_affected, before, after)
 
     @torch.no_grad()
     def sensitivity(self, data, outputs=None, *, per_graph=False, return_attention_weights=False):

@@ -345,6 +345,46 @@ def placement_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexe
     return [int(conn[i]) for i in np.sort(first) if int(conn[i]) in hit]
 
 
+def _sources_of(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], conn_a: int, freq_threshold: float):
+    """``(node, sources)`` of the lightpath ``conn_a`` of ``sample``: its number in first-seen order, and the conn ids, in
+    first-seen order, of the other lightpaths within the threshold of one of its channels on that channel's link
+    (``lut_neighbourhood``'s rule for a lightpath the caller names)."""
+    link_idx, freq_idx, vec = _occupied(sample)
+    conn = vec[feature_indexes["conn_id"], :].astype(np.int64)
+    _, first = np.unique(conn, return_index=True)
+    order = [int(conn[i]) for i in np.sort(first)]
+    hit = set()
+    for t in np.flatnonzero(conn == conn_a):
+        on_link = np.flatnonzero((link_idx == link_idx[t]) & (conn != conn_a))
+        diff = np.abs(freq[freq_idx[t]] - freq[freq_idx[on_link]])
+        hit.update(conn[on_link[(diff > 0) & (diff < freq_threshold)]].tolist())
+    return order.index(conn_a), [c for c in order if c in hit]
+
+
+def placement_impact(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], values_row: np.ndarray, cells,
+                     freq_threshold: float = 0.05):
+    """Which established lightpaths a candidate of ``LightpathPredictor.place_impact`` disturbs and what their rows sum,
+    stated on the host: one tuple ``(conn, node_before, node_after, sources_before, sources_after)`` per affected
+    lightpath, in the sample's first-seen order -- the conns are ``placement_neighbourhood``'s list, because the
+    interference rule is symmetric: the candidate's interferers are the lightpaths the candidate interferes with.
+    ``node_before`` / ``node_after``: the lightpath's number in first-seen order of ``sample`` / of the sample with the
+    candidate placed (``place_lightpath``; its refusals apply), i.e. its node in ``create_lightpath_graph``'s graph of the
+    retest sample without / with the candidate.  ``sources_before`` / ``sources_after``: the conn ids whose messages its row
+    sums there, in message order (first-seen order), each taken from its own sample by the rule of ``lut_neighbourhood``.
+    The candidate fills free channels only, so ``sources_after`` is ``sources_before`` with the candidate's conn inserted
+    at the candidate's first-seen position: behind the lightpaths whose first channel ``l * Q + q`` lies below the smallest
+    of the candidate's cells."""
+    fi = feature_indexes
+    sample, freq = np.asarray(sample, dtype=np.float64), np.asarray(freq, dtype=np.float64)
+    edited, _ = place_lightpath(sample, values_row, cells, fi)
+    out = []
+    for conn in placement_neighbourhood(sample, freq, fi, cells, freq_threshold):
+        node_before, sources_before = _sources_of(sample, freq, fi, conn, freq_threshold)
+        node_after, sources_after = _sources_of(edited, freq, fi, conn, freq_threshold)
+        out.append((conn, node_before, node_after, sources_before, sources_after))
+    return out
+
+
 def topological_links(sample: np.ndarray, feature_indexes: Dict[str, int]):
     """What ``TopologicalPredictor.from_status`` takes of one sample ``[lp_feat, link, freq]``, stated on the host:
     ``(edge_index [2, m] int64, conn [m] int64)``.  The lightpaths are the distinct ``trunc(conn_id)`` of the occupied

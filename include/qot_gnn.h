@@ -1260,6 +1260,41 @@ int qot_topological_infer_place_release(const int64_t* node_ids, const int64_t* 
                                         int64_t n_cells, const int64_t* release, const int64_t* release_ptr, int64_t R,
                                         qot_stream_t stream);
 
+/* ---- the place entry together with a RETEST of the established lightpaths the candidate disturbs, one launch
+ * (LightpathPredictor.place_impact) -- out[k] and count[k] are the place entry's, bit for bit.  The
+ * candidate's interferers are, by symmetry of the interference rule, the only lightpaths of its sample whose own
+ * neighbourhood it changes.  n_affected[k] (int64) is their number; the first A = max_affected of them by rising
+ * first-seen number get a slot i: affected[k, i] (int64 [K, A]) is the lightpath's trunc(conn_id), before[k, i] / after[k,
+ * i] (fp32 [K, A, O]) the row of that lightpath scored as the lightpath under test of sample samples[k] without / with the
+ * candidate established next to it.  "Scored as the lightpath under test": the row that graphs mode of the eval entry
+ * gives the lightpath's node in the QOT_SG_LIGHTPATH graph of the sample in which its channels carry osnr = snr = ber = -1
+ * and -- after -- values[k] with osnr = snr = ber = 0 lies in the candidate's cells: the lightpath's own feature row with 1
+ * in the is_lut column, the messages of its own interferers (found by the status entry's walk over its channels of the
+ * unedited sample) by rising first-seen number with their is_lut as the sample has it, and -- after -- the candidate's
+ * row, is_lut 0, at the candidate's first-seen position: behind the lightpaths whose first channel l * Q + q lies below
+ * the smallest of its cells.  cols must not scale osnr, snr or ber (the caller's check: cols lives on the device).  Slots
+ * i >= min(n_affected[k], A) hold -1 / NaN; n_affected[k] > A is no error.  A refused candidate (the place entry's status
+ * bits, no new one) has a NaN out row, count 0, n_affected 0, affected -1, before and after NaN.  data is never written.
+ * One 256-thread workgroup per candidate: the place entry's cost plus one slot walk per channel of a slotted lightpath and
+ * two rows per slot.
+ *
+ * The argument list is the place entry's up to M, then affected, n_affected, before, after, max_affected.  Return codes
+ * before any launch: the place entry's, QOT_ERR_BADARG for max_affected outside 1 .. QOT_PLACE_MAX_AFFECTED or -- when K >
+ * 0 -- a NULL affected, n_affected, before or after.  K == 0: QOT_OK, no launch. */
+#define QOT_PLACE_MAX_AFFECTED 32           /* retested lightpaths per candidate (their byte maps: 32 x 256 B of LDS) */
+int qot_lightpath_infer_place_impact(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                                     const int64_t* edge_ptr, const int64_t* lut_idx, int64_t n_lut, int64_t N, int64_t E,
+                                     int64_t K, const float* w, const float* att_src, const float* att_dst,
+                                     const float* conv_bias, float slope_att, const float* bn_weight, const float* bn_bias,
+                                     const float* bn_mean, const float* bn_var, float bn_eps, const float* w0, const float* b0,
+                                     const float* w3, const float* b3, float slope_head, float* out, int64_t* count, int F,
+                                     int C, int O, int heads, int lut_col, int32_t* status, const double* data,
+                                     const double* freq, const int64_t* samples, int64_t S, int P, int64_t L, int64_t Q,
+                                     int conn_row, int osnr_row, int snr_row, int ber_row, const double* cols, int ncol,
+                                     double freq_threshold, const double* values, const int64_t* cells,
+                                     const int64_t* cell_ptr, int64_t M, int64_t* affected, int64_t* n_affected, float* before,
+                                     float* after, int max_affected, qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,20 @@ neighbour slot, 0.05 away, does not interfere.  The rows of ``place(release=)`` 
 
     python tools/bench_infer.py --kind lightpath --place 1 8 64 1024 --release 2 [--out profiles/bench_infer_lightpath_place_release.jsonl]
     python tools/bench_infer.py --kind topological --place 1 8 64 1024 --release 2 [--out profiles/bench_infer_topological_place_release.jsonl]
+
+``--kind lightpath --place-impact K [K ...]``: the admission decision's second half -- ``predict.place_impact(status, ...)``
+(csrc/infer_lightpath_place_impact.hip, DESIGN.md 4.25: the K candidates' rows and, in the same launch, the rows of the
+established lightpaths each one disturbs, before and after) against (a) the only way before: two
+``infer.materialise_retest`` calls (one sample per (candidate, interferer) pair, without and with the candidate), each
+followed by ``to_graph.device_batch`` and ``predict`` -- with the pairs worked out on the host beforehand
+(``to_graph.placement_neighbourhood``) and their arguments uploaded, which favours (a) -- and (b) plain ``predict.place`` of
+the same candidates: what the retest costs beyond admission, timed in an alternation of its own.  One
+``synthetic_network_status`` sample on the 60 x 72 grid without a lightpath under test of its own; every candidate takes one
+slot on 1 - 4 links and has two interferers or more (asserted on the inputs); C = 32, F = 5, threshold 0.12,
+``max_affected`` 8.  The rows of ``place_impact`` and (a), and of ``place_impact`` and (b), are compared first (equal bits);
+two medians count as different when they are further apart than the sum of their interquartile ranges.
+
+    python tools/bench_infer.py --kind lightpath --place-impact 1 8 64 1024 [--out profiles/bench_infer_lightpath_place_impact.jsonl]
 """
 import argparse
 import json
@@ -899,6 +913,128 @@ def main_place_release(args, device, commit):
               f"{ratio(r, 'release_pair', 'place')} |")
 
 
+def measure_place_impact(K, device, rounds, warmup, thr=0.12, max_affected=8):
+    """``place_impact`` of K candidates against (a) two ``materialise_retest`` calls + ``device_batch`` + ``predict`` over
+    the (candidate, interferer) pairs, worked out on the host beforehand, and (b) plain ``place`` of the same candidates."""
+    import numpy as np
+    from gnn_qot_estimation_amd import infer, to_graph as TG
+    torch.manual_seed(0)
+    predict = q.LightpathPredictor(q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval())
+    ns = TG.synthetic_network_status(1, seed=0)             # the 60 x 72 grid
+    fi, feats = ns.feature_indexes, list(TG.DEFAULT_FEATURES)
+    data = ns.data.copy()
+    under_test = (data[0, fi["osnr"]] == -1) & (data[0, fi["snr"]] == -1) & (data[0, fi["ber"]] == -1)
+    data[0][:, under_test] = 0.0                            # the sample's own lightpath under test goes, as in --place:
+    L, Q = data.shape[2], data.shape[3]                     # every retest sample of (a) then holds one LUT node, its pair's
+    free = ~np.any(data[0] != 0, axis=0)
+    conn_of = data[0, fi["conn_id"]].astype(np.int64)
+    # per free cell, the lightpaths within two slots on its link (0.10 < thr); a candidate takes one slot on the links where
+    # that set is not empty, as many of them as it needs to meet two lightpaths or more
+    near = {(l, g): {int(conn_of[l, f]) for f in range(max(0, g - 2), min(Q, g + 3)) if not free[l, f]}
+            for l in range(L) for g in range(Q) if free[l, g]}
+    by_slot = {}
+    for (l, g), who in near.items():
+        if who:
+            by_slot.setdefault(g, []).append(l)
+    slots = sorted(g for g, ls in by_slot.items() if len(set().union(*(near[l, g] for l in ls))) >= 2)
+    assert slots, "no slot of the sample lets a candidate meet two lightpaths"
+    rng = np.random.default_rng(K)
+    values, cells, ptr, pairs = np.zeros((K, len(ns.lp_feat))), [], [0], []
+    for k in range(K):
+        slot = slots[int(rng.integers(len(slots)))]
+        links, met = [], set()
+        for l in rng.permutation(by_slot[slot]):
+            links.append(int(l))
+            met |= near[int(l), slot]
+            if len(met) >= 2 and len(links) >= int(rng.integers(1, 5)):
+                break
+        mine = np.stack([np.asarray(links), np.full(len(links), slot)])
+        cells.append(mine)
+        ptr.append(ptr[-1] + len(links))
+        v = values[k]
+        v[fi["conn_id"]], v[fi["src_id"]], v[fi["dst_id"]] = 10000 + k, 1, 2
+        v[fi["mod_order"]], v[fi["path_len"]] = float(rng.choice([4, 8, 16, 32, 64])), float(rng.integers(24214, 7834746))
+        v[fi["num_spans"]], v[fi["freq"]] = float(rng.integers(1, 107)), ns.freq[slot]
+        v[fi["osnr"]] = v[fi["snr"]] = v[fi["ber"]] = -1.0
+        affected = TG.placement_neighbourhood(data[0], ns.freq, fi, mine, thr)
+        assert len(affected) >= 2, (k, affected)            # a condition on the inputs: two interferers or more each
+        pairs += [(k, i, c) for i, c in enumerate(affected[:max_affected])]
+    st = TG.NetworkStatus(data, ns.target, ns.lp_feat, ns.metric, ns.link, ns.freq).to_device(device)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device)       # noqa: E731
+    samples, values_d = torch.zeros(K, dtype=torch.int64, device=device), torch.from_numpy(values).to(device)
+    cells_d, ptr_d = dev(np.concatenate(cells, axis=1)), dev(ptr)
+    # (a)'s arguments, one row per pair, prepared beforehand: which favours (a)
+    T = len(pairs)
+    pk, pi = dev([k for k, _, _ in pairs]), dev([i for _, i, _ in pairs])
+    psamples, pconns, pvalues = torch.zeros(T, dtype=torch.int64, device=device), dev([c for _, _, c in pairs]), values_d[pk]
+    pcells = dev(np.concatenate([cells[k] for k, _, _ in pairs], axis=1))
+    pptr = dev(np.cumsum([0] + [cells[k].shape[1] for k, _, _ in pairs]))
+
+    def retest():
+        before = predict(TG.device_batch(infer.materialise_retest(st, psamples, pconns), "lightpath", feats, None, thr))[0]
+        after = predict(TG.device_batch(infer.materialise_retest(st, psamples, pconns, pvalues, pcells, pptr), "lightpath",
+                                        feats, None, thr))[0]
+        return before, after
+    ways = {"impact": lambda: predict.place_impact(st, samples, values_d, cells_d, ptr_d, feats, thr, max_affected),
+            "retest": retest,
+            "place": lambda: predict.place(st, samples, values_d, cells_d, ptr_d, feats, thr)}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    r = got["impact"]
+    assert torch.equal(r.before[pk, pi], got["retest"][0]) and torch.equal(r.after[pk, pi], got["retest"][1]), K
+    assert torch.equal(r.out, got["place"][0]) and torch.equal(r.count, got["place"][1]) and int(r.n_affected.min()) >= 2
+    assert torch.equal(r.affected[pk, pi], pconns) and bool(torch.isfinite(got["retest"][1]).all())
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    # two alternations, as --release: plain place is not timed right behind (a)'s copies of the sample
+    times = {k: [] for k in ("impact", "retest", "impact_pair", "place")}
+    for _ in range(rounds):
+        times["impact"].append(timed_event(ways["impact"]))
+        times["retest"].append(timed_event(ways["retest"]))
+    for _ in range(warmup):
+        ways["impact"](), ways["place"]()
+    for _ in range(rounds):
+        times["impact_pair"].append(timed_event(ways["impact"]))
+        times["place"].append(timed_event(ways["place"]))
+    res = dict(shape=f"status {L} x {Q}", kind="lightpath_place_impact", K=K, max_affected=max_affected, cells=int(ptr[-1]),
+               pairs=T, affected_min=int(r.n_affected.min()), affected_max=int(r.n_affected.max()),
+               lightpaths=len(set(conn_of[~free].tolist())), S=1, P=int(st.data.shape[1]), L=L, Q=Q, C=32, F=5,
+               freq_threshold=thr, rounds=rounds, equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_place_impact(args, device, commit):
+    rows = []
+    for K in args.place_impact:
+        res = measure_place_impact(K, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| grid | K | pairs | place_impact ms (IQR) | (a) 2 x (materialise_retest + device_batch + predict) ms (IQR) | "
+          "(a) / impact | place_impact beside (b) ms (IQR) | (b) plain place ms (IQR) | impact / (b) |")
+    print("|---|---|---|---|---|---|---|---|---|")
+
+    def ratio(r, num, den):                                 # differ: by more than the sum of the IQRs
+        same = abs(r[num + "_ms"] - r[den + "_ms"]) <= r[num + "_iqr_ms"] + r[den + "_iqr_ms"]
+        return "no difference" if same else f"{r[num + '_ms'] / r[den + '_ms']:.2f}x"
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['L']} x {r['Q']} | {r['K']} | {r['pairs']} | {cell('impact')} | {cell('retest')} | "
+              f"{ratio(r, 'retest', 'impact')} | {cell('impact_pair')} | {cell('place')} | {ratio(r, 'impact_pair', 'place')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -1075,7 +1211,15 @@ def main():
     ap.add_argument("--release", type=int, default=None, metavar="R",
                     help="with --place: every candidate releases R lightpaths of the sample in the same launch (place(..., "
                          "release=)), against materialise_placement(release=) + from_status and against plain place")
+    ap.add_argument("--place-impact", type=int, nargs="+", default=None, metavar="K", dest="place_impact",
+                    help="--kind lightpath: predict.place_impact on K candidates of one status sample against "
+                         "materialise_retest + device_batch + predict over the (candidate, interferer) pairs and against "
+                         "plain place")
     args = ap.parse_args()
+    if args.place_impact is not None and (args.kind != "lightpath" or args.place is not None or args.from_status
+                                          or args.mc is not None or args.grad or args.what_if is not None
+                                          or any(k < 1 for k in args.place_impact)):
+        raise SystemExit("--kind lightpath --place-impact K [K ...] (K >= 1) is a run of its own")
     if args.place is None and (args.links != 60 or args.cells is not None or args.release is not None):
         raise SystemExit("--links, --cells and --release go with --place")
     if args.release is not None and args.release < 1:
@@ -1099,6 +1243,8 @@ def main():
         raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    if args.place_impact is not None:
+        return main_place_impact(args, device, commit)
     if args.place is not None and args.release is not None:
         return main_place_release(args, device, commit)
     if args.place is not None:
