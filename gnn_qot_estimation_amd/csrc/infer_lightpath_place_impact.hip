@@ -17,9 +17,10 @@
 //   1, 2  infer_lightpath_status_dev.hpp's lp_place_scan, as infer_lightpath_place.hip: nb[] holds the interferers.
 //   2b    all four waves: the marked lightpaths are ranked by rising number (slot i < A: the i-th); the conn_id row is
 //         rescanned 256 channels at a time, as phase 2 of infer_lightpath_status.hip does; for a channel of the lightpath j
-//         in slot i the wave that found it runs lp_mark_slots with conn_a = conn_j into nb_i, that lightpath's own byte
-//         map (A x 256 bytes of LDS; plain same-value stores).  The walk runs on the unedited sample: the candidate is
-//         not seen there, and is a source of every affected lightpath by symmetry.
+//         in slot i the wave that found it runs lp_mark_slots(conn_a = conn_j) into nb_i, that lightpath's own byte map
+//         (A x 256 bytes of LDS; plain same-value stores).  The rescan is infer_lightpath_status_dev.hpp's
+//         lp_mark_slotted, shared with infer_lightpath_retest.hip.  The walk runs on the unedited sample: the candidate
+//         is not seen there, and is a source of every affected lightpath by symmetry.
 //   3     wave 0 alone, the others have ended.  For each slot, one after the other: j's sources by rising number -> LDS
 //         (lp_stage_marked), j's own row from its first channel with is_lut forced to 1, lp_row -> before[k, i]; then the
 //         sources at or behind `pos` are staged again one row further (the marks below `pos` are cleared first; the rows
@@ -122,25 +123,7 @@ __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_place_impact_ker
     if (marked && rank < A) slot_lp[rank] = (int16_t)tid;
     const int ns = total < A ? total : A;                          // slots in use
     __syncthreads();
-    for (int base = 0; base < LQ; base += sg::kThreads) {
-        const int c = base + tid;
-        int slot = -1;
-        if (c < LQ) {
-            int64_t conn;
-            if (channel_conn(d, st.P, LQ, st.conn_row, c, conn))
-                for (int i = 0; i < ns; ++i)
-                    if (T.conn[slot_lp[i]] == conn) { slot = i; break; }
-        }
-        unsigned long long mask = __ballot(slot >= 0);
-        while (mask) {                                             // (wave-uniform: this wave's channels of slotted lightpaths)
-            const int src = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const int i = __shfl(slot, src);                       // 0 .. ns - 1
-            const int c1 = base + w * 64 + src;
-            const int l = c1 / st.Q, q1 = c1 - l * st.Q;
-            lp_mark_slots(d, st, LQ, l, q1, freq, T, n, T.conn[slot_lp[i]], maps + i * sg::kCap, lane);
-        }
-    }
+    lp_mark_slotted(d, st, LQ, freq, T, n, slot_lp, ns, maps);     // (infer_lightpath_status_dev.hpp; every slot < ns is in use)
     __syncthreads();
     if (w != 0) return;
 

@@ -6,7 +6,10 @@
 // (lp_mark_slots) and the staging of the marked lightpaths' feature rows by rising lightpath number (lp_stage_marked) --
 // so who interferes, and in which order the messages are summed, is the same code in both.  infer_lightpath_place.hip and
 // infer_lightpath_place_impact.hip (place_impact, DESIGN.md 4.25: the candidate's row and the retest of the lightpaths it
-// disturbs) further share the candidate's arguments (LpPlaceArgs) and phases 1 and 2 of a candidate (lp_place_scan).
+// disturbs) further share the candidate's arguments (LpPlaceArgs) and phases 1 and 2 of a candidate (lp_place_scan);
+// infer_lightpath_place_impact.hip and infer_lightpath_retest.hip (retest, DESIGN.md 4.26: every established lightpath of a
+// sample as the lightpath under test) share the rescan that marks the neighbourhoods of up to 32 slotted lightpaths at once
+// (lp_mark_slotted).
 #pragma once
 #include "infer_lightpath_dev.hpp"
 #include "status_scan_dev.hpp"
@@ -64,6 +67,38 @@ __device__ __forceinline__ int lp_stage_marked(const double* __restrict__ d, con
         na += __popcll(m);
     }
     return na;
+}
+
+// The whole workgroup: the neighbourhoods of up to 32 SLOTTED lightpaths of one sample in one rescan of its conn_id row
+// (phase 2b of infer_lightpath_place_impact.hip, phase 2 of infer_lightpath_retest.hip).  slot_lp[i], i < ns: the
+// lightpath number slot i retests; -1: an empty slot.  256 channels at a time: a channel of the lightpath in slot i (the
+// first slot that holds it) raises its lane in a ballot, and the wave that found it runs lp_mark_slots with conn_a = that
+// lightpath's conn into maps + i * kCap, the slot's own byte map (zeroed by the caller; plain same-value stores).  The
+// caller's barriers stand before (slot_lp, maps, T, freq complete) and behind (the maps complete) the call.
+__device__ __forceinline__ void lp_mark_slotted(const double* __restrict__ d, const LpStatusArgs& st, int LQ, const double* freq,
+                                                const sg::Table& T, int n, const int16_t* slot_lp, int ns, uint8_t* maps) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int base = 0; base < LQ; base += sg::kThreads) {
+        const int c = base + tid;
+        int slot = -1;
+        if (c < LQ) {
+            int64_t conn;
+            if (channel_conn(d, st.P, LQ, st.conn_row, c, conn))
+                for (int i = 0; i < ns; ++i) {
+                    const int j = slot_lp[i];
+                    if (j >= 0 && T.conn[j] == conn) { slot = i; break; }
+                }
+        }
+        unsigned long long mask = __ballot(slot >= 0);
+        while (mask) {                                             // (wave-uniform: this wave's channels of slotted lightpaths)
+            const int src = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const int i = __shfl(slot, src);                       // 0 .. ns - 1
+            const int c1 = base + w * 64 + src;
+            const int l = c1 / st.Q, q1 = c1 - l * st.Q;
+            lp_mark_slots(d, st, LQ, l, q1, freq, T, n, T.conn[slot_lp[i]], maps + i * sg::kCap, lane);
+        }
+    }
 }
 
 // One candidate of LightpathPredictor.place: the raw lp_feat vector values[k] in the channels cells[:, cell_ptr[k] :

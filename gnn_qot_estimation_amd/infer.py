@@ -499,7 +499,7 @@ class _DeviceState:
         self._status.zero_()
         if code:
             causes = (tuple(getattr(self, "_CAUSES", ())) + tuple(getattr(self, "_PLACE_CAUSES", ()))
-                      + tuple(getattr(self, "_RELEASE_CAUSES", ())))
+                      + tuple(getattr(self, "_RELEASE_CAUSES", ())) + tuple(getattr(self, "_RETEST_CAUSES", ())))
             named = "; ".join(text for bit, text in causes if code & bit)
             raise _lib.QotError("%s flagged the batch (status %d): %s%s" % (self._FLAGS[0], code, self._FLAGS[1],
                                                                            named and " -- here: " + named))
@@ -1371,6 +1371,74 @@ def materialise_retest(status, samples, conns, values=None, cells=None, cell_ptr
                                  status.link)
 
 
+RETEST_MAX_LIGHTPATHS = 256     # include/qot_gnn.h: QOT_SG_MAX_LIGHTPATHS, slots per sample of LightpathPredictor.retest
+RETEST_MAX_CHUNK = 32           # include/qot_gnn.h: QOT_LP_RETEST_MAX_CHUNK, slots one workgroup runs one after the other
+LP_RETEST_NO_SUCH_CONN = 4096   # include/qot_gnn.h: QOT_LP_RETEST_NO_SUCH_CONN, the one status bit qot_lightpath_infer_retest adds
+_RETEST_CAUSES = (
+    (LP_RETEST_NO_SUCH_CONN, "retest: a named conn_id is no lightpath of the sample"),
+)
+
+# what LightpathPredictor.retest returns: out [G, M, O] float32, NaN padded; conn [G, M] int64 conn ids, -1 padded; n [G]
+# int64, the lightpaths of each sample (may exceed M); count [G] int64, from_status's count
+Retest = namedtuple("Retest", "out conn n count")
+
+# M; conns: None or the caller's int64 [G, M] tensor; chunk: None (retest_chunk decides) or the caller's int
+_LpRetest = namedtuple("_LpRetest", "status M conns chunk")
+
+
+def retest_chunk(num_samples: int, max_lightpaths: int, compute_units: int) -> int:
+    """Slots per workgroup of ``qot_lightpath_infer_retest``'s grid ``G * ceil(M / chunk)``, ``1 ... RETEST_MAX_CHUNK``, in
+    the manner of ``mc_chunk``.  The grid is that of the largest chunk for which ``G * ceil(M / chunk)`` workgroups still
+    reach the device's compute-unit count (a larger chunk shares the discovery and the rescan of the sample among more
+    slots, but leaves units idle and runs more rows one after the other); the chunk returned is the smallest with that
+    many workgroups, so that they carry equal shares.  Once ``G`` alone fills the device that is the grid of chunk 32
+    (M = 256: 32).  1 when no chunk reaches the device.  Pure host arithmetic; no result of ``retest`` depends on it."""
+    G, M, cus = int(num_samples), int(max_lightpaths), int(compute_units)
+    if not 1 <= M <= RETEST_MAX_LIGHTPATHS:
+        raise ValueError(f"retest_chunk: max_lightpaths must be in 1 ... {RETEST_MAX_LIGHTPATHS}, got {M}")
+    if G < 1 or G * M < cus:
+        return 1
+    need = max(-(-cus // G), 1)                            # workgroups per sample that reach the device
+    largest = M if need <= 1 else (M - 1) // (need - 1)    # largest chunk with ceil(M / chunk) >= need
+    blocks = -(-M // min(largest, RETEST_MAX_CHUNK))
+    return -(-M // blocks)
+
+
+def lightpath_retest_args(status, in_channels, is_lut_index, conns=None, features_to_consider=to_graph.DEFAULT_FEATURES,
+                          freq_threshold=0.05, max_lightpaths=RETEST_MAX_LIGHTPATHS, chunk=None,
+                          who="LightpathPredictor.retest"):
+    """The argument checks of ``LightpathPredictor.retest`` that need no device: returns an ``_LpRetest`` (``status``: the
+    ``_LpStatus`` of ``lightpath_status_args``; ``M``; ``conns``; ``chunk``) or raises -- ``TypeError`` for a ``status``
+    that is no ``DeviceStatus``; ``ValueError`` for a ``chunk`` that is neither ``None`` nor an int in ``1 ...
+    RETEST_MAX_CHUNK``, for ``conns`` that is not an int64 tensor ``[G, M]`` with ``M`` in ``1 ... RETEST_MAX_LIGHTPATHS``
+    on the chunk's device (the call itself compares ``G`` with ``samples``), or -- without ``conns`` -- a ``max_lightpaths``
+    that is no int in that range (with ``conns`` it is ignored); ``EnvelopeError`` for a feature list that holds ``osnr``, ``snr`` or
+    ``ber`` (the retest rewrites those rows); then everything ``lightpath_status_args`` refuses, a chunk on the CPU last."""
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= RETEST_MAX_CHUNK):
+        raise ValueError(f"{who}: chunk must be None or an int in 1 ... {RETEST_MAX_CHUNK}, got {chunk!r}")
+    if conns is None:
+        M = max_lightpaths
+        if isinstance(M, bool) or not isinstance(M, int) or not 1 <= M <= RETEST_MAX_LIGHTPATHS:
+            raise ValueError(f"{who}: max_lightpaths must be an int in 1 ... {RETEST_MAX_LIGHTPATHS}, got {M!r}")
+    else:
+        got = f"{conns.dtype} {tuple(conns.shape)}" if isinstance(conns, torch.Tensor) else type(conns).__name__
+        if (not isinstance(conns, torch.Tensor) or conns.dim() != 2 or conns.dtype != torch.int64
+                or not 1 <= conns.shape[1] <= RETEST_MAX_LIGHTPATHS):
+            raise ValueError(f"{who}: conns must be an int64 tensor [G, M] of conn_id values (-1: an empty slot) with M "
+                             f"in 1 ... {RETEST_MAX_LIGHTPATHS}, got {got}")
+        if conns.device != status.data.device:
+            raise ValueError(f"{who}: conns is on {conns.device}, the status chunk on {status.data.device}")
+        M = int(conns.shape[1])
+    labels = [n for n in features_to_consider if n in _LABEL_ROWS]
+    if labels:
+        raise EnvelopeError(f"{who}: {', '.join(repr(n) for n in labels)} cannot be a feature: retesting a lightpath rewrites "
+                            f"its osnr, snr and ber")
+    sa = lightpath_status_args(status, in_channels, is_lut_index, features_to_consider, freq_threshold, who)
+    return _LpRetest(sa, M, conns, chunk)
+
+
 # what LightpathPredictor._prepare hands to _launch: the model's shape, the batch on dev, which rows (rows mode: batch,
 # idx; graphs mode: a fresh count) and how many
 _LpPrepared = namedtuple("_LpPrepared", "F C O dev x ei batch ptr eptr idx B rows count")
@@ -1408,6 +1476,9 @@ class LightpathPredictor(_DeviceState):
     ``predict.place_impact(status, samples, values, cells, cell_ptr)``: ``place``'s rows together with the retest of the
     established lightpaths each candidate disturbs -- their rows as the lightpath under test before and after the candidate
     is lit -- one launch and no host read (see there).
+    ``predict.retest(status)``: every ESTABLISHED lightpath of the status samples, or a named subset (``conns=``), retested
+    as the lightpath under test -- the standing question about a network state, a margin audit -- one launch and no host
+    read (see there).
 
     Envelope -- ``EnvelopeError`` naming the condition otherwise: a model on the GPU with ``num_layers == 1``, 1 ... 16 input
     features, hidden width 1 ... 256, 1 ... 8 outputs; ``data.x`` of shape ``[N, F]``.  No cap on in-degree, graph size or
@@ -1420,7 +1491,8 @@ class LightpathPredictor(_DeviceState):
                                      "node or a drop position out of range, bit 2 a candidate's feature row without 1.0 "
                                      "in the LUT column; from_status: bit 3 a bad conn_id, bit 4 too many lightpaths, bit 5 "
                                      "a sample number out of range; place: those, bit 6 a bad cell, bit 7 an occupied "
-                                     "cell, bit 8 a conn_id taken, bit 9 values not under test)")
+                                     "cell, bit 8 a conn_id taken, bit 9 values not under test; retest: from_status's, bit "
+                                     "12 a named conn_id the sample does not hold)")
     # the bits of qot_lightpath_infer_status, named when check_status() finds them: the device builder's own words
     _CAUSES = tuple((bit, next(t for b, t in to_graph._SG_CAUSES if b == sg)) for bit, sg in (
         (LP_STATUS_BAD_CONN, to_graph.SG_BAD_CONN), (LP_STATUS_TOO_MANY, to_graph.SG_TOO_MANY),
@@ -1429,6 +1501,8 @@ class LightpathPredictor(_DeviceState):
     _PLACE_CAUSES = _LP_PLACE_CAUSES
     # ... and the two of qot_lightpath_infer_place_release (place with release=), behind those
     _RELEASE_CAUSES = _LP_RELEASE_CAUSES
+    # ... and the one of qot_lightpath_infer_retest (retest with conns=), behind those
+    _RETEST_CAUSES = _RETEST_CAUSES
 
     def __init__(self, model):
         super().__init__()
@@ -1577,17 +1651,7 @@ class LightpathPredictor(_DeviceState):
         dev = self._device()
         if status.device != dev:
             raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
-        if samples is None:
-            picks, G = None, sa.S
-        elif isinstance(samples, torch.Tensor):
-            if samples.dim() != 1 or samples.dtype != torch.int64:
-                raise ValueError(f"{who}: samples must be a sequence or a 1-d int64 tensor, got {samples.dtype} "
-                                 f"{tuple(samples.shape)}")
-            picks = _i64(samples, dev)
-            G = int(picks.shape[0])
-        else:
-            picks = torch.tensor([int(v) for v in samples], dtype=torch.int64).to(dev)
-            G = int(picks.shape[0])
+        picks, G = self._status_picks(samples, sa.S, dev, who)
         p = self._prepare(None, True, shape, samples=G)
         out = torch.empty(G, p.O, dtype=torch.float32, device=dev)
         if G == 0:
@@ -1596,6 +1660,91 @@ class LightpathPredictor(_DeviceState):
         count = self._launch("qot_lightpath_infer_status", p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L, sa.Q,
                              sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold)
         return out, count
+
+    @staticmethod
+    def _status_picks(samples, S, dev, who):
+        """``samples`` of ``from_status`` and ``retest`` as ``(picks, G)``: ``None`` (all ``S``, in order), the caller's 1-d
+        int64 tensor (used in place when it is on ``dev``) or a sequence (uploaded)."""
+        if samples is None:
+            return None, S
+        if isinstance(samples, torch.Tensor):
+            if samples.dim() != 1 or samples.dtype != torch.int64:
+                raise ValueError(f"{who}: samples must be a sequence or a 1-d int64 tensor, got {samples.dtype} "
+                                 f"{tuple(samples.shape)}")
+            picks = _i64(samples, dev)
+        else:
+            picks = torch.tensor([int(v) for v in samples], dtype=torch.int64).to(dev)
+        return picks, int(picks.shape[0])
+
+    @torch.no_grad()
+    def retest(self, status, samples=None, conns=None, features_to_consider=to_graph.DEFAULT_FEATURES, freq_threshold=0.05,
+               max_lightpaths=RETEST_MAX_LIGHTPATHS, *, chunk=None):
+        """The standing question about a network state: the predicted QoT of every lightpath that is already lit, each
+        RETESTED as the lightpath under test, as ``Retest(out [G, M, O] float32, conn [G, M] int64, n [G] int64, count [G]
+        int64)`` in ONE kernel launch (``csrc/infer_lightpath_retest.hip``), with nothing read back and
+        ``status.data`` never written; legal inside ``torch.cuda.graph`` capture under the conditions of ``from_status``
+        (index arguments as int64 device tensors, one call made first).  Margin audits, finding the lightpaths nearest
+        their threshold before admitting more traffic, ranking reroute candidates: one call instead of one edited sample
+        and one graph per lightpath.
+
+        ``status``, ``samples``, ``features_to_consider`` and ``freq_threshold`` are ``from_status``'s, checked by the same
+        routines.  ``n[g]``: the lightpaths of sample ``samples[g]``; ``count[g]``: ``from_status``'s count, the sample's
+        own flagged lightpaths.
+
+        ``conns=None``: every lightpath, ``M = max_lightpaths`` (an int in ``1 ... 256``) slots per sample.  ``conn[g,
+        :min(n, M)]`` are the ``trunc(conn_id)`` values in first-seen order -- the node order of ``to_graph.device_batch(
+        status, "lightpath")`` -- and ``out[g, i]`` the eval-mode row of lightpath ``conn[g, i]``.  The slots behind hold
+        -1 / NaN; ``n[g] > M`` is no error: the first ``M`` are written.  A sample without a lightpath gives ``n = 0``.
+        (Every workgroup of the grid ``G * ceil(M / chunk)`` scans its sample before it knows whether its slots hold a
+        lightpath: with many samples pass a bound on the lightpaths per sample, e.g. ``n.max()`` of an earlier call,
+        rather than 256 -- DESIGN.md 4.26 has the figures.)
+
+        ``conns [G, M]`` (int64, on the chunk's device, used in place; ``M`` in ``1 ... 256``; ``max_lightpaths`` is
+        ignored): a named subset.  Slot ``(g, i)`` retests the lightpath whose ``trunc(conn_id)`` is ``conns[g, i]``; -1
+        marks an empty slot (NaN row, ``conn`` -1, no error); a conn named twice gives equal rows; a conn the sample does
+        not hold gives NaN in that slot only, ``conn[g, i] = -1``, and ``check_status()`` raises naming the cause (status
+        bit ``LP_RETEST_NO_SUCH_CONN = 4096``).
+
+        ``infer.materialise_retest`` is the definition, as for ``place_impact``'s ``before``: ``out[g, i]`` is, bit for
+        bit, the row ``self(to_graph.device_batch(materialise_retest(status, [samples[g]], [conn[g, i]]), "lightpath",
+        ...))`` gives the node of that conn; ``to_graph.retest_neighbourhood`` states the nodes and the messages on the
+        host.  The sample's own flagged lightpath stays flagged: it is retested like the others, and it carries ``is_lut =
+        1`` where it is a message source.
+
+        ``chunk``: the slots one workgroup runs one after the other, ``1 ... 32``; ``None``: ``retest_chunk(G, M,
+        compute_units)``.  Every result is bitwise independent of it.
+
+        Refusals before any launch (``lightpath_retest_args``): ``from_status``'s; ``ValueError`` for a bad
+        ``max_lightpaths``, ``chunk`` or ``conns`` (a bool is no int); ``EnvelopeError`` for a feature list that holds
+        ``osnr``, ``snr`` or ``ber`` -- the retest rewrites those rows.  ``G == 0`` gives empty tensors without a launch.
+        On the device ``from_status``'s three refusals apply (a bad ``conn_id``, more than 256 lightpaths, a sample number
+        outside the chunk): all ``M`` rows of that sample are NaN, its ``conn`` -1, ``n = count = 0``, the other samples
+        are untouched, and ``check_status()`` raises naming the cause.  There is no ``release=``, no retest for the
+        topological model (it has no per-lightpath row), and the rows of one workgroup are computed by one wave."""
+        who = "LightpathPredictor.retest"
+        shape = self._check_model()
+        ra = lightpath_retest_args(status, shape[0], self.model.is_lut_index, conns, features_to_consider, freq_threshold,
+                                   max_lightpaths, chunk, who)
+        sa, M = ra.status, ra.M
+        dev = self._device()
+        if status.device != dev:
+            raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
+        picks, G = self._status_picks(samples, sa.S, dev, who)
+        if conns is not None and int(conns.shape[0]) != G:
+            raise ValueError(f"{who}: conns has {int(conns.shape[0])} rows, samples names {G} samples")
+        p = self._prepare(None, True, shape, samples=G)
+        out = torch.empty(G, M, p.O, dtype=torch.float32, device=dev)
+        conn = torch.empty(G, M, dtype=torch.int64, device=dev)
+        n = torch.empty(G, dtype=torch.int64, device=dev)
+        if G == 0:
+            return Retest(out, conn, n, p.count)
+        if chunk is None:
+            chunk = retest_chunk(G, M, torch.cuda.get_device_properties(dev).multi_processor_count)
+        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
+        count = self._launch("qot_lightpath_infer_retest", p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L, sa.Q,
+                             sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
+                             None if conns is None else conns.contiguous(), conn, n, M, chunk)
+        return Retest(out, conn, n, count)
 
     @torch.no_grad()
     def place(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES,

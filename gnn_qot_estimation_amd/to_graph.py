@@ -361,6 +361,21 @@ def _sources_of(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str,
     return order.index(conn_a), [c for c in order if c in hit]
 
 
+def retest_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], freq_threshold: float = 0.05):
+    """What ``LightpathPredictor.retest`` takes of one sample ``[lp_feat, link, freq]``, stated on the host: one tuple
+    ``(conn, node, sources)`` per lightpath of the sample, in first-seen order -- so ``node`` counts 0, 1, ...: the
+    lightpath's node in ``create_lightpath_graph``'s graph of the sample, with or without that lightpath flagged
+    (``infer.materialise_retest`` changes ``osnr``, ``snr`` and ``ber`` only, hence nobody's channels).  ``sources``: the conn
+    ids whose messages the lightpath's row sums when it is retested, in message order (first-seen order), by the rule of
+    ``lut_neighbourhood`` for a lightpath the caller names.  An empty sample gives ``[]``."""
+    fi = feature_indexes
+    sample, freq = np.asarray(sample, dtype=np.float64), np.asarray(freq, dtype=np.float64)
+    _, _, vec = _occupied(sample)
+    conn = vec[fi["conn_id"], :].astype(np.int64)
+    _, first = np.unique(conn, return_index=True)
+    return [(int(conn[i]),) + _sources_of(sample, freq, fi, int(conn[i]), freq_threshold) for i in np.sort(first)]
+
+
 def placement_impact(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], values_row: np.ndarray, cells,
                      freq_threshold: float = 0.05):
     """Which established lightpaths a candidate of ``LightpathPredictor.place_impact`` disturbs and what their rows sum,

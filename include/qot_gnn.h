@@ -1295,6 +1295,39 @@ int qot_lightpath_infer_place_impact(const float* x, const int64_t* edge_index, 
                                      const int64_t* cell_ptr, int64_t M, int64_t* affected, int64_t* n_affected, float* before,
                                      float* after, int max_affected, qot_stream_t stream);
 
+/* ---- every ESTABLISHED lightpath of a network-status sample, or a named subset, retested as the lightpath under test in
+ * one launch (LightpathPredictor.retest) -- Sample samples[g] (NULL: sample g) has n[g] (int64) lightpaths
+ * and count[g] flagged ones (the status entry's count).  M = max_lightpaths slots per sample: conn[g, i] (int64 [G, M]) is
+ * the trunc(conn_id) of the lightpath in slot i, out[g, i] (fp32 [G, M, O]) that lightpath "scored as the lightpath under
+ * test" as the place_impact entry defines it for `before`: its own feature row with 1 in the is_lut column, the messages of
+ * its own interferers by rising first-seen number with their is_lut as the sample has it.  conns == NULL: slot i holds
+ * lightpath number i of the first-seen order (the node order of the QOT_SG_LIGHTPATH graph) while i < n[g]; n[g] > M is no
+ * error.  conns (int64 [G, M]): slot i holds the lightpath whose conn is conns[g, i]; -1 is an empty slot; a conn named
+ * twice gives equal rows; a conn the sample does not hold leaves the slot empty and sets QOT_LP_RETEST_NO_SUCH_CONN.  An
+ * empty slot holds conn -1 and a NaN row.  cols must not scale osnr, snr or ber (the caller's check).  data is never
+ * written.  G * ceil(M / chunk) 256-thread workgroups; a workgroup discovers its sample, marks the neighbourhoods of its
+ * chunk slots in one rescan and computes their rows one after the other in one wave, so no result depends on chunk.
+ *
+ * The argument list is the status entry's up to freq_threshold, then conns, conn, n, max_lightpaths, chunk.  Return codes
+ * before any launch: the status entry's, QOT_ERR_BADARG for max_lightpaths outside 1 .. QOT_SG_MAX_LIGHTPATHS or chunk
+ * outside 1 .. QOT_LP_RETEST_MAX_CHUNK, QOT_ERR_UNSUPPORTED for G * ceil(M / chunk) >= 2^31, QOT_ERR_BADARG -- when G > 0 --
+ * for a NULL conn or n.  G == 0: QOT_OK, no launch.
+ * status: QOT_LP_STATUS_BAD_CONN / TOO_MANY / BAD_SAMPLE as the status entry -- all M rows of that sample NaN, its conn
+ * -1, n = count = 0, the other samples untouched -- and the bit below.  Nothing read from data or conns is used as an
+ * index: conns are only compared. */
+#define QOT_LP_RETEST_MAX_CHUNK 32          /* slots one workgroup runs one after the other (their byte maps: 32 x 256 B of LDS) */
+#define QOT_LP_RETEST_NO_SUCH_CONN 4096     /* a named conn that is no lightpath of the sample */
+int qot_lightpath_infer_retest(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                               const int64_t* edge_ptr, const int64_t* lut_idx, int64_t n_lut, int64_t N, int64_t E, int64_t G,
+                               const float* w, const float* att_src, const float* att_dst, const float* conv_bias,
+                               float slope_att, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                               const float* bn_var, float bn_eps, const float* w0, const float* b0, const float* w3,
+                               const float* b3, float slope_head, float* out, int64_t* count, int F, int C, int O, int heads,
+                               int lut_col, int32_t* status, const double* data, const double* freq, const int64_t* samples,
+                               int64_t S, int P, int64_t L, int64_t Q, int conn_row, int osnr_row, int snr_row, int ber_row,
+                               const double* cols, int ncol, double freq_threshold, const int64_t* conns, int64_t* conn,
+                               int64_t* n, int max_lightpaths, int chunk, qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,18 @@ slot on 1 - 4 links and has two interferers or more (asserted on the inputs); C 
 two medians count as different when they are further apart than the sum of their interquartile ranges.
 
     python tools/bench_infer.py --kind lightpath --place-impact 1 8 64 1024 [--out profiles/bench_infer_lightpath_place_impact.jsonl]
+
+``--kind lightpath --retest S [S ...]``: the standing question about a network state -- ``predict.retest(status)``
+(csrc/infer_lightpath_retest.hip, DESIGN.md 4.26: every established lightpath of S status samples retested as the lightpath
+under test, one launch) against (a) the only way before: ``infer.materialise_retest`` over all (sample, lightpath) pairs --
+one edited copy of a sample per pair -- then ``to_graph.device_batch`` and ``predict``, with the pairs worked out on the
+host beforehand and uploaded, which favours (a); and (b) ``predict.from_status`` of the same samples, one row per sample:
+what a retested row costs beside it, timed in an alternation of its own.  S ``synthetic_network_status`` samples on the 60 x
+72 grid, each with its own lightpath under test; C = 32, F = 5, threshold 0.12, ``max_lightpaths`` 256, ``chunk`` as
+``infer.retest_chunk`` picks it (reported).  The rows of ``retest`` and (a) are compared first (equal bits); two medians
+count as different when they are further apart than the sum of their interquartile ranges.
+
+    python tools/bench_infer.py --kind lightpath --retest 1 8 64 512 [--out profiles/bench_infer_lightpath_retest.jsonl]
 """
 import argparse
 import json
@@ -1035,6 +1047,96 @@ def main_place_impact(args, device, commit):
               f"{ratio(r, 'retest', 'impact')} | {cell('impact_pair')} | {cell('place')} | {ratio(r, 'impact_pair', 'place')} |")
 
 
+def measure_retest(S, device, rounds, warmup, thr=0.12, max_lightpaths=256):
+    """``retest`` of every lightpath of S status samples against (a) ``materialise_retest`` over all (sample, lightpath)
+    pairs + ``device_batch`` + ``predict`` -- the pairs worked out on the host beforehand -- and (b) ``from_status`` of the
+    same samples: one row per sample."""
+    import numpy as np
+    from gnn_qot_estimation_amd import infer, to_graph as TG
+    torch.manual_seed(0)
+    predict = q.LightpathPredictor(q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval())
+    ns = TG.synthetic_network_status(S, seed=0)             # the 60 x 72 grid
+    fi, feats = ns.feature_indexes, list(TG.DEFAULT_FEATURES)
+    L, Q = ns.data.shape[2], ns.data.shape[3]
+    orders = []                                             # per sample: its conns in first-seen (scan) order
+    for s in range(S):
+        occupied = np.any(ns.data[s] != 0, axis=0).ravel()
+        conn = ns.data[s, fi["conn_id"]].ravel()[occupied].astype(np.int64)
+        _, first = np.unique(conn, return_index=True)
+        orders.append(conn[np.sort(first)].tolist())
+    pairs = [(s, i, c) for s in range(S) for i, c in enumerate(orders[s][:max_lightpaths])]
+    T = len(pairs)
+    st = ns.to_device(device)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device)       # noqa: E731
+    ps, pi, pconns = dev([s for s, _, _ in pairs]), dev([i for _, i, _ in pairs]), dev([c for _, _, c in pairs])
+    chunk = infer.retest_chunk(S, max_lightpaths, torch.cuda.get_device_properties(device).multi_processor_count)
+
+    def materialise():
+        batch = TG.device_batch(infer.materialise_retest(st, ps, pconns), "lightpath", feats, None, thr)
+        return predict(batch)[0], batch
+    ways = {"retest": lambda: predict.retest(st, None, None, feats, thr, max_lightpaths),
+            "materialise": materialise,
+            "from_status": lambda: predict.from_status(st, None, feats, thr)}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    r, (rows, batch) = got["retest"], got["materialise"]
+    luts = predict.model._lut_rows(batch)
+    at = torch.searchsorted(luts, batch.ptr.to(device)[:-1] + pi)
+    assert torch.equal(luts[at], batch.ptr.to(device)[:-1] + pi)
+    assert torch.equal(r.out[ps, pi], rows[at]) and bool(torch.isfinite(rows[at]).all()), S       # equal bits
+    assert torch.equal(r.conn[ps, pi], pconns) and r.n.tolist() == [len(o) for o in orders]
+    assert torch.equal(r.count, got["from_status"][1])
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    # two alternations, as --place-impact: from_status is not timed right behind (a)'s copies of the samples
+    times = {k: [] for k in ("retest", "materialise", "retest_pair", "from_status")}
+    for _ in range(rounds):
+        times["retest"].append(timed_event(ways["retest"]))
+        times["materialise"].append(timed_event(ways["materialise"]))
+    for _ in range(warmup):
+        ways["retest"](), ways["from_status"]()
+    for _ in range(rounds):
+        times["retest_pair"].append(timed_event(ways["retest"]))
+        times["from_status"].append(timed_event(ways["from_status"]))
+    res = dict(shape=f"status {L} x {Q}", kind="lightpath_retest", S=S, max_lightpaths=max_lightpaths, chunk=chunk, pairs=T,
+               lightpaths_min=int(r.n.min()), lightpaths_max=int(r.n.max()), P=int(st.data.shape[1]), L=L, Q=Q, C=32, F=5,
+               freq_threshold=thr, rounds=rounds, equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_retest(args, device, commit):
+    rows = []
+    for S in args.retest:
+        res = measure_retest(S, device, args.rounds, args.warmup, max_lightpaths=args.max_lightpaths)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| grid | S | pairs | chunk | retest ms (IQR) | (a) materialise_retest + device_batch + predict ms (IQR) | "
+          "(a) / retest | retest beside (b) ms (IQR) | (b) from_status ms (IQR) | retest / (b) |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+
+    def ratio(r, num, den):                                 # differ: by more than the sum of the IQRs
+        same = abs(r[num + "_ms"] - r[den + "_ms"]) <= r[num + "_iqr_ms"] + r[den + "_iqr_ms"]
+        return "no difference" if same else f"{r[num + '_ms'] / r[den + '_ms']:.2f}x"
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['L']} x {r['Q']} | {r['S']} | {r['pairs']} | {r['chunk']} | {cell('retest')} | {cell('materialise')} | "
+              f"{ratio(r, 'materialise', 'retest')} | {cell('retest_pair')} | {cell('from_status')} | "
+              f"{ratio(r, 'retest_pair', 'from_status')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -1215,7 +1317,19 @@ def main():
                     help="--kind lightpath: predict.place_impact on K candidates of one status sample against "
                          "materialise_retest + device_batch + predict over the (candidate, interferer) pairs and against "
                          "plain place")
+    ap.add_argument("--retest", type=int, nargs="+", default=None, metavar="S",
+                    help="--kind lightpath: predict.retest on every lightpath of S status samples against materialise_retest "
+                         "+ device_batch + predict over the (sample, lightpath) pairs and against from_status")
+    ap.add_argument("--max-lightpaths", type=int, default=256, metavar="M", dest="max_lightpaths",
+                    help="with --retest: the slots per sample (the grid is S * ceil(M / chunk) workgroups, each of which "
+                         "discovers its sample: 32 against 256 tells what the workgroups without a lightpath cost)")
     args = ap.parse_args()
+    if args.retest is None and args.max_lightpaths != 256:
+        raise SystemExit("--max-lightpaths goes with --retest")
+    if args.retest is not None and (args.kind != "lightpath" or args.place is not None or args.from_status
+                                    or args.mc is not None or args.grad or args.what_if is not None
+                                    or args.place_impact is not None or any(s < 1 for s in args.retest)):
+        raise SystemExit("--kind lightpath --retest S [S ...] (S >= 1) is a run of its own")
     if args.place_impact is not None and (args.kind != "lightpath" or args.place is not None or args.from_status
                                           or args.mc is not None or args.grad or args.what_if is not None
                                           or any(k < 1 for k in args.place_impact)):
@@ -1245,6 +1359,8 @@ def main():
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     if args.place_impact is not None:
         return main_place_impact(args, device, commit)
+    if args.retest is not None:
+        return main_retest(args, device, commit)
     if args.place is not None and args.release is not None:
         return main_place_release(args, device, commit)
     if args.place is not None:
