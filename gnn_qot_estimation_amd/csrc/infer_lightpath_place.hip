@@ -35,7 +35,7 @@ namespace qot {
 namespace {
 
 __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_place_kernel(const LpArgs a, const LpStatusArgs st,
-                                                                             const LpPlaceArgs pl) {
+                                                                             const sg::PlaceArgs pl) {
     __shared__ sg::Table T;
     __shared__ double freq[sg::kQCap];
     __shared__ LpLds L;
@@ -48,9 +48,9 @@ __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_place_kernel(con
     const int64_t k = blockIdx.x;
     float* orow = a.out + k * a.O;
 
-    // ---- phases 1 and 2 (infer_lightpath_status_dev.hpp, shared with infer_lightpath_place_impact.hip) ----
+    // ---- phases 1 and 2 (infer_lightpath_status_dev.hpp, shared with the place_impact and place_release kernels) ----
     LpPlaceScan r;
-    const int bad = lp_place_scan(st, pl, k, T, freq, nb, lut_mask, &bad_all, r);    // (block-uniform, behind a barrier)
+    const int bad = lp_place_scan<false>(st, pl, sg::ReleaseArgs{}, k, T, freq, nb, lut_mask, &bad_all, nullptr, r);   // (block-uniform)
     if (w != 0) return;
     if (bad) {
         if (lane == 0) st.count[k] = 0;
@@ -96,15 +96,14 @@ extern "C" int qot_lightpath_infer_place(const float* x, const int64_t* edge_ind
     if (rc != QOT_OK) return rc;
     if (M < 0) return QOT_ERR_BADARG;
     if (K == 0) return QOT_OK;
-    if (!w || !att_src || !att_dst || !conv_bias || !bn_weight || !bn_bias || !bn_mean || !bn_var || !w0 || !b0 || !w3 || !b3 ||
-        !out || !count || !data || !freq || !cols || S == 0 || !samples || !values || !cell_ptr || (M > 0 && !cells))
+    const LpArgs a = lp_status_args(K, w, att_src, att_dst, conv_bias, slope_att, bn_weight, bn_bias, bn_mean, bn_var, bn_eps,
+                                    w0, b0, w3, b3, slope_head, out, F, C, O, lut_col, status);
+    if (!lp_weights_present(a) || !out || !count || !data || !freq || !cols || S == 0 || !samples || !values || !cell_ptr ||
+        (M > 0 && !cells))
         return QOT_ERR_BADARG;
-    const LpArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, K, w, att_src, att_dst, conv_bias, slope_att,
-                   bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, nullptr, F, C, O, lut_col,
-                   status};
     const LpStatusArgs st{data, freq, samples, S, P, (int)L, (int)Q, conn_row, osnr_row, snr_row, ber_row, cols,
                           freq_threshold, count};
-    const LpPlaceArgs pl{values, cells, cell_ptr, M};
+    const sg::PlaceArgs pl{values, cells, cell_ptr, M};
     lightpath_infer_place_kernel<<<(int)K, sg::kThreads, 0, stream>>>(a, st, pl);
     QOT_LAUNCH_CHECK();
     return QOT_OK;

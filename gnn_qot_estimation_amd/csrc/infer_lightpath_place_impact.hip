@@ -62,7 +62,7 @@ __device__ __forceinline__ void lp_impact_pad(const LpArgs& a, const LpImpactArg
 }
 
 __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_place_impact_kernel(const LpArgs a, const LpStatusArgs st,
-                                                                                    const LpPlaceArgs pl,
+                                                                                    const sg::PlaceArgs pl,
                                                                                     const LpImpactArgs im) {
     __shared__ sg::Table T;
     __shared__ double freq[sg::kQCap];
@@ -84,9 +84,9 @@ __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_place_impact_ker
     for (int t = tid; t < A * (sg::kCap / 4); t += sg::kThreads) nbs[t] = 0;
     if (tid == 0) cmin = 0x7fffffff;
 
-    // ---- phases 1 and 2 (infer_lightpath_status_dev.hpp, shared with infer_lightpath_place.hip) ----
+    // ---- phases 1 and 2 (infer_lightpath_status_dev.hpp, shared with the place and place_release kernels) ----
     LpPlaceScan r;
-    const int bad = lp_place_scan(st, pl, k, T, freq, nb, lut_mask, &bad_all, r);    // (block-uniform)
+    const int bad = lp_place_scan<false>(st, pl, sg::ReleaseArgs{}, k, T, freq, nb, lut_mask, &bad_all, nullptr, r);   // (block-uniform)
     if (bad) {
         if (w == 0) {
             if (lane == 0) {
@@ -212,16 +212,14 @@ extern "C" int qot_lightpath_infer_place_impact(const float* x, const int64_t* e
     if (rc != QOT_OK) return rc;
     if (M < 0 || max_affected < 1 || max_affected > kLpMaxAffected) return QOT_ERR_BADARG;
     if (K == 0) return QOT_OK;
-    if (!w || !att_src || !att_dst || !conv_bias || !bn_weight || !bn_bias || !bn_mean || !bn_var || !w0 || !b0 || !w3 || !b3 ||
-        !out || !count || !data || !freq || !cols || S == 0 || !samples || !values || !cell_ptr || (M > 0 && !cells) ||
-        !affected || !n_affected || !before || !after)
+    const LpArgs a = lp_status_args(K, w, att_src, att_dst, conv_bias, slope_att, bn_weight, bn_bias, bn_mean, bn_var, bn_eps,
+                                    w0, b0, w3, b3, slope_head, out, F, C, O, lut_col, status);
+    if (!lp_weights_present(a) || !out || !count || !data || !freq || !cols || S == 0 || !samples || !values || !cell_ptr ||
+        (M > 0 && !cells) || !affected || !n_affected || !before || !after)
         return QOT_ERR_BADARG;
-    const LpArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, K, w, att_src, att_dst, conv_bias, slope_att,
-                   bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, nullptr, F, C, O, lut_col,
-                   status};
     const LpStatusArgs st{data, freq, samples, S, P, (int)L, (int)Q, conn_row, osnr_row, snr_row, ber_row, cols,
                           freq_threshold, count};
-    const LpPlaceArgs pl{values, cells, cell_ptr, M};
+    const sg::PlaceArgs pl{values, cells, cell_ptr, M};
     const LpImpactArgs im{affected, n_affected, before, after, max_affected};
     lightpath_infer_place_impact_kernel<<<(int)K, sg::kThreads, 0, stream>>>(a, st, pl, im);
     QOT_LAUNCH_CHECK();

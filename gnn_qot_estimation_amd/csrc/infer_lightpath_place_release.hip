@@ -11,7 +11,9 @@
 // walk on the UNEDITED sample with the gone lightpaths' marks cleared, staged by rising first-seen number of the unedited
 // table -- the survivors' relative order -- with the self loop last.
 //
-// One workgroup (256 threads) per candidate:
+// One workgroup (256 threads) per candidate.  Phases 0 to 2 are infer_lightpath_status_dev.hpp's lp_place_scan<true>, the
+// scan of infer_lightpath_place.hip with the release interleaved; the release rule itself (the slice, who is gone, when an
+// occupied cell is legal) does not depend on the model and is status_scan_dev.hpp's sg::release_* over sg::Release:
 //   0  the release slice, checked against [0, R] and the cap of 32 before `release` is read, -> LDS.
 //   1  discover() on the unedited sample; thread t compares lightpath t's conn with the slice (gone[t]; every slice entry
 //      that meets a lightpath is ticked), and -- a survivor only -- reads its is_lut flag and compares its conn with the
@@ -35,138 +37,39 @@
 namespace qot {
 namespace {
 
-constexpr int kLpMaxRelease = QOT_PLACE_MAX_RELEASE;     // 32
-
-struct LpPlaceReleaseArgs {
-    const double* values;               // [K, P] raw lp_feat vectors
-    const int64_t* cells;               // [2, M]: link indices, then frequency indices
-    const int64_t* cell_ptr;            // [K + 1]
-    int64_t M;
-    const int64_t* release;             // [R] conn_id values
-    const int64_t* release_ptr;         // [K + 1]
-    int64_t R;
-};
-
 __global__ __launch_bounds__(sg::kThreads) void lightpath_infer_place_release_kernel(const LpArgs a, const LpStatusArgs st,
-                                                                                     const LpPlaceReleaseArgs pl) {
+                                                                                     const sg::PlaceArgs pl,
+                                                                                     const sg::ReleaseArgs rl) {
     __shared__ sg::Table T;
     __shared__ double freq[sg::kQCap];
     __shared__ LpLds L;
     __shared__ float rows[sg::kCap * kLpXs];
     __shared__ float xi[kLpMaxF];
     __shared__ uint8_t nb[sg::kCap];
-    __shared__ uint8_t gone[sg::kCap];
-    __shared__ int64_t rel[kLpMaxRelease];
-    __shared__ uint8_t found[kLpMaxRelease];
-    __shared__ unsigned long long lut_mask[sg::kWaves], gone_mask[sg::kWaves];
+    __shared__ sg::Release rs;
+    __shared__ unsigned long long lut_mask[sg::kWaves];
     __shared__ int bad_all;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t k = blockIdx.x;
     float* orow = a.out + k * a.O;
-    const double* v = pl.values + k * (int64_t)st.P;
 
-    // ---- what the candidate's own arguments say (every value is uniform over the block) ----
-    bool ok;
-    const int64_t s = sg::sample_of(st.samples, k, st.S, ok);
-    const int64_t lo = pl.cell_ptr[k], hi = pl.cell_ptr[k + 1];
-    const int64_t rlo = pl.release_ptr[k], rhi = pl.release_ptr[k + 1];
-    int64_t conn_a = 0;
-    int early = ok ? 0 : QOT_LP_STATUS_BAD_SAMPLE;
-    if (lo < 0 || hi <= lo || hi > pl.M) early |= QOT_LP_PLACE_BAD_CELL;
-    if (rlo < 0 || rhi < rlo || rhi > pl.R || rhi - rlo > kLpMaxRelease) early |= QOT_LP_PLACE_BAD_RELEASE;
-    if (!sg::sg_conn(v[st.conn_row], conn_a)) early |= QOT_LP_STATUS_BAD_CONN;
-    if (!sg::sg_is_lut_vec(v, st.osnr_row, st.snr_row, st.ber_row)) early |= QOT_LP_PLACE_NOT_LUT;
-    if (early) {                                                   // block-uniform
-        if (w == 0) {
-            if (lane == 0) st.count[k] = 0;
-            lp_refuse(a, orow, lane, early);
-        }
-        return;
-    }
-    const int nr = (int)(rhi - rlo);                               // 0 .. 32
-    const int LQ = st.L * st.Q;
-    const double* d = st.data + s * (int64_t)st.P * LQ;
-    for (int q = tid; q < st.Q; q += sg::kThreads) freq[q] = st.freq[q];
-    nb[tid] = 0;
-    if (tid < nr) {
-        rel[tid] = pl.release[rlo + tid];
-        found[tid] = 0;
-    }
-    if (tid == 0) bad_all = 0;
-
-    // ---- phase 1: the lightpaths of the unedited sample; who is gone; the survivors' flags and conns ----
-    const int bad = sg::discover(d, st.P, LQ, st.conn_row, T, nullptr);      // (begins and ends with a barrier)
-    const int n = T.n;
-    int mine = ((bad & QOT_SG_BAD_CONN) ? QOT_LP_STATUS_BAD_CONN : 0) | ((bad & QOT_SG_TOO_MANY) ? QOT_LP_STATUS_TOO_MANY : 0);
-    bool g = false;
-    if (tid < n) {
-        const int64_t conn = T.conn[tid];
-        for (int j = 0; j < nr; ++j)
-            if (rel[j] == conn) {                                  // (a conn named twice: both entries are ticked)
-                g = true;
-                found[j] = 1;
-            }
-        if (!g && conn == conn_a) mine |= QOT_LP_PLACE_CONN_TAKEN;
-    }
-    gone[tid] = g ? 1 : 0;
-    const bool flag = tid < n && !g && sg::sg_is_lut(d, LQ, st.osnr_row, st.snr_row, st.ber_row, T.first[tid]);
-    const unsigned long long fm = __ballot(flag), gm = __ballot(g);
-    if (lane == 0) {
-        lut_mask[w] = fm;
-        gone_mask[w] = gm;
-    }
-    if (mine) atomicOr(&bad_all, mine);
-    __syncthreads();
-    int cnt = 1, n_gone = 0;                                       // the candidate itself
-#pragma unroll
-    for (int j = 0; j < sg::kWaves; ++j) {
-        cnt += __popcll(lut_mask[j]);
-        n_gone += __popcll(gone_mask[j]);
-    }
-    mine = 0;
-    if (tid < nr && !found[tid]) mine |= QOT_LP_PLACE_NO_SUCH_CONN;
-    if (tid == 0 && n - n_gone >= sg::kCap) mine |= QOT_LP_STATUS_TOO_MANY;   // the edited sample would hold 257
-    if (mine) atomicOr(&bad_all, mine);
-    __syncthreads();
-    if (bad_all) {                                                 // block-uniform
-        if (w == 0) {
-            if (lane == 0) st.count[k] = 0;
-            lp_refuse(a, orow, lane, bad_all);
-        }
-        return;
-    }
-    __syncthreads();                                               // (bad_all is written again below)
-
-    // ---- phase 2: the candidate's cells, a wave each ----
-    for (int64_t c = lo + w; c < hi; c += sg::kWaves) {            // (wave-uniform)
-        const int64_t l = pl.cells[c], q1 = pl.cells[pl.M + c];
-        int cell = 0;
-        int64_t conn;
-        if (l < 0 || l >= st.L || q1 < 0 || q1 >= st.Q) {
-            cell = QOT_LP_PLACE_BAD_CELL;
-        } else if (channel_conn(d, st.P, LQ, st.conn_row, (int)l * st.Q + (int)q1, conn)) {
-            bool freed = false;                                    // occupied: legal when its owner is gone
-            for (int i = lane; i < n; i += kWave) freed |= (T.conn[i] == conn && gone[i] != 0);
-            if (!__any(freed)) cell = QOT_LP_PLACE_OCCUPIED;
-        }
-        if (cell) {
-            if (lane == 0) atomicOr(&bad_all, cell);
-            continue;
-        }
-        lp_mark_slots(d, st, LQ, (int)l, (int)q1, freq, T, n, conn_a, nb, lane);
-    }
-    __syncthreads();
+    // ---- phases 0 to 2 (infer_lightpath_status_dev.hpp's scan in its release form) ----
+    LpPlaceScan r;
+    const int bad = lp_place_scan<true>(st, pl, rl, k, T, freq, nb, lut_mask, &bad_all, &rs, r);     // (block-uniform)
     if (w != 0) return;
-    if (bad_all) {                                                 // (wave-uniform)
+    if (bad) {
         if (lane == 0) st.count[k] = 0;
-        lp_refuse(a, orow, lane, bad_all);
+        lp_refuse(a, orow, lane, bad);
         return;
     }
-    if (lane == 0) st.count[k] = cnt;
+    const double* d = r.d;
+    const double* v = r.v;
+    const int LQ = r.LQ, n = r.n;
+    if (lane == 0) st.count[k] = r.cnt;
 
     // ---- phase 3: the gone send no message; the survivors' rows by rising lightpath number, then the row ----
     for (int j = lane; j < n; j += kWave)                          // (lp_stage_marked's lane j reads the bytes lane j wrote)
-        if (gone[j]) nb[j] = 0;
+        if (rs.gone[j]) nb[j] = 0;
     const int na = lp_stage_marked(d, st, LQ, a.F, T, n, nb, rows, lane);
     if (lane < a.F) xi[lane] = sg::sg_feature_vec(v, st.P, st.osnr_row, st.snr_row, st.ber_row, st.cols, lane);
     __syncthreads();
@@ -203,17 +106,16 @@ extern "C" int qot_lightpath_infer_place_release(const float* x, const int64_t* 
     if (rc != QOT_OK) return rc;
     if (M < 0 || R < 0) return QOT_ERR_BADARG;
     if (K == 0) return QOT_OK;
-    if (!w || !att_src || !att_dst || !conv_bias || !bn_weight || !bn_bias || !bn_mean || !bn_var || !w0 || !b0 || !w3 || !b3 ||
-        !out || !count || !data || !freq || !cols || S == 0 || !samples || !values || !cell_ptr || (M > 0 && !cells) ||
-        !release_ptr || (R > 0 && !release))
+    const LpArgs a = lp_status_args(K, w, att_src, att_dst, conv_bias, slope_att, bn_weight, bn_bias, bn_mean, bn_var, bn_eps,
+                                    w0, b0, w3, b3, slope_head, out, F, C, O, lut_col, status);
+    if (!lp_weights_present(a) || !out || !count || !data || !freq || !cols || S == 0 || !samples || !values || !cell_ptr ||
+        (M > 0 && !cells) || !release_ptr || (R > 0 && !release))
         return QOT_ERR_BADARG;
-    const LpArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, K, w, att_src, att_dst, conv_bias, slope_att,
-                   bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, nullptr, F, C, O, lut_col,
-                   status};
     const LpStatusArgs st{data, freq, samples, S, P, (int)L, (int)Q, conn_row, osnr_row, snr_row, ber_row, cols,
                           freq_threshold, count};
-    const LpPlaceReleaseArgs pl{values, cells, cell_ptr, M, release, release_ptr, R};
-    lightpath_infer_place_release_kernel<<<(int)K, sg::kThreads, 0, stream>>>(a, st, pl);
+    const sg::PlaceArgs pl{values, cells, cell_ptr, M};
+    const sg::ReleaseArgs rl{release, release_ptr, R};
+    lightpath_infer_place_release_kernel<<<(int)K, sg::kThreads, 0, stream>>>(a, st, pl, rl);
     QOT_LAUNCH_CHECK();
     return QOT_OK;
 }

@@ -138,12 +138,9 @@ extern "C" int qot_lightpath_infer_status(const float* x, const int64_t* edge_in
                                       S, P, L, Q, conn_row, osnr_row, snr_row, ber_row, ncol, freq_threshold);
     if (rc != QOT_OK) return rc;
     if (G == 0) return QOT_OK;
-    if (!w || !att_src || !att_dst || !conv_bias || !bn_weight || !bn_bias || !bn_mean || !bn_var || !w0 || !b0 || !w3 || !b3 ||
-        !out || !count || !data || !freq || !cols || S == 0)
-        return QOT_ERR_BADARG;
-    const LpArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, G, w, att_src, att_dst, conv_bias, slope_att,
-                   bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, nullptr, F, C, O, lut_col,
-                   status};
+    const LpArgs a = lp_status_args(G, w, att_src, att_dst, conv_bias, slope_att, bn_weight, bn_bias, bn_mean, bn_var, bn_eps,
+                                    w0, b0, w3, b3, slope_head, out, F, C, O, lut_col, status);
+    if (!lp_weights_present(a) || !out || !count || !data || !freq || !cols || S == 0) return QOT_ERR_BADARG;
     const LpStatusArgs st{data, freq, samples, S, P, (int)L, (int)Q, conn_row, osnr_row, snr_row, ber_row, cols,
                           freq_threshold, count};
     lightpath_infer_status_kernel<<<(int)G, sg::kThreads, 0, stream>>>(a, st);

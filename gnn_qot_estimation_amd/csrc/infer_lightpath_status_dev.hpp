@@ -4,12 +4,14 @@
 // the row of a candidate that the sample does not hold yet).  Stated once here for both: the sample's arguments, who
 // occupies a channel (channel_conn), the walk over the slots of one link that marks the interferers of one channel
 // (lp_mark_slots) and the staging of the marked lightpaths' feature rows by rising lightpath number (lp_stage_marked) --
-// so who interferes, and in which order the messages are summed, is the same code in both.  infer_lightpath_place.hip and
+// so who interferes, and in which order the messages are summed, is the same code in both.  infer_lightpath_place.hip,
 // infer_lightpath_place_impact.hip (place_impact, DESIGN.md 4.25: the candidate's row and the retest of the lightpaths it
-// disturbs) further share the candidate's arguments (LpPlaceArgs) and phases 1 and 2 of a candidate (lp_place_scan);
-// infer_lightpath_place_impact.hip and infer_lightpath_retest.hip (retest, DESIGN.md 4.26: every established lightpath of a
-// sample as the lightpath under test) share the rescan that marks the neighbourhoods of up to 32 slotted lightpaths at once
-// (lp_mark_slotted).
+// disturbs) and infer_lightpath_place_release.hip (place(release=...)) further share phases 1 and 2 of a
+// candidate (lp_place_scan<kRelease>; the candidate's and the release's arguments and the release rule itself are
+// status_scan_dev.hpp's, shared with the topological place kernels); infer_lightpath_place_impact.hip and
+// infer_lightpath_retest.hip (retest, DESIGN.md 4.26: every established lightpath of a sample as the lightpath under test)
+// share the rescan that marks the neighbourhoods of up to 32 slotted lightpaths at once (lp_mark_slotted).  The five
+// entries share their envelope, the weight test and the LpArgs of a call without a batch (the host inlines at the end).
 #pragma once
 #include "infer_lightpath_dev.hpp"
 #include "status_scan_dev.hpp"
@@ -101,33 +103,31 @@ __device__ __forceinline__ void lp_mark_slotted(const double* __restrict__ d, co
     }
 }
 
-// One candidate of LightpathPredictor.place: the raw lp_feat vector values[k] in the channels cells[:, cell_ptr[k] :
-// cell_ptr[k + 1]] of sample samples[k]
-struct LpPlaceArgs {
-    const double* values;               // [K, P] raw lp_feat vectors
-    const int64_t* cells;               // [2, M]: link indices, then frequency indices
-    const int64_t* cell_ptr;            // [K + 1]
-    int64_t M;
-};
-
 // what lp_place_scan leaves for the phases behind it (every value is uniform over the block)
 struct LpPlaceScan {
     const double* d;                    // the candidate's sample
     const double* v;                    // values[k]
     int64_t conn_a, lo, hi;             // the candidate's truncated conn, its slice of cells
-    int LQ, n, cnt;                     // L * Q; the sample's lightpaths; its flagged ones + 1
+    int LQ, n, cnt;                     // L * Q; the sample's lightpaths; its flagged ones (kRelease: survivors) + 1
 };
 
-// Phases 1 and 2 of candidate k by its whole workgroup: the candidate's own arguments; discover() on the
-// unedited sample, thread t reads lightpath t's is_lut flag on its first channel and compares its conn with the
-// candidate's; then wave w takes the cells lo + w, lo + w + 4, ...: range check, the channel must be free, and the wave's
-// lanes walk the Q slots of the cell's link and mark nb[] (lp_mark_slots; a duplicate cell marks the same bytes again).
-// T, freq [kQCap], nb [kCap], lut_mask [kWaves] and bad_all are the caller's LDS.  Returns the candidate's refusal bits
+// Phases 1 and 2 of candidate k (sg::PlaceArgs, status_scan_dev.hpp) by its whole workgroup: the
+// candidate's own arguments; discover() on the unedited sample, thread t reads lightpath t's is_lut flag on its first
+// channel and compares its conn with the candidate's; then wave w takes the cells lo + w, lo + w + 4, ...: range check, the
+// channel must be free, and the wave's lanes walk the Q slots of the cell's link and mark nb[] (lp_mark_slots; a duplicate
+// cell marks the same bytes again).
+// kRelease (place(release=...); rl and rs are read and written in this form only): phase 0 checks the
+// release slice and loads it; in phase 1 thread t first matches lightpath t against the slice (status_scan_dev.hpp's
+// release_* routines: rs->gone, the ticks), only a survivor is flagged, counted and compared with the candidate's conn, a
+// second round refuses a slice entry nobody ticked and survivors + 1 > 256; in phase 2 an occupied cell is legal when its
+// owner is gone.  The marks of the gone stay in nb[]: the caller clears them (rs->gone) before it stages.
+// T, freq [kQCap], nb [kCap], lut_mask [kWaves], bad_all and rs are the caller's LDS.  Returns the candidate's refusal bits
 // (QOT_LP_STATUS_* / QOT_LP_PLACE_*), the same in every thread, behind a barrier: 0 -- T, freq, nb and r are complete;
 // otherwise nothing has been written to global memory and the caller refuses the candidate.
-__device__ __forceinline__ int lp_place_scan(const LpStatusArgs& st, const LpPlaceArgs& pl, int64_t k, sg::Table& T,
-                                             double* freq, uint8_t* nb, unsigned long long* lut_mask, int* bad_all,
-                                             LpPlaceScan& r) {
+template <bool kRelease>
+__device__ __forceinline__ int lp_place_scan(const LpStatusArgs& st, const sg::PlaceArgs& pl, const sg::ReleaseArgs& rl,
+                                             int64_t k, sg::Table& T, double* freq, uint8_t* nb, unsigned long long* lut_mask,
+                                             int* bad_all, sg::Release* rs, LpPlaceScan& r) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const double* v = pl.values + k * (int64_t)st.P;
 
@@ -135,9 +135,12 @@ __device__ __forceinline__ int lp_place_scan(const LpStatusArgs& st, const LpPla
     bool ok;
     const int64_t s = sg::sample_of(st.samples, k, st.S, ok);
     const int64_t lo = pl.cell_ptr[k], hi = pl.cell_ptr[k + 1];
-    int64_t conn_a = 0;
+    int64_t conn_a = 0, rlo = 0;
+    int nr = 0;                                                    // the release slice's length, 0 .. 32
     int early = ok ? 0 : QOT_LP_STATUS_BAD_SAMPLE;
     if (lo < 0 || hi <= lo || hi > pl.M) early |= QOT_LP_PLACE_BAD_CELL;
+    if constexpr (kRelease)
+        if ((nr = sg::release_slice(rl, k, rlo)) < 0) early |= QOT_LP_PLACE_BAD_RELEASE;
     if (!sg::sg_conn(v[st.conn_row], conn_a)) early |= QOT_LP_STATUS_BAD_CONN;
     if (!sg::sg_is_lut_vec(v, st.osnr_row, st.snr_row, st.ber_row)) early |= QOT_LP_PLACE_NOT_LUT;
     if (early) return early;                                       // block-uniform
@@ -145,19 +148,30 @@ __device__ __forceinline__ int lp_place_scan(const LpStatusArgs& st, const LpPla
     const double* d = st.data + s * (int64_t)st.P * LQ;
     for (int q = tid; q < st.Q; q += sg::kThreads) freq[q] = st.freq[q];
     nb[tid] = 0;
+    if constexpr (kRelease) sg::release_load(*rs, rl, rlo, nr);
     if (tid == 0) *bad_all = 0;
 
     // ---- phase 1: the lightpaths of the unedited sample, their flags, the candidate's conn among them ----
     const int bad = sg::discover(d, st.P, LQ, st.conn_row, T, nullptr);      // (begins and ends with a barrier)
     const int n = T.n;
     int mine = ((bad & QOT_SG_BAD_CONN) ? QOT_LP_STATUS_BAD_CONN : 0) | ((bad & QOT_SG_TOO_MANY) ? QOT_LP_STATUS_TOO_MANY : 0);
-    if (tid < n && T.conn[tid] == conn_a) mine |= QOT_LP_PLACE_CONN_TAKEN;
-    if (tid == 0 && n >= sg::kCap) mine |= QOT_LP_STATUS_TOO_MANY;            // the edited sample would hold n + 1
+    bool alive = tid < n;                                          // lightpath tid is in the edited sample
+    if constexpr (kRelease) alive = sg::release_match(*rs, nr, alive, alive ? T.conn[tid] : 0);
+    if (alive && T.conn[tid] == conn_a) mine |= QOT_LP_PLACE_CONN_TAKEN;
+    if (!kRelease && tid == 0 && n >= sg::kCap) mine |= QOT_LP_STATUS_TOO_MANY;   // the edited sample would hold n + 1
     if (mine) atomicOr(bad_all, mine);
-    const bool flag = tid < n && sg::sg_is_lut(d, LQ, st.osnr_row, st.snr_row, st.ber_row, T.first[tid]);
+    const bool flag = alive && sg::sg_is_lut(d, LQ, st.osnr_row, st.snr_row, st.ber_row, T.first[tid]);
     const unsigned long long fm = __ballot(flag);
     if (lane == 0) lut_mask[w] = fm;
     __syncthreads();
+    if constexpr (kRelease) {                                      // a second round: what needs every thread's match
+        int first;
+        const int n_gone = sg::release_gone(*rs, first);
+        mine = sg::release_unmatched(*rs, nr) ? QOT_LP_PLACE_NO_SUCH_CONN : 0;
+        if (tid == 0 && n - n_gone >= sg::kCap) mine |= QOT_LP_STATUS_TOO_MANY;   // the edited sample would hold 257
+        if (mine) atomicOr(bad_all, mine);
+        __syncthreads();
+    }
     if (*bad_all) return *bad_all;                                 // block-uniform; nobody writes it again
     int cnt = 1;                                                   // the candidate itself
 #pragma unroll
@@ -169,8 +183,12 @@ __device__ __forceinline__ int lp_place_scan(const LpStatusArgs& st, const LpPla
         const int64_t l = pl.cells[c], q1 = pl.cells[pl.M + c];
         int cell = 0;
         int64_t conn;
-        if (l < 0 || l >= st.L || q1 < 0 || q1 >= st.Q) cell = QOT_LP_PLACE_BAD_CELL;
-        else if (channel_conn(d, st.P, LQ, st.conn_row, (int)l * st.Q + (int)q1, conn)) cell = QOT_LP_PLACE_OCCUPIED;
+        if (l < 0 || l >= st.L || q1 < 0 || q1 >= st.Q) {
+            cell = QOT_LP_PLACE_BAD_CELL;
+        } else if (channel_conn(d, st.P, LQ, st.conn_row, (int)l * st.Q + (int)q1, conn)) {
+            if constexpr (kRelease) cell = sg::release_freed(*rs, T, n, conn, lane) ? 0 : QOT_LP_PLACE_OCCUPIED;
+            else cell = QOT_LP_PLACE_OCCUPIED;
+        }
         if (cell) {
             if (lane == 0) atomicOr(bad_all, cell);
             continue;
@@ -203,6 +221,21 @@ inline int lp_status_envelope(const void* x, const void* edge_index, const void*
         return QOT_ERR_BADARG;
     if (!(freq_threshold > 0.0) || !(freq_threshold <= 1.7976931348623157e308)) return QOT_ERR_BADARG;
     return QOT_OK;
+}
+
+// the LpArgs of a call without a batch: G rows of out, no graph arguments
+inline LpArgs lp_status_args(int64_t G, const float* w, const float* att_src, const float* att_dst, const float* conv_bias,
+                             float slope_att, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                             const float* bn_var, float bn_eps, const float* w0, const float* b0, const float* w3,
+                             const float* b3, float slope_head, float* out, int F, int C, int O, int lut_col, int32_t* status) {
+    return LpArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, G, w, att_src, att_dst, conv_bias, slope_att,
+                  bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w0, b0, w3, b3, slope_head, out, nullptr, F, C, O, lut_col,
+                  status};
+}
+
+// all twelve weights of the model are present
+inline bool lp_weights_present(const LpArgs& a) {
+    return a.w && a.att_src && a.att_dst && a.conv_bias && a.bn_w && a.bn_b && a.bn_mean && a.bn_var && a.w0 && a.b0 && a.w3 && a.b3;
 }
 
 }  // namespace qot

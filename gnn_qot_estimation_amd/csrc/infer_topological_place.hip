@@ -31,16 +31,9 @@
 
 namespace qot {
 
-struct TopoPlaceArgs {
-    const double* values;               // [K, P] raw lp_feat vectors
-    const int64_t* cells;               // [2, M]: link indices, then frequency indices
-    const int64_t* cell_ptr;            // [K + 1]
-    int64_t M;
-};
-
 template <int H, int D>
 __global__ __launch_bounds__(kInferThreads) void topological_infer_place_kernel(const InferArgs a, const TopoStatusArgs st,
-                                                                                const TopoPlaceArgs pl) {
+                                                                                const sg::PlaceArgs pl) {
     static_assert(kInferThreads == sg::kThreads, "the scan and the forward share one workgroup");
     extern __shared__ float4 infer_place_lds_raw[];
     float* lds = reinterpret_cast<float*>(infer_place_lds_raw);
@@ -128,12 +121,12 @@ extern "C" int qot_topological_infer_place(const int64_t* node_ids, const int64_
     if (n_cells < 0) return QOT_ERR_BADARG;
     if (K == 0) return QOT_OK;
     if (ld4 < 4 * H || (ld4 & 3) || ldm < V) return QOT_ERR_BADARG;
-    if (!node_ids || !t4 || !M || !P || !w_edge || !w1 || !b1 || !wcat || !bias2 || !w0 || !b0 || !w3 || !b3 || !out || !links ||
-        !data || !cols || S == 0 || !samples || !values || !cell_ptr || (n_cells > 0 && !cells))
+    const InferArgs a = topo_status_infer_args(node_ids, N, K, n_max, max_e, t4, ld4, M, ldm, P, V, w_edge, w1, b1, wcat, bias2,
+                                               w0, b0, w3, b3, slope_conv, slope_head, out, O, status);
+    if (!topo_weights_present(a) || !out || !links || !data || !cols || S == 0 || !samples || !values || !cell_ptr ||
+        (n_cells > 0 && !cells))
         return QOT_ERR_BADARG;
-    const InferArgs a{node_ids, nullptr, nullptr, nullptr, nullptr, N, 0, K, n_max, max_e, t4, ld4, M, ldm, P, V,
-                      w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, O, status};
     const TopoStatusArgs st{data, samples, S, rows_p, (int)L, (int)Q, conn_row, src_row, dst_row, cols, links};
-    const TopoPlaceArgs pl{values, cells, cell_ptr, n_cells};
+    const sg::PlaceArgs pl{values, cells, cell_ptr, n_cells};
     QOT_INFER_DISPATCH(topological_infer_place_kernel, H, D, dim3((unsigned)K), image, (hipStream_t)stream_, a, st, pl)
 }

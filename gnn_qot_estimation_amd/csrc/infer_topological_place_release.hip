@@ -12,7 +12,10 @@
 // slot of the first gone lightpath, or slot n when nobody is gone: a table of 256 with one released has room for it.  Its
 // number is free to choose: the forward sums the links in canonical (source, target) order, whatever a lightpath's number.
 //
-// One workgroup (256 threads) per candidate:
+// One workgroup (256 threads) per candidate.  The candidate's and the release's arguments are status_scan_dev.hpp's
+// (sg::PlaceArgs, sg::ReleaseArgs), shared with the lightpath kernels.  Steps 1 to 3 state the release rule in this file,
+// over LDS arrays of its own; it is the rule status_scan_dev.hpp states as sg::release_* for the lightpath scan, and a
+// change to one belongs in the other (DESIGN.md 4.24 says why the two are not one yet).
 //   1  block-uniform checks of the candidate's own arguments: sample number, cell_ptr slice, conn_id, and the release_ptr
 //      slice against [0, R] and the cap of 32 before `release` is read; the slice -> LDS.
 //   2  discover() on the unedited sample; thread t compares lightpath t's conn with the slice (gone[t]; every slice entry
@@ -36,24 +39,15 @@
 
 namespace qot {
 
-constexpr int kTopoMaxRelease = QOT_PLACE_MAX_RELEASE;   // 32
+constexpr int kTopoMaxRelease = sg::kMaxRelease;         // 32
 // the static LDS this kernel adds to kTopoStatusStatic: gone, the slice, its ticks, the gone masks
 constexpr size_t kTopoReleaseStatic = sg::kCap + (size_t)kTopoMaxRelease * 9 + sg::kWaves * 8;
-
-struct TopoPlaceReleaseArgs {
-    const double* values;               // [K, P] raw lp_feat vectors
-    const int64_t* cells;               // [2, M]: link indices, then frequency indices
-    const int64_t* cell_ptr;            // [K + 1]
-    int64_t M;
-    const int64_t* release;             // [R] conn_id values
-    const int64_t* release_ptr;         // [K + 1]
-    int64_t R;
-};
 
 template <int H, int D>
 __global__ __launch_bounds__(kInferThreads) void topological_infer_place_release_kernel(const InferArgs a,
                                                                                         const TopoStatusArgs st,
-                                                                                        const TopoPlaceReleaseArgs pl) {
+                                                                                        const sg::PlaceArgs pl,
+                                                                                        const sg::ReleaseArgs rl) {
     static_assert(kInferThreads == sg::kThreads, "the scan and the forward share one workgroup");
     extern __shared__ float4 infer_place_release_lds_raw[];
     float* lds = reinterpret_cast<float*>(infer_place_release_lds_raw);
@@ -76,11 +70,11 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_place_release
     bool ok;
     const int64_t s = sg::sample_of(st.samples, k, st.S, ok);
     const int64_t lo = pl.cell_ptr[k], hi = pl.cell_ptr[k + 1];
-    const int64_t rlo = pl.release_ptr[k], rhi = pl.release_ptr[k + 1];
+    const int64_t rlo = rl.release_ptr[k], rhi = rl.release_ptr[k + 1];
     int64_t conn_a = 0;
     int early = ok ? 0 : QOT_TOPO_STATUS_BAD_SAMPLE;
     if (lo < 0 || hi <= lo || hi > pl.M) early |= QOT_TOPO_PLACE_BAD_CELL;
-    if (rlo < 0 || rhi < rlo || rhi > pl.R || rhi - rlo > kTopoMaxRelease) early |= QOT_TOPO_PLACE_BAD_RELEASE;
+    if (rlo < 0 || rhi < rlo || rhi > rl.R || rhi - rlo > kTopoMaxRelease) early |= QOT_TOPO_PLACE_BAD_RELEASE;
     if (!sg::sg_conn(v[st.conn_row], conn_a)) early |= QOT_TOPO_STATUS_BAD_CONN;
     if (early) {                                                   // block-uniform
         topo_status_refuse(a, early, orow, st.links + k);
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(kInferThreads) void topological_infer_place_release
     const double* d = st.data + s * (int64_t)st.P * LQ;
     for (int c = tid; c < sg::kCells; c += sg::kThreads) mat[c] = -1;
     if (tid < nr) {
-        rel[tid] = pl.release[rlo + tid];
+        rel[tid] = rl.release[rlo + tid];
         found[tid] = 0;
     }
     if (tid == 0) bad_all = 0;
@@ -180,13 +174,13 @@ extern "C" int qot_topological_infer_place_release(const int64_t* node_ids, cons
     if (n_cells < 0 || R < 0) return QOT_ERR_BADARG;
     if (K == 0) return QOT_OK;
     if (ld4 < 4 * H || (ld4 & 3) || ldm < V) return QOT_ERR_BADARG;
-    if (!node_ids || !t4 || !M || !P || !w_edge || !w1 || !b1 || !wcat || !bias2 || !w0 || !b0 || !w3 || !b3 || !out || !links ||
-        !data || !cols || S == 0 || !samples || !values || !cell_ptr || (n_cells > 0 && !cells) || !release_ptr ||
-        (R > 0 && !release))
+    const InferArgs a = topo_status_infer_args(node_ids, N, K, n_max, max_e, t4, ld4, M, ldm, P, V, w_edge, w1, b1, wcat, bias2,
+                                               w0, b0, w3, b3, slope_conv, slope_head, out, O, status);
+    if (!topo_weights_present(a) || !out || !links || !data || !cols || S == 0 || !samples || !values || !cell_ptr ||
+        (n_cells > 0 && !cells) || !release_ptr || (R > 0 && !release))
         return QOT_ERR_BADARG;
-    const InferArgs a{node_ids, nullptr, nullptr, nullptr, nullptr, N, 0, K, n_max, max_e, t4, ld4, M, ldm, P, V,
-                      w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, O, status};
     const TopoStatusArgs st{data, samples, S, rows_p, (int)L, (int)Q, conn_row, src_row, dst_row, cols, links};
-    const TopoPlaceReleaseArgs pl{values, cells, cell_ptr, n_cells, release, release_ptr, R};
-    QOT_INFER_DISPATCH(topological_infer_place_release_kernel, H, D, dim3((unsigned)K), image, (hipStream_t)stream_, a, st, pl)
+    const sg::PlaceArgs pl{values, cells, cell_ptr, n_cells};
+    const sg::ReleaseArgs rl{release, release_ptr, R};
+    QOT_INFER_DISPATCH(topological_infer_place_release_kernel, H, D, dim3((unsigned)K), image, (hipStream_t)stream_, a, st, pl, rl)
 }

@@ -90,11 +90,9 @@ extern "C" int qot_topological_infer_status(const int64_t* node_ids, const int64
     if (rc != QOT_OK) return rc;
     if (G == 0) return QOT_OK;
     if (ld4 < 4 * H || (ld4 & 3) || ldm < V) return QOT_ERR_BADARG;
-    if (!node_ids || !t4 || !M || !P || !w_edge || !w1 || !b1 || !wcat || !bias2 || !w0 || !b0 || !w3 || !b3 || !out || !links ||
-        !data || !cols || S == 0)
-        return QOT_ERR_BADARG;
-    const InferArgs a{node_ids, nullptr, nullptr, nullptr, nullptr, N, 0, G, n_max, max_e, t4, ld4, M, ldm, P, V,
-                      w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, O, status};
+    const InferArgs a = topo_status_infer_args(node_ids, N, G, n_max, max_e, t4, ld4, M, ldm, P, V, w_edge, w1, b1, wcat, bias2,
+                                               w0, b0, w3, b3, slope_conv, slope_head, out, O, status);
+    if (!topo_weights_present(a) || !out || !links || !data || !cols || S == 0) return QOT_ERR_BADARG;
     const TopoStatusArgs st{data, samples, S, rows_p, (int)L, (int)Q, conn_row, src_row, dst_row, cols, links};
     QOT_INFER_DISPATCH(topological_infer_status_kernel, H, D, dim3((unsigned)G), image, (hipStream_t)stream_, a, st)
 }

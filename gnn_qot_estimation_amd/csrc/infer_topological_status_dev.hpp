@@ -5,6 +5,9 @@
 // the forward's image, the mapping of the scan's status bits, the links of a sample as an edge source (InferStatusEdges)
 // and everything behind the pair contest (topo_status_forward): the row-major walk of the winner matrix, the link words
 // and the forward -- so which links a winner matrix gives, their order and the sums over them are the same code in both.
+// infer_topological_place_release.hip (place(release=...)) is the third user.  The three entries share
+// their envelope, the weight test and the InferArgs of a call without a batch (the host inlines at the end); the
+// candidate's and the release's arguments are status_scan_dev.hpp's, shared with the lightpath kernels.
 #pragma once
 #include "infer_dev.hpp"
 #include "status_scan_dev.hpp"
@@ -120,6 +123,21 @@ inline int topo_status_envelope(const void* edge_index, const void* edge_attr, c
     if (conn_row < 0 || conn_row >= rows_p || src_row < 0 || src_row >= rows_p || dst_row < 0 || dst_row >= rows_p)
         return QOT_ERR_BADARG;
     return QOT_OK;
+}
+
+// the InferArgs of a call without a batch: G rows of out over the N nodes of the topology, no graph arguments
+inline InferArgs topo_status_infer_args(const int64_t* node_ids, int64_t N, int64_t G, int n_max, int max_e, const float* t4,
+                                        int ld4, const float* M, int ldm, const float* P, int V, const float* w_edge,
+                                        const float* w1, const float* b1, const float* wcat, const float* bias2,
+                                        const float* w0, const float* b0, const float* w3, const float* b3, float slope_conv,
+                                        float slope_head, float* out, int O, int32_t* status) {
+    return InferArgs{node_ids, nullptr, nullptr, nullptr, nullptr, N, 0, G, n_max, max_e, t4, ld4, M, ldm, P, V,
+                     w_edge, w1, b1, wcat, bias2, w0, b0, w3, b3, slope_conv, slope_head, out, O, status};
+}
+
+// node_ids and all twelve weights of the model are present
+inline bool topo_weights_present(const InferArgs& a) {
+    return a.node_ids && a.t4 && a.M && a.P && a.w_edge && a.w1 && a.b1 && a.wcat && a.bias2 && a.w0 && a.b0 && a.w3 && a.b3;
 }
 
 }  // namespace qot

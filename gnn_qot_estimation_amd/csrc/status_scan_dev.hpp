@@ -4,8 +4,11 @@
 // DESIGN.md 4.23; the two *_place_release.hip files): all run discover(), so the lightpaths of a sample,
 // their numbering and their first channels are the same table in all.  Stated once here: the workgroup's geometry and caps, the first-seen
 // table and its insert, the sample pick, the occupancy / conn rule of one channel (sg_conn, channel_conn), the fp64 column scaling
-// (scaled) and, for the topological representation, the block scan, the pair contest that fills the 75 x 75 winner
-// matrix (topo_winners) and the row-major run of cells a thread walks (topo_run).
+// (scaled), a candidate's and a release's kernel arguments for both models (PlaceArgs, ReleaseArgs), the release rule of
+// place(release=...), which does not depend on the model (the LDS struct Release and the release_* routines; the lightpath
+// scan runs them, infer_topological_place_release.hip states why it does not yet) and, for the topological representation,
+// the block scan, the pair contest that fills the 75 x 75 winner matrix (topo_winners) and the row-major run of cells a
+// thread walks (topo_run).
 //
 // Channels are scanned in the order c = l * Q + q, 256 at a time: occupied = any of the P values != 0; the distinct
 // trunc(conn_id) values are appended, in first-seen order, to an LDS table (conn, first channel).
@@ -138,6 +141,91 @@ __device__ __forceinline__ int64_t sample_of(const int64_t* samples, int64_t g, 
     const int64_t s = samples ? samples[g] : g;
     ok = s >= 0 && s < S;
     return s;
+}
+
+// ---- a candidate lightpath and a release, for both models' place kernels ----
+// One candidate of a predictor's place: the raw lp_feat vector values[k] in the channels cells[:, cell_ptr[k] :
+// cell_ptr[k + 1]] of sample samples[k]
+struct PlaceArgs {
+    const double* values;               // [K, P] raw lp_feat vectors
+    const int64_t* cells;               // [2, M]: link indices, then frequency indices
+    const int64_t* cell_ptr;            // [K + 1]
+    int64_t M;
+};
+
+// place(release=...): the lightpaths of candidate k's sample with one of the conns release[release_ptr[k] :
+// release_ptr[k + 1]] are gone before it is placed.  A kernel parameter of the two release kernels only.
+struct ReleaseArgs {
+    const int64_t* release;             // [R] conn_id values
+    const int64_t* release_ptr;         // [K + 1]
+    int64_t R;
+};
+
+constexpr int kMaxRelease = QOT_PLACE_MAX_RELEASE;   // 32
+
+// the LDS state of one candidate's release: the slice, its ticks, who is gone
+struct Release {
+    int64_t rel[kMaxRelease];
+    unsigned long long gone_mask[kWaves];
+    uint8_t gone[kCap];
+    uint8_t found[kMaxRelease];
+};
+
+// The routines below state the rule and return conditions; the caller maps them to its model's status bits.
+// the slice of candidate k, checked against [0, R] and the cap before `release` is read: its length, or -1 (bad slice)
+__device__ __forceinline__ int release_slice(const ReleaseArgs& rl, int64_t k, int64_t& rlo) {
+    rlo = rl.release_ptr[k];
+    const int64_t rhi = rl.release_ptr[k + 1];
+    return (rlo < 0 || rhi < rlo || rhi > rl.R || rhi - rlo > kMaxRelease) ? -1 : (int)(rhi - rlo);
+}
+
+// the slice -> LDS, nothing ticked (visible behind the caller's next barrier)
+__device__ __forceinline__ void release_load(Release& rs, const ReleaseArgs& rl, int64_t rlo, int nr) {
+    const int tid = threadIdx.x;
+    if (tid < nr) {
+        rs.rel[tid] = rl.release[rlo + tid];
+        rs.found[tid] = 0;
+    }
+}
+
+// Thread t and lightpath t (mine: t < n; conn: its conn): every slice entry that names it is ticked (a conn named twice:
+// both entries), gone[t] and the wave's gone mask are written.  Returns whether the lightpath survives.
+__device__ __forceinline__ bool release_match(Release& rs, int nr, bool mine, int64_t conn) {
+    const int tid = threadIdx.x;
+    bool g = false;
+    if (mine)
+        for (int j = 0; j < nr; ++j)
+            if (rs.rel[j] == conn) {
+                g = true;
+                rs.found[j] = 1;
+            }
+    rs.gone[tid] = g ? 1 : 0;
+    const unsigned long long gm = __ballot(g);
+    if ((tid & 63) == 0) rs.gone_mask[tid >> 6] = gm;
+    return mine && !g;
+}
+
+// behind the barrier that follows release_match: how many lightpaths are gone and the first gone one's number (-1: nobody)
+__device__ __forceinline__ int release_gone(const Release& rs, int& first) {
+    int n_gone = 0;
+    first = -1;
+#pragma unroll
+    for (int j = kWaves - 1; j >= 0; --j) {
+        const unsigned long long m = rs.gone_mask[j];
+        n_gone += __popcll(m);
+        if (m) first = j * kWave + __builtin_ctzll(m);
+    }
+    return n_gone;
+}
+
+// behind the same barrier: thread t's slice entry met no lightpath of the sample
+__device__ __forceinline__ bool release_unmatched(const Release& rs, int nr) { return (int)threadIdx.x < nr && !rs.found[threadIdx.x]; }
+
+// one wave: is the owner (conn) of an occupied channel gone?  The wave's lanes share the table.
+__device__ __forceinline__ bool release_freed(const Release& rs, const Table& T, int n, int64_t conn, int lane) {
+    bool freed = false;
+    for (int i = lane; i < n; i += kWave) freed |= (T.conn[i] == conn && rs.gone[i] != 0);
+    return __any(freed);
 }
 
 // the is_lut flag of a lightpath: osnr == snr == ber == -1 on its first channel c

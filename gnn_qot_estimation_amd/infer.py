@@ -441,6 +441,21 @@ def place_release_args(status, K, release, release_ptr, who="place"):
     return _PlaceRelease(R, release, release_ptr)
 
 
+def _status_picks(samples, S, dev, who):
+    """``samples`` of both ``from_status`` calls and of ``retest`` as ``(picks, G)``: ``None`` (all ``S``, in order), the
+    caller's 1-d int64 tensor (used in place when it is on ``dev``) or a sequence (uploaded)."""
+    if samples is None:
+        return None, S
+    if isinstance(samples, torch.Tensor):
+        if samples.dim() != 1 or samples.dtype != torch.int64:
+            raise ValueError(f"{who}: samples must be a sequence or a 1-d int64 tensor, got {samples.dtype} "
+                             f"{tuple(samples.shape)}")
+        picks = _i64(samples, dev)
+    else:
+        picks = torch.tensor([int(v) for v in samples], dtype=torch.int64).to(dev)
+    return picks, int(picks.shape[0])
+
+
 def _place_index_lists(dev, *lists):
     """The int64 index lists of a ``place`` call on ``dev``: those on the host go up in ONE copy, those on the device
     stay the caller's tensors."""
@@ -864,14 +879,7 @@ class TopologicalPredictor(_DeviceState):
         emb = self.model.node_embeddings.weight
         dev = emb.device
         sa = topological_status_args(status, D, features_to_consider, samples, emb.shape[0], dev, who)
-        if samples is None:
-            picks, G = None, sa.S
-        elif isinstance(samples, torch.Tensor):
-            picks = _i64(samples, dev)
-            G = int(picks.shape[0])
-        else:
-            picks = torch.tensor([int(v) for v in samples], dtype=torch.int64).to(dev)
-            G = int(picks.shape[0])
+        picks, G = _status_picks(samples, sa.S, dev, who)          # (a tensor's dtype: topological_status_args has refused)
         out = torch.empty(G, O, dtype=torch.float32, device=dev)
         links = torch.empty(G, dtype=torch.int64, device=dev)
         if G == 0:
@@ -956,17 +964,12 @@ class TopologicalPredictor(_DeviceState):
         links = torch.empty(pa.K, dtype=torch.int64, device=dev)
         if pa.K == 0:
             return out, links
+        picks, ptr, *rptr = _place_index_lists(dev, pa.samples, pa.cell_ptr, *(() if ra is None else (ra.release_ptr,)))
+        name, extra = "qot_topological_infer_place", ()
         if ra is not None:
-            picks, ptr, rptr = _place_index_lists(dev, pa.samples, pa.cell_ptr, ra.release_ptr)
-            self._launch_status("qot_topological_infer_place_release", status, pa.status, (H, D, O), out, links, picks,
-                                values.contiguous(), cells.contiguous(), ptr, pa.M, ra.release.contiguous(), rptr, ra.R)
-            return out, links
-        picks, ptr = pa.samples, pa.cell_ptr
-        if not picks.is_cuda and not ptr.is_cuda:           # both lists are on the host: one upload for the two
-            both = torch.cat([picks, ptr]).to(dev)
-            picks, ptr = both[:pa.K], both[pa.K:]
-        self._launch_status("qot_topological_infer_place", status, pa.status, (H, D, O), out, links, _i64(picks, dev),
-                            values.contiguous(), cells.contiguous(), _i64(ptr, dev), pa.M)
+            name, extra = "qot_topological_infer_place_release", (ra.release.contiguous(), rptr[0], ra.R)
+        self._launch_status(name, status, pa.status, (H, D, O), out, links, picks, values.contiguous(), cells.contiguous(), ptr,
+                            pa.M, *extra)
         return out, links
 
 
@@ -1648,33 +1651,32 @@ class LightpathPredictor(_DeviceState):
         who = "LightpathPredictor.from_status"
         shape = self._check_model()
         sa = lightpath_status_args(status, shape[0], self.model.is_lut_index, features_to_consider, freq_threshold, who)
+        dev = self._status_device(status, who)
+        picks, G = _status_picks(samples, sa.S, dev, who)
+        out = torch.empty(G, shape[2], dtype=torch.float32, device=dev)
+        if G == 0:
+            return out, self._empty_count(shape)
+        return out, self._launch_status("qot_lightpath_infer_status", status, sa, shape, G, picks, out)
+
+    def _status_device(self, status, who):
+        """The model's device, which a status call's chunk must be on."""
         dev = self._device()
         if status.device != dev:
             raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
-        picks, G = self._status_picks(samples, sa.S, dev, who)
-        p = self._prepare(None, True, shape, samples=G)
-        out = torch.empty(G, p.O, dtype=torch.float32, device=dev)
-        if G == 0:
-            return out, p.count
-        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
-        count = self._launch("qot_lightpath_infer_status", p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L, sa.Q,
-                             sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold)
-        return out, count
+        return dev
 
-    @staticmethod
-    def _status_picks(samples, S, dev, who):
-        """``samples`` of ``from_status`` and ``retest`` as ``(picks, G)``: ``None`` (all ``S``, in order), the caller's 1-d
-        int64 tensor (used in place when it is on ``dev``) or a sequence (uploaded)."""
-        if samples is None:
-            return None, S
-        if isinstance(samples, torch.Tensor):
-            if samples.dim() != 1 or samples.dtype != torch.int64:
-                raise ValueError(f"{who}: samples must be a sequence or a 1-d int64 tensor, got {samples.dtype} "
-                                 f"{tuple(samples.shape)}")
-            picks = _i64(samples, dev)
-        else:
-            picks = torch.tensor([int(v) for v in samples], dtype=torch.int64).to(dev)
-        return picks, int(picks.shape[0])
+    def _empty_count(self, shape):
+        """``count`` of a status call without rows: nothing is uploaded, nothing launched."""
+        return self._prepare(None, True, shape, samples=0).count
+
+    def _launch_status(self, name, status, sa, shape, rows, picks, out, *extra):
+        """One launch of a status entry point (``from_status``, ``retest``, ``place``, ``place_impact``): no batch, ``rows``
+        rows, the sample arguments of ``sa`` (an ``_LpStatus``) with the column table of its feature list, then ``extra``.
+        Returns ``count``.  (Not for ``rows == 0``: the column table is an upload; see ``_empty_count``.)"""
+        p = self._prepare(None, True, shape, samples=rows)
+        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
+        return self._launch(name, p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L, sa.Q, sa.conn_row, sa.osnr_row,
+                            sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold, *extra)
 
     @torch.no_grad()
     def retest(self, status, samples=None, conns=None, features_to_consider=to_graph.DEFAULT_FEATURES, freq_threshold=0.05,
@@ -1726,24 +1728,19 @@ class LightpathPredictor(_DeviceState):
         ra = lightpath_retest_args(status, shape[0], self.model.is_lut_index, conns, features_to_consider, freq_threshold,
                                    max_lightpaths, chunk, who)
         sa, M = ra.status, ra.M
-        dev = self._device()
-        if status.device != dev:
-            raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
-        picks, G = self._status_picks(samples, sa.S, dev, who)
+        dev = self._status_device(status, who)
+        picks, G = _status_picks(samples, sa.S, dev, who)
         if conns is not None and int(conns.shape[0]) != G:
             raise ValueError(f"{who}: conns has {int(conns.shape[0])} rows, samples names {G} samples")
-        p = self._prepare(None, True, shape, samples=G)
-        out = torch.empty(G, M, p.O, dtype=torch.float32, device=dev)
+        out = torch.empty(G, M, shape[2], dtype=torch.float32, device=dev)
         conn = torch.empty(G, M, dtype=torch.int64, device=dev)
         n = torch.empty(G, dtype=torch.int64, device=dev)
         if G == 0:
-            return Retest(out, conn, n, p.count)
+            return Retest(out, conn, n, self._empty_count(shape))
         if chunk is None:
             chunk = retest_chunk(G, M, torch.cuda.get_device_properties(dev).multi_processor_count)
-        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
-        count = self._launch("qot_lightpath_infer_retest", p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L, sa.Q,
-                             sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
-                             None if conns is None else conns.contiguous(), conn, n, M, chunk)
+        count = self._launch_status("qot_lightpath_infer_retest", status, sa, shape, G, picks, out,
+                                    None if conns is None else conns.contiguous(), conn, n, M, chunk)
         return Retest(out, conn, n, count)
 
     @torch.no_grad()
@@ -1802,29 +1799,16 @@ class LightpathPredictor(_DeviceState):
                                   features_to_consider, freq_threshold, who)
         ra = place_release_args(status, pa.K, release, release_ptr, who)
         sa = pa.status
-        dev = self._device()
-        if status.device != dev:
-            raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
-        p = self._prepare(None, True, shape, samples=pa.K)
-        out = torch.empty(pa.K, p.O, dtype=torch.float32, device=dev)
+        dev = self._status_device(status, who)
+        out = torch.empty(pa.K, shape[2], dtype=torch.float32, device=dev)
         if pa.K == 0:
-            return out, p.count
+            return out, self._empty_count(shape)
+        picks, ptr, *rptr = _place_index_lists(dev, pa.samples, pa.cell_ptr, *(() if ra is None else (ra.release_ptr,)))
+        name, extra = "qot_lightpath_infer_place", ()
         if ra is not None:
-            picks, ptr, rptr = _place_index_lists(dev, pa.samples, pa.cell_ptr, ra.release_ptr)
-            cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
-            count = self._launch("qot_lightpath_infer_place_release", p, out, status.data, status.freq, picks, sa.S, sa.P,
-                                 sa.L, sa.Q, sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
-                                 values.contiguous(), cells.contiguous(), ptr, pa.M, ra.release.contiguous(), rptr, ra.R)
-            return out, count
-        picks, ptr = pa.samples, pa.cell_ptr
-        if not picks.is_cuda and not ptr.is_cuda:           # both lists are on the host: one upload for the two
-            both = torch.cat([picks, ptr]).to(dev)
-            picks, ptr = both[:pa.K], both[pa.K:]
-        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
-        count = self._launch("qot_lightpath_infer_place", p, out, status.data, status.freq, _i64(picks, dev), sa.S, sa.P, sa.L,
-                             sa.Q, sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
-                             values.contiguous(), cells.contiguous(), _i64(ptr, dev), pa.M)
-        return out, count
+            name, extra = "qot_lightpath_infer_place_release", (ra.release.contiguous(), rptr[0], ra.R)
+        return out, self._launch_status(name, status, sa, shape, pa.K, picks, out, values.contiguous(), cells.contiguous(), ptr,
+                                        pa.M, *extra)
 
     @torch.no_grad()
     def place_impact(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES,
@@ -1864,23 +1848,18 @@ class LightpathPredictor(_DeviceState):
         pa = lightpath_place_impact_args(status, shape[0], self.model.is_lut_index, samples, values, cells, cell_ptr,
                                          features_to_consider, freq_threshold, max_affected, who)
         sa = pa.status
-        dev = self._device()
-        if status.device != dev:
-            raise EnvelopeError(f"{who}: the status chunk is on {status.device}, the model on {dev}")
-        p = self._prepare(None, True, shape, samples=pa.K)
-        K, A = pa.K, max_affected
-        out = torch.empty(K, p.O, dtype=torch.float32, device=dev)
+        dev = self._status_device(status, who)
+        K, A, O = pa.K, max_affected, shape[2]
+        out = torch.empty(K, O, dtype=torch.float32, device=dev)
         affected = torch.empty(K, A, dtype=torch.int64, device=dev)
         n_affected = torch.empty(K, dtype=torch.int64, device=dev)
-        before = torch.empty(K, A, p.O, dtype=torch.float32, device=dev)
-        after = torch.empty(K, A, p.O, dtype=torch.float32, device=dev)
+        before = torch.empty(K, A, O, dtype=torch.float32, device=dev)
+        after = torch.empty(K, A, O, dtype=torch.float32, device=dev)
         if K == 0:
-            return PlaceImpact(out, p.count, affected, n_affected, before, after)
+            return PlaceImpact(out, self._empty_count(shape), affected, n_affected, before, after)
         picks, ptr = _place_index_lists(dev, pa.samples, pa.cell_ptr)
-        cols, _, ncol = to_graph._column_tables(status, "lightpath", sa.features)
-        count = self._launch("qot_lightpath_infer_place_impact", p, out, status.data, status.freq, picks, sa.S, sa.P, sa.L,
-                             sa.Q, sa.conn_row, sa.osnr_row, sa.snr_row, sa.ber_row, cols, ncol, sa.freq_threshold,
-                             values.contiguous(), cells.contiguous(), ptr, pa.M, affected, n_affected, before, after, A)
+        count = self._launch_status("qot_lightpath_infer_place_impact", status, sa, shape, K, picks, out, values.contiguous(),
+                                    cells.contiguous(), ptr, pa.M, affected, n_affected, before, after, A)
         return PlaceImpact(out, count, affected, n_affected, before, after)
 
     @torch.no_grad()

@@ -207,13 +207,16 @@ def test_entry_is_declared_bound_and_built():
     csrc = os.path.join(ROOT, "gnn_qot_estimation_amd", "csrc")
     shared = open(os.path.join(csrc, "infer_lightpath_status_dev.hpp")).read()
     # the shared routines are stated once, in the header, and neither kernel restates them or the phases they share
-    for piece in ("bool channel_conn(", "void lp_mark_slots(", "int lp_stage_marked(", "int lp_place_scan(", "struct LpPlaceArgs {"):
-        assert shared.count(piece) == 1
+    # (the candidate's argument struct is both models': sg::PlaceArgs of status_scan_dev.hpp, which the header includes)
+    scan = open(os.path.join(csrc, "status_scan_dev.hpp")).read()
+    assert '#include "status_scan_dev.hpp"' in shared
+    for piece in ("bool channel_conn(", "void lp_mark_slots(", "int lp_stage_marked(", "int lp_place_scan(", "struct PlaceArgs {"):
+        assert (scan if piece == "struct PlaceArgs {" else shared).count(piece) == 1
         for f in ("infer_lightpath_place.hip", "infer_lightpath_place_impact.hip"):
             src = open(os.path.join(csrc, f)).read()
             assert '#include "infer_lightpath_status_dev.hpp"' in src and piece not in src, (f, piece)
     src = open(os.path.join(csrc, "infer_lightpath_place_impact.hip")).read()
-    for used in ("lp_place_scan(", "lp_mark_slots(", "lp_stage_marked(", "sg_feature(", "sg_feature_vec(", "lp_row<false, LpStaged>("):
+    for used in ("lp_place_scan<false>(", "lp_mark_slots(", "lp_stage_marked(", "sg_feature(", "sg_feature_vec(", "lp_row<false, LpStaged>("):
         assert used in src, used
     assert "discover(" in shared
 

@@ -293,9 +293,39 @@ def test_entries_are_declared_bound_and_built():
         assert rel_sig[1][len(place_sig[1]) - 1:] == [_lib._p, _lib._p, _lib._i64, _lib._p]
         assert f" infer_{model}_place_release.hip " in mk
         src = open(os.path.join(csrc, f"infer_{model}_place_release.hip")).read()
-        assert f'#include "{dev_hpp}"' in src and "sg::discover(" in src and "__shared__ int64_t rel[" in src
-        for piece in ("void lp_mark_slots(", "int lp_stage_marked(", "int topo_winners(", "void topo_status_forward("):
+        # both take the shared argument structs; the lightpath kernel runs the sample's scan and the release through the
+        # shared candidate scan over status_scan_dev.hpp's LDS struct, the topological kernel keeps its own statement of
+        # steps 1 to 3 (its header says why)
+        assert f'#include "{dev_hpp}"' in src and "const sg::PlaceArgs pl" in src and "const sg::ReleaseArgs rl" in src
+        if model == "lightpath":
+            assert "lp_place_scan<true>(" in src and "__shared__ sg::Release rs;" in src
+            for piece in ("sg::discover(", "rel[", "found[", "gone_mask["):
+                assert piece not in src, piece
+        else:
+            assert "sg::discover(" in src and "__shared__ int64_t rel[" in src
+        for piece in ("void lp_mark_slots(", "int lp_stage_marked(", "int topo_winners(", "void topo_status_forward(",
+                      "int lp_place_scan("):
             assert piece not in src                                             # the shared routines are used, not restated
+    # the release rule of the shared scan is status_scan_dev.hpp's
+    scan = open(os.path.join(csrc, "status_scan_dev.hpp")).read()
+    for piece in ("struct PlaceArgs {", "struct ReleaseArgs {", "struct Release {", "int64_t rel[kMaxRelease];",
+                  "uint8_t found[kMaxRelease];", "uint8_t gone[kCap];", "unsigned long long gone_mask[kWaves];",
+                  "int release_slice(", "void release_load(", "bool release_match(", "int release_gone(",
+                  "bool release_unmatched(", "bool release_freed("):
+        assert scan.count(piece) == 1, piece
+    lp_dev = open(os.path.join(csrc, "infer_lightpath_status_dev.hpp")).read()
+    assert lp_dev.count("int lp_place_scan(") == 1 and "template <bool kRelease>" in lp_dev and "sg::discover(" in lp_dev
+    for call in ("sg::release_slice(", "sg::release_load(", "sg::release_match(", "sg::release_gone(", "sg::release_unmatched(",
+                 "sg::release_freed("):
+        assert call in lp_dev, call
+    # the lightpath place kernels reach discover() through the scan; the candidate structs of old are gone
+    for f in ("infer_lightpath_place.hip", "infer_lightpath_place_impact.hip", "infer_lightpath_place_release.hip"):
+        assert "sg::discover(" not in open(os.path.join(csrc, f)).read(), f
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".hpp")):
+            text = open(os.path.join(csrc, f)).read()
+            for gone in ("LpPlaceReleaseArgs", "TopoPlaceReleaseArgs", "LpPlaceArgs", "TopoPlaceArgs"):
+                assert gone not in text, (f, gone)
 
 
 def test_entries_answer_their_envelopes_before_any_launch():
