@@ -197,6 +197,9 @@ SIGNATURES = {
                                                               _int, C.c_double, _p, _p, _p, _i64, _p, _p, _i64, _p]),
     "qot_lightpath_infer_place_impact": (_int, _LP_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _int, _p,
                                                              _int, C.c_double, _p, _p, _p, _i64, _p, _p, _p, _p, _int, _p]),
+    "qot_lightpath_infer_reroute_impact": (_int, _LP_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _int, _p,
+                                                               _int, C.c_double, _p, _p, _p, _i64, _p, _p, _i64, _p, _p, _p,
+                                                               _p, _p, _p, _int, _p]),
     "qot_lightpath_infer_retest": (_int, _LP_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _int, _p, _int,
                                                        C.c_double, _p, _p, _p, _int, _int, _p]),
     "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),

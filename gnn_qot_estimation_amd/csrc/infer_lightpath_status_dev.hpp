@@ -10,7 +10,9 @@
 // candidate (lp_place_scan<kRelease>; the candidate's and the release's arguments and the release rule itself are
 // status_scan_dev.hpp's, shared with the topological place kernels); infer_lightpath_place_impact.hip and
 // infer_lightpath_retest.hip (retest, DESIGN.md 4.26: every established lightpath of a sample as the lightpath under test)
-// share the rescan that marks the neighbourhoods of up to 32 slotted lightpaths at once (lp_mark_slotted).  The five
+// share the rescan that marks the neighbourhoods of up to 32 slotted lightpaths at once (lp_mark_slotted).
+// infer_lightpath_reroute_impact.hip (reroute_impact, DESIGN.md 4.27: place_impact for a candidate that releases
+// lightpaths) runs the scan in either form and the rescan twice, for the released lightpaths and for the affected.  The six
 // entries share their envelope, the weight test and the LpArgs of a call without a batch (the host inlines at the end).
 #pragma once
 #include "infer_lightpath_dev.hpp"

@@ -1256,6 +1256,22 @@ def lightpath_place_args(status, in_channels, is_lut_index, samples, values, cel
     return _LpPlace(sa, K, M, samples, cell_ptr)
 
 
+def _release_in_place(edited, conn_row, ra):
+    """The release of ``materialise_placement`` and ``materialise_retest``: sample ``k`` of ``edited [K, P, L, Q]`` has all P
+    rows zeroed in every occupied channel whose ``trunc(conn_id)`` is in ``ra.release[ra.release_ptr[k]:ra.release_ptr[k +
+    1]]`` (``ra``: ``place_release_args``' answer; ``None`` or no conn: nothing happens)."""
+    if ra is None or not ra.R:
+        return
+    K, dev = edited.shape[0], edited.device
+    who_k = torch.repeat_interleave(torch.arange(K, device=dev), ra.release_ptr.to(dev).diff(), output_size=ra.R)
+    cv = edited[:, conn_row]                                                      # [K, L, Q]
+    named = (edited != 0).any(1) & (cv.abs() <= 2.0 ** 53)                       # occupied, with a conn to compare
+    conn = torch.where(named, cv, torch.zeros_like(cv)).trunc().to(torch.int64)
+    hit = (conn.index_select(0, who_k) == ra.release[:, None, None]) & named.index_select(0, who_k)       # [R, L, Q]
+    gone = torch.zeros(K, *hit.shape[1:], dtype=torch.int32, device=dev).index_add_(0, who_k, hit.int())
+    edited.masked_fill_((gone > 0)[:, None], 0.0)
+
+
 def materialise_placement(status, samples, values, cells, cell_ptr, release=None, release_ptr=None):
     """The K edited samples that ``LightpathPredictor.place`` and ``TopologicalPredictor.place`` score without building
     them: the DEFINITION of both calls and what they save.  Returns a ``DeviceStatus`` of K samples; sample ``k`` is
@@ -1281,14 +1297,7 @@ def materialise_placement(status, samples, values, cells, cell_ptr, release=None
     dev = status.data.device
     samples, cell_ptr = samples.to(dev), cell_ptr.to(dev)
     edited = status.data.index_select(0, samples)
-    if ra is not None and ra.R:
-        who_k = torch.repeat_interleave(torch.arange(K, device=dev), ra.release_ptr.to(dev).diff(), output_size=ra.R)
-        cv = edited[:, status.feature_indexes["conn_id"]]                         # [K, L, Q]
-        named = (edited != 0).any(1) & (cv.abs() <= 2.0 ** 53)                   # occupied, with a conn to compare
-        conn = torch.where(named, cv, torch.zeros_like(cv)).trunc().to(torch.int64)
-        hit = (conn.index_select(0, who_k) == ra.release[:, None, None]) & named.index_select(0, who_k)   # [R, L, Q]
-        gone = torch.zeros(edited.shape[0], *hit.shape[1:], dtype=torch.int32, device=dev).index_add_(0, who_k, hit.int())
-        edited.masked_fill_((gone > 0)[:, None], 0.0)
+    _release_in_place(edited, status.feature_indexes["conn_id"], ra)
     cand = torch.repeat_interleave(torch.arange(K, device=dev), cell_ptr.diff(), output_size=M)
     edited[cand, :, cells[0], cells[1]] = values.index_select(0, cand)
     return to_graph.DeviceStatus(edited, status.target.index_select(0, samples), status.freq, status.lp_feat, status.metric,
@@ -1301,6 +1310,9 @@ _LABEL_ROWS = ("osnr", "snr", "ber")
 # what LightpathPredictor.place_impact returns: place(...)'s out [K, O] and count [K]; affected [K, A] int64 conn ids, -1
 # padded, and n_affected [K] int64, their true number; before / after [K, A, O] float32, NaN padded
 PlaceImpact = namedtuple("PlaceImpact", "out count affected n_affected before after")
+# what LightpathPredictor.reroute_impact returns: PlaceImpact's six for place(..., release=); gains [K, A] bool, the
+# candidate is a source of after (False padded); lost [K, A] int64, the released sources of before (-1 padded)
+RerouteImpact = namedtuple("RerouteImpact", "out count affected n_affected before after gains lost")
 
 
 def lightpath_place_impact_args(status, in_channels, is_lut_index, samples, values, cells, cell_ptr,
@@ -1322,9 +1334,14 @@ def lightpath_place_impact_args(status, in_channels, is_lut_index, samples, valu
                                 freq_threshold, who)
 
 
-def materialise_retest(status, samples, conns, values=None, cells=None, cell_ptr=None):
+def materialise_retest(status, samples, conns, values=None, cells=None, cell_ptr=None, *, release=None, release_ptr=None):
     """The samples in which an ESTABLISHED lightpath is the lightpath under test, without or with a candidate established
-    next to it: the DEFINITION of ``LightpathPredictor.place_impact``'s ``before`` and ``after``.  Returns a
+    next to it: the DEFINITION of ``LightpathPredictor.place_impact``'s ``before`` and ``after`` -- and, with ``release``
+    and ``release_ptr`` (keyword-only; as ``place`` takes them, T slices, checked by ``place_release_args``), of
+    ``LightpathPredictor.reroute_impact``'s ``after``: then one edit runs before the two below, with or without
+    ``values`` -- (0) sample ``t`` has all P rows zeroed in every occupied channel whose ``trunc(conn_id)`` is in
+    ``release[release_ptr[t]:release_ptr[t + 1]]``, ``materialise_placement``'s rule exactly: a conn that names no
+    lightpath of the sample releases nothing.  Without the two keywords nothing changes.  Returns a
     ``DeviceStatus`` of T samples; sample ``t`` is ``status.data[samples[t]]`` with two edits, in this order.  (1) Only
     when ``values`` is given (then ``cells`` and ``cell_ptr`` too, all as ``place`` takes them, T candidates): ``values[t]``
     is written into each of the channels ``cells[:, cell_ptr[t]:cell_ptr[t + 1]]`` with its ``osnr``, ``snr`` and ``ber``
@@ -1354,12 +1371,14 @@ def materialise_retest(status, samples, conns, values=None, cells=None, cell_ptr
         if samples.shape[0] != T:
             raise ValueError(f"{who}: samples names {samples.shape[0]} samples, conns {T} lightpaths")
         edited = status.data.index_select(0, samples)
+        _release_in_place(edited, fi["conn_id"], place_release_args(status, T, release, release_ptr, who))
     else:
         K, M, samples, cell_ptr = _place_lists(status, samples, values, cells, cell_ptr, who)
         if K != T:
             raise ValueError(f"{who}: values has {K} rows, conns names {T} lightpaths")
         samples, cell_ptr = samples.to(dev), cell_ptr.to(dev)
         edited = status.data.index_select(0, samples)
+        _release_in_place(edited, fi["conn_id"], place_release_args(status, T, release, release_ptr, who))
         established = values.clone()
         established[:, [fi[n] for n in _LABEL_ROWS]] = 0.0
         cand = torch.repeat_interleave(torch.arange(K, device=dev), cell_ptr.diff(), output_size=M)
@@ -1479,6 +1498,9 @@ class LightpathPredictor(_DeviceState):
     ``predict.place_impact(status, samples, values, cells, cell_ptr)``: ``place``'s rows together with the retest of the
     established lightpaths each candidate disturbs -- their rows as the lightpath under test before and after the candidate
     is lit -- one launch and no host read (see there).
+    ``predict.reroute_impact(status, samples, values, cells, cell_ptr, release=, release_ptr=)``: ``place_impact`` with
+    established lightpaths released in the same launch -- the lightpaths beside the new route gain an interferer, those
+    beside the old route lose one; both are retested (see there).
     ``predict.retest(status)``: every ESTABLISHED lightpath of the status samples, or a named subset (``conns=``), retested
     as the lightpath under test -- the standing question about a network state, a margin audit -- one launch and no host
     read (see there).
@@ -1670,7 +1692,7 @@ class LightpathPredictor(_DeviceState):
         return self._prepare(None, True, shape, samples=0).count
 
     def _launch_status(self, name, status, sa, shape, rows, picks, out, *extra):
-        """One launch of a status entry point (``from_status``, ``retest``, ``place``, ``place_impact``): no batch, ``rows``
+        """One launch of a status entry point (``from_status``, ``retest``, ``place``, ``place_impact``, ``reroute_impact``): no batch, ``rows``
         rows, the sample arguments of ``sa`` (an ``_LpStatus``) with the column table of its feature list, then ``extra``.
         Returns ``count``.  (Not for ``rows == 0``: the column table is an upload; see ``_empty_count``.)"""
         p = self._prepare(None, True, shape, samples=rows)
@@ -1842,7 +1864,8 @@ class LightpathPredictor(_DeviceState):
         ``snr`` or ``ber`` -- the retest rewrites those rows.  ``K == 0`` gives empty tensors without a launch.  On the
         device every refusal of ``place`` applies, with the same status bits: the refused candidate has a NaN ``out`` row,
         ``count`` 0, ``n_affected`` 0, ``affected`` all -1, ``before`` and ``after`` all NaN; the other candidates are
-        untouched, and ``check_status()`` raises naming the cause.  There is no ``release=`` here."""
+        untouched, and ``check_status()`` raises naming the cause.  There is no ``release=`` here: a reroute, or an
+        admission together with a tear-down, is ``reroute_impact``'s."""
         who = "LightpathPredictor.place_impact"
         shape = self._check_model()
         pa = lightpath_place_impact_args(status, shape[0], self.model.is_lut_index, samples, values, cells, cell_ptr,
@@ -1861,6 +1884,67 @@ class LightpathPredictor(_DeviceState):
         count = self._launch_status("qot_lightpath_infer_place_impact", status, sa, shape, K, picks, out, values.contiguous(),
                                     cells.contiguous(), ptr, pa.M, affected, n_affected, before, after, A)
         return PlaceImpact(out, count, affected, n_affected, before, after)
+
+    @torch.no_grad()
+    def reroute_impact(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES,
+                       freq_threshold=0.05, max_affected=8, *, release=None, release_ptr=None):
+        """``place_impact`` for a REROUTE, or an admission together with a tear-down: whom the move helps and whom it
+        hurts, as ``RerouteImpact(out [K, O] float32, count [K] int64, affected [K, A] int64, n_affected [K] int64, before
+        [K, A, O] float32, after [K, A, O] float32, gains [K, A] bool, lost [K, A] int64)`` with ``A = max_affected``, in
+        ONE kernel launch (``csrc/infer_lightpath_reroute_impact.hip``), with nothing read back and
+        ``status.data`` never written; legal inside ``torch.cuda.graph`` capture under the conditions of ``place`` (index
+        arguments as device tensors, one call made first).  Restoration after a link failure, defragmentation, "admit A
+        by tearing down B": the lightpaths beside the new route gain an interferer, those beside the old route lose one.
+
+        The arguments are ``place(..., release=, release_ptr=)``'s, checked by the same routines, plus ``max_affected``
+        (``place_impact``'s).  ``release=None``: no candidate releases anything.  ``out`` and ``count`` are ``place(...,
+        release=, release_ptr=)``'s, bit for bit.  The affected lightpaths of candidate ``k`` are the SURVIVORS of its
+        sample (the lightpaths it does not release) that (a) interfere with the candidate --
+        ``to_graph.placement_neighbourhood(..., release=)``'s list -- or (b) interfere, in the unedited sample, with a
+        released lightpath; a released lightpath is never affected.  ``affected[k, :n]``, ``n = min(n_affected[k], A)``:
+        their ``conn_id`` values in the sample's first-seen order; ``n_affected[k]`` is their true number, more than ``A``
+        is no error.  ``before[k, i]``: the eval-mode row of lightpath ``affected[k, i]`` retested in the unedited sample
+        (``place_impact``'s ``before``: the released lightpaths still send their messages).  ``after[k, i]``: the same row
+        in the sample with the release applied and the candidate established (unflagged, ``is_lut`` 0): the surviving
+        sources in the survivors' order, the candidate's row at its first-seen position among them where the lightpath
+        gains the candidate.  ``gains[k, i]``: the candidate is a source of ``after``.  ``lost[k, i]``: the released
+        lightpaths that were sources of ``before`` (a conn named twice counts once).  The slots behind ``n`` hold -1
+        (``affected``, ``lost``), NaN and False.
+
+        ``materialise_retest`` is the definition: ``before[k, i]`` is, bit for bit, the row ``self(to_graph.device_batch(
+        materialise_retest(status, [samples[k]], [affected[k, i]]), "lightpath", ...))`` gives the node of that conn, and
+        ``after[k, i]`` the same with ``values[k:k + 1]``, the candidate's cells, ``[0, m]`` and its release slice
+        (``release=, release_ptr=[0, r]``) passed in as well; ``to_graph.reroute_impact`` states the nodes, the messages,
+        ``gains`` and ``lost`` on the host.
+
+        Refusals before any launch: ``place_impact``'s (``lightpath_place_impact_args``) and those of ``place``'s
+        release lists (``place_release_args``).  ``K == 0`` gives empty tensors without a launch.  On the device every
+        refusal of ``place(release=)`` applies, with the same status bits: the refused candidate has a NaN ``out`` row,
+        ``count`` 0, ``n_affected`` 0, ``affected`` and ``lost`` all -1, ``gains`` False, ``before`` and ``after`` all
+        NaN; the other candidates are untouched, and ``check_status()`` raises naming the cause.  There is no pure
+        tear-down (a candidate needs a cell), and the rows of one candidate are computed by one wave."""
+        who = "LightpathPredictor.reroute_impact"
+        shape = self._check_model()
+        pa = lightpath_place_impact_args(status, shape[0], self.model.is_lut_index, samples, values, cells, cell_ptr,
+                                         features_to_consider, freq_threshold, max_affected, who)
+        ra = place_release_args(status, pa.K, release, release_ptr, who)
+        sa = pa.status
+        dev = self._status_device(status, who)
+        K, A, O = pa.K, max_affected, shape[2]
+        out = torch.empty(K, O, dtype=torch.float32, device=dev)
+        affected = torch.empty(K, A, dtype=torch.int64, device=dev)
+        n_affected = torch.empty(K, dtype=torch.int64, device=dev)
+        before = torch.empty(K, A, O, dtype=torch.float32, device=dev)
+        after = torch.empty(K, A, O, dtype=torch.float32, device=dev)
+        gains = torch.empty(K, A, dtype=torch.bool, device=dev)
+        lost = torch.empty(K, A, dtype=torch.int64, device=dev)
+        if K == 0:
+            return RerouteImpact(out, self._empty_count(shape), affected, n_affected, before, after, gains, lost)
+        picks, ptr, *rptr = _place_index_lists(dev, pa.samples, pa.cell_ptr, *(() if ra is None else (ra.release_ptr,)))
+        rel = (None, None, 0) if ra is None else (ra.release.contiguous(), rptr[0], ra.R)
+        count = self._launch_status("qot_lightpath_infer_reroute_impact", status, sa, shape, K, picks, out, values.contiguous(),
+                                    cells.contiguous(), ptr, pa.M, *rel, affected, n_affected, before, after, gains, lost, A)
+        return RerouteImpact(out, count, affected, n_affected, before, after, gains, lost)
 
     @torch.no_grad()
     def sensitivity(self, data, outputs=None, *, per_graph=False, return_attention_weights=False):

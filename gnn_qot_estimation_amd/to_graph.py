@@ -400,6 +400,41 @@ def placement_impact(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict
     return out
 
 
+def reroute_impact(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], values_row: np.ndarray, cells,
+                   freq_threshold: float = 0.05, release=()):
+    """Whom a candidate of ``LightpathPredictor.reroute_impact`` helps and whom it hurts, stated on the host: one tuple
+    ``(conn, node_before, node_after, sources_before, sources_after, gains, lost)`` per affected lightpath, in the sample's
+    first-seen order.  Affected are the SURVIVORS (the lightpaths not in ``release``) that interfere with the candidate --
+    ``placement_neighbourhood(..., release=)``'s list -- or had, in the unedited ``sample``, at least one released
+    lightpath among their sources; a released lightpath is never affected.  ``node_before`` / ``sources_before``: the
+    lightpath's number and the conn ids whose messages its row sums in ``sample`` (``_sources_of``: the released
+    lightpaths still send theirs); ``node_after`` / ``sources_after``: the same in the sample with ``release`` released and
+    the candidate placed (``place_lightpath(..., release=)``; its refusals apply).  ``gains``: the candidate is one of
+    ``sources_after``; ``lost``: the released lightpaths among ``sources_before``, each once.  With ``release=()`` the
+    first five fields are ``placement_impact``'s tuples, ``gains`` is True and ``lost`` 0."""
+    fi = feature_indexes
+    sample, freq = np.asarray(sample, dtype=np.float64), np.asarray(freq, dtype=np.float64)
+    values_row = np.asarray(values_row, dtype=np.float64)
+    edited, _ = place_lightpath(sample, values_row, cells, fi, release)
+    _, gone = _released(sample, release, fi)
+    near = set(placement_neighbourhood(sample, freq, fi, cells, freq_threshold, release))
+    own = int(values_row[fi["conn_id"]])
+    _, _, vec = _occupied(sample)
+    conn = vec[fi["conn_id"], :].astype(np.int64)
+    _, first = np.unique(conn, return_index=True)
+    out = []
+    for c in [int(conn[i]) for i in np.sort(first)]:
+        if c in gone:
+            continue
+        node_before, sources_before = _sources_of(sample, freq, fi, c, freq_threshold)
+        lost = sum(s in gone for s in sources_before)
+        if c not in near and not lost:
+            continue
+        node_after, sources_after = _sources_of(edited, freq, fi, c, freq_threshold)
+        out.append((c, node_before, node_after, sources_before, sources_after, own in sources_after, lost))
+    return out
+
+
 def topological_links(sample: np.ndarray, feature_indexes: Dict[str, int]):
     """What ``TopologicalPredictor.from_status`` takes of one sample ``[lp_feat, link, freq]``, stated on the host:
     ``(edge_index [2, m] int64, conn [m] int64)``.  The lightpaths are the distinct ``trunc(conn_id)`` of the occupied

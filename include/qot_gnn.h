@@ -1328,6 +1328,45 @@ int qot_lightpath_infer_retest(const float* x, const int64_t* edge_index, const 
                                const double* cols, int ncol, double freq_threshold, const int64_t* conns, int64_t* conn,
                                int64_t* n, int max_lightpaths, int chunk, qot_stream_t stream);
 
+/* ---- the place_impact entry with established lightpaths RELEASED in the same launch: who a reroute, or an admission
+ * together with a tear-down, helps and whom it hurts (LightpathPredictor.reroute_impact) -- out[k] and
+ * count[k] are the place_release entry's, bit for bit.  The affected lightpaths of candidate k are the SURVIVORS of its
+ * sample (the lightpaths it does not release) that (a) interfere with the candidate or (b) interfere, in the unedited
+ * sample, with a released lightpath; a released lightpath is never affected.  n_affected[k] (int64) is their number; the
+ * first A = max_affected of them by rising first-seen number of the unedited sample get a slot i: affected[k, i] (int64 [K,
+ * A]) is the lightpath's trunc(conn_id); before[k, i] (fp32 [K, A, O]) the lightpath "scored as the lightpath under test"
+ * of the unedited sample, as the place_impact entry defines it -- the released lightpaths still send their messages;
+ * after[k, i] the same in edited_k of the place_release entry with the candidate established (values[k] with osnr = snr =
+ * ber = 0, is_lut 0): the messages of the lightpath's surviving interferers by rising first-seen number and, where the
+ * candidate interferes with it, the candidate's row at the candidate's first-seen position among the survivors, behind
+ * the lightpaths whose first channel l * Q + q lies below the smallest of its cells.  gains[k, i] (uint8 [K, A]) is 1
+ * where the candidate is a source of after; lost[k, i] (int64 [K, A]) the released lightpaths that were sources of before,
+ * a conn named twice counted once.  cols must not scale osnr, snr or ber (the caller's check).  Slots i >=
+ * min(n_affected[k], A) hold affected -1, NaN rows, gains 0, lost -1; n_affected[k] > A is no error.  A refused candidate
+ * (the place_release entry's status bits, no new one) has a NaN out row, count 0, n_affected 0 and every slot empty.  data
+ * is never written.  One 256-thread workgroup per candidate: the place_impact entry's cost plus one more rescan of the
+ * conn_id row for the released lightpaths' neighbourhoods.
+ *
+ * The argument list is the place_release entry's up to R, then affected, n_affected, before, after, gains, lost,
+ * max_affected.  release == release_ptr == NULL with R == 0: no candidate releases anything.  Return codes before any
+ * launch: the place entry's, QOT_ERR_BADARG for R < 0, for max_affected outside 1 .. QOT_PLACE_MAX_AFFECTED or -- when K > 0
+ * -- a NULL release or release_ptr with R > 0, or a NULL affected, n_affected, before, after, gains or lost.  K == 0:
+ * QOT_OK, no launch.  Nothing read from data, values or release is used as an index: conns are only compared. */
+int qot_lightpath_infer_reroute_impact(const float* x, const int64_t* edge_index, const int64_t* batch,
+                                       const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* lut_idx, int64_t n_lut,
+                                       int64_t N, int64_t E, int64_t K, const float* w, const float* att_src,
+                                       const float* att_dst, const float* conv_bias, float slope_att, const float* bn_weight,
+                                       const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps,
+                                       const float* w0, const float* b0, const float* w3, const float* b3, float slope_head,
+                                       float* out, int64_t* count, int F, int C, int O, int heads, int lut_col, int32_t* status,
+                                       const double* data, const double* freq, const int64_t* samples, int64_t S, int P,
+                                       int64_t L, int64_t Q, int conn_row, int osnr_row, int snr_row, int ber_row,
+                                       const double* cols, int ncol, double freq_threshold, const double* values,
+                                       const int64_t* cells, const int64_t* cell_ptr, int64_t M, const int64_t* release,
+                                       const int64_t* release_ptr, int64_t R, int64_t* affected, int64_t* n_affected,
+                                       float* before, float* after, uint8_t* gains, int64_t* lost, int max_affected,
+                                       qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,18 @@ what a retested row costs beside it, timed in an alternation of its own.  S ``sy
 count as different when they are further apart than the sum of their interquartile ranges.
 
     python tools/bench_infer.py --kind lightpath --retest 1 8 64 512 [--out profiles/bench_infer_lightpath_retest.jsonl]
+
+``--kind lightpath --reroute-impact K [K ...] [--release R]``: whom a reroute helps and whom it hurts --
+``predict.reroute_impact(status, ..., release=, release_ptr=)`` (csrc/infer_lightpath_reroute_impact.hip)
+against (a) the only way before: two ``infer.materialise_retest`` calls over the (candidate, affected lightpath) pairs, the
+second with the candidate and ``release=``, each followed by ``to_graph.device_batch`` and ``predict`` -- the pairs worked
+out on the host beforehand (``to_graph.reroute_impact``) and uploaded, which favours (a); (b) ``predict.place_impact`` of the
+same candidates with nothing released; (c) ``predict.place(release=)``.  Each is timed in an alternation of its own with
+``reroute_impact``.  ``--place-impact``'s sample and candidates; every candidate releases R lightpaths (default 2), the first
+of them one that some survivor loses as a source (asserted on the inputs).  The rows of ``reroute_impact`` and (a), and its
+``out`` / ``count`` and (c)'s, are compared first (equal bits).
+
+    python tools/bench_infer.py --kind lightpath --reroute-impact 1 8 64 1024 --release 2 [--out profiles/bench_infer_lightpath_reroute_impact.jsonl]
 """
 import argparse
 import json
@@ -1047,6 +1059,149 @@ def main_place_impact(args, device, commit):
               f"{ratio(r, 'retest', 'impact')} | {cell('impact_pair')} | {cell('place')} | {ratio(r, 'impact_pair', 'place')} |")
 
 
+def measure_reroute_impact(K, R, device, rounds, warmup, thr=0.12, max_affected=8):
+    """``reroute_impact`` of K candidates, R released lightpaths each, against (a) two ``materialise_retest`` calls (the
+    second with ``release=``) + ``device_batch`` + ``predict`` over the (candidate, affected lightpath) pairs, worked out on
+    the host beforehand, (b) ``place_impact`` of the same candidates with nothing released and (c) ``place(release=)``."""
+    import numpy as np
+    from gnn_qot_estimation_amd import infer, to_graph as TG
+    torch.manual_seed(0)
+    predict = q.LightpathPredictor(q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval())
+    ns = TG.synthetic_network_status(1, seed=0)             # the 60 x 72 grid
+    fi, feats = ns.feature_indexes, list(TG.DEFAULT_FEATURES)
+    data = ns.data.copy()
+    under_test = (data[0, fi["osnr"]] == -1) & (data[0, fi["snr"]] == -1) & (data[0, fi["ber"]] == -1)
+    data[0][:, under_test] = 0.0                            # as --place-impact: every retest sample of (a) holds one LUT node
+    L, Q = data.shape[2], data.shape[3]
+    free = ~np.any(data[0] != 0, axis=0)
+    conn_of = data[0, fi["conn_id"]].astype(np.int64)
+    conns = sorted(set(conn_of[~free].tolist()))
+    if R > min(len(conns) - 2, infer.PLACE_MAX_RELEASE):
+        raise SystemExit(f"--release {R}: the sample holds {len(conns)} lightpaths, the cap is {infer.PLACE_MAX_RELEASE}")
+    # the candidates are --place-impact's: one slot on the links where a lightpath sits within two slots (0.10 < thr)
+    near = {(l, g): {int(conn_of[l, f]) for f in range(max(0, g - 2), min(Q, g + 3)) if not free[l, f]}
+            for l in range(L) for g in range(Q) if free[l, g]}
+    by_slot = {}
+    for (l, g), who in near.items():
+        if who:
+            by_slot.setdefault(g, []).append(l)
+    slots = sorted(g for g, ls in by_slot.items() if len(set().union(*(near[l, g] for l in ls))) >= 2)
+    assert slots, "no slot of the sample lets a candidate meet two lightpaths"
+    # who loses whom: the released lightpaths are drawn among those with a neighbour of their own
+    sources = {c: set(TG._sources_of(data[0], ns.freq, fi, c, thr)[1]) for c in conns}
+    sociable = [c for c in conns if sources[c]]
+    rng = np.random.default_rng(K)
+    values, cells, ptr, release, pairs = np.zeros((K, len(ns.lp_feat))), [], [0], [], []
+    kinds = [0, 0, 0]                                       # affected lightpaths that gain only, lose only, do both
+    for k in range(K):
+        slot = slots[int(rng.integers(len(slots)))]
+        links, met = [], set()
+        for l in rng.permutation(by_slot[slot]):
+            links.append(int(l))
+            met |= near[int(l), slot]
+            if len(met) >= 2 and len(links) >= int(rng.integers(1, 5)):
+                break
+        mine = np.stack([np.asarray(links), np.full(len(links), slot)])
+        cells.append(mine)
+        ptr.append(ptr[-1] + len(links))
+        v = values[k]
+        v[fi["conn_id"]], v[fi["src_id"]], v[fi["dst_id"]] = 10000 + k, 1, 2
+        v[fi["mod_order"]], v[fi["path_len"]] = float(rng.choice([4, 8, 16, 32, 64])), float(rng.integers(24214, 7834746))
+        v[fi["num_spans"]], v[fi["freq"]] = float(rng.integers(1, 107)), ns.freq[slot]
+        v[fi["osnr"]] = v[fi["snr"]] = v[fi["ber"]] = -1.0
+        while True:                                         # released: a lightpath with a source of its own, then R - 1 others
+            first = sociable[int(rng.integers(len(sociable)))]
+            rel = [first] + [int(c) for c in rng.choice([c for c in conns if c != first], size=R - 1, replace=False)]
+            if sources[first] - set(rel):                   # ... that leave it a surviving neighbour
+                break
+        release += rel
+        impact = TG.reroute_impact(data[0], ns.freq, fi, v, mine, thr, rel)
+        assert any(t[6] for t in impact), (k, impact)       # a condition on the inputs: somebody loses a source
+        for t in impact:
+            kinds[0 if not t[6] else 1 if not t[5] else 2] += 1
+        pairs += [(k, i, t[0]) for i, t in enumerate(impact[:max_affected])]
+    st = TG.NetworkStatus(data, ns.target, ns.lp_feat, ns.metric, ns.link, ns.freq).to_device(device)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device)       # noqa: E731
+    samples, values_d = torch.zeros(K, dtype=torch.int64, device=device), torch.from_numpy(values).to(device)
+    cells_d, ptr_d = dev(np.concatenate(cells, axis=1)), dev(ptr)
+    rel_d, rptr_d = dev(release), dev(np.arange(K + 1) * R)
+    # (a)'s arguments, one row per pair, prepared beforehand: which favours (a)
+    T = len(pairs)
+    pk, pi = dev([k for k, _, _ in pairs]), dev([i for _, i, _ in pairs])
+    psamples, pconns, pvalues = torch.zeros(T, dtype=torch.int64, device=device), dev([c for _, _, c in pairs]), values_d[pk]
+    pcells = dev(np.concatenate([cells[k] for k, _, _ in pairs], axis=1))
+    pptr = dev(np.cumsum([0] + [cells[k].shape[1] for k, _, _ in pairs]))
+    prel, prptr = dev(np.concatenate([release[k * R:(k + 1) * R] for k, _, _ in pairs])), dev(np.arange(T + 1) * R)
+
+    def retest():
+        before = predict(TG.device_batch(infer.materialise_retest(st, psamples, pconns), "lightpath", feats, None, thr))[0]
+        after = predict(TG.device_batch(infer.materialise_retest(st, psamples, pconns, pvalues, pcells, pptr, release=prel,
+                                                                 release_ptr=prptr), "lightpath", feats, None, thr))[0]
+        return before, after
+    ways = {"reroute": lambda: predict.reroute_impact(st, samples, values_d, cells_d, ptr_d, feats, thr, max_affected,
+                                                      release=rel_d, release_ptr=rptr_d),
+            "retest": retest,
+            "impact": lambda: predict.place_impact(st, samples, values_d, cells_d, ptr_d, feats, thr, max_affected),
+            "release": lambda: predict.place(st, samples, values_d, cells_d, ptr_d, feats, thr, release=rel_d, release_ptr=rptr_d)}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    r = got["reroute"]
+    assert torch.equal(r.before[pk, pi], got["retest"][0]) and torch.equal(r.after[pk, pi], got["retest"][1]), K
+    assert torch.equal(r.out, got["release"][0]) and torch.equal(r.count, got["release"][1])
+    assert torch.equal(r.affected[pk, pi], pconns) and bool(torch.isfinite(got["retest"][1]).all())
+    assert int(r.lost.max()) >= 1 and int(r.n_affected.min()) >= 1
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    # three alternations, as --place-impact: neither launch is timed right behind (a)'s copies of the sample
+    times = {}
+    for mine, other in (("reroute", "retest"), ("reroute_b", "impact"), ("reroute_c", "release")):
+        times[mine], times[other] = [], []
+        for _ in range(warmup):
+            ways["reroute"](), ways[other]()
+        for _ in range(rounds):
+            times[mine].append(timed_event(ways["reroute"]))
+            times[other].append(timed_event(ways[other]))
+    res = dict(shape=f"status {L} x {Q}", kind="lightpath_reroute_impact", K=K, R=R, max_affected=max_affected,
+               cells=int(ptr[-1]), pairs=T, affected_min=int(r.n_affected.min()), affected_max=int(r.n_affected.max()),
+               gain_only=kinds[0], lose_only=kinds[1], both=kinds[2], lightpaths=len(conns), S=1, P=int(st.data.shape[1]),
+               L=L, Q=Q, C=32, F=5, freq_threshold=thr, rounds=rounds, equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_reroute_impact(args, device, commit):
+    rows = []
+    for K in args.reroute_impact:
+        res = measure_reroute_impact(K, args.release or 2, device, args.rounds, args.warmup)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| grid | K | R | pairs | reroute_impact ms (IQR) | (a) 2 x (materialise_retest + device_batch + predict) ms (IQR) | "
+          "(a) / reroute | beside (b) ms (IQR) | (b) place_impact ms (IQR) | reroute / (b) | beside (c) ms (IQR) | "
+          "(c) place(release=) ms (IQR) | reroute / (c) |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+
+    def ratio(r, num, den):                                 # differ: by more than the sum of the IQRs
+        same = abs(r[num + "_ms"] - r[den + "_ms"]) <= r[num + "_iqr_ms"] + r[den + "_iqr_ms"]
+        return "no difference" if same else f"{r[num + '_ms'] / r[den + '_ms']:.2f}x"
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['L']} x {r['Q']} | {r['K']} | {r['R']} | {r['pairs']} | {cell('reroute')} | {cell('retest')} | "
+              f"{ratio(r, 'retest', 'reroute')} | {cell('reroute_b')} | {cell('impact')} | {ratio(r, 'reroute_b', 'impact')} | "
+              f"{cell('reroute_c')} | {cell('release')} | {ratio(r, 'reroute_c', 'release')} |")
+
+
 def measure_retest(S, device, rounds, warmup, thr=0.12, max_lightpaths=256):
     """``retest`` of every lightpath of S status samples against (a) ``materialise_retest`` over all (sample, lightpath)
     pairs + ``device_batch`` + ``predict`` -- the pairs worked out on the host beforehand -- and (b) ``from_status`` of the
@@ -1317,6 +1472,10 @@ def main():
                     help="--kind lightpath: predict.place_impact on K candidates of one status sample against "
                          "materialise_retest + device_batch + predict over the (candidate, interferer) pairs and against "
                          "plain place")
+    ap.add_argument("--reroute-impact", type=int, nargs="+", default=None, metavar="K", dest="reroute_impact",
+                    help="--kind lightpath: predict.reroute_impact on K candidates of one status sample, each releasing R "
+                         "lightpaths (--release R, default 2), against materialise_retest(release=) + device_batch + predict "
+                         "over the (candidate, affected lightpath) pairs, against place_impact and against place(release=)")
     ap.add_argument("--retest", type=int, nargs="+", default=None, metavar="S",
                     help="--kind lightpath: predict.retest on every lightpath of S status samples against materialise_retest "
                          "+ device_batch + predict over the (sample, lightpath) pairs and against from_status")
@@ -1334,8 +1493,14 @@ def main():
                                           or args.mc is not None or args.grad or args.what_if is not None
                                           or any(k < 1 for k in args.place_impact)):
         raise SystemExit("--kind lightpath --place-impact K [K ...] (K >= 1) is a run of its own")
-    if args.place is None and (args.links != 60 or args.cells is not None or args.release is not None):
-        raise SystemExit("--links, --cells and --release go with --place")
+    if args.reroute_impact is not None and (args.kind != "lightpath" or args.place is not None or args.from_status
+                                            or args.mc is not None or args.grad or args.what_if is not None
+                                            or args.place_impact is not None or args.retest is not None
+                                            or any(k < 1 for k in args.reroute_impact)):
+        raise SystemExit("--kind lightpath --reroute-impact K [K ...] (K >= 1) is a run of its own")
+    if args.place is None and (args.links != 60 or args.cells is not None
+                               or (args.release is not None and args.reroute_impact is None)):
+        raise SystemExit("--links and --cells go with --place, --release with --place or --reroute-impact")
     if args.release is not None and args.release < 1:
         raise SystemExit("--release R (R >= 1)")
     if args.links < 6 or (args.cells is not None and not 1 <= args.cells <= args.links):
@@ -1357,6 +1522,8 @@ def main():
         raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    if args.reroute_impact is not None:
+        return main_reroute_impact(args, device, commit)
     if args.place_impact is not None:
         return main_place_impact(args, device, commit)
     if args.retest is not None:
