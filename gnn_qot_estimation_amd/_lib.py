@@ -202,6 +202,8 @@ SIGNATURES = {
                                                                _p, _p, _p, _int, _p]),
     "qot_lightpath_infer_retest": (_int, _LP_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _int, _p, _int,
                                                        C.c_double, _p, _p, _p, _int, _int, _p]),
+    "qot_lightpath_infer_place_slots": (_int, _LP_COMMON + [_p, _p, _p, _i64, _int, _i64, _i64, _int, _int, _int, _int, _p,
+                                                            _int, C.c_double, _p, _p, _p, _i64, _int, _int, _int, _p, _p]),
     "qot_status_graph_scratch_bytes": (_sz, [_i64, _i64, _i64, _int]),
     "qot_status_graph_count": (_int, [_p, _p, _p, _i64, _i64, _int, _i64, _i64, _int, _int, _int, C.c_double, _int, _p, _sz, _p,
                                       _p]),

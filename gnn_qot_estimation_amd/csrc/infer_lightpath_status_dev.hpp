@@ -12,7 +12,9 @@
 // infer_lightpath_retest.hip (retest, DESIGN.md 4.26: every established lightpath of a sample as the lightpath under test)
 // share the rescan that marks the neighbourhoods of up to 32 slotted lightpaths at once (lp_mark_slotted).
 // infer_lightpath_reroute_impact.hip (reroute_impact, DESIGN.md 4.27: place_impact for a candidate that releases
-// lightpaths) runs the scan in either form and the rescan twice, for the released lightpaths and for the affected.  The six
+// lightpaths) runs the scan in either form and the rescan twice, for the released lightpaths and for the affected.
+// infer_lightpath_place_slots.hip (place_slots, DESIGN.md 4.28: a route swept over every start slot of the grid) takes the
+// walk and the staging from here and marks up to 32 start slots' neighbourhoods behind one discover().  The seven
 // entries share their envelope, the weight test and the LpArgs of a call without a batch (the host inlines at the end).
 #pragma once
 #include "infer_lightpath_dev.hpp"

@@ -1193,22 +1193,29 @@ _LP_PLACE_CAUSES = (
 _LpPlace = namedtuple("_LpPlace", "status K M samples cell_ptr")
 
 
-def _place_lists(status, samples, values, cells, cell_ptr, who):
+def _place_lists(status, samples, values, cells, cell_ptr, who, routes=False):
     """The checks of the candidate lists that ``lightpath_place_args`` and ``materialise_placement`` share: returns ``(K,
     M, samples, cell_ptr)`` with the last two as 1-d int64 tensors -- the caller's own tensor where one was given -- or
-    raises the named ``ValueError``."""
+    raises the named ``ValueError``.  ``routes`` (``lightpath_place_slots_args`` and ``materialise_slot_sweep``): the same
+    checks of ``R`` routes, with ``links [M]`` in the place of ``cells`` and ``link_ptr`` in the place of ``cell_ptr``."""
     def got(t):
         return f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
 
+    one, K_, cells_, ptr_ = ("route", "R", "links", "link_ptr") if routes else ("candidate", "K", "cells", "cell_ptr")
     P = int(status.data.shape[1])
     if not isinstance(values, torch.Tensor) or values.dim() != 2 or values.dtype != torch.float64 or values.shape[1] != P:
-        raise ValueError(f"{who}: values must be a float64 tensor [K, {P}] (one raw lp_feat vector per candidate), got "
+        raise ValueError(f"{who}: values must be a float64 tensor [{K_}, {P}] (one raw lp_feat vector per {one}), got "
                          f"{got(values)}")
     K = int(values.shape[0])
-    if not isinstance(cells, torch.Tensor) or cells.dim() != 2 or cells.dtype != torch.int64 or cells.shape[0] != 2:
-        raise ValueError(f"{who}: cells must be an int64 tensor [2, M] (link index, frequency index), got {got(cells)}")
-    M = int(cells.shape[1])
-    for name, t in (("values", values), ("cells", cells)):
+    if routes:
+        if not isinstance(cells, torch.Tensor) or cells.dim() != 1 or cells.dtype != torch.int64:
+            raise ValueError(f"{who}: links must be a 1-d int64 tensor [M] of link indices, got {got(cells)}")
+        M = int(cells.shape[0])
+    else:
+        if not isinstance(cells, torch.Tensor) or cells.dim() != 2 or cells.dtype != torch.int64 or cells.shape[0] != 2:
+            raise ValueError(f"{who}: cells must be an int64 tensor [2, M] (link index, frequency index), got {got(cells)}")
+        M = int(cells.shape[1])
+    for name, t in (("values", values), (cells_, cells)):
         if t.device != status.data.device:
             raise ValueError(f"{who}: {name} is on {t.device}, the status chunk on {status.data.device}")
     if isinstance(samples, torch.Tensor):
@@ -1222,20 +1229,20 @@ def _place_lists(status, samples, values, cells, cell_ptr, who):
     else:
         samples = torch.tensor([int(v) for v in samples], dtype=torch.int64).reshape(-1)
         if samples.shape[0] != K:
-            raise ValueError(f"{who}: samples names {samples.shape[0]} candidates, values has {K} rows")
+            raise ValueError(f"{who}: samples names {samples.shape[0]} {one}s, values has {K} rows")
     if isinstance(cell_ptr, torch.Tensor):
         if cell_ptr.dim() != 1 or cell_ptr.dtype != torch.int64 or cell_ptr.shape[0] != K + 1:
-            raise ValueError(f"{who}: cell_ptr must be a sequence or a 1-d int64 tensor of K + 1 = {K + 1} offsets into "
-                             f"cells, got {got(cell_ptr)}")
+            raise ValueError(f"{who}: {ptr_} must be a sequence or a 1-d int64 tensor of {K_} + 1 = {K + 1} offsets into "
+                             f"{cells_}, got {got(cell_ptr)}")
     else:
         cell_ptr = torch.tensor([int(v) for v in cell_ptr], dtype=torch.int64).reshape(-1)
         if cell_ptr.shape[0] != K + 1:
-            raise ValueError(f"{who}: cell_ptr must hold K + 1 = {K + 1} offsets into cells, got {cell_ptr.shape[0]}")
+            raise ValueError(f"{who}: {ptr_} must hold {K_} + 1 = {K + 1} offsets into {cells_}, got {cell_ptr.shape[0]}")
     if not cell_ptr.is_cuda:                               # on the host: checked here; on the device: by the kernel
         if int(cell_ptr[0]) != 0 or int(cell_ptr[-1]) != M or (K and int(cell_ptr.diff().min()) < 0):
-            raise ValueError(f"{who}: cell_ptr must be non-decreasing from 0 to M = {M}, got {cell_ptr.tolist()}")
+            raise ValueError(f"{who}: {ptr_} must be non-decreasing from 0 to M = {M}, got {cell_ptr.tolist()}")
         if K and int(cell_ptr.diff().min()) == 0:
-            raise ValueError(f"{who}: candidate {int(cell_ptr.diff().argmin())} has an empty slice of cells")
+            raise ValueError(f"{who}: {one} {int(cell_ptr.diff().argmin())} has an empty slice of {cells_}")
     return K, M, samples, cell_ptr
 
 
@@ -1302,6 +1309,127 @@ def materialise_placement(status, samples, values, cells, cell_ptr, release=None
     edited[cand, :, cells[0], cells[1]] = values.index_select(0, cand)
     return to_graph.DeviceStatus(edited, status.target.index_select(0, samples), status.freq, status.lp_feat, status.metric,
                                  status.link)
+
+
+PLACE_SLOTS_MAX_CHUNK = 32      # include/qot_gnn.h: QOT_LP_PLACE_SLOTS_MAX_CHUNK, start slots one workgroup runs one after the other
+PLACE_SLOTS_MAX_WIDTH = 8       # include/qot_gnn.h: QOT_LP_PLACE_SLOTS_MAX_WIDTH, slots a candidate occupies on every link
+
+# what LightpathPredictor.place_slots returns: out [R, Q, O] float32, the row of the candidate of route r that starts at
+# slot q, NaN where it is not free; free [R, Q] bool; count [R] int64, place's count (the same at every slot)
+PlaceSlots = namedtuple("PlaceSlots", "out free count")
+# what materialise_slot_sweep returns: place's argument lists of the K free (route, start slot) pairs -- samples [K],
+# values [K, P], cells [2, Mc], cell_ptr [K + 1] -- which pair each is, route [K] and slot [K], and free [R, Q] bool
+SlotSweep = namedtuple("SlotSweep", "samples values cells cell_ptr route slot free")
+
+# samples / link_ptr: int64 tensors, on the host checked (link_ptr) and to be uploaded, or on the device and used in place;
+# slot_row: the lp_feat row that carries the start slot's frequency, -1 for none; chunk: None or the caller's int
+_LpPlaceSlots = namedtuple("_LpPlaceSlots", "status R M samples link_ptr slot_row width chunk")
+
+
+def place_slots_chunk(num_routes: int, num_slots: int, compute_units: int) -> int:
+    """Start slots per workgroup of ``qot_lightpath_infer_place_slots``'s grid ``R * ceil(Q / chunk)``, ``1 ...
+    PLACE_SLOTS_MAX_CHUNK``, by ``retest_chunk``'s reasoning with the ``Q`` start slots of a route in the place of the
+    ``M`` slots of a sample: the grid is that of the largest chunk for which ``R * ceil(Q / chunk)`` workgroups still reach
+    the device's compute-unit count (a larger chunk shares the discovery of the sample among more start slots, but leaves
+    units idle and runs more rows one after the other on one wave); the chunk returned is the smallest with that many
+    workgroups, so that they carry equal shares.  Once ``R`` alone fills the device that is the grid of chunk 32.  1 when
+    no chunk reaches the device.  Pure host arithmetic; no result of ``place_slots`` depends on it."""
+    R, Q, cus = int(num_routes), int(num_slots), int(compute_units)
+    if not 1 <= Q <= LP_STATUS_MAX_FREQS:
+        raise ValueError(f"place_slots_chunk: num_slots must be in 1 ... {LP_STATUS_MAX_FREQS}, got {Q}")
+    if R < 1 or R * Q < cus:
+        return 1
+    need = max(-(-cus // R), 1)                            # workgroups per route that reach the device
+    largest = Q if need <= 1 else (Q - 1) // (need - 1)    # largest chunk with ceil(Q / chunk) >= need
+    blocks = -(-Q // min(largest, PLACE_SLOTS_MAX_CHUNK))
+    return -(-Q // blocks)
+
+
+def _slot_sweep_options(status, width, slot_feature, who):
+    """``width`` and ``slot_feature`` of ``place_slots`` and ``materialise_slot_sweep``: returns the ``lp_feat`` row that
+    carries the start slot's frequency, -1 for ``None``, or raises the named ``ValueError``."""
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= PLACE_SLOTS_MAX_WIDTH:
+        raise ValueError(f"{who}: width must be an int in 1 ... {PLACE_SLOTS_MAX_WIDTH}, got {width!r}")
+    if slot_feature is None:
+        return -1
+    if slot_feature not in status.feature_indexes:
+        raise ValueError(f"{who}: slot_feature {slot_feature!r} is no lp_feat row of the status (None: values unchanged at "
+                         f"every slot)")
+    if slot_feature in ("conn_id",) + _LABEL_ROWS:
+        raise ValueError(f"{who}: slot_feature cannot be {slot_feature!r}: the candidate's conn_id and its osnr = snr = ber = "
+                         f"-1 are what place tests")
+    return int(status.feature_indexes[slot_feature])
+
+
+def lightpath_place_slots_args(status, in_channels, is_lut_index, samples, values, links, link_ptr,
+                               features_to_consider=to_graph.DEFAULT_FEATURES, freq_threshold=0.05, width=1,
+                               slot_feature="freq", chunk=None, who="LightpathPredictor.place_slots"):
+    """The argument checks of ``LightpathPredictor.place_slots`` that need no device: returns an ``_LpPlaceSlots``
+    (``status``: the ``_LpStatus`` of ``lightpath_status_args``; ``R``, ``M``; ``samples`` and ``link_ptr`` as 1-d int64
+    tensors; ``slot_row``, ``width``, ``chunk``) or raises -- ``TypeError`` for a ``status`` that is no ``DeviceStatus``;
+    ``ValueError`` naming the argument for what ``_place_lists`` refuses of ``values`` (float64 ``[R, P]``), ``links``
+    (int64 ``[M]``), ``samples`` and ``link_ptr`` (a host ``link_ptr`` not non-decreasing from 0 to ``M`` or with an empty
+    slice; one on the device is checked by the kernel), a ``width`` that is no int in ``1 ... PLACE_SLOTS_MAX_WIDTH``, a
+    ``slot_feature`` that is no row of ``lp_feat`` or one of ``conn_id``, ``osnr``, ``snr``, ``ber``, a ``chunk`` that is
+    neither ``None`` nor an int in ``1 ... PLACE_SLOTS_MAX_CHUNK``, a bad ``freq_threshold``; then ``EnvelopeError`` for
+    everything ``lightpath_status_args`` refuses, a chunk on the CPU last."""
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    R, M, samples, link_ptr = _place_lists(status, samples, values, links, link_ptr, who, routes=True)
+    slot_row = _slot_sweep_options(status, width, slot_feature, who)
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk <= PLACE_SLOTS_MAX_CHUNK):
+        raise ValueError(f"{who}: chunk must be None or an int in 1 ... {PLACE_SLOTS_MAX_CHUNK}, got {chunk!r}")
+    sa = lightpath_status_args(status, in_channels, is_lut_index, features_to_consider, freq_threshold, who)
+    return _LpPlaceSlots(sa, R, M, samples, link_ptr, slot_row, width, chunk)
+
+
+def materialise_slot_sweep(status, samples, values, links, link_ptr, *, width=1, slot_feature="freq"):
+    """The explicit ``place`` argument lists of every FREE (route, start slot) pair that ``LightpathPredictor.place_slots``
+    scores without building them: the DEFINITION of that call and what it saves -- the occupancy pass, the host read of
+    the free slots and the list building.  Arguments as ``place_slots`` (``_place_lists`` and the same ``width`` /
+    ``slot_feature`` checks).  Returns ``SlotSweep(samples [K], values [K, P], cells [2, Mc], cell_ptr [K + 1], route [K],
+    slot [K], free [R, Q])``, routes rising and start slots rising inside a route.  ``free[r, q]``: every channel of
+    ``route x {q ... q + width - 1}`` of sample ``samples[r]`` has all P values equal to 0, and ``q + width <= Q``.
+    Candidate ``k`` is route ``route[k]`` started at ``slot[k]``: sample ``samples[route[k]]``; ``values[route[k]]`` with
+    -- unless ``slot_feature`` is ``None`` -- ``status.freq[slot[k]]`` in the ``slot_feature`` row; its cells link by link
+    in the route's order (a duplicate link gives duplicate cells), the ``width`` slots rising inside a link.  With those
+    lists ``place_slots(...).out[route[k], slot[k]]`` is, bit for bit, ``place(status, samples, values, cells,
+    cell_ptr)[0][k]``.  Pure torch on the status' device (CPU tensors as well), no kernel of ours; it reads the free pairs
+    back to the host (``nonzero``); ``status`` is not modified."""
+    who = "materialise_slot_sweep"
+    if not isinstance(status, to_graph.DeviceStatus):
+        raise TypeError(f"{who} takes a DeviceStatus (NetworkStatus.to_device), got {type(status).__name__}")
+    R, M, samples, link_ptr = _place_lists(status, samples, values, links, link_ptr, who, routes=True)
+    slot_row = _slot_sweep_options(status, width, slot_feature, who)
+    dev = status.data.device
+    Q = int(status.data.shape[3])
+    samples, link_ptr = samples.to(dev), link_ptr.to(dev)
+    length = link_ptr.diff()                                                      # [R] links per route
+    of_route = torch.repeat_interleave(torch.arange(R, device=dev), length, output_size=M)
+    occupied = (status.data != 0).any(1)                                          # [S, L, Q]
+    blocked = torch.zeros(R, Q, dtype=torch.int32, device=dev)
+    blocked.index_add_(0, of_route, occupied[samples.index_select(0, of_route), links].int())
+    free = torch.zeros(R, Q, dtype=torch.bool, device=dev)
+    if width <= Q:
+        clear = blocked == 0
+        run = clear[:, :Q - width + 1].clone()
+        for t in range(1, width):
+            run &= clear[:, t:Q - width + 1 + t]
+        free[:, :Q - width + 1] = run
+    route, slot = free.nonzero(as_tuple=True)                                     # (the host read)
+    K = int(route.shape[0])
+    per = length.index_select(0, route) * width                                   # [K] cells per candidate
+    cell_ptr = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    cell_ptr[1:] = per.cumsum(0)
+    Mc = int(cell_ptr[-1])
+    cand = torch.repeat_interleave(torch.arange(K, device=dev), per, output_size=Mc)
+    pos = torch.arange(Mc, device=dev) - cell_ptr.index_select(0, cand)
+    link = links.index_select(0, link_ptr.index_select(0, route.index_select(0, cand)) + pos // width)
+    cells = torch.stack([link, slot.index_select(0, cand) + pos % width])
+    vals = values.index_select(0, route)
+    if slot_row >= 0:
+        vals[:, slot_row] = status.freq.index_select(0, slot)
+    return SlotSweep(samples.index_select(0, route), vals, cells, cell_ptr, route, slot, free)
 
 
 PLACE_MAX_AFFECTED = 32         # include/qot_gnn.h: QOT_PLACE_MAX_AFFECTED, retested lightpaths per candidate
@@ -1495,6 +1623,9 @@ class LightpathPredictor(_DeviceState):
     ``predict.place(status, samples, values, cells, cell_ptr)``: K candidate (route, slot) assignments of a NEW lightpath,
     each placed into a status sample that does not hold it yet -- the interferers are found by the kernel -- one launch and
     no host read (see there).
+    ``predict.place_slots(status, samples, values, links, link_ptr)``: the step before ``place`` -- R routes, each swept over
+    every start slot of the grid; an occupied slot is an answer (``free``), not an error -- one launch and no host read
+    (see there).
     ``predict.place_impact(status, samples, values, cells, cell_ptr)``: ``place``'s rows together with the retest of the
     established lightpaths each candidate disturbs -- their rows as the lightpath under test before and after the candidate
     is lit -- one launch and no host read (see there).
@@ -1516,7 +1647,8 @@ class LightpathPredictor(_DeviceState):
                                      "node or a drop position out of range, bit 2 a candidate's feature row without 1.0 "
                                      "in the LUT column; from_status: bit 3 a bad conn_id, bit 4 too many lightpaths, bit 5 "
                                      "a sample number out of range; place: those, bit 6 a bad cell, bit 7 an occupied "
-                                     "cell, bit 8 a conn_id taken, bit 9 values not under test; retest: from_status's, bit "
+                                     "cell, bit 8 a conn_id taken, bit 9 values not under test; place_slots: place's "
+                                     "without bit 7, bit 6 a bad link or link_ptr slice; retest: from_status's, bit "
                                      "12 a named conn_id the sample does not hold)")
     # the bits of qot_lightpath_infer_status, named when check_status() finds them: the device builder's own words
     _CAUSES = tuple((bit, next(t for b, t in to_graph._SG_CAUSES if b == sg)) for bit, sg in (
@@ -1831,6 +1963,72 @@ class LightpathPredictor(_DeviceState):
             name, extra = "qot_lightpath_infer_place_release", (ra.release.contiguous(), rptr[0], ra.R)
         return out, self._launch_status(name, status, sa, shape, pa.K, picks, out, values.contiguous(), cells.contiguous(), ptr,
                                         pa.M, *extra)
+
+    @torch.no_grad()
+    def place_slots(self, status, samples, values, links, link_ptr, features_to_consider=to_graph.DEFAULT_FEATURES,
+                    freq_threshold=0.05, *, width=1, slot_feature="freq", chunk=None):
+        """The step before ``place``: given a route, which frequency slot?  Sweeps each of R routes over EVERY start slot
+        of the grid, ``PlaceSlots(out [R, Q, O] float32, free [R, Q] bool, count [R] int64)`` in ONE kernel launch
+        (``csrc/infer_lightpath_place_slots.hip``), with nothing read back and ``status.data`` never
+        written; legal inside ``torch.cuda.graph`` capture under the conditions of ``place`` (index arguments as device
+        tensors, one call made first).  First-fit is ``free.int().argmax(1)``, best predicted OSNR ``out[..., 0]
+        .masked_fill(~free, -inf).argmax(1)``: neither needs the free slots on the host, nor K candidate lists that
+        differ in one feature.  An occupied slot is an answer (``free == False``, a NaN row), NOT an error: it sets no
+        status bit.
+
+        ``status``, ``samples`` and ``values [R, P]`` (float64, on the device) are ``place``'s, one row per route.
+        ``links [M]`` int64 on the device: link indices; route ``r`` is ``links[link_ptr[r]:link_ptr[r + 1]]`` -- non-empty,
+        a duplicate link allowed, no cap on its length.  ``link_ptr``: R + 1 offsets, by ``cell_ptr``'s rules: a host
+        sequence is checked here and uploaded, an int64 device tensor is used in place and checked by the kernel.
+        ``width``: an int in ``1 ... 8``, the same for the whole call: the candidate that starts at slot ``q`` occupies the
+        slots ``q ... q + width - 1`` on every link of its route (spectrum continuity and contiguity); a start slot ``q >
+        Q - width`` is never free.  ``slot_feature``: the name of an ``lp_feat`` row, or ``None``.  With a name the
+        candidate at start slot ``q`` carries ``status.freq[q]`` in that row in the place of ``values[r]``'s entry -- what
+        ``synthetic_network_status`` writes for a lightpath; with ``None`` ``values[r]`` is used unchanged at every slot.
+
+        ``infer.materialise_slot_sweep`` is the definition: with ``sw`` its answer, ``out[sw.route[k], sw.slot[k]]`` is,
+        bit for bit, ``self.place(status, sw.samples, sw.values, sw.cells, sw.cell_ptr, ...)[0][k]``, every other row of
+        ``out`` is NaN, ``free`` equals ``sw.free``, and ``count[r]`` is ``place``'s count -- the flagged lightpaths of the
+        sample plus one, the same at every slot.  ``to_graph.slot_sweep`` states the free slots and each one's message
+        sources on the host.  A route's rows depend on its sample and itself alone.
+
+        ``chunk``: the start slots one workgroup runs one after the other, ``1 ... 32``; ``None``:
+        ``place_slots_chunk(R, Q, compute_units)``.  Every result is bitwise independent of it.
+
+        Refusals before any launch (``lightpath_place_slots_args``): ``TypeError`` for a ``status`` that is no
+        ``DeviceStatus``; ``ValueError`` for ``values``, ``links``, ``samples`` or ``link_ptr`` of the wrong dtype, shape
+        or device, a host ``link_ptr`` that is not non-decreasing from 0 to M or has an empty slice, a ``width`` outside
+        ``1 ... 8``, a ``slot_feature`` that is no row of ``status.lp_feat`` or one of ``conn_id``, ``osnr``, ``snr``,
+        ``ber``, a bad ``chunk`` or ``freq_threshold``; ``EnvelopeError`` for everything ``from_status`` refuses and for
+        ``R * Q >= 2^31``.  ``R == 0`` or ``Q == 0`` gives empty tensors without a launch.  On the device, per route since
+        nothing is read back: a sample number outside the chunk, a bad slice of a device ``link_ptr`` or a link index
+        outside ``[0, L)``, a ``conn_id`` that is not finite or beyond +-2^53 in ``values[r]`` or in the sample,
+        ``values[r]`` without ``osnr == snr == ber == -1``, a ``conn_id`` the sample holds already, a sample of 256
+        lightpaths -- all Q rows of that route are NaN, all of ``free[r]`` False, ``count[r]`` 0, the other routes are
+        untouched, and ``check_status()`` raises naming the cause with ``place``'s bits.
+
+        Out of scope: ``release=``, a ``width`` per route, a sub-range of the slots, a sweep for
+        ``TopologicalPredictor``, and spreading the rows of one workgroup over its four waves (the row routine's barriers
+        depend on the message count, so a workgroup's rows are computed by one wave, as in ``retest``)."""
+        who = "LightpathPredictor.place_slots"
+        shape = self._check_model()
+        pa = lightpath_place_slots_args(status, shape[0], self.model.is_lut_index, samples, values, links, link_ptr,
+                                        features_to_consider, freq_threshold, width, slot_feature, chunk, who)
+        sa = pa.status
+        dev = self._status_device(status, who)
+        R, Q, O = pa.R, sa.Q, shape[2]
+        if R * Q >= 1 << 31:
+            raise EnvelopeError(f"{who}: routes x frequency slots must stay below 2^31, got {R} x {Q}")
+        out = torch.empty(R, Q, O, dtype=torch.float32, device=dev)
+        free = torch.empty(R, Q, dtype=torch.bool, device=dev)
+        if R == 0 or Q == 0:                                   # (Q == 0: no slot to count a sample's lightpaths at)
+            return PlaceSlots(out, free, torch.zeros(R, dtype=torch.int64, device=dev))
+        if chunk is None:
+            chunk = place_slots_chunk(R, Q, torch.cuda.get_device_properties(dev).multi_processor_count)
+        picks, ptr = _place_index_lists(dev, pa.samples, pa.link_ptr)
+        count = self._launch_status("qot_lightpath_infer_place_slots", status, sa, shape, R, picks, out, values.contiguous(),
+                                    links.contiguous(), ptr, pa.M, pa.slot_row, width, chunk, free)
+        return PlaceSlots(out, free, count)
 
     @torch.no_grad()
     def place_impact(self, status, samples, values, cells, cell_ptr, features_to_consider=to_graph.DEFAULT_FEATURES,

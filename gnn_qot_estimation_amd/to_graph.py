@@ -345,6 +345,32 @@ def placement_neighbourhood(sample: np.ndarray, freq: np.ndarray, feature_indexe
     return [int(conn[i]) for i in np.sort(first) if int(conn[i]) in hit]
 
 
+def slot_sweep(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], links, freq_threshold: float = 0.05,
+               width: int = 1):
+    """One route of ``LightpathPredictor.place_slots``, stated on the host: ``(free [Q] bool, neighbours)``.  ``links``:
+    the link indices of the route (non-empty; a duplicate link changes nothing).  The candidate that starts at slot ``q``
+    takes the cells ``links x {q ... q + width - 1}``; ``free[q]``: every one of those channels of ``sample [lp_feat, link,
+    freq]`` has all its values equal to 0, and ``q + width <= Q`` -- the start slots at which ``place_lightpath`` accepts
+    the cells.  ``neighbours[q]``: ``placement_neighbourhood`` of those cells for a free ``q`` -- who sends a message into
+    the candidate's row, in message order -- and ``None`` otherwise."""
+    sample = np.asarray(sample, dtype=np.float64)
+    L, Q = sample.shape[1], sample.shape[2]
+    links = np.asarray(links, dtype=np.int64).reshape(-1)
+    if links.size < 1 or ((links < 0) | (links >= L)).any():
+        raise ValueError(f"links must hold at least one link index in 0 ... {L - 1}, got {links.tolist()}")
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or width < 1:
+        raise ValueError(f"width must be a positive int, got {width!r}")
+    clear = ~np.any(sample[:, links, :] != 0, axis=(0, 1))                       # [Q]: the slot is free on every link
+    free = np.zeros(Q, dtype=bool)
+    neighbours = [None] * Q
+    for q in range(Q - width + 1):
+        if clear[q:q + width].all():
+            free[q] = True
+            cells = np.array([[l, q + t] for l in links.tolist() for t in range(width)], dtype=np.int64).T
+            neighbours[q] = placement_neighbourhood(sample, freq, feature_indexes, cells, freq_threshold)
+    return free, neighbours
+
+
 def _sources_of(sample: np.ndarray, freq: np.ndarray, feature_indexes: Dict[str, int], conn_a: int, freq_threshold: float):
     """``(node, sources)`` of the lightpath ``conn_a`` of ``sample``: its number in first-seen order, and the conn ids, in
     first-seen order, of the other lightpaths within the threshold of one of its channels on that channel's link

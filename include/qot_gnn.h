@@ -1367,6 +1367,45 @@ int qot_lightpath_infer_reroute_impact(const float* x, const int64_t* edge_index
                                        float* before, float* after, uint8_t* gains, int64_t* lost, int max_affected,
                                        qot_stream_t stream);
 
+/* ---- the place entry for every start slot of R routes in one launch: given a route, which frequency slot?
+ * (LightpathPredictor.place_slots) -- Route r is the links links[link_ptr[r] : link_ptr[r + 1]] (links [M]
+ * int64 link indices, link_ptr [R + 1] int64; a slice must be non-empty, a duplicate link is allowed, no cap on its length)
+ * in sample samples[r] (required) with the raw lp_feat vector values[r] (fp64 [R, P]).  The candidate that starts at slot q
+ * occupies the slots q .. q + width - 1 on every link of the route.  free[r, q] (uint8 [R, Q]) is 1 when every one of those
+ * channels is free (all P values 0) and q + width <= Q; out[r, q] (fp32 [R, Q, O]) is then, bit for bit, the place entry's
+ * row for that candidate -- cells route x {q .. q + width - 1} in any order, values[r] with, when slot_row >= 0, freq[q] in
+ * the lp_feat row slot_row (slot_row -1: values[r] unchanged at every slot) -- and a NaN row otherwise.  An occupied slot
+ * is an answer: it sets no status bit.  count[r] (int64 [R]) is the place entry's count, the flagged lightpaths of the
+ * sample plus one, the same at every slot.  data is never written.  R * ceil(Q / chunk) 256-thread workgroups; a workgroup
+ * discovers its sample once, marks the neighbourhoods of its chunk start slots with four waves and computes their rows one
+ * after the other in one wave, so no result depends on chunk; O(L Q + chunk * route * width * Q) per workgroup; no
+ * workspace.
+ *
+ * The argument list is the place entry's up to values (R takes K's place; the envelope is asked for R * Q rows), then links,
+ * link_ptr, M, slot_row, width, chunk, free.  Return codes before any launch: the status entry's, QOT_ERR_UNSUPPORTED for
+ * R * Q >= 2^31 or R * ceil(Q / chunk) >= 2^31, QOT_ERR_BADARG for M < 0, slot_row outside -1 .. P - 1, width outside 1 ..
+ * QOT_LP_PLACE_SLOTS_MAX_WIDTH, chunk outside 1 .. QOT_LP_PLACE_SLOTS_MAX_CHUNK or -- when R > 0 -- a NULL samples, values,
+ * link_ptr or free, or NULL links with M > 0.  R == 0: QOT_OK, no launch.
+ * status, per route since nothing is read back -- all Q rows of the route NaN, its free 0, its count 0, the other routes
+ * untouched -- with the place entry's bits: QOT_LP_STATUS_BAD_SAMPLE; QOT_LP_PLACE_BAD_CELL for a link_ptr slice that is
+ * empty, descending or beyond M or a link index outside [0, L); QOT_LP_STATUS_BAD_CONN; QOT_LP_PLACE_NOT_LUT;
+ * QOT_LP_PLACE_CONN_TAKEN; QOT_LP_STATUS_TOO_MANY.  QOT_LP_PLACE_OCCUPIED is never set.  Nothing read from data or values
+ * is used as an index; a link index is range-checked before it is. */
+#define QOT_LP_PLACE_SLOTS_MAX_CHUNK 32     /* start slots one workgroup runs one after the other (their byte maps: 32 x 256 B of LDS) */
+#define QOT_LP_PLACE_SLOTS_MAX_WIDTH 8      /* slots a candidate occupies on every link of its route */
+int qot_lightpath_infer_place_slots(const float* x, const int64_t* edge_index, const int64_t* batch, const int64_t* node_ptr,
+                                    const int64_t* edge_ptr, const int64_t* lut_idx, int64_t n_lut, int64_t N, int64_t E,
+                                    int64_t R, const float* w, const float* att_src, const float* att_dst,
+                                    const float* conv_bias, float slope_att, const float* bn_weight, const float* bn_bias,
+                                    const float* bn_mean, const float* bn_var, float bn_eps, const float* w0, const float* b0,
+                                    const float* w3, const float* b3, float slope_head, float* out, int64_t* count, int F,
+                                    int C, int O, int heads, int lut_col, int32_t* status, const double* data,
+                                    const double* freq, const int64_t* samples, int64_t S, int P, int64_t L, int64_t Q,
+                                    int conn_row, int osnr_row, int snr_row, int ber_row, const double* cols, int ncol,
+                                    double freq_threshold, const double* values, const int64_t* links,
+                                    const int64_t* link_ptr, int64_t M, int slot_row, int width, int chunk, uint8_t* free,
+                                    qot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,18 @@ of them one that some survivor loses as a source (asserted on the inputs).  The 
 ``out`` / ``count`` and (c)'s, are compared first (equal bits).
 
     python tools/bench_infer.py --kind lightpath --reroute-impact 1 8 64 1024 --release 2 [--out profiles/bench_infer_lightpath_reroute_impact.jsonl]
+
+``--kind lightpath --place-slots R [R ...] [--width W] [--chunk C]``: given a route, which slot? --
+``predict.place_slots(status, ...)`` (csrc/infer_lightpath_place_slots.hip, DESIGN.md 4.28: R routes of 3 links, each swept
+over all 72 start slots of one 60 x 72 ``synthetic_network_status`` sample, one launch, nothing read back) against (a) the
+only way before: ``infer.materialise_slot_sweep`` -- the occupancy pass, the host read of the free slots, the building of
+``place``'s lists -- followed by ``predict.place``; (b) ``predict.place`` on those lists built outside the timed region,
+timed in an alternation of its own: what the shared scan is worth without the saved host work (``place`` spreads one
+workgroup per free slot over the device, ``place_slots`` runs the rows of a chunk one after the other on one wave).  C =
+32, F = 5, threshold 0.12, the chunk ``infer.place_slots_chunk`` picks unless ``--chunk`` names one (reported).  ``free`` and
+the rows of the three ways are compared first (equal bits).
+
+    python tools/bench_infer.py --kind lightpath --place-slots 1 8 64 [--width W] [--out profiles/bench_infer_lightpath_place_slots.jsonl]
 """
 import argparse
 import json
@@ -1292,6 +1304,101 @@ def main_retest(args, device, commit):
               f"{ratio(r, 'retest_pair', 'from_status')} |")
 
 
+def measure_place_slots(R, device, rounds, warmup, thr=0.12, width=1, chunk=None):
+    """``place_slots`` of R routes of 3 links over every start slot of one status sample against (a) the only way
+    before -- ``materialise_slot_sweep`` (occupancy, the host read of the free slots, list building) + ``place`` -- and (b)
+    ``place`` on those lists built outside the timed region: what the shared scan is worth without the saved host work."""
+    import numpy as np
+    from gnn_qot_estimation_amd import infer, to_graph as TG
+    torch.manual_seed(0)
+    predict = q.LightpathPredictor(q.LightpathGNN(5, 32, 3, 1, dropout_p=0.0).to(device).eval())
+    ns = TG.synthetic_network_status(1, seed=0)             # the 60 x 72 grid
+    fi, feats = ns.feature_indexes, list(TG.DEFAULT_FEATURES)
+    data = ns.data.copy()
+    under_test = (data[0, fi["osnr"]] == -1) & (data[0, fi["snr"]] == -1) & (data[0, fi["ber"]] == -1)
+    data[0][:, under_test] = 0.0                            # as --place: the sample's own lightpath under test goes
+    L, Q = data.shape[2], data.shape[3]
+    rng = np.random.default_rng(R)
+    values, links = np.zeros((R, len(ns.lp_feat))), []
+    for r in range(R):
+        links += [int(l) for l in rng.choice(L, size=3, replace=False)]
+        v = values[r]
+        v[fi["conn_id"]], v[fi["src_id"]], v[fi["dst_id"]] = 10000 + r, 1, 2
+        v[fi["mod_order"]], v[fi["path_len"]] = float(rng.choice([4, 8, 16, 32, 64])), float(rng.integers(24214, 7834746))
+        v[fi["num_spans"]] = float(rng.integers(1, 107))
+        v[fi["osnr"]] = v[fi["snr"]] = v[fi["ber"]] = -1.0
+    st = TG.NetworkStatus(data, ns.target, ns.lp_feat, ns.metric, ns.link, ns.freq).to_device(device)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device)       # noqa: E731
+    samples, values_d, links_d, ptr_d = torch.zeros(R, dtype=torch.int64, device=device), torch.from_numpy(values).to(device), \
+        dev(links), dev(3 * np.arange(R + 1))
+    used = chunk or infer.place_slots_chunk(R, Q, torch.cuda.get_device_properties(device).multi_processor_count)
+    sw = infer.materialise_slot_sweep(st, samples, values_d, links_d, ptr_d, width=width)      # (b)'s lists, built beforehand
+    K = int(sw.route.shape[0])
+    assert 0 < K < R * Q, (K, R, Q)                         # a condition on the inputs: free and occupied slots both
+
+    def materialise():
+        m = infer.materialise_slot_sweep(st, samples, values_d, links_d, ptr_d, width=width)
+        return predict.place(st, m.samples, m.values, m.cells, m.cell_ptr, feats, thr)[0], m
+    ways = {"slots": lambda: predict.place_slots(st, samples, values_d, links_d, ptr_d, feats, thr, width=width, chunk=chunk),
+            "materialise": materialise,
+            "place": lambda: predict.place(st, sw.samples, sw.values, sw.cells, sw.cell_ptr, feats, thr)[0]}
+    got = {k: fn() for k, fn in ways.items()}
+    torch.cuda.synchronize()
+    predict.check_status()
+    r, (rows, m) = got["slots"], got["materialise"]
+    assert torch.equal(r.free, sw.free) and torch.equal(m.free, sw.free)
+    assert torch.equal(r.out[sw.route, sw.slot], rows) and torch.equal(rows, got["place"]), R   # equal bits
+    assert bool(torch.isfinite(rows).all()) and bool(torch.isnan(r.out[~r.free]).all())
+    for _ in range(warmup):
+        for fn in ways.values():
+            fn()
+    # two alternations, as --retest: plain place is not timed right behind (a)'s list building
+    times = {k: [] for k in ("slots", "materialise", "slots_pair", "place")}
+    for _ in range(rounds):
+        times["slots"].append(timed_event(ways["slots"]))
+        times["materialise"].append(timed_event(ways["materialise"]))
+    for _ in range(warmup):
+        ways["slots"](), ways["place"]()
+    for _ in range(rounds):
+        times["slots_pair"].append(timed_event(ways["slots"]))
+        times["place"].append(timed_event(ways["place"]))
+    res = dict(shape=f"status {L} x {Q}", kind="lightpath_place_slots", R=R, route_links=3, width=width, chunk=used, free=K,
+               cells=int(sw.cells.shape[1]), P=int(st.data.shape[1]), L=L, Q=Q, C=32, F=5, freq_threshold=thr, rounds=rounds,
+               equal_bits=True)
+    for k, ts in times.items():
+        q1, _, q3 = statistics.quantiles(ts, n=4)
+        res[f"{k}_ms"], res[f"{k}_iqr_ms"] = statistics.median(ts), q3 - q1
+        res[f"{k}_min_ms"], res[f"{k}_max_ms"] = min(ts), max(ts)
+    return res
+
+
+def main_place_slots(args, device, commit):
+    rows = []
+    for R in args.place_slots:
+        res = measure_place_slots(R, device, args.rounds, args.warmup, width=args.width, chunk=args.chunk)
+        res["commit"] = commit or None
+        res["device"] = torch.cuda.get_device_name(0)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("\n| grid | R | width | chunk | free | place_slots ms (IQR) | (a) materialise_slot_sweep + place ms (IQR) | "
+          "(a) / place_slots | place_slots beside (b) ms (IQR) | (b) place on prebuilt lists ms (IQR) | place_slots / (b) |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+
+    def ratio(r, num, den):                                 # differ: by more than the sum of the IQRs
+        same = abs(r[num + "_ms"] - r[den + "_ms"]) <= r[num + "_iqr_ms"] + r[den + "_iqr_ms"]
+        return "no difference" if same else f"{r[num + '_ms'] / r[den + '_ms']:.2f}x"
+    for r in rows:
+        cell = lambda k: f"{r[k + '_ms']:.3f} ({r[k + '_iqr_ms']:.3f})"                     # noqa: E731
+        print(f"| {r['L']} x {r['Q']} | {r['R']} | {r['width']} | {r['chunk']} | {r['free']} | {cell('slots')} | "
+              f"{cell('materialise')} | {ratio(r, 'materialise', 'slots')} | {cell('slots_pair')} | {cell('place')} | "
+              f"{ratio(r, 'slots_pair', 'place')} |")
+
+
 LIGHTPATH_SIZES = (1, 8, 512, 65536)
 
 
@@ -1482,7 +1589,22 @@ def main():
     ap.add_argument("--max-lightpaths", type=int, default=256, metavar="M", dest="max_lightpaths",
                     help="with --retest: the slots per sample (the grid is S * ceil(M / chunk) workgroups, each of which "
                          "discovers its sample: 32 against 256 tells what the workgroups without a lightpath cost)")
+    ap.add_argument("--place-slots", type=int, nargs="+", default=None, metavar="R", dest="place_slots",
+                    help="--kind lightpath: predict.place_slots on R routes of 3 links over every start slot of one status "
+                         "sample against materialise_slot_sweep + place and against place on prebuilt lists")
+    ap.add_argument("--width", type=int, default=1, metavar="W",
+                    help="with --place-slots: the slots a candidate occupies on every link of its route (1 ... 8)")
+    ap.add_argument("--chunk", type=int, default=None, metavar="C",
+                    help="with --place-slots: the start slots per workgroup (1 ... 32) instead of infer.place_slots_chunk's")
     args = ap.parse_args()
+    if args.place_slots is None and (args.width != 1 or args.chunk is not None):
+        raise SystemExit("--width and --chunk go with --place-slots")
+    if args.place_slots is not None and (args.kind != "lightpath" or args.place is not None or args.from_status
+                                         or args.mc is not None or args.grad or args.what_if is not None
+                                         or args.place_impact is not None or args.reroute_impact is not None
+                                         or args.retest is not None or any(r < 1 for r in args.place_slots)
+                                         or not 1 <= args.width <= 8 or (args.chunk is not None and not 1 <= args.chunk <= 32)):
+        raise SystemExit("--kind lightpath --place-slots R [R ...] (R >= 1) [--width 1 ... 8] [--chunk 1 ... 32] is a run of its own")
     if args.retest is None and args.max_lightpaths != 256:
         raise SystemExit("--max-lightpaths goes with --retest")
     if args.retest is not None and (args.kind != "lightpath" or args.place is not None or args.from_status
@@ -1522,6 +1644,8 @@ def main():
         raise SystemExit("bench_infer.py needs an MI355X: no GPU is visible (nothing is measured on the CPU)")
     device = torch.device("cuda:0")
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+    if args.place_slots is not None:
+        return main_place_slots(args, device, commit)
     if args.reroute_impact is not None:
         return main_reroute_impact(args, device, commit)
     if args.place_impact is not None:
