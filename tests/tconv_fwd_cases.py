@@ -229,7 +229,11 @@ def _logits64(c, qkvs):
 
 @functools.lru_cache(maxsize=None)
 def tconv_case(name, cus=TRIP_CUS):
-    cfg = CASES[name]
+    return build_case(name, CASES[name], cus)
+
+
+def build_case(name, cfg, cus=TRIP_CUS):
+    """The case ``name`` of a table entry ``cfg`` (tests/tconv_bwd_cases.py has entries of its own)."""
     gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))          # by name: adding a case moves no other
     H, D = cfg["H"], cfg["D"]
     sizes = _sizes(cfg, cus)

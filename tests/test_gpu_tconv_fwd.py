@@ -14,7 +14,8 @@ The form is forced through the ``QOT_NO_TCONV_*`` switches and the entry point t
 ``_lib.call`` names; every floating ``torch.empty`` is filled with NaN for the duration; each (case, form) runs twice
 (bitwise equal); every tensor's worst ``error / bound`` is printed before anything is asserted (``pytest -s``; a record,
 not a threshold).  One end-to-end check per form (table and parameters in, fp64 oracle, ``helpers.TOL``) shows that the
-stages are wired together; it is not the sharp check.  The backward stays with tests/test_gpu_grad_scale.py."""
+stages are wired together; it is not the sharp check.  The backward kernels are checked the same way in
+tests/test_gpu_tconv_bwd.py."""
 import pytest
 import torch
 import torch.nn.functional as F
